@@ -109,7 +109,16 @@ def parse_args(argv=None):
                     help="how many times the K-step block is run in all for "
                          "the `repeat` object (the first is the timed region "
                          "behind `value`; 1 = no extra blocks)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed region's last Gibbs iteration "
+                         "computed as DIR/<name>.npy (float64): coef (the kept "
+                         "sample, one row per rank), global_scale, logp, "
+                         "n_cg_iter, local_scale and obs_prec (rank 0's "
+                         "chain); taken before the `repeat` blocks")
+    args = ap.parse_args(argv)
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
+    return args
 
 
 def build_dense_problem(torch, cfg, seed, device):
@@ -733,6 +742,15 @@ def main():
         if has_stats else None)
     elapsed = chains.max_over_ranks(elapsed)
     progress("timed region done (%.3f s)" % elapsed)
+    # --dump-outputs: what the timed region's last iteration computed, copied
+    # to the host now (the `repeat` blocks below reuse the sample buffer)
+    dump = None
+    if args.dump_outputs is not None and rank == 0:
+        _, obs_k, ls_k, _ = chain.get_state()
+        dump = dict(coef=gathered[:, K - 1].cpu().numpy(),
+                    global_scale=gs[-1:], logp=lp[-1:], n_cg_iter=ncg[-1:],
+                    local_scale=ls_k, obs_prec=np.atleast_1d(obs_k))
+        assert sum(v.nbytes for v in dump.values()) <= 64 << 20
     timing = design.get_timing() if timing_on else {
         "dot": (0, 0.), "tdot": (0, 0.), "operator": (0, 0.)}
     if args.timing_blocks == "first":
@@ -1052,6 +1070,11 @@ def main():
                 args.cpu_baseline_iters, args.seed)
         else:
             line["cpu_baseline"] = None
+        if dump is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in dump.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"),
+                        np.ascontiguousarray(arr, dtype=np.float64))
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(line) + "\n").encode())
     chain.close()

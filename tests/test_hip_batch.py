@@ -217,8 +217,6 @@ def test_dense_batched_products_on_the_matrix_cores(K, shape, storage):
     (two sweeps) 9 row tiles -- the kernel is instantiated per tile count."""
     from bayesbridge_amd import HipChainBatch
     n, p = shape
-    if storage == 'float64' and n * p > 5e7:
-        pytest.skip("one storage type is enough at this size")
     X, y, hip = _dense_problem(n, p, storage=storage)
     batch = HipChainBatch(_chains(hip, y, 'linear', list(range(K))), allow_slow=True)
     rng = np.random.default_rng(9)

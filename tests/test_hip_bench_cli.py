@@ -90,6 +90,36 @@ def test_dense_line_has_a_cpu_baseline():
     assert line["multi_chain"]["k=4"]["chain_iters_per_sec"] > 0
 
 
+def test_dump_outputs_are_the_last_timed_step_and_repeat_run_to_run(tmp_path):
+    """--dump-outputs DIR: the timed region's last iteration as float64 .npy
+    files.  Same arguments => same inputs and (no atomics in any sum) the same
+    outputs bit for bit; the `repeat` blocks after the timed region do not
+    change them; one more timed step does."""
+    import numpy as np
+    from bench import CONFIGS
+    n, p, _ = CONFIGS["tiny"]
+    flags = ("--config", "tiny", "--warmup", "2", "--burnin", "4",
+             "--cpu-baseline-iters", "0", "--multi-chain", "0")
+    runs = {}
+    for tag, steps, repeat in (("a", 5, 1), ("b", 5, 3), ("c", 6, 1)):
+        out = tmp_path / tag
+        line = _bench(*flags, "--steps", str(steps), "--repeat", str(repeat),
+                      "--dump-outputs", str(out))
+        assert line["steps"] == steps
+        runs[tag] = {f.stem: np.load(f) for f in out.glob("*.npy")}
+        assert line["config"]["n_cg_iter_timed"][-1] == \
+            runs[tag]["n_cg_iter"][0]
+    shapes = {"coef": (1, p + 1), "global_scale": (1,), "logp": (1,),
+              "n_cg_iter": (1,), "local_scale": (p,), "obs_prec": (n,)}
+    a, b, c = runs["a"], runs["b"], runs["c"]
+    assert {k: v.shape for k, v in a.items()} == shapes
+    for k, v in a.items():
+        assert v.dtype == np.float64 and np.all(np.isfinite(v)), k
+        assert np.array_equal(v, b[k]), k
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert not np.array_equal(a["coef"], c["coef"])
+
+
 def test_gpus_2_launches_two_ranks_by_itself():
     line = _bench("--gpus", "2", "--config", "tiny", "--steps", "4",
                   "--warmup", "1", "--burnin", "2")
@@ -161,15 +191,16 @@ print('RCCL_OK')
     assert "RCCL_OK" in out.stdout
 
 
-def test_gpus_8_dry_run_over_gloo():
-    """The driver's 8-GPU launch in miniature: `bench.py --gpus 8` starts eight
-    ranks by itself (ports, eight generators and eight host-side layout
+def test_gpus_4_dry_run_over_gloo():
+    """The driver's 8-GPU launch in miniature: `bench.py --gpus 4` starts four
+    ranks by itself (ports, four generators and four host-side layout
     builders side by side); on a 1-GPU box they share the device (one stream
-    per chain, BBX_CHAIN_FORK=0) and gather over gloo."""
-    line = _bench("--gpus", "8", "--config", "tiny", "--steps", "3",
+    per chain, BBX_CHAIN_FORK=0) and gather over gloo.  Four ranks: with this
+    process and the launcher no more than six processes hold the one GPU."""
+    line = _bench("--gpus", "4", "--config", "tiny", "--steps", "3",
                   "--warmup", "1", "--burnin", "2", timeout=1500)
-    assert line["n_gpus"] == 8
-    assert line["config"]["parallelism"] == "chains=8"
+    assert line["n_gpus"] == 4
+    assert line["config"]["parallelism"] == "chains=4"
     assert line["value"] > 0
     assert line["config"]["startup_s"] > 0
     assert line["config"]["peak_host_rss_mb"] > 0
@@ -179,10 +210,10 @@ def test_gpus_8_dry_run_over_gloo():
     for key in ("startup_s", "peak_host_rss_mb", "builder_threads", "timed_s",
                 "run_s", "gather_ms", "iters_per_sec", "mean_n_cg_iter",
                 "burnin_ms_per_step", "device_index", "device_name", "pid"):
-        assert len(pr[key]) == 8, key
+        assert len(pr[key]) == 4, key
     assert all(v > 0 for v in pr["timed_s"]) and all(v > 0 for v in pr["run_s"])
     assert all(r <= t + 1e-3 for r, t in zip(pr["run_s"], pr["timed_s"]))
     assert all(v >= 0 for v in pr["gather_ms"])
-    assert len(set(pr["pid"])) == 8
+    assert len(set(pr["pid"])) == 4
     # `value` is N * K / the slowest rank's timed seconds
-    assert abs(line["value"] - 8 * 3 / max(pr["timed_s"])) < 2e-2 * line["value"]
+    assert abs(line["value"] - 4 * 3 / max(pr["timed_s"])) < 2e-2 * line["value"]
