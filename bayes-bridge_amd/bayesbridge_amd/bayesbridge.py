@@ -45,7 +45,7 @@ class SamplerOptions():
                  hmc_curvature_est_stabilized=False, rng='device'):
         if coef_sampler_type not in ('cholesky', 'cg', 'hmc'):
             raise ValueError("Unsupported regression coefficient sampler.")
-        if coef_sampler_type != 'cg':
+        if coef_sampler_type == 'hmc':
             # gibbs_util.py:49-50 says the same about CuPy matrices
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
         if rng not in ('device', 'reference'):
@@ -75,15 +75,25 @@ class SamplerOptions():
             coef_sampler_type = options['coef_sampler_type']
         if coef_sampler_type not in (None, 'cholesky', 'cg', 'hmc'):
             raise ValueError("Unsupported sampler type.")
-        if coef_sampler_type not in (None, 'cg'):
+        if coef_sampler_type not in (None, 'cg') and not (
+                coef_sampler_type == 'cholesky'
+                and _is_hip_dense(design)):
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
         if model_name not in ('linear', 'logit'):
             raise ValueError("Only linear and logit models use the CG sampler.")
         n_obs, n_pred = design.shape
         if n_pred > n_obs:
             warn("Sampler has not been optimized for 'small n' problem.")
-        options['coef_sampler_type'] = 'cg'
+        # the reference defaults to 'cholesky' for dense designs
+        # (gibbs_util.py:53-65); here 'cg' stays the default for every design
+        options['coef_sampler_type'] = coef_sampler_type or 'cg'
         return SamplerOptions(**options)
+
+
+def _is_hip_dense(design):
+    """The 'cholesky' sampler runs on HIP dense designs only."""
+    return getattr(design, 'use_hip', False) is True \
+        and getattr(design, 'is_sparse', True) is False
 
 
 class BayesBridge():
@@ -169,6 +179,10 @@ class BayesBridge():
         if not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
                 coef_sampler_type, options, self.model.name, self.model.design)
+        if options.coef_sampler_type == 'cholesky':
+            if not _is_hip_dense(self.model.design):
+                raise ValueError(
+                    "Only 'cg' sampler supported with HIP matrices.")
         if params_to_save == 'all':
             params_to_save = ('coef', 'local_scale', 'global_scale', 'logp',
                               'obs_prec')
@@ -317,6 +331,9 @@ class BayesBridge():
         if not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
                 None, options, self.model.name, self.model.design)
+        if options.coef_sampler_type != 'cg':
+            raise ValueError("batched chains draw the coefficients with 'cg' "
+                             "only")
         if options.rng != 'device':
             raise ValueError("batched chains use the device RNG")
         if not set(params_to_save) <= {'coef', 'global_scale', 'logp'}:
@@ -367,6 +384,13 @@ class BayesBridge():
         samples[name] shaped (n_chain, ..., n_sample) on rank 0.  `batch`:
         False (default; chain k's samples do not depend on the number of
         ranks), 'auto' or a width -- see chains.run_chains."""
+        if options is not None:
+            kind = options.coef_sampler_type \
+                if isinstance(options, SamplerOptions) \
+                else dict(options).get('coef_sampler_type')
+            if kind not in (None, 'cg'):
+                raise ValueError("gibbs_multichain draws the coefficients "
+                                 "with 'cg' only")
         from . import chains
         return chains.run_chains(self, n_chain, n_iter, n_burnin, thin, seed,
                                  init, params_to_save, options, batch=batch)
@@ -496,11 +520,13 @@ class BayesBridge():
         if resume_from is None:
             self.rg.set_seed(seed)
             sampler = HipRegressionCoefficientSampler(
-                self.n_pred, self.prior_sd_for_unshrunk, 'cg', prior.slab_size)
+                self.n_pred, self.prior_sd_for_unshrunk,
+                options.coef_sampler_type, prior.slab_size, rand_gen=self.rg)
         else:
             self.rg.set_state(resume_from['_random_gen_state'])
             sampler = HipRegressionCoefficientSampler(
-                self.n_pred, self.prior_sd_for_unshrunk, 'cg', prior.slab_size)
+                self.n_pred, self.prior_sd_for_unshrunk,
+                options.coef_sampler_type, prior.slab_size, rand_gen=self.rg)
             sampler.set_internal_state(resume_from['_reg_coef_sampler_state'])
         rg = self.rg
         nu = self.n_unshrunk
@@ -576,6 +602,8 @@ class BayesBridge():
                                    sampler)
         samples, sampling_info = self._pre_allocate(
             n_iter - n_burnin, thin, params_to_save)
+        if options.coef_sampler_type == 'cholesky':
+            sampling_info = {}       # gibbs_util.py:147-160: no n_cg_iter
         n_status_update = min(n_iter, n_status_update)
         stamp = time.time()
         for mcmc_iter in range(1, n_iter + 1):
@@ -587,7 +615,8 @@ class BayesBridge():
                 omega = obs_prec
                 y_gaussian = (model.n_success - model.n_trial / 2) / obs_prec
             coef, info = sampler.sample_gaussian_posterior(
-                y_gaussian, design, omega, gscale, lscale, 'cg')
+                y_gaussian, design, omega, gscale, lscale,
+                options.coef_sampler_type)
             obs_prec = update_obs_precision(coef)
             gscale = update_global_scale(
                 gscale, coef[nu:], bridge_exp, method=options.gscale_update)
@@ -608,7 +637,8 @@ class BayesBridge():
                         samples['obs_prec'][:, idx] = obs_prec
                 if 'logp' in samples:
                     samples['logp'][idx] = logp
-                sampling_info['n_cg_iter'][idx] = info['n_cg_iter']
+                if 'n_cg_iter' in info:
+                    sampling_info['n_cg_iter'][idx] = info['n_cg_iter']
             if n_status_update and \
                     mcmc_iter % int(n_iter / n_status_update) == 0:
                 now = time.time()
@@ -655,6 +685,7 @@ class BayesBridge():
             self._chain.seed = seed
             self._chain_seed = seed
         chain = self._chain
+        chain.set_coef_sampler(options.coef_sampler_type)
         init_used, optim_info = self._device_setup(chain, seed, init, options,
                                                    resume_from)
         # status lines as the reference prints them (gibbs_util.py:214-238),
@@ -672,6 +703,18 @@ class BayesBridge():
             chain.set_progress(int(n_iter / n_status_update), report)
         else:
             chain.set_progress(0)
+        try:
+            return self._device_run(chain, seed, n_iter, n_burnin, thin,
+                                    params_to_save, device_out, init_used,
+                                    optim_info)
+        except _lib.BbxError as e:
+            if chain.coef_sampler == 'cholesky' and 'cholesky' in str(e):
+                raise np.linalg.LinAlgError(str(e)) from e
+            raise
+
+    def _device_run(self, chain, seed, n_iter, n_burnin, thin, params_to_save,
+                    device_out, init_used, optim_info):
+        model = self.model
         device_out = dict(device_out or {})
         host_params = tuple(k for k in params_to_save if k not in device_out)
         samples, _ = self._pre_allocate(n_iter - n_burnin, thin, host_params)
@@ -797,6 +840,8 @@ class BayesBridge():
             if key in samples:
                 samples[key][:] = kept[key]
         sampling_info['n_cg_iter'][:] = kept['n_cg_iter']
+        if getattr(chain, 'coef_sampler', 'cg') == 'cholesky':
+            sampling_info = {}       # gibbs_util.py:147-160: no n_cg_iter
         coef, obs_prec, lscale, gscale = chain.get_state()
         mean, square, n_avg = chain.get_summary()
         extra = {

@@ -327,8 +327,8 @@ class HipDesignMatrix():
 
     def compute_fisher_info(self, weight, diag_only=False):
         raise NotImplementedError(
-            "compute_fisher_info belongs to the 'cholesky' sampler, which is "
-            "outside the CG hot path this backend implements.")
+            "compute_fisher_info (the 'cholesky' sampler's Gram) is "
+            "implemented for dense designs only.")
 
     def compute_transposed_fisher_info(self, weight, include_intrcpt=False):
         raise NotImplementedError(
@@ -507,6 +507,28 @@ class HipDenseDesignMatrix(HipDesignMatrix):
     @property
     def is_sparse(self):
         return False
+
+    def release_sampler_memory(self):
+        """Frees the 'cholesky' sampler's work memory on the device (a P x P
+        f64 matrix, a second one for linear models' cached X~^T X~, the Gram
+        partials); the next draw allocates it again."""
+        _lib.check(self._lib.bbx_chol_release(self._h))
+
+    def compute_fisher_info(self, weight, diag_only=False):
+        """X~^T diag(weight) X~ (dense_matrix.py:54-58), or its diagonal, from
+        the device's matrix-core Gram (csrc/cholesky.hip), as a NumPy array.
+        X~ is the stored matrix (intercept column, centred): with
+        storage_dtype='float32' this is the Gram of the f32-rounded X~,
+        accumulated in f64.  `weight` None means ones."""
+        n, P = self.shape
+        w = None
+        if weight is not None:
+            w = np.ascontiguousarray(np.broadcast_to(
+                np.asarray(weight, dtype=np.float64), (n,)))
+        out = np.empty(P if diag_only else (P, P), dtype=np.float64)
+        _lib.check(self._lib.bbx_design_fisher_info(
+            self._h, _ptr(w), int(bool(diag_only)), _ptr(out)))
+        return out
 
     @property
     def nnz(self):

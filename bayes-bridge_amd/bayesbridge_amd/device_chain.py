@@ -151,6 +151,18 @@ class HipGibbsChain():
         _lib.check(self._lib.bbx_chain_set_gscale_update(
             self._c, _GSCALE_MODES[method]))
 
+    coef_sampler = 'cg'
+
+    def set_coef_sampler(self, kind):
+        """'cg' (default) or 'cholesky' (dense designs only): how the chain
+        draws beta | rest.  The 'cholesky' draw takes its P normals from the
+        stream of `eta(iteration)[1]` and keeps no running summary."""
+        code = {'cg': _lib.SAMPLER_CG, 'cholesky': _lib.SAMPLER_CHOLESKY}
+        if kind not in code:
+            raise ValueError("coef sampler must be 'cg' or 'cholesky'")
+        _lib.check(self._lib.bbx_chain_set_coef_sampler(self._c, code[kind]))
+        self.coef_sampler = kind
+
     def eta(self, iteration):
         """(eta1[n], eta2[P]): the normals of the CG draw at 0-based
         `iteration` (cg_sampler.py:61-62), regenerated from the counters."""

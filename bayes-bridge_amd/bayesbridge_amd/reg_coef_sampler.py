@@ -63,12 +63,62 @@ class RegressionCoeffficientPosteriorSummarizer():
         return self.coef_scaled_summarizer.estimate_post_sd()
 
 
+def chol_sample(design, obs_prec, prior_prec_sqrt, z, normals=None,
+                rand_gen=None):
+    """generate_gaussian_with_weight (direct_gaussian_sampler.py:4-44) on a
+    HIP dense design: the Gram, the Cholesky factorisation and both triangular
+    solves run on the device (bbx_chol_sample).  `normals`: the P standard
+    normals; None draws them as the reference does, np.random.randn(P) (or
+    rand_gen.np_random.randn(P)).  An `obs_prec` whose entries are all equal
+    (linear models) takes the scalar path: F = obs_prec * X~^T X~ with X~^T X~
+    cached on the design -- the same matrix rounded differently from the
+    reference's X~^T (obs_prec X~).  A matrix that is not numerically positive
+    definite raises numpy.linalg.LinAlgError."""
+    from ctypes import c_void_p
+    from . import _lib
+    if getattr(design, 'is_sparse', True) is not False \
+            or not getattr(design, 'use_hip', False):
+        raise ValueError("the 'cholesky' sampler needs a HIP dense design")
+    n, P = design.shape
+    obs_prec = np.ascontiguousarray(np.broadcast_to(
+        np.asarray(obs_prec, dtype=np.float64), (n,)))
+    pps = np.ascontiguousarray(prior_prec_sqrt, dtype=np.float64)
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    if pps.shape != (P,) or z.shape != (P,):
+        raise ValueError("prior_prec_sqrt and z must have length %d" % P)
+    if normals is None:
+        src = np.random if rand_gen is None else rand_gen.np_random
+        normals = src.randn(P)
+    normals = np.ascontiguousarray(normals, dtype=np.float64)
+    if normals.shape != (P,):
+        raise ValueError("normals must have length %d" % P)
+    out = np.empty(P)
+
+    def ptr(a):
+        return a.ctypes.data_as(c_void_p)
+    lib = design._lib
+    if n > 0 and np.all(obs_prec == obs_prec[0]):
+        st = lib.bbx_chol_sample_scalar(design._h, float(obs_prec[0]),
+                                        ptr(pps), ptr(z), ptr(normals),
+                                        ptr(out))
+    else:
+        st = lib.bbx_chol_sample(design._h, ptr(obs_prec), ptr(pps), ptr(z),
+                                 ptr(normals), ptr(out))
+    if st == _lib.ERR_NUMERIC:
+        raise np.linalg.LinAlgError(_lib.last_error())
+    _lib.check(st)
+    return out
+
+
 class HipRegressionCoefficientSampler():
 
     def __init__(self, n_coef, prior_sd_for_unshrunk, sampling_method='cg',
-                 regularizing_slab_size=float('inf')):
-        if sampling_method != 'cg':
+                 regularizing_slab_size=float('inf'), rand_gen=None):
+        if sampling_method not in ('cg', 'cholesky'):
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
+        # source of the 'cholesky' draw's normals: the global NumPy stream,
+        # which ReferenceRandom.np_random is (direct_gaussian_sampler.py:30)
+        self.rand_gen = rand_gen
         self.prior_sd_for_unshrunk = np.asarray(prior_sd_for_unshrunk,
                                                 dtype=np.float64)
         self.n_unshrunk = len(self.prior_sd_for_unshrunk)
@@ -85,8 +135,8 @@ class HipRegressionCoefficientSampler():
 
     def sample_gaussian_posterior(self, y, design, obs_prec, gscale, lscale,
                                   method='cg'):
-        """reg_coef_sampler.py:60-103, 'cg' branch."""
-        if method != 'cg':
+        """reg_coef_sampler.py:60-103, 'cg' and 'cholesky' branches."""
+        if method not in ('cg', 'cholesky'):
             raise NotImplementedError()
         v = design.Tdot(obs_prec * y)                                    # :74
         prior_sd = np.concatenate((
@@ -95,6 +145,10 @@ class HipRegressionCoefficientSampler():
                                        self.regularizing_slab_size)))
         with np.errstate(divide='ignore'):
             prior_prec_sqrt = 1 / prior_sd                               # :79
+        if method == 'cholesky':
+            # :81-84: no summariser update, no sampling info
+            return chol_sample(design, obs_prec, prior_prec_sqrt, v,
+                               rand_gen=self.rand_gen), {}
         guess = self.regcoef_summarizer.extrapolate_coef_condmean(
             gscale, lscale)
         sd = self.regcoef_summarizer.estimate_coef_precond_scale_sd()

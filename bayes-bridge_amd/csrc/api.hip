@@ -935,6 +935,125 @@ static int gram_matvec_device(bbx_design* h, const double* d_obs_prec,
   return launch_tdot(h, t, part_slot(h, PS_SUMW), ep, d_out);
 }
 
+// ---- cholesky sampler (cholesky.hip) ----------------------------------------
+int bbx_design_fisher_info_dev(bbx_design* h, const double* d_weight,
+                               int diag_only, double* d_out) {
+  BBX_TRY(check_handle(h));
+  if (!d_out) return fail(BBX_ERR_INVALID, "NULL output");
+  return no_throw([&]() -> int {
+    return fisher_info_device(h, d_weight, diag_only, d_out);
+  });
+}
+
+int bbx_design_fisher_info(bbx_design* h, const double* weight, int diag_only,
+                           double* out) {
+  BBX_TRY(check_handle(h));
+  if (!out) return fail(BBX_ERR_INVALID, "NULL output");
+  if (h->sparse)
+    return fail(BBX_ERR_INVALID,
+                "compute_fisher_info: dense designs only (this one is sparse)");
+  return no_throw([&]() -> int {
+    BBX_HIP(hipSetDevice(h->device));
+    double* d_w = nullptr;
+    if (weight) {
+      d_w = h->stage_n.as<double>();
+      BBX_HIP(hipMemcpyAsync(d_w, weight, sizeof(double) * (size_t)h->n,
+                             hipMemcpyHostToDevice, h->stream));
+    }
+    if (diag_only) {
+      double* d_o = h->stage_P.as<double>();
+      BBX_TRY(fisher_info_device(h, d_w, 1, d_o));
+      BBX_HIP(hipMemcpyAsync(out, d_o, sizeof(double) * (size_t)h->P,
+                             hipMemcpyDeviceToHost, h->stream));
+    } else {
+      // the full matrix stays in the handle's work matrix; copy out from there
+      BBX_TRY(fisher_info_device(h, d_w, 0, nullptr));
+    }
+    if (!diag_only) {
+      const int64_t ld = (h->P + 63) / 64 * 64;
+      BBX_HIP(hipMemcpy2DAsync(out, sizeof(double) * h->P, h->chol_A.ptr,
+                               sizeof(double) * ld, sizeof(double) * h->P,
+                               h->P, hipMemcpyDeviceToHost, h->stream));
+    }
+    BBX_HIP(hipStreamSynchronize(h->stream));
+    return BBX_OK;
+  });
+}
+
+int bbx_chol_sample_dev(bbx_design* h, const double* d_obs_prec,
+                        const double* d_prior_prec_sqrt, const double* d_z,
+                        const double* d_normals, double* d_coef_out) {
+  BBX_TRY(check_handle(h));
+  if (!d_obs_prec || !d_prior_prec_sqrt || !d_z || !d_normals || !d_coef_out)
+    return fail(BBX_ERR_INVALID, "NULL array argument");
+  return no_throw([&]() -> int {
+    return chol_sample_device(h, d_obs_prec, 1., nullptr, d_prior_prec_sqrt, d_z,
+                              d_normals, d_coef_out);
+  });
+}
+
+static int chol_sample_host(bbx_design* h, const double* obs_prec,
+                            double obs_prec_scalar,
+                            const double* prior_prec_sqrt, const double* z,
+                            const double* normals, double* coef_out) {
+  if (!prior_prec_sqrt || !z || !normals || !coef_out)
+    return fail(BBX_ERR_INVALID, "NULL array argument");
+  if (h->sparse)
+    return fail(BBX_ERR_INVALID,
+                "the cholesky sampler needs a dense design (this one is sparse)");
+  return no_throw([&]() -> int {
+    BBX_HIP(hipSetDevice(h->device));
+    const size_t Pb = sizeof(double) * (size_t)h->P;
+    double* st[4];
+    for (int k = 0; k < 4; ++k) {
+      st[k] = chol_stage(h, k);
+      if (!st[k]) return -1;
+    }
+    double* d_w = nullptr;
+    if (obs_prec) {
+      d_w = h->stage_n.as<double>();
+      BBX_HIP(hipMemcpyAsync(d_w, obs_prec, sizeof(double) * (size_t)h->n,
+                             hipMemcpyHostToDevice, h->stream));
+    }
+    BBX_HIP(hipMemcpyAsync(st[0], prior_prec_sqrt, Pb, hipMemcpyHostToDevice,
+                           h->stream));
+    BBX_HIP(hipMemcpyAsync(st[1], z, Pb, hipMemcpyHostToDevice, h->stream));
+    BBX_HIP(hipMemcpyAsync(st[2], normals, Pb, hipMemcpyHostToDevice,
+                           h->stream));
+    BBX_TRY(chol_sample_device(h, d_w, obs_prec_scalar, nullptr, st[0], st[1],
+                               st[2], st[3]));
+    BBX_HIP(hipMemcpyAsync(coef_out, st[3], Pb, hipMemcpyDeviceToHost,
+                           h->stream));
+    BBX_HIP(hipStreamSynchronize(h->stream));
+    return BBX_OK;
+  });
+}
+
+int bbx_chol_sample(bbx_design* h, const double* obs_prec,
+                    const double* prior_prec_sqrt, const double* z,
+                    const double* normals, double* coef_out) {
+  BBX_TRY(check_handle(h));
+  if (!obs_prec) return fail(BBX_ERR_INVALID, "NULL array argument");
+  return chol_sample_host(h, obs_prec, 1., prior_prec_sqrt, z, normals,
+                          coef_out);
+}
+
+int bbx_chol_release(bbx_design* h) {
+  BBX_TRY(check_handle(h));
+  BBX_HIP(hipSetDevice(h->device));
+  BBX_HIP(hipStreamSynchronize(h->stream));
+  chol_release(h);
+  return BBX_OK;
+}
+
+int bbx_chol_sample_scalar(bbx_design* h, double obs_prec,
+                           const double* prior_prec_sqrt, const double* z,
+                           const double* normals, double* coef_out) {
+  BBX_TRY(check_handle(h));
+  return chol_sample_host(h, nullptr, obs_prec, prior_prec_sqrt, z, normals,
+                          coef_out);
+}
+
 int bbx_design_gram_matvec_dev(bbx_design* h, const double* d_obs_prec,
                                const double* d_v, double* d_out) {
   BBX_TRY(check_handle(h));

@@ -693,6 +693,9 @@ int bbx_batch_create_opts(bbx_design* design, int n_chain,
     for (int e = 0; e < c; ++e)
       if (chains[e] == chains[c])
         return fail(BBX_ERR_INVALID, "a chain appears twice in the batch");
+    if (chains[c]->coef_sampler != BBX_SAMPLER_CG)
+      return fail(BBX_ERR_INVALID,
+                  "batched chains draw the coefficients with BBX_SAMPLER_CG only");
     if (chains[c]->n_unshrunk != chains[0]->n_unshrunk)
       return fail(BBX_ERR_INVALID,
                   "the chains of a batch must agree on n_unshrunk");

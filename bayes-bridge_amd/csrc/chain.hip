@@ -660,13 +660,16 @@ int chain_post_draw(bbx_chain* c, bool have_psi, int phases,
 
   if (phases & POST_BRANCH) {
   // --- running summaries of beta (with the tau and lambda it was drawn
-  // under), then tau | beta, then lambda | tau, beta, then log posterior
-  BBX_LAUNCH(chain_summary_kernel, dim3(NPART), dim3(256), 0, s_b, P,
-                     nu, c->slab, (long long)c->n_averaged, sc,
-                     c->lscale.as<double>(), c->coef.as<double>(),
-                     c->mean.as<double>(), c->square.as<double>(),
-                     fork ? branch_prio() : 0);
-  c->n_averaged += 1;
+  // under; the 'cholesky' draw keeps none, reg_coef_sampler.py:81-84), then
+  // tau | beta, then lambda | tau, beta, then log posterior
+  if (c->coef_sampler == BBX_SAMPLER_CG) {
+    BBX_LAUNCH(chain_summary_kernel, dim3(NPART), dim3(256), 0, s_b, P,
+                       nu, c->slab, (long long)c->n_averaged, sc,
+                       c->lscale.as<double>(), c->coef.as<double>(),
+                       c->mean.as<double>(), c->square.as<double>(),
+                       fork ? branch_prio() : 0);
+    c->n_averaged += 1;
+  }
   // the chain's own partial slots: the branches of a batch's chains run side by side
   double* pp = c->misc_part.as<double>();
   BBX_LAUNCH(chain_coef_sums_kernel, dim3(NPART), dim3(256), 0, s_b, P,
@@ -779,6 +782,29 @@ static int chain_step(bbx_chain* c, int maxiter, double atol, int* n_cg_iter) {
   int info = 0;
   // (the normals of this draw, if the previous iteration filled them ahead)
   const bool have_eta = c->eta_iter == (long long)it && c->eta1_next.ptr;
+  if (c->coef_sampler == BBX_SAMPLER_CHOLESKY) {
+    // the direct draw (cholesky.hip) with the P normals of the CG draw's eta2
+    // stream: bbx_chain_eta(it) returns them.  It synchronises: coef is final.
+    bbx_design* h = c->h;
+    if (!have_eta) {
+      if (!c->eta2_next.ptr)
+        BBX_TRY(c->eta2_next.alloc(sizeof(double) * (size_t)h->P));
+      BBX_TRY(launch_fill_normal(h, h->P, cg_draw_seed(c, it), STREAM_ETA2,
+                                 c->eta2_next.as<double>()));
+    }
+    const bool linear = c->model == BBX_MODEL_LINEAR;
+    const int st = chol_sample_device(
+        h, linear ? nullptr : c->obs_prec.as<double>(), 1.,
+        linear ? &c->scalars.as<ChainScalars>()->obs_prec : nullptr,
+        c->phi.as<double>(), c->z.as<double>(), c->eta2_next.as<double>(),
+        c->coef.as<double>());
+    c->eta_iter = -1;
+    if (st < 0) return st;
+    c->coef_sample = nullptr;   // not written by the draw: chain_save_sample copies
+    if (n_cg_iter) *n_cg_iter = 0;
+    BBX_TRY(chain_post_draw(c, false, POST_ALL));
+    return 0;
+  }
   struct TailScope {
     bbx_design* h;
     ~TailScope() {
@@ -1457,3 +1483,17 @@ int bbx_device_normal(int device, uint64_t seed, uint64_t stream,
 }
 
 }  // extern "C"
+
+int bbx_chain_set_coef_sampler(bbx_chain* c, int sampler) {
+  return no_throw([&]() -> int {
+    BBX_TRY(chain_check(c));
+    if (sampler != BBX_SAMPLER_CG && sampler != BBX_SAMPLER_CHOLESKY)
+      return fail(BBX_ERR_INVALID,
+                  "sampler must be BBX_SAMPLER_CG or BBX_SAMPLER_CHOLESKY");
+    if (sampler == BBX_SAMPLER_CHOLESKY && c->h->sparse)
+      return fail(BBX_ERR_INVALID,
+                  "the cholesky sampler needs a dense design (this one is sparse)");
+    c->coef_sampler = sampler;
+    return BBX_OK;
+  });
+}

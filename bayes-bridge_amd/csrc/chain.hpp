@@ -39,6 +39,7 @@ struct bbx_chain {
   int64_t n_averaged = 0;  // summariser count
   bool mean_zero = true;   // running mean still all zeros => CG warm start 0
   int gscale_update = BBX_GSCALE_SAMPLE;
+  int coef_sampler = BBX_SAMPLER_CG;   // bbx_chain_set_coef_sampler
   // bbx_chain_set_progress: called from the host loop of a run every
   // `progress_every` iterations (gibbs_util.py:214-238 prints from there)
   void (*progress)(int, void*) = nullptr;

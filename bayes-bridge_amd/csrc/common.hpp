@@ -227,6 +227,10 @@ struct bbx_design {
   int dense_fused_wgs = 0;
   int64_t dense_ld = 0;
   int dense_chunks = 1;
+  // cholesky sampler (cholesky.hip): A / its factor, the cached X~^T X~ of
+  // linear models, the Gram's row-chunk partials, P-vectors + pivot flag
+  bbx::DevMem chol_A, chol_gram, chol_slab, chol_vec;
+  bool chol_gram_ready = false;
 
   // --- LDS-tiled layout (BBX_FORMAT_TILED): see spmv_tiled.hip
   void* tiled = nullptr;           // bbx::TiledPair*
@@ -587,6 +591,16 @@ void timer_drop_skipped(bbx_design* h, int n_iter);
 // behind the finish kernel: work on ANOTHER stream that reads d_coef must wait
 // on that event (chain_post_draw does).  When maxiter was exhausted the solve
 // ends with hipStreamSynchronize.  n_iter_out / info_out are final on return.
+// cholesky.hip: the dense Fisher information and the direct draw
+int fisher_info_device(bbx_design* h, const double* d_w, int diag_only,
+                       double* d_out);
+int chol_sample_device(bbx_design* h, const double* d_obs_prec,
+                       double obs_prec_scalar, const double* d_obs_prec_scalar,
+                       const double* d_pps,
+                       const double* d_v, const double* d_normals,
+                       double* d_coef_out);
+double* chol_stage(bbx_design* h, int k);
+void chol_release(bbx_design* h);   // frees the sampler's P x P buffers
 int cg_sample_device(bbx_design* h, const double* d_omega, const double* d_phi,
                      const double* d_z, const double* d_x0,
                      const double* d_sd, int n_unshrunk, const double* d_eta1,

@@ -40,7 +40,7 @@ extern "C" {
  *      bbx_setup_lock_acquire/_release, bbx_design_useful_bytes.  A binding
  *      compares bbx_version() with the BBX_VERSION it was written against
  *      (bayesbridge_amd/_lib.py does) instead of calling with a stale arity. */
-#define BBX_VERSION 103 /* 0.1.3 */
+#define BBX_VERSION 104 /* 0.1.4 */
 
 /* status codes */
 #define BBX_OK 0
@@ -309,6 +309,54 @@ int bbx_design_gram_matvec(bbx_design* h, const double* obs_prec,
 int bbx_design_gram_matvec_dev(bbx_design* h, const double* d_obs_prec,
                                const double* d_v, double* d_out);
 
+/*
+ * Fisher information of a DENSE design (dense_matrix.py:54-58):
+ *   out = X~^T diag(weight) X~     (P x P, row-major, symmetric), or
+ *   out = diag of it                (P entries) when diag_only != 0,
+ * with weight[n] (NULL: ones).  X~ is the stored matrix: intercept column,
+ * centred, and for f32 storage the f32-rounded values (accumulated in f64).
+ * Bitwise reproducible.  A sparse design returns BBX_ERR_INVALID.
+ * Host pointers, synchronous; `_dev`: device pointers, asynchronous on the
+ * handle's stream (d_out is ready after bbx_design_synchronize()).
+ */
+int bbx_design_fisher_info(bbx_design* h, const double* weight, int diag_only,
+                           double* out);
+int bbx_design_fisher_info_dev(bbx_design* h, const double* d_weight,
+                               int diag_only, double* d_out);
+
+/*
+ * The direct ('cholesky') coefficient draw of direct_gaussian_sampler.py:4-44
+ * on a DENSE design:
+ *   F = X~^T diag(obs_prec) X~, d = prior_prec_sqrt^2 + diag(F), s = 1/sqrt(d),
+ *   A = diag(s) F diag(s) + diag((s prior_prec_sqrt)^2) = U^T U (U upper),
+ *   coef_out = s .* (A^-1 (s .* z) + U^-1 normals)
+ * with obs_prec[n], prior_prec_sqrt[P], z[P] (= X~^T (obs_prec .* y)) and
+ * normals[P] (the reference's np.random.randn(P)).
+ * bbx_chol_sample_scalar: obs_prec is one number (linear models); F is then
+ * obs_prec * (X~^T X~) with X~^T X~ computed once per design and cached, which
+ * rounds differently from forming X~^T (obs_prec X~).
+ * Returns BBX_ERR_NUMERIC, with the first non-positive pivot in
+ * bbx_last_error(), when A is not numerically positive definite (coef_out is
+ * then unspecified; the design stays usable); BBX_ERR_INVALID on a sparse
+ * design or a NULL array.  All forms synchronise the handle's stream before
+ * they return: coef_out / d_coef_out is complete on return.
+ */
+int bbx_chol_sample(bbx_design* h, const double* obs_prec,
+                    const double* prior_prec_sqrt, const double* z,
+                    const double* normals, double* coef_out);
+int bbx_chol_sample_dev(bbx_design* h, const double* d_obs_prec,
+                        const double* d_prior_prec_sqrt, const double* d_z,
+                        const double* d_normals, double* d_coef_out);
+int bbx_chol_sample_scalar(bbx_design* h, double obs_prec,
+                           const double* prior_prec_sqrt, const double* z,
+                           const double* normals, double* coef_out);
+/* The sampler keeps its work memory on the design after a call: a P x P f64
+ * matrix (A and its factor, Pp = P rounded up to 64: 8 Pp^2 bytes, 2.9 GB at
+ * 19 200 columns), a second one once bbx_chol_sample_scalar has cached
+ * X~^T X~, and up to 256 MB of Gram partials.  bbx_chol_release frees all of
+ * it (the next call allocates it again); bbx_design_destroy does too. */
+int bbx_chol_release(bbx_design* h);
+
 /* The hipStream_t (as void*) every kernel of this handle is launched on, and a
  * blocking wait on it. */
 int bbx_design_stream(bbx_design* h, void** stream);
@@ -457,6 +505,14 @@ int bbx_chain_set_seed(bbx_chain* c, uint64_t seed);
 /* How tau is updated each iteration: BBX_GSCALE_SAMPLE (default),
  * BBX_GSCALE_OPTIMIZE or BBX_GSCALE_FIXED (bayesbridge.py:412-448 `method`). */
 int bbx_chain_set_gscale_update(bbx_chain* c, int mode);
+/* How the chain draws beta | rest: BBX_SAMPLER_CG (default) or, on DENSE
+ * designs only (else BBX_ERR_INVALID), BBX_SAMPLER_CHOLESKY -- the direct draw
+ * of bbx_chol_sample with the P normals of the CG draw's eta2 stream
+ * (bbx_chain_eta), no running summary (its state is left as it is), n_cg_iter
+ * 0 and no unconverged solves.  bbx_batch_create refuses such chains. */
+#define BBX_SAMPLER_CG 0
+#define BBX_SAMPLER_CHOLESKY 1
+int bbx_chain_set_coef_sampler(bbx_chain* c, int sampler);
 /*
  * Regenerates, on the device, the standard normals the chain's CG draw
  * consumes at 0-based iteration `iteration` (cg_sampler.py:61-62: eta1[n] for

@@ -1,0 +1,58 @@
+"""CPU (hipcc cross-compile): no kernel of the cholesky sampler (cholesky.hip:
+weighted Gram on the f64 matrix cores, blocked factorisation, triangular
+solves) uses scratch or spills registers -- the Gram keeps 16 f64 MFMA
+accumulators per wave, a spill there would stream them through scratch."""
+import os
+import re
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+# every __global__ of cholesky.hip (templates: one per storage type)
+KERNELS = ("gram_tiles_kernel", "gram_reduce_kernel", "gram_diag_kernel",
+           "gram_diag_reduce_kernel", "chol_scale_kernel",
+           "chol_assemble_kernel", "chol_info_reset_kernel",
+           "chol_diag_kernel", "chol_panel_kernel", "chol_syrk_kernel",
+           "trsv_fwd_kernel", "chol_add_kernel", "trsv_bwd_kernel",
+           "chol_finish_kernel")
+
+
+def _resource_table(src, tmp_path):
+    out = subprocess.run(
+        [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950",
+         "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",
+         str(tmp_path / "t.o")],
+        capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    # "remark: Function Name: <mangled>" then one "remark:     <key>: <value>"
+    # line per resource
+    current, table = None, {}
+    for line in out.stderr.splitlines():
+        m = re.search(r"remark:\s+Function Name: (\S+)", line)
+        if m:
+            current = m.group(1)
+            table[current] = {}
+            continue
+        m = re.search(r"remark:\s+([A-Za-z][A-Za-z ]*?(?: \[[^\]]*\])?): (\d+)", line)
+        if m and current:
+            table[current][m.group(1)] = int(m.group(2))
+    return table
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_cholesky_kernels_do_not_spill(tmp_path):
+    table = _resource_table(
+        os.path.join(ROOT, "bayes-bridge_amd", "csrc", "cholesky.hip"),
+        tmp_path)
+    for k in KERNELS:
+        assert any(k in name for name in table), (k, sorted(table))
+    assert sum("gram_tiles_kernel" in k for k in table) == 2
+    assert sum("gram_diag_kernelI" in k for k in table) == 2
+    for name, res in table.items():
+        assert res["VGPRs Spill"] == 0, (name, res)
+        assert res["SGPRs Spill"] == 0, (name, res)
+        assert res["ScratchSize [bytes/lane]"] == 0, (name, res)
