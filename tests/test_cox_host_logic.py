@@ -9,6 +9,7 @@ import warnings
 import numpy as np
 import pytest
 
+import cox_cases as cc
 import cox_oracle as co
 from conftest import ROOT
 from test_cholesky_kernel_resources import HIPCC, _resource_table
@@ -128,6 +129,122 @@ def test_unsorted_rows_are_refused_by_the_risk_sets():
     from bayesbridge_amd.model import cox_sort_permutation
     with pytest.raises(ValueError):
         cox_sort_permutation(np.array([1., np.inf]), np.array([np.inf, np.inf]))
+
+
+# (ne, n_cens) at the scans' partition edges: one chunk element, ragged and
+# empty trailing chunks (255, 257, 2047, 2049 = 256 * 8 + 1), exact chunks
+BUILDER_SIZES = [(1, 0), (2, 1), (3, 0), (1, 2), (255, 2), (256, 1),
+                 (257, 256), (2047, 0), (2048, 2049), (2049, 2047)]
+
+
+def _builder_case(ne, n_cens, values='normal'):
+    b = cc.event_boundaries(ne)
+    hot = [b[len(b) // 2] if len(b) else 0] + ([ne] if n_cens else [])
+    return cc.cox_case(ne, n_cens, values=values, hot=hot)
+
+
+@pytest.mark.parametrize('ne,n_cens', BUILDER_SIZES)
+def test_case_builder_risk_sets_equal_the_loops(ne, n_cens):
+    from bayesbridge_amd.model import cox_risk_sets, cox_sort_permutation
+    case = _builder_case(ne, n_cens)
+    et, ct = case.event_time, case.censoring_time
+    assert cox_sort_permutation(et, ct) is None
+    assert not np.any(ct < np.min(et))        # nothing for preprocess to drop
+    got = cox_risk_sets(et, ct)
+    want = co.risk_sets_by_loops(et, ct)
+    assert got[0] == want[0] == ne
+    for a, b in zip(got[1:], want[1:]):
+        np.testing.assert_array_equal(a, b)
+
+
+@pytest.mark.parametrize('ne,n_cens', BUILDER_SIZES + [(524289, 1)])
+def test_case_builder_places_ties_and_hot_rows(ne, n_cens):
+    from bayesbridge_amd.model import cox_risk_sets
+    case = _builder_case(ne, n_cens)
+    et = case.event_time[:ne]
+    # the chunk and tile boundaries of the event scans, forward and reversed
+    L = cc.chunk_len(ne)
+    bounds = cc.event_boundaries(ne)
+    assert set(bounds) == {t for t in range(1, ne) if t % L == 0
+                           or (t % L) % cc.SCAN_TILE == 0
+                           or (ne - t) % L == 0
+                           or ((ne - t) % L) % cc.SCAN_TILE == 0}
+    runs = cc.tie_runs(ne)
+    if L > 8:                                  # every boundary inside a run
+        assert np.all(et[bounds - 1] == et[bounds])
+    for a, b in runs:
+        assert a < b and np.all(et[a:b] == et[a])
+    if ne >= 255:
+        assert len(np.unique(et)) > ne // 5    # runs, not one big tie
+    _, start, end, _ = cox_risk_sets(case.event_time, case.censoring_time)
+    if n_cens:
+        ct = case.censoring_time[ne:]
+        assert ct[0] == et[-1]
+        assert np.any(np.isin(ct, et))         # a censored time tied
+        if n_cens > 100:
+            assert np.any(~np.isin(ct, et))
+        if np.any(et < et[-1]) and n_cens > 1:
+            assert np.any(end == ne)
+    eta = case.X @ case.beta
+    np.testing.assert_allclose(eta[case.hot], eta.max(), rtol=1e-12)
+    rest = np.setdiff1d(np.arange(ne + n_cens), case.hot)
+    if len(rest):
+        assert eta[rest].max() < eta.max() - .5
+    assert case.hot[0] in bounds or ne == 1
+    # sparse hot rows: the columns with beta > 0
+    sp = _builder_case(ne, n_cens, 'binary') if ne < 10000 else None
+    if sp is not None:
+        e2 = sp.X @ sp.beta
+        assert np.all(e2[sp.hot] == np.sum(np.maximum(sp.beta, 0)))
+        assert np.all(e2 <= e2[sp.hot[0]])
+
+
+def test_steep_case_spans_1e30_across_tiles():
+    case = cc.steep_case(1048577, 1)
+    from bayesbridge_amd.model import cox_risk_sets
+    risk = cox_risk_sets(case.event_time, case.censoring_time)
+    eta = case.X @ case.beta
+    inv_H = 1. / co.risk_sums(np.exp(eta - eta.max()), *risk[:3])
+    L = cc.chunk_len(risk[0])
+    assert L > cc.SCAN_TILE
+    assert inv_H.max() / inv_H.min() > 1e30
+    # somewhere, 8 consecutive events see 1/H grow by more than 2^53
+    assert np.max(inv_H[8:] / inv_H[:-8]) > 2. ** 53 * 1e3
+
+
+@pytest.mark.parametrize('ne,n_cens', BUILDER_SIZES)
+@pytest.mark.parametrize('values', ['normal', 'binary', 'valued'])
+def test_extended_reference_bounds_the_float64_oracle(ne, n_cens, values):
+    """The float64 oracle (sequential cumsums) lies within EDGE_TOL times the
+    componentwise bound of the extended-precision reference; the two faults
+    the GPU tests must see -- a hot row at a scan boundary dropped from its
+    risk sets, end_k > ne for end_k >= ne -- lie 100 x EDGE_TOL beyond it."""
+    from bayesbridge_amd.model import cox_risk_sets
+    case = _builder_case(ne, n_cens, values)
+    risk = cox_risk_sets(case.event_time, case.censoring_time)
+    X = case.X.toarray() if values != 'normal' else case.X
+    rs = np.random.RandomState(1)
+    for scale in (.1, 1., 3.):
+        beta = case.beta * scale
+        v = rs.randn(len(beta))
+        ll, grad = co.loglik_grad(X, beta, *risk)
+        el, eg, lb, gb = co.loglik_grad_ext(case.X, beta, *risk)
+        assert abs(ll - el) <= co.EDGE_TOL * lb
+        assert np.all(np.abs(grad - eg) <= co.EDGE_TOL * gb)
+        hv = co.hessian_matvec(X, beta, v, *risk)
+        eh, hb = co.hessian_matvec_ext(case.X, beta, v, *risk)
+        assert np.all(np.abs(hv - eh) <= co.EDGE_TOL * hb)
+        if ne == 1 and n_cens == 0:
+            continue            # grad == 0 exactly: nothing to perturb
+        far = co.distance_in_tolerances(
+            co.loglik_grad_ext(case.X, beta, *risk, drop=case.hot[0]),
+            (el, eg, lb, gb))
+        assert far > 100.
+        if np.any(risk[2] == ne):
+            far = co.distance_in_tolerances(
+                co.loglik_grad_ext(case.X, beta, *risk, strict_end=True),
+                (el, eg, lb, gb))
+            assert far > 100.
 
 
 class _Design:
