@@ -14,6 +14,11 @@ gathered on rank 0 over RCCL once, inside the timed region.
 ranks itself (`python -m torch.distributed.run ... bench.py ...` as a child
 process, before this process touches torch or HIP) and relays rank 0's line.
 
+A plain run does only what the headline needs: set-up, burn-in, the W warm-up
+and K timed steps, --dump-outputs, the line.  `--full` adds what is measured
+beside it, after the timed region: the `repeat` blocks, `multi_chain`, the
+CPU baselines, the live roofline traffic and the stream probes.
+
 Prints ONE JSON line (see DESIGN.md "Measurement" for every field).
 """
 import argparse
@@ -64,18 +69,29 @@ def parse_args(argv=None):
     ap.add_argument("--config", default="config3", choices=sorted(CONFIGS))
     ap.add_argument("--storage", default="auto",
                     choices=["auto", "csr", "tiled"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not "
+                         "need, after the timed region: the `repeat` blocks, "
+                         "`multi_chain`, the CPU baselines, the live "
+                         "`roofline.traffic` passes and the stream probes "
+                         "(`stream_probe_gbs`, `cache_bound`).  Without it "
+                         "the run sets up, warms up, times the K steps, "
+                         "writes --dump-outputs and prints the line.  "
+                         "--repeat, --multi-chain, --cpu-baseline-iters and "
+                         "--live-traffic, when given, set their own extra in "
+                         "either mode")
     ap.add_argument("--cpu-baseline-iters", type=int, default=None,
                     help="Gibbs iterations of each CPU baseline (0 = skip; "
-                         "default 5, 2 for the dense configs: one config-4 "
-                         "iteration is ~110 operator applications of two "
-                         "12.8 GB dgemv each)")
+                         "default 0, with --full 5, 2 for the dense configs: "
+                         "one config-4 iteration is ~110 operator "
+                         "applications of two 12.8 GB dgemv each)")
     ap.add_argument("--seed", type=int, default=111)
-    ap.add_argument("--live-traffic", type=int, default=1, choices=[0, 1],
+    ap.add_argument("--live-traffic", type=int, default=None, choices=[0, 1],
                     help="rank 0 at N = 1, sparse configs 2 / 3: measure "
                          "`roofline.traffic` in this run by two rocprofv3 --pmc "
                          "child passes over the product kernels (adds ~40 s "
                          "after the timed region); 0: the committed profile's "
-                         "figure")
+                         "figure.  Default: 1 with --full, else 0")
     ap.add_argument("--dense-storage", default="float32",
                     choices=["float32", "float64"],
                     help="config4 only: storage type of the dense matrix "
@@ -84,8 +100,9 @@ def parse_args(argv=None):
     ap.add_argument("--multi-chain", default=None,
                     help="comma-separated batch widths for the `multi_chain` "
                          "object (k chains on ONE GPU sharing every pass over "
-                         "X; rank 0 at N = 1 only; '0' = skip).  Default: 2,4 "
-                         "for the sparse configs, 4,8,16,32 for config4")
+                         "X; rank 0 at N = 1 only; '0' = skip).  Default: "
+                         "skip; with --full 2,4 for the sparse configs, "
+                         "4,8,16,32 for the dense ones")
     ap.add_argument("--multi-chain-steps", type=int, default=20)
     ap.add_argument("--cg-fold", type=int, default=None, choices=[0, 1],
                     help="A/B: force the 3-launch CG iteration (direction step "
@@ -105,10 +122,11 @@ def parse_args(argv=None):
                          "holds ~24 stamped launches per kernel, between one "
                          "in 8 and one in 64 (a stamped launch costs ~8 us: "
                          "LABNOTES R5.11)")
-    ap.add_argument("--repeat", type=int, default=5,
+    ap.add_argument("--repeat", type=int, default=None,
                     help="how many times the K-step block is run in all for "
                          "the `repeat` object (the first is the timed region "
-                         "behind `value`; 1 = no extra blocks)")
+                         "behind `value`; 1 = no extra blocks).  Default: 5 "
+                         "with --full, else 1")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the timed region's last Gibbs iteration "
                          "computed as DIR/<name>.npy (float64): coef (the kept "
@@ -118,6 +136,22 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.dump_outputs is not None and args.steps < 1:
         ap.error("--dump-outputs needs --steps >= 1")
+    return args
+
+
+def resolve_extras(args, dense):
+    """The defaults of the measurements beside the headline: on with --full,
+    off without it; an option given on the command line wins either way."""
+    if args.repeat is None:
+        args.repeat = 5 if args.full else 1
+    if args.live_traffic is None:
+        args.live_traffic = int(args.full)
+    if args.cpu_baseline_iters is None:
+        args.cpu_baseline_iters = (2 if dense else 5) if args.full else 0
+    widths = args.multi_chain
+    if widths is None:
+        widths = ("4,8,16,32" if dense else "2,4") if args.full else "0"
+    args.multi_chain = [int(v) for v in widths.split(",") if int(v) > 1]
     return args
 
 
@@ -604,8 +638,7 @@ def main():
         assert len(set(ids)) == world, ids
 
     dense = CONFIGS[args.config][2] is None
-    if args.cpu_baseline_iters is None:
-        args.cpu_baseline_iters = 2 if dense else 5
+    resolve_extras(args, dense)
     solo = rank == 0 and world == 1 and env_world is None
     x_host = None
     unit = math.gamma(2 / ALPHA) / math.gamma(1 / ALPHA)   # prior.py:163-167
@@ -676,9 +709,6 @@ def main():
     # right up to t0: a gap here lets the clocks fall and block 0 paid for the
     # ramp (LABNOTES R5.1).
     widths = args.multi_chain
-    if widths is None:
-        widths = "4,8,16,32" if dense else "2,4"
-    widths = [int(v) for v in widths.split(",") if int(v) > 1]
     want_state = solo and (args.cpu_baseline_iters > 0 or bool(widths))
     d_buf = torch.empty((max(K, W, 1), P), dtype=torch.float64, device=device)
     d_coef = d_buf[:max(K, 1)]          # (the warm-up may keep more samples)
@@ -879,16 +909,24 @@ def main():
             mean_ncg, op_bytes, dot_wb, tdot_wb, n, P, bool(dense and fused_b),
             vec_passes=17 if (cg_launches == 3 and not dense) else 15)
         iter_gbs = iter_bytes / ms_step / 1e6
-        # measured on this box, same size as one launch's algorithmic bytes
-        # and at 2 GB: what a plain streaming kernel reaches
-        probe_small = _lib.hbm_probe(int(per[dom]["bytes"]), 50, dev_index)
-        probe_large = _lib.hbm_probe(2 << 30, 10, dev_index)
+        # (--full) measured on this box, same size as one launch's algorithmic
+        # bytes and at 2 GB: what a plain streaming kernel reaches
+        stream_probe = None
+        if args.full:
+            probe_small = _lib.hbm_probe(int(per[dom]["bytes"]), 50, dev_index)
+            probe_large = _lib.hbm_probe(2 << 30, 10, dev_index)
+            stream_probe = {
+                "read_same_bytes": round(probe_small[0], 1),
+                "copy_same_bytes": round(probe_small[1], 1),
+                "read_2GiB": round(probe_large[0], 1),
+                "copy_2GiB": round(probe_large[1], 1)}
         # Workloads whose two orientations fit the 256 MiB Infinity Cache next
         # to each other are re-read from the die, launch after launch: the HBM
         # peak is not their ceiling.  The same-size read probe above re-reads
         # its buffer 50 times, i.e. measures exactly that on-die rate.
         cache_bound = None
-        if not dense and (dot_wb + tdot_wb) <= (256 << 20):
+        if stream_probe is not None and not dense \
+                and (dot_wb + tdot_wb) <= (256 << 20):
             cache_bound = dict(
                 resident_bytes=int(dot_wb + tdot_wb),
                 ceiling="plain read stream of the launch's bytes, re-read "
@@ -929,11 +967,7 @@ def main():
                            what="algorithmic bytes of one whole Gibbs "
                                 "iteration / ms_per_step"),
             cache_bound=cache_bound,
-            stream_probe_gbs={
-                "read_same_bytes": round(probe_small[0], 1),
-                "copy_same_bytes": round(probe_small[1], 1),
-                "read_2GiB": round(probe_large[0], 1),
-                "copy_2GiB": round(probe_large[1], 1)},
+            stream_probe_gbs=stream_probe,
             other={k: dict(avg_ms=round(v["avg_ms"], 5),
                            gbs=round(v["gbs"], 1), launches=v["launches"],
                            bytes=v["bytes"])
@@ -951,6 +985,8 @@ def main():
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
+            # --full: the extras beside the headline were on by default
+            "full": args.full,
             "config": {
                 "workload": (
                     "%s: linear, dense N(0,1) %dx%d stored %s (torch Philox "

@@ -5,14 +5,14 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out
 # plain bench lines
-python3 bench.py > $O/r03_bench.json 2> $O/r03_bench.err
-python3 bench.py --steps 20 --warmup 5 > $O/r03_bench_driverflags.json 2>> $O/r03_bench.err
-python3 bench.py --config config2 > $O/r03_bench_config2.json 2>> $O/r03_bench.err
-python3 bench.py --config config4 --steps 10 --warmup 3 --multi-chain-steps 6 > $O/r03_bench_config4.json 2>> $O/r03_bench.err
-python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 1 --steps 20 --warmup 5 --cpu-baseline-iters 0 > $O/r03_bench_1rank_rccl.json 2>> $O/r03_bench.err
+python3 bench.py --full > $O/r03_bench.json 2> $O/r03_bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/r03_bench_driverflags.json 2>> $O/r03_bench.err
+python3 bench.py --full --config config2 > $O/r03_bench_config2.json 2>> $O/r03_bench.err
+python3 bench.py --full --config config4 --steps 10 --warmup 3 --multi-chain-steps 6 > $O/r03_bench_config4.json 2>> $O/r03_bench.err
+python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29655 bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-baseline-iters 0 > $O/r03_bench_1rank_rccl.json 2>> $O/r03_bench.err
 # kernel traces of the same commands
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/r03_trace -- python3 bench.py --cpu-baseline-iters 0 > $O/r03_bench_under_rocprof.json 2> $O/r03_trace.log
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/r03_dense_trace -- python3 bench.py --config config4 --steps 10 --warmup 3 --multi-chain-steps 6 --cpu-baseline-iters 0 > $O/r03_dense_bench_under_rocprof.json 2> $O/r03_dense_trace.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/r03_trace -- python3 bench.py --full --cpu-baseline-iters 0 > $O/r03_bench_under_rocprof.json 2> $O/r03_trace.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/r03_dense_trace -- python3 bench.py --full --config config4 --steps 10 --warmup 3 --multi-chain-steps 6 --cpu-baseline-iters 0 > $O/r03_dense_bench_under_rocprof.json 2> $O/r03_dense_trace.log
 # HBM traffic of the dominant kernel (PMC, separate passes)
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/r03_fetch -- python3 scripts/bench_spmv.py config3 tiled 10 > $O/r03_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/r03_write -- python3 scripts/bench_spmv.py config3 tiled 10 > $O/r03_write.log 2>&1
@@ -20,7 +20,7 @@ rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/r03_write -- python3 script
 { python3 scripts/bench_spmv.py config3 tiled 200; python3 scripts/bench_spmv.py config2 tiled 200; } 2>&1 | grep -E "tiled geometry|avg|max abs err" > $O/r03_spmv.txt
 { for k in 2 4; do python3 scripts/bench_batch_products.py config3 $k 20; done; } 2>&1 | grep avg > $O/r03_batch_products.txt
 { for k in 4 8 16 32; do python3 scripts/bench_dense_batch.py 200000 8000 $k 5; done; } 2>&1 | grep avg > $O/r03_dense_batch_new.txt   # prepended to profiles/r03_dense_batch.txt by hand (its history stays)
-python3 bench.py --config config4 --dense-storage float64 --steps 10 --warmup 3 --multi-chain-steps 6 --cpu-baseline-iters 0 > $O/r03_bench_config4_f64.json 2>> $O/r03_bench.err
+python3 bench.py --full --config config4 --dense-storage float64 --steps 10 --warmup 3 --multi-chain-steps 6 --cpu-baseline-iters 0 > $O/r03_bench_config4_f64.json 2>> $O/r03_bench.err
 python3 scripts/bench_small_batches.py 2>&1 | grep -E "^dense|^sparse" > $O/r03_small_batches.txt
 BENCH_MIXED_PAIR=1 python3 scripts/bench_mixed.py 5 50 2>&1 | grep -E "pair products" > $O/r03_mixed_pair.txt
 bash scripts/dense_batch_traffic.sh > /dev/null 2>&1

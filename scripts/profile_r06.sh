@@ -8,16 +8,16 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out
 mkdir -p $O/r06p
 # ---- plain bench lines
-python3 bench.py > $O/r06_bench.json 2> $O/r06_bench.err
-python3 bench.py --steps 20 --warmup 5 > $O/r06_bench_driverflags.json 2>> $O/r06_bench.err
-python3 bench.py --config config2 > $O/r06_bench_config2.json 2>> $O/r06_bench.err
-python3 bench.py --config config4 --steps 10 --warmup 3 --multi-chain-steps 6 > $O/r06_bench_config4.json 2>> $O/r06_bench.err
-python3 bench.py --config config4 --dense-storage float64 --steps 10 --warmup 3 --multi-chain-steps 6 > $O/r06_bench_config4_f64.json 2>> $O/r06_bench.err
-python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 1 --steps 20 --warmup 5 --cpu-baseline-iters 0 > $O/r06_bench_1rank_rccl.json 2>> $O/r06_bench.err
+python3 bench.py --full > $O/r06_bench.json 2> $O/r06_bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/r06_bench_driverflags.json 2>> $O/r06_bench.err
+python3 bench.py --full --config config2 > $O/r06_bench_config2.json 2>> $O/r06_bench.err
+python3 bench.py --full --config config4 --steps 10 --warmup 3 --multi-chain-steps 6 > $O/r06_bench_config4.json 2>> $O/r06_bench.err
+python3 bench.py --full --config config4 --dense-storage float64 --steps 10 --warmup 3 --multi-chain-steps 6 > $O/r06_bench_config4_f64.json 2>> $O/r06_bench.err
+python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29655 bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-baseline-iters 0 > $O/r06_bench_1rank_rccl.json 2>> $O/r06_bench.err
 # ---- kernel traces of the bench commands (per-launch durations)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/r06_trace -- python3 bench.py --cpu-baseline-iters 0 > $O/r06_bench_under_rocprof.json 2> $O/r06_trace.log
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/r06_dense_trace -- python3 bench.py --config config4 --steps 10 --warmup 3 --multi-chain 0 --cpu-baseline-iters 0 > $O/r06_dense_bench_under_rocprof.json 2> $O/r06_dense_trace.log
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/r06_dense64_trace -- python3 bench.py --config config4 --dense-storage float64 --steps 10 --warmup 3 --multi-chain 0 --cpu-baseline-iters 0 > $O/r06_dense64_bench_under_rocprof.json 2> $O/r06_dense64_trace.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/r06_trace -- python3 bench.py --full --cpu-baseline-iters 0 > $O/r06_bench_under_rocprof.json 2> $O/r06_trace.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/r06_dense_trace -- python3 bench.py --full --config config4 --steps 10 --warmup 3 --multi-chain 0 --cpu-baseline-iters 0 > $O/r06_dense_bench_under_rocprof.json 2> $O/r06_dense_trace.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/r06_dense64_trace -- python3 bench.py --full --config config4 --dense-storage float64 --steps 10 --warmup 3 --multi-chain 0 --cpu-baseline-iters 0 > $O/r06_dense64_bench_under_rocprof.json 2> $O/r06_dense64_trace.log
 # ---- HBM traffic (PMC, separate passes): the CG loop's kernels inside a chain
 # (direction kernel, X~ v, X~^T w, the epilogue kernel), the K = 2
 # products, the single-pass dense operator in f32 and f64 storage

@@ -7,7 +7,7 @@ mkdir -p $out
 for cfg in config3 config2 config4; do
   for tb in first all none; do
     for rep in 1 2; do
-      python bench.py --config $cfg --timing-blocks $tb --cpu-baseline-iters 0 \
+      python bench.py --full --config $cfg --timing-blocks $tb --cpu-baseline-iters 0 \
         --multi-chain 0 > $out/b0_${cfg}_${tb}_$rep.json 2> $out/b0_${cfg}_${tb}_$rep.err
     done
   done

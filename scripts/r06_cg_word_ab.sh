@@ -12,10 +12,10 @@ print("value %.1f it/s; blocks %s; us/cg-iter %s; n_cg %s; host %s" % (d["value"
 for cfg in config3 config2; do
   for rep in 1 2; do
     echo "== $cfg base (round-5 look: memcpy + event), run $rep"
-    BBX_PACKAGE_DIR=$PWD/ab_base/bayes-bridge_amd python3 bench.py --config $cfg --cpu-baseline-iters 0 --multi-chain 0 2>/dev/null | python3 -c "$pick"
+    BBX_PACKAGE_DIR=$PWD/ab_base/bayes-bridge_amd python3 bench.py --full --config $cfg --cpu-baseline-iters 0 --multi-chain 0 2>/dev/null | python3 -c "$pick"
     for a in 1 2 3; do
       echo "== $cfg progress word, BBX_CG_AHEAD=$a, run $rep"
-      BBX_CG_AHEAD=$a python3 bench.py --config $cfg --cpu-baseline-iters 0 --multi-chain 0 2>/dev/null | python3 -c "$pick"
+      BBX_CG_AHEAD=$a python3 bench.py --full --config $cfg --cpu-baseline-iters 0 --multi-chain 0 2>/dev/null | python3 -c "$pick"
     done
   done
 done

@@ -6,7 +6,7 @@ pick='import json,sys
 d=json.loads(sys.stdin.readline())
 r=d["repeat"]; ro=d["roofline"]["other"]
 print("value %.1f it/s; us/cg-iter %s; grids %s; dot %.2f us tdot %.2f us" % (d["value"], r["us_per_cg_iter"], d["config"]["launch_grids"], 1e3*ro["dot"]["avg_ms"], 1e3*ro["tdot"]["avg_ms"]))'
-run() { echo "== $1"; env $1 python3 bench.py --config config2 --cpu-baseline-iters 0 --multi-chain 0 2>/dev/null | python3 -c "$pick"; }
+run() { echo "== $1"; env $1 python3 bench.py --full --config config2 --cpu-baseline-iters 0 --multi-chain 0 2>/dev/null | python3 -c "$pick"; }
 for rep in 1 2; do
 run "BBX_NOP=1"
 run "BBX_TILED_PR=392"

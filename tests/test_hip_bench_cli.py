@@ -1,7 +1,8 @@
 """GPU: bench.py's contract end to end on a small configuration -- one JSON
-line with the roofline / cpu_baseline objects, and `--gpus 2` launching two
-ranks by itself (on a 1-GPU box they share the device and gather over gloo;
-on an 8-GPU node the same path runs one rank per GPU over RCCL)."""
+line, with the roofline / cpu_baseline objects under --full, and `--gpus 2`
+launching two ranks by itself (on a 1-GPU box they share the device and
+gather over gloo; on an 8-GPU node the same path runs one rank per GPU over
+RCCL)."""
 import json
 import os
 import subprocess
@@ -28,7 +29,7 @@ def _bench(*flags, timeout=900):
 
 def test_single_gpu_line_has_roofline_and_both_cpu_baselines():
     line = _bench("--config", "tiny", "--steps", "6", "--warmup", "2",
-                  "--burnin", "4", "--cpu-baseline-iters", "5")
+                  "--burnin", "4", "--cpu-baseline-iters", "5", "--full")
     assert line["n_gpus"] == 1 and line["steps"] == 6 and line["warmup"] == 2
     assert line["unit"] == "Gibbs iters/sec" and line["value"] > 0
     assert abs(line["value"] - 1e3 / line["ms_per_step"]) < 1e-2 * line["value"]
@@ -63,7 +64,7 @@ def test_roofline_traffic_is_measured_in_the_run():
     the Infinity Cache)."""
     line = _bench("--config", "config2", "--steps", "20", "--warmup", "5",
                   "--burnin", "30", "--cpu-baseline-iters", "0",
-                  "--multi-chain", "0", "--repeat", "1")
+                  "--multi-chain", "0", "--repeat", "1", "--full")
     r = line["roofline"]
     assert r["traffic_source"].startswith("measured in this run"), \
         r["traffic_source"]
@@ -79,7 +80,7 @@ def test_dense_line_has_a_cpu_baseline():
     (NumPy dgemv products + SciPy cg, BLAS threads stated), like the sparse
     line carries the SciPy CSR one."""
     line = _bench("--config", "tiny-dense", "--steps", "6", "--warmup", "2",
-                  "--burnin", "4", "--multi-chain", "4")
+                  "--burnin", "4", "--multi-chain", "4", "--full")
     assert line["value"] > 0 and line["roofline"]["bound"] == "hbm"
     assert "dense" in line["config"]["workload"]
     b = line["cpu_baseline"]
@@ -118,6 +119,42 @@ def test_dump_outputs_are_the_last_timed_step_and_repeat_run_to_run(tmp_path):
         assert np.array_equal(v, b[k]), k
     assert sum(v.nbytes for v in a.values()) <= 64 << 20
     assert not np.array_equal(a["coef"], c["coef"])
+
+
+def test_plain_run_leaves_the_extras_to_full(tmp_path):
+    """Without --full the line carries the headline and what the timed region
+    itself measured: one block, no multi_chain, no CPU baseline, no stream
+    probes.  --full adds them after the timed region, which both runs share
+    bit for bit: same n_cg per timed step, same dumped outputs."""
+    import numpy as np
+    flags = ("--config", "tiny", "--steps", "5", "--warmup", "2",
+             "--burnin", "4")
+    plain = _bench(*flags, "--dump-outputs", str(tmp_path / "plain"))
+    full = _bench(*flags, "--full", "--dump-outputs", str(tmp_path / "full"))
+    assert plain["full"] is False and full["full"] is True
+    for line in (plain, full):
+        assert line["metric"] == "Gibbs iters/sec (cg sampler)"
+        assert line["unit"] == "Gibbs iters/sec" and line["dtype"] == "f64"
+        assert line["higher_is_better"] is True and line["steps"] == 5
+        assert abs(line["value"] - 1e3 / line["ms_per_step"]) \
+            < 1e-2 * line["value"]
+        assert line["roofline"]["operator"]["launches"] > 0
+    assert len(plain["repeat"]["values"]) == 1
+    assert "multi_chain" not in plain and plain["cpu_baseline"] is None
+    assert "cpu_baseline_omp" not in plain
+    assert plain["roofline"]["stream_probe_gbs"] is None
+    assert len(full["repeat"]["values"]) == 5
+    assert full["multi_chain"]["k=2"]["chain_iters_per_sec"] > 0
+    assert full["cpu_baseline"]["kind"] == "port"
+    assert full["cpu_baseline_omp"]["kind"] == "port-omp"
+    assert full["roofline"]["stream_probe_gbs"]["read_2GiB"] > 0
+    assert plain["config"]["n_cg_iter_timed"] == \
+        full["config"]["n_cg_iter_timed"]
+    got = {tag: {f.stem: np.load(f) for f in (tmp_path / tag).glob("*.npy")}
+           for tag in ("plain", "full")}
+    assert got["plain"].keys() == got["full"].keys() and got["plain"]
+    for k, v in got["plain"].items():
+        assert np.array_equal(v, got["full"][k]), k
 
 
 def test_gpus_2_launches_two_ranks_by_itself():
