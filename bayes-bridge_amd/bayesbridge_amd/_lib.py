@@ -12,14 +12,14 @@ from ctypes import (POINTER, byref, c_char_p, c_double, c_int, c_int32,
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libbbx.so")
 
-ABI_VERSION = 105          # BBX_VERSION of include/bbx.h
+ABI_VERSION = 106          # BBX_VERSION of include/bbx.h
 FORMAT_AUTO, FORMAT_CSR, FORMAT_TILED = 0, 1, 2
 F64, F32 = 0, 1
 MODEL_LINEAR, MODEL_LOGIT = 0, 1
 GSCALE_SAMPLE, GSCALE_OPTIMIZE, GSCALE_FIXED = 0, 1, 2
 BATCH_ALLOW_SLOW = 1
 ERR_NUMERIC = -4           # BBX_ERR_NUMERIC
-SAMPLER_CG, SAMPLER_CHOLESKY = 0, 1
+SAMPLER_CG, SAMPLER_CHOLESKY, SAMPLER_WOODBURY = 0, 1, 2
 # Philox stream ids of the chain's draws (csrc/philox.hpp)
 STREAM_ETA1, STREAM_ETA2 = 1, 2
 
@@ -115,6 +115,18 @@ def _declare(lib):
             [hp, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
         "bbx_chol_sample_scalar": (
             [hp, c_double, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+        "bbx_design_transposed_fisher_info": ([hp, c_void_p, c_void_p], c_int),
+        "bbx_design_transposed_fisher_info_dev": (
+            [hp, c_void_p, c_void_p], c_int),
+        "bbx_woodbury_sample": (
+            [hp, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+            c_int),
+        "bbx_woodbury_sample_dev": (
+            [hp, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+            c_int),
+        "bbx_woodbury_sample_scalar": (
+            [hp, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+            c_int),
         "bbx_design_stream": ([hp, POINTER(c_void_p)], c_int),
         "bbx_design_synchronize": ([hp], c_int),
         "bbx_cg_sample": (

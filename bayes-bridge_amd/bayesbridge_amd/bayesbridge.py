@@ -51,7 +51,7 @@ class SamplerOptions():
 
     def __init__(self, coef_sampler_type='cg', global_scale_update='sample',
                  hmc_curvature_est_stabilized=False, rng=None):
-        if coef_sampler_type not in ('cholesky', 'cg', 'hmc'):
+        if coef_sampler_type not in ('cholesky', 'cg', 'hmc', 'woodbury'):
             raise ValueError("Unsupported regression coefficient sampler.")
         if rng is None:
             rng = 'reference' if coef_sampler_type == 'hmc' else 'device'
@@ -85,7 +85,8 @@ class SamplerOptions():
                 warn("Duplicate specification of method for sampling "
                      "regression coefficient. Will use the dictionary one.")
             coef_sampler_type = options['coef_sampler_type']
-        if coef_sampler_type not in (None, 'cholesky', 'cg', 'hmc'):
+        if coef_sampler_type not in (None, 'cholesky', 'cg', 'hmc',
+                                     'woodbury'):
             raise ValueError("Unsupported sampler type.")
         if model_name == 'cox':
             # gibbs_util.py:76-81: only HMC draws the Cox coefficients
@@ -95,14 +96,19 @@ class SamplerOptions():
             options['coef_sampler_type'] = 'hmc'
             return SamplerOptions(**options)
         if coef_sampler_type not in (None, 'cg') and not (
-                coef_sampler_type == 'cholesky'
+                coef_sampler_type in ('cholesky', 'woodbury')
                 and _is_hip_dense(design)):
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
         if model_name not in ('linear', 'logit'):
             raise ValueError("Only linear and logit models use the CG sampler.")
         n_obs, n_pred = design.shape
         if n_pred > n_obs:
-            warn("Sampler has not been optimized for 'small n' problem.")
+            # (the reference's TODO here, gibbs_util.py:66-68, is the
+            # 'woodbury' sampler of this backend; it is not chosen by default)
+            warn("Sampler has not been optimized for 'small n' problem."
+                 + ("" if coef_sampler_type == 'woodbury' else
+                    " (coef_sampler_type='woodbury' draws dense designs "
+                    "from an n x n system.)"))
         # the reference defaults to 'cholesky' for dense designs
         # (gibbs_util.py:53-65); here 'cg' stays the default for every design
         options['coef_sampler_type'] = coef_sampler_type or 'cg'
@@ -110,7 +116,7 @@ class SamplerOptions():
 
 
 def _is_hip_dense(design):
-    """The 'cholesky' sampler runs on HIP dense designs only."""
+    """The 'cholesky' and 'woodbury' samplers run on HIP dense designs only."""
     return getattr(design, 'use_hip', False) is True \
         and getattr(design, 'is_sparse', True) is False
 
@@ -198,7 +204,7 @@ class BayesBridge():
         if not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
                 coef_sampler_type, options, self.model.name, self.model.design)
-        if options.coef_sampler_type == 'cholesky':
+        if options.coef_sampler_type in ('cholesky', 'woodbury'):
             if not _is_hip_dense(self.model.design):
                 raise ValueError(
                     "Only 'cg' sampler supported with HIP matrices.")
@@ -646,7 +652,7 @@ class BayesBridge():
                                    sampler)
         samples, sampling_info = self._pre_allocate(
             n_iter - n_burnin, thin, params_to_save)
-        if options.coef_sampler_type == 'cholesky':
+        if options.coef_sampler_type in ('cholesky', 'woodbury'):
             sampling_info = {}       # gibbs_util.py:147-160: no n_cg_iter
         info_keys = HMC_INFO_KEYS if options.coef_sampler_type == 'hmc' \
             else ('n_cg_iter',)
@@ -757,7 +763,9 @@ class BayesBridge():
                                     params_to_save, device_out, init_used,
                                     optim_info)
         except _lib.BbxError as e:
-            if chain.coef_sampler == 'cholesky' and 'cholesky' in str(e):
+            if chain.coef_sampler in ('cholesky', 'woodbury') \
+                    and chain.coef_sampler in str(e) \
+                    and 'positive definite' in str(e):
                 raise np.linalg.LinAlgError(str(e)) from e
             raise
 
@@ -889,7 +897,7 @@ class BayesBridge():
             if key in samples:
                 samples[key][:] = kept[key]
         sampling_info['n_cg_iter'][:] = kept['n_cg_iter']
-        if getattr(chain, 'coef_sampler', 'cg') == 'cholesky':
+        if getattr(chain, 'coef_sampler', 'cg') in ('cholesky', 'woodbury'):
             sampling_info = {}       # gibbs_util.py:147-160: no n_cg_iter
         coef, obs_prec, lscale, gscale = chain.get_state()
         mean, square, n_avg = chain.get_summary()

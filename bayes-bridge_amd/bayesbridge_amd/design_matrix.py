@@ -332,7 +332,8 @@ class HipDesignMatrix():
 
     def compute_transposed_fisher_info(self, weight, include_intrcpt=False):
         raise NotImplementedError(
-            "outside the CG hot path this backend implements.")
+            "compute_transposed_fisher_info (the 'woodbury' sampler's Gram) "
+            "is implemented for dense designs only.")
 
 
 class HipSparseDesignMatrix(HipDesignMatrix):
@@ -509,9 +510,10 @@ class HipDenseDesignMatrix(HipDesignMatrix):
         return False
 
     def release_sampler_memory(self):
-        """Frees the 'cholesky' sampler's work memory on the device (a P x P
-        f64 matrix, a second one for linear models' cached X~^T X~, the Gram
-        partials); the next draw allocates it again."""
+        """Frees the 'cholesky' and 'woodbury' samplers' work memory on the
+        device (a P x P or n x n f64 matrix, a second one for linear models'
+        cached X~^T X~, the Gram partials, work vectors); the next draw
+        allocates it again."""
         _lib.check(self._lib.bbx_chol_release(self._h))
 
     def compute_fisher_info(self, weight, diag_only=False):
@@ -528,6 +530,25 @@ class HipDenseDesignMatrix(HipDesignMatrix):
         out = np.empty(P if diag_only else (P, P), dtype=np.float64)
         _lib.check(self._lib.bbx_design_fisher_info(
             self._h, _ptr(w), int(bool(diag_only)), _ptr(out)))
+        return out
+
+    def compute_transposed_fisher_info(self, weight, include_intrcpt=True):
+        """X~ diag(weight) X~^T as an (n, n) NumPy array, from the device's
+        matrix-core Gram over the columns (csrc/woodbury.hip).  The reference
+        declares the method with an empty body (dense_matrix.py:60-61); here
+        `weight` has one entry >= 0 per column of X~ (length P, the
+        intercept column first when the design has one) and the intercept
+        column is part of the sum unless `include_intrcpt` is False (its
+        weight then counts as 0).  X~ is the stored matrix: centred, and
+        with storage_dtype='float32' f32-rounded; the sum runs in f64."""
+        n, P = self.shape
+        w = np.array(np.broadcast_to(
+            np.asarray(weight, dtype=np.float64), (P,)), dtype=np.float64)
+        if not include_intrcpt and self.intercept_added:
+            w[0] = 0.
+        out = np.empty((n, n), dtype=np.float64)
+        _lib.check(self._lib.bbx_design_transposed_fisher_info(
+            self._h, _ptr(w), _ptr(out)))
         return out
 
     @property

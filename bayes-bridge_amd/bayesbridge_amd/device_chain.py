@@ -154,12 +154,16 @@ class HipGibbsChain():
     coef_sampler = 'cg'
 
     def set_coef_sampler(self, kind):
-        """'cg' (default) or 'cholesky' (dense designs only): how the chain
-        draws beta | rest.  The 'cholesky' draw takes its P normals from the
-        stream of `eta(iteration)[1]` and keeps no running summary."""
-        code = {'cg': _lib.SAMPLER_CG, 'cholesky': _lib.SAMPLER_CHOLESKY}
+        """'cg' (default), 'cholesky' or 'woodbury' (the last two on dense
+        designs only): how the chain draws beta | rest.  The 'cholesky' draw
+        takes its P normals from the stream of `eta(iteration)[1]`; the
+        'woodbury' draw its n normals from `eta(iteration)[0]` and its P
+        normals from `eta(iteration)[1]`.  Neither keeps a running summary."""
+        code = {'cg': _lib.SAMPLER_CG, 'cholesky': _lib.SAMPLER_CHOLESKY,
+                'woodbury': _lib.SAMPLER_WOODBURY}
         if kind not in code:
-            raise ValueError("coef sampler must be 'cg' or 'cholesky'")
+            raise ValueError(
+                "coef sampler must be 'cg', 'cholesky' or 'woodbury'")
         _lib.check(self._lib.bbx_chain_set_coef_sampler(self._c, code[kind]))
         self.coef_sampler = kind
 

@@ -110,11 +110,65 @@ def chol_sample(design, obs_prec, prior_prec_sqrt, z, normals=None,
     return out
 
 
+def woodbury_sample(design, obs_prec, prior_prec_sqrt, y, normals_n=None,
+                    normals_P=None, rand_gen=None):
+    """The coefficients' Gaussian conditional, N(A^-1 X~^T (obs_prec y), A^-1)
+    with A = X~^T diag(obs_prec) X~ + diag(prior_prec_sqrt^2), drawn from an
+    n x n system on the device (bbx_woodbury_sample): for HIP
+    dense designs with more columns than rows.  Zeros of `prior_prec_sqrt`
+    mark coefficients with a flat prior (at most 32).  `normals_n`, `normals_P`:
+    the n + P standard normals; None draws them from np.random (or
+    rand_gen.np_random) in this order: randn(n), then randn(P).  An `obs_prec`
+    whose entries are all equal (linear models) is passed as one number.  A
+    matrix that is not numerically positive definite raises
+    numpy.linalg.LinAlgError."""
+    from ctypes import c_void_p
+    from . import _lib
+    if getattr(design, 'is_sparse', True) is not False \
+            or not getattr(design, 'use_hip', False):
+        raise ValueError("the 'woodbury' sampler needs a HIP dense design")
+    n, P = design.shape
+    obs_prec = np.ascontiguousarray(np.broadcast_to(
+        np.asarray(obs_prec, dtype=np.float64), (n,)))
+    pps = np.ascontiguousarray(prior_prec_sqrt, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if pps.shape != (P,) or y.shape != (n,):
+        raise ValueError("prior_prec_sqrt must have length %d, y length %d"
+                         % (P, n))
+    src = np.random if rand_gen is None else rand_gen.np_random
+    if normals_n is None:
+        normals_n = src.randn(n)
+    if normals_P is None:
+        normals_P = src.randn(P)
+    normals_n = np.ascontiguousarray(normals_n, dtype=np.float64)
+    normals_P = np.ascontiguousarray(normals_P, dtype=np.float64)
+    if normals_n.shape != (n,) or normals_P.shape != (P,):
+        raise ValueError("normals_n must have length %d, normals_P length %d"
+                         % (n, P))
+    out = np.empty(P)
+
+    def ptr(a):
+        return a.ctypes.data_as(c_void_p)
+    lib = design._lib
+    if n > 0 and np.all(obs_prec == obs_prec[0]):
+        st = lib.bbx_woodbury_sample_scalar(
+            design._h, float(obs_prec[0]), ptr(pps), ptr(y), ptr(normals_n),
+            ptr(normals_P), ptr(out))
+    else:
+        st = lib.bbx_woodbury_sample(
+            design._h, ptr(obs_prec), ptr(pps), ptr(y), ptr(normals_n),
+            ptr(normals_P), ptr(out))
+    if st == _lib.ERR_NUMERIC:
+        raise np.linalg.LinAlgError(_lib.last_error())
+    _lib.check(st)
+    return out
+
+
 class HipRegressionCoefficientSampler():
 
     def __init__(self, n_coef, prior_sd_for_unshrunk, sampling_method='cg',
                  regularizing_slab_size=float('inf'), rand_gen=None):
-        if sampling_method not in ('cg', 'cholesky'):
+        if sampling_method not in ('cg', 'cholesky', 'woodbury'):
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
         # source of the 'cholesky' draw's normals: the global NumPy stream,
         # which ReferenceRandom.np_random is (direct_gaussian_sampler.py:30)
@@ -135,9 +189,21 @@ class HipRegressionCoefficientSampler():
 
     def sample_gaussian_posterior(self, y, design, obs_prec, gscale, lscale,
                                   method='cg'):
-        """reg_coef_sampler.py:60-103, 'cg' and 'cholesky' branches."""
-        if method not in ('cg', 'cholesky'):
+        """reg_coef_sampler.py:60-103, 'cg' and 'cholesky' branches, and the
+        'woodbury' draw the reference does not have."""
+        if method not in ('cg', 'cholesky', 'woodbury'):
             raise NotImplementedError()
+        if method == 'woodbury':
+            # the n-space draw needs y itself, not X~^T (obs_prec y); like
+            # 'cholesky' it keeps no summary and returns no sampling info
+            prior_sd = np.concatenate((
+                self.prior_sd_for_unshrunk,
+                compute_prior_shrunk_scale(gscale, lscale,
+                                           self.regularizing_slab_size)))
+            with np.errstate(divide='ignore'):
+                prior_prec_sqrt = 1 / prior_sd
+            return woodbury_sample(design, obs_prec, prior_prec_sqrt, y,
+                                   rand_gen=self.rand_gen), {}
         v = design.Tdot(obs_prec * y)                                    # :74
         prior_sd = np.concatenate((
             self.prior_sd_for_unshrunk,

@@ -1054,6 +1054,107 @@ int bbx_chol_sample_scalar(bbx_design* h, double obs_prec,
                           coef_out);
 }
 
+// ---- woodbury sampler (woodbury.hip) ----------------------------------------
+int bbx_design_transposed_fisher_info_dev(bbx_design* h, const double* d_weight,
+                                          double* d_out) {
+  BBX_TRY(check_handle(h));
+  if (!d_weight || !d_out) return fail(BBX_ERR_INVALID, "NULL array argument");
+  return no_throw([&]() -> int {
+    return transposed_fisher_info_device(h, d_weight, d_out);
+  });
+}
+
+int bbx_design_transposed_fisher_info(bbx_design* h, const double* weight,
+                                      double* out) {
+  BBX_TRY(check_handle(h));
+  if (!weight || !out) return fail(BBX_ERR_INVALID, "NULL array argument");
+  if (h->sparse)
+    return fail(BBX_ERR_INVALID,
+                "compute_transposed_fisher_info: dense designs only (this one "
+                "is sparse)");
+  return no_throw([&]() -> int {
+    BBX_HIP(hipSetDevice(h->device));
+    double* d_w = wb_stage(h, 1);
+    if (!d_w) return -1;
+    DevMem d_o;
+    BBX_TRY(d_o.alloc(sizeof(double) * (size_t)h->n * (size_t)h->n));
+    BBX_HIP(hipMemcpyAsync(d_w, weight, sizeof(double) * (size_t)h->P,
+                           hipMemcpyHostToDevice, h->stream));
+    BBX_TRY(transposed_fisher_info_device(h, d_w, d_o.as<double>()));
+    BBX_HIP(hipMemcpyAsync(out, d_o.ptr, sizeof(double) * (size_t)h->n * (size_t)h->n,
+                           hipMemcpyDeviceToHost, h->stream));
+    BBX_HIP(hipStreamSynchronize(h->stream));
+    return BBX_OK;
+  });
+}
+
+int bbx_woodbury_sample_dev(bbx_design* h, const double* d_obs_prec,
+                            const double* d_prior_prec_sqrt, const double* d_y,
+                            const double* d_normals_n,
+                            const double* d_normals_P, double* d_coef_out) {
+  BBX_TRY(check_handle(h));
+  if (!d_obs_prec || !d_prior_prec_sqrt || !d_y || !d_normals_n ||
+      !d_normals_P || !d_coef_out)
+    return fail(BBX_ERR_INVALID, "NULL array argument");
+  return no_throw([&]() -> int {
+    return woodbury_sample_device(h, d_obs_prec, 1., nullptr, d_prior_prec_sqrt,
+                                  d_y, 0, d_normals_n, d_normals_P, d_coef_out);
+  });
+}
+
+static int woodbury_sample_host(bbx_design* h, const double* obs_prec,
+                                double obs_prec_scalar,
+                                const double* prior_prec_sqrt, const double* y,
+                                const double* normals_n, const double* normals_P,
+                                double* coef_out) {
+  if (!prior_prec_sqrt || !y || !normals_n || !normals_P || !coef_out)
+    return fail(BBX_ERR_INVALID, "NULL array argument");
+  if (h->sparse)
+    return fail(BBX_ERR_INVALID,
+                "the woodbury sampler needs a dense design (this one is sparse)");
+  return no_throw([&]() -> int {
+    BBX_HIP(hipSetDevice(h->device));
+    const size_t Pb = sizeof(double) * (size_t)h->P;
+    const size_t nb = sizeof(double) * (size_t)h->n;
+    double* st[6];
+    for (int k = 0; k < 6; ++k) {
+      st[k] = wb_stage(h, k);
+      if (!st[k]) return -1;
+    }
+    if (obs_prec)
+      BBX_HIP(hipMemcpyAsync(st[0], obs_prec, nb, hipMemcpyHostToDevice, h->stream));
+    BBX_HIP(hipMemcpyAsync(st[1], prior_prec_sqrt, Pb, hipMemcpyHostToDevice,
+                           h->stream));
+    BBX_HIP(hipMemcpyAsync(st[2], y, nb, hipMemcpyHostToDevice, h->stream));
+    BBX_HIP(hipMemcpyAsync(st[3], normals_n, nb, hipMemcpyHostToDevice, h->stream));
+    BBX_HIP(hipMemcpyAsync(st[4], normals_P, Pb, hipMemcpyHostToDevice, h->stream));
+    BBX_TRY(woodbury_sample_device(h, obs_prec ? st[0] : nullptr, obs_prec_scalar,
+                                   nullptr, st[1], st[2], 0, st[3], st[4], st[5]));
+    BBX_HIP(hipMemcpyAsync(coef_out, st[5], Pb, hipMemcpyDeviceToHost, h->stream));
+    BBX_HIP(hipStreamSynchronize(h->stream));
+    return BBX_OK;
+  });
+}
+
+int bbx_woodbury_sample(bbx_design* h, const double* obs_prec,
+                        const double* prior_prec_sqrt, const double* y,
+                        const double* normals_n, const double* normals_P,
+                        double* coef_out) {
+  BBX_TRY(check_handle(h));
+  if (!obs_prec) return fail(BBX_ERR_INVALID, "NULL array argument");
+  return woodbury_sample_host(h, obs_prec, 1., prior_prec_sqrt, y, normals_n,
+                              normals_P, coef_out);
+}
+
+int bbx_woodbury_sample_scalar(bbx_design* h, double obs_prec,
+                               const double* prior_prec_sqrt, const double* y,
+                               const double* normals_n, const double* normals_P,
+                               double* coef_out) {
+  BBX_TRY(check_handle(h));
+  return woodbury_sample_host(h, nullptr, obs_prec, prior_prec_sqrt, y,
+                              normals_n, normals_P, coef_out);
+}
+
 int bbx_design_gram_matvec_dev(bbx_design* h, const double* d_obs_prec,
                                const double* d_v, double* d_out) {
   BBX_TRY(check_handle(h));

@@ -805,6 +805,37 @@ static int chain_step(bbx_chain* c, int maxiter, double atol, int* n_cg_iter) {
     BBX_TRY(chain_post_draw(c, false, POST_ALL));
     return 0;
   }
+  if (c->coef_sampler == BBX_SAMPLER_WOODBURY) {
+    // the n-space draw (woodbury.hip): delta = the n normals of the CG draw's
+    // eta1 stream, xi = the P normals of its eta2 stream (bbx_chain_eta(it)
+    // returns both).  It synchronises: coef is final.
+    bbx_design* h = c->h;
+    if (!have_eta) {
+      if (!c->eta1_next.ptr)
+        BBX_TRY(c->eta1_next.alloc(sizeof(double) * (size_t)h->n));
+      if (!c->eta2_next.ptr)
+        BBX_TRY(c->eta2_next.alloc(sizeof(double) * (size_t)h->P));
+      BBX_TRY(launch_fill_normal(h, h->n, cg_draw_seed(c, it), STREAM_ETA1,
+                                 c->eta1_next.as<double>()));
+      BBX_TRY(launch_fill_normal(h, h->P, cg_draw_seed(c, it), STREAM_ETA2,
+                                 c->eta2_next.as<double>()));
+    }
+    const bool linear = c->model == BBX_MODEL_LINEAR;
+    // logit: kappa = Omega y (the pseudo-outcome is kappa / Omega)
+    const int st = woodbury_sample_device(
+        h, linear ? nullptr : c->obs_prec.as<double>(), 1.,
+        linear ? &c->scalars.as<ChainScalars>()->obs_prec : nullptr,
+        c->phi.as<double>(),
+        linear ? c->outcome.as<double>() : c->kappa.as<double>(),
+        linear ? 0 : 1, c->eta1_next.as<double>(), c->eta2_next.as<double>(),
+        c->coef.as<double>());
+    c->eta_iter = -1;
+    if (st < 0) return st;
+    c->coef_sample = nullptr;   // not written by the draw: chain_save_sample copies
+    if (n_cg_iter) *n_cg_iter = 0;
+    BBX_TRY(chain_post_draw(c, false, POST_ALL));
+    return 0;
+  }
   struct TailScope {
     bbx_design* h;
     ~TailScope() {
@@ -1487,9 +1518,18 @@ int bbx_device_normal(int device, uint64_t seed, uint64_t stream,
 int bbx_chain_set_coef_sampler(bbx_chain* c, int sampler) {
   return no_throw([&]() -> int {
     BBX_TRY(chain_check(c));
-    if (sampler != BBX_SAMPLER_CG && sampler != BBX_SAMPLER_CHOLESKY)
+    if (sampler != BBX_SAMPLER_CG && sampler != BBX_SAMPLER_CHOLESKY &&
+        sampler != BBX_SAMPLER_WOODBURY)
       return fail(BBX_ERR_INVALID,
-                  "sampler must be BBX_SAMPLER_CG or BBX_SAMPLER_CHOLESKY");
+                  "sampler must be BBX_SAMPLER_CG, BBX_SAMPLER_CHOLESKY or "
+                  "BBX_SAMPLER_WOODBURY");
+    if (sampler == BBX_SAMPLER_WOODBURY && c->h->sparse)
+      return fail(BBX_ERR_INVALID,
+                  "the woodbury sampler needs a dense design (this one is sparse)");
+    if (sampler == BBX_SAMPLER_WOODBURY && c->model != BBX_MODEL_LINEAR &&
+        c->model != BBX_MODEL_LOGIT)
+      return fail(BBX_ERR_INVALID,
+                  "the woodbury sampler draws linear and logit models only");
     if (sampler == BBX_SAMPLER_CHOLESKY && c->h->sparse)
       return fail(BBX_ERR_INVALID,
                   "the cholesky sampler needs a dense design (this one is sparse)");

@@ -624,7 +624,40 @@ int chol_sample_device(bbx_design* h, const double* d_obs_prec,
   return BBX_OK;
 }
 
+// The factorisation and the solve for other callers (woodbury.hip), on a matrix
+// of nb blocks of 64 with leading dimension ld whose padding is the identity.
+// `info` must hold CHOL_NO_FAIL (0x7fffffff) before.
+size_t gram_slab_limit() { return gram_slab_bytes(); }
+
+int chol_factor_enqueue(hipStream_t st, double* A, int64_t ld, int nb, int* info) {
+  for (int k = 0; k < nb; ++k) {
+    BBX_LAUNCH(chol_diag_kernel, dim3(1), dim3(256), 0, st, A, ld, k, info);
+    const int m = nb - k - 1;
+    if (m > 0) {
+      BBX_LAUNCH(chol_panel_kernel, dim3(m), dim3(256), 0, st, A, ld, k);
+      BBX_LAUNCH(chol_syrk_kernel, dim3(m * (m + 1) / 2), dim3(256), 0, st, A,
+                 ld, k);
+    }
+  }
+  BBX_HIP(hipGetLastError());
+  return BBX_OK;
+}
+
+// x = (L L^T)^-1 b; b is overwritten, y (ld doubles) is scratch, x != y != b
+int chol_solve_enqueue(hipStream_t st, const double* A, int64_t ld, int nb,
+                       double* b, double* y, double* x) {
+  for (int k = 0; k < nb; ++k)
+    BBX_LAUNCH(trsv_fwd_kernel, dim3(std::max(1, nb - k - 1)), dim3(256), 0, st,
+               A, ld, k, b, y);
+  for (int k = nb - 1; k >= 0; --k)
+    BBX_LAUNCH(trsv_bwd_kernel, dim3(std::max(1, k)), dim3(256), 0, st, A, ld, k,
+               y, x);
+  BBX_HIP(hipGetLastError());
+  return BBX_OK;
+}
+
 void chol_release(bbx_design* h) {
+  woodbury_release(h);
   h->chol_A.release();
   h->chol_gram.release();
   h->chol_slab.release();

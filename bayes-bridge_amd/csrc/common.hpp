@@ -231,6 +231,11 @@ struct bbx_design {
   // linear models, the Gram's row-chunk partials, P-vectors + pivot flag
   bbx::DevMem chol_A, chol_gram, chol_slab, chol_vec;
   bool chol_gram_ready = false;
+  // woodbury sampler (woodbury.hip): its n- and P-vectors; the n x n matrix
+  // and the Gram partials share chol_A and chol_slab
+  bbx::DevMem wb_vec;
+  // designs wider than 19 200 columns: [panel][row] partials of X~ v (dense.hip)
+  bbx::DevMem dense_wide_part;
 
   // --- LDS-tiled layout (BBX_FORMAT_TILED): see spmv_tiled.hip
   void* tiled = nullptr;           // bbx::TiledPair*
@@ -601,6 +606,24 @@ int chol_sample_device(bbx_design* h, const double* d_obs_prec,
                        double* d_coef_out);
 double* chol_stage(bbx_design* h, int k);
 void chol_release(bbx_design* h);   // frees the sampler's P x P buffers
+// woodbury.hip: the n x n Gram over the columns and the n-space draw
+size_t gram_slab_limit();
+int chol_factor_enqueue(hipStream_t st, double* A, int64_t ld, int nb, int* info);
+int chol_solve_enqueue(hipStream_t st, const double* A, int64_t ld, int nb,
+                       double* b, double* y, double* x);
+int transposed_fisher_info_device(bbx_design* h, const double* d_weight,
+                                  double* d_out);
+int woodbury_sample_device(bbx_design* h, const double* d_obs_prec,
+                           double obs_scalar, const double* d_obs_scalar,
+                           const double* d_pps, const double* d_y, int y_is_wy,
+                           const double* d_delta, const double* d_xi,
+                           double* d_coef_out);
+double* wb_stage(bbx_design* h, int k);
+void woodbury_release(bbx_design* h);
+int launch_dot_dense(bbx_design* h, const double* d_v, const double* d_rowscale,
+                     double* d_t);
+int launch_tdot_dense(bbx_design* h, const double* d_w, const double* d_sumw_part,
+                      const TdotEpilogue& ep, double* d_out);
 int cg_sample_device(bbx_design* h, const double* d_omega, const double* d_phi,
                      const double* d_z, const double* d_x0,
                      const double* d_sd, int n_unshrunk, const double* d_eta1,

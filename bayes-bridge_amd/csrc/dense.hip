@@ -924,14 +924,112 @@ __global__ __launch_bounds__(256) void dense_ingest_kernel(
   }
 }
 
+// Designs wider than dense_dot_kernel's LDS copy of the vector holds (19 200
+// columns): column panels of DENSE_WIDE_PANEL columns.  Workgroup (x: group of 8
+// rows, y: panel) stages its panel of v in LDS; a wave streams two rows of the
+// panel at a time, so that a quad of v read from LDS serves two quads of X.
+// Every (panel, row) partial sum has its own slot and dense_dot_wide_reduce_kernel
+// adds the panels in panel order: no atomics, a repeated call gives the same bits.
+constexpr int DENSE_WIDE_PANEL = 4096;
+constexpr int DENSE_WIDE_ROWS = 8;    // rows per workgroup (4 waves x 2)
+
+template <typename T>
+__global__ __launch_bounds__(256) void dense_dot_wide_kernel(
+    int64_t n, int64_t P, int64_t ld, const T* __restrict__ X,
+    const double* __restrict__ v, double* __restrict__ part,
+    const int* __restrict__ skip_flag) {
+  if (skip_flag && *skip_flag) return;  // the CG solve has already stopped
+  using V4 = typename Vec4<T>::type;
+  __shared__ __attribute__((aligned(32))) double vs[DENSE_WIDE_PANEL];
+  const int64_t c0 = (int64_t)blockIdx.y * DENSE_WIDE_PANEL;
+  const int64_t width = min((int64_t)DENSE_WIDE_PANEL, ld - c0);  // % 4 == 0
+  for (int64_t j = threadIdx.x; j < width; j += 256)
+    vs[j] = (c0 + j < P) ? v[c0 + j] : 0.;
+  __syncthreads();
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+  const int64_t row = (int64_t)blockIdx.x * DENSE_WIDE_ROWS + 2 * wave;
+  if (row >= n) return;
+  const bool two = row + 1 < n;
+  const V4* __restrict__ xa = reinterpret_cast<const V4*>(X + row * ld + c0);
+  const V4* __restrict__ xb =
+      reinterpret_cast<const V4*>(X + (two ? row + 1 : row) * ld + c0);
+  const double4* __restrict__ v4 = reinterpret_cast<const double4*>(vs);
+  const int64_t nq = width / 4;
+  double a0 = 0., a1 = 0., b0 = 0., b1 = 0.;
+  int64_t q = lane;
+  for (; q + WAVE < nq; q += 2 * WAVE) {
+    const V4 x0 = stream_load(xa + q), x1 = stream_load(xa + q + WAVE),
+             y0 = stream_load(xb + q), y1 = stream_load(xb + q + WAVE);
+    const double4 w0 = v4[q], w1 = v4[q + WAVE];
+    a0 += (double)x0.x * w0.x + (double)x0.z * w0.z;
+    a1 += (double)x0.y * w0.y + (double)x0.w * w0.w;
+    b0 += (double)y0.x * w0.x + (double)y0.z * w0.z;
+    b1 += (double)y0.y * w0.y + (double)y0.w * w0.w;
+    a0 += (double)x1.x * w1.x + (double)x1.z * w1.z;
+    a1 += (double)x1.y * w1.y + (double)x1.w * w1.w;
+    b0 += (double)y1.x * w1.x + (double)y1.z * w1.z;
+    b1 += (double)y1.y * w1.y + (double)y1.w * w1.w;
+  }
+  for (; q < nq; q += WAVE) {
+    const V4 x0 = stream_load(xa + q), y0 = stream_load(xb + q);
+    const double4 w0 = v4[q];
+    a0 += (double)x0.x * w0.x + (double)x0.z * w0.z;
+    a1 += (double)x0.y * w0.y + (double)x0.w * w0.w;
+    b0 += (double)y0.x * w0.x + (double)y0.z * w0.z;
+    b1 += (double)y0.y * w0.y + (double)y0.w * w0.w;
+  }
+  const double a = wave_allsum(a0 + a1), b = wave_allsum(b0 + b1);
+  if (lane == 0) {
+    part[(int64_t)blockIdx.y * n + row] = a;
+    if (two) part[(int64_t)blockIdx.y * n + row + 1] = b;
+  }
+}
+
+__global__ __launch_bounds__(256) void dense_dot_wide_reduce_kernel(
+    int64_t n, int panels, const double* __restrict__ part,
+    const double* __restrict__ rowscale, double* __restrict__ out,
+    const int* __restrict__ skip_flag) {
+  if (skip_flag && *skip_flag) return;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double a = 0.;
+  for (int k = 0; k < panels; ++k) a += part[(int64_t)k * n + i];
+  if (rowscale) a *= rowscale[i];
+  out[i] = a;
+}
+
+static int launch_dot_dense_wide(bbx_design* h, const double* d_v,
+                                 const double* d_rowscale, double* d_t) {
+  const int64_t ld = h->dense_ld;
+  const int panels = (int)((ld + DENSE_WIDE_PANEL - 1) / DENSE_WIDE_PANEL);
+  const size_t need = sizeof(double) * (size_t)panels * (size_t)h->n;
+  if (h->dense_wide_part.bytes < need) BBX_TRY(h->dense_wide_part.alloc(need));
+  double* part = h->dense_wide_part.as<double>();
+  const dim3 grid((unsigned)((h->n + DENSE_WIDE_ROWS - 1) / DENSE_WIDE_ROWS),
+                  (unsigned)panels);
+  BBX_TRY(timer_begin(h, 0));
+  if (h->dense_dtype == BBX_F32)
+    BBX_LAUNCH(dense_dot_wide_kernel<float>, grid, dim3(256), 0, h->stream, h->n,
+               h->P, ld, h->dense.as<float>(), d_v, part, h->skip_flag);
+  else
+    BBX_LAUNCH(dense_dot_wide_kernel<double>, grid, dim3(256), 0, h->stream,
+               h->n, h->P, ld, h->dense.as<double>(), d_v, part, h->skip_flag);
+  BBX_LAUNCH(dense_dot_wide_reduce_kernel, dim3((unsigned)((h->n + 255) / 256)),
+             dim3(256), 0, h->stream, h->n, panels, part, d_rowscale, d_t,
+             h->skip_flag);
+  BBX_TRY(timer_end(h, 0));
+  BBX_HIP(hipGetLastError());
+  return BBX_OK;
+}
+
 int launch_dot_dense(bbx_design* h, const double* d_v,
                      const double* d_rowscale, double* d_t) {
   int64_t nb = (h->n + 3) / 4;
   if (nb > 1024) nb = 1024;   // 4 rows in flight per block, vector staged once
   if (nb < 1) nb = 1;
   const size_t lds = sizeof(double) * (size_t)h->dense_ld;
-  if (lds > 150 * 1024)
-    return fail(BBX_ERR_INVALID, "dense operator: more than 19200 columns");
+  if (lds > 150 * 1024)   // more than 19 200 columns
+    return launch_dot_dense_wide(h, d_v, d_rowscale, d_t);
   // opt-in matrix-core variant (A/B only: LABNOTES.md 3.3)
   static const bool use_mfma =
       getenv("BBX_DENSE_MFMA") && atoi(getenv("BBX_DENSE_MFMA")) == 1;

@@ -33,7 +33,11 @@
 extern "C" {
 #endif
 
-/* 105: + the Cox likelihood and its HMC trajectory (bbx_cox_*).
+/* 106: + bbx_design_transposed_fisher_info, bbx_woodbury_sample (the n-space
+ *      draw for dense designs with more columns than rows; the reference leaves
+ *      it as a TODO, gibbs_util.py:66-68), BBX_SAMPLER_WOODBURY; dense designs
+ *      of more than 19 200 columns.
+ * 105: + the Cox likelihood and its HMC trajectory (bbx_cox_*).
  * 103: + bbx_design_cg_stats (solves and launches enqueued past the stopping
  *      iteration since the last reset), bbx_launch_count, bbx_chain_set_progress.
  * 102: + bbx_design_create_csr64 (64-bit index arrays, 2^31 or more entries).
@@ -41,7 +45,7 @@ extern "C" {
  *      bbx_setup_lock_acquire/_release, bbx_design_useful_bytes.  A binding
  *      compares bbx_version() with the BBX_VERSION it was written against
  *      (bayesbridge_amd/_lib.py does) instead of calling with a stale arity. */
-#define BBX_VERSION 105 /* 0.1.5 */
+#define BBX_VERSION 106 /* 0.1.6 */
 
 /* status codes */
 #define BBX_OK 0
@@ -358,6 +362,58 @@ int bbx_chol_sample_scalar(bbx_design* h, double obs_prec,
  * it (the next call allocates it again); bbx_design_destroy does too. */
 int bbx_chol_release(bbx_design* h);
 
+/*
+ * Transposed Fisher information of a DENSE design (the reference declares
+ * compute_transposed_fisher_info, dense_matrix.py:60-61, with an empty body;
+ * the meaning is fixed here):
+ *   out = X~ diag(weight) X~^T      (n x n, row-major, symmetric bit for bit)
+ * with weight[P] >= 0 over ALL columns of the stored matrix, the intercept
+ * column included (give it weight 0 to leave it out).  f64 accumulation on
+ * the matrix cores, bitwise reproducible.  A sparse design, n > 19 200 or a
+ * NULL array returns BBX_ERR_INVALID.  Host pointers, synchronous; `_dev`:
+ * device pointers, asynchronous on the handle's stream.
+ */
+int bbx_design_transposed_fisher_info(bbx_design* h, const double* weight,
+                                      double* out);
+int bbx_design_transposed_fisher_info_dev(bbx_design* h, const double* d_weight,
+                                          double* d_out);
+
+/*
+ * The n-space ('woodbury') coefficient draw on a DENSE design, for P > n: the
+ * same Gaussian as bbx_chol_sample / bbx_cg_sample,
+ *   N(A^-1 X~^T (obs_prec .* y), A^-1),  A = X~^T diag(obs_prec) X~ + diag(prior_prec_sqrt^2),
+ * from an n x n system (Bhattacharya, Chakraborty and Mallick 2016, extended
+ * to coefficients with a flat prior; DESIGN.md 11 has the algebra):
+ * n^2 P + n^3 / 3 flops and 8 n^2 bytes instead of n P^2 + P^3 / 3 and 8 P^2.
+ *   obs_prec[n] > 0 (bbx_woodbury_sample_scalar: one number, linear models);
+ *   prior_prec_sqrt[P] >= 0: 1 / prior sd; a ZERO marks a coefficient with a
+ *     flat prior (the intercept under the default prior), at most 32 of them,
+ *     and their columns must be linearly independent;
+ *   y[n]: the (pseudo-)outcome;
+ *   normals_n[n], normals_P[P]: standard normals; normals_P[j] belongs to
+ *     coefficient j;
+ *   coef_out[P].
+ * Returns BBX_ERR_NUMERIC, with the first non-positive pivot in
+ * bbx_last_error(), when a factorisation fails; BBX_ERR_INVALID on a sparse
+ * design, n > 19 200 (the n x n matrix would pass 2.9 GB), more than 32 flat
+ * coefficients, a negative prior_prec_sqrt or a NULL array.  All forms
+ * synchronise the handle's stream before they return.  Work memory (8 n_pad^2
+ * bytes, n_pad = n rounded up to 64, the Gram partials of at most 256 MB, and
+ * about 80 n-vectors) stays on the design until bbx_chol_release.
+ */
+int bbx_woodbury_sample(bbx_design* h, const double* obs_prec,
+                        const double* prior_prec_sqrt, const double* y,
+                        const double* normals_n, const double* normals_P,
+                        double* coef_out);
+int bbx_woodbury_sample_dev(bbx_design* h, const double* d_obs_prec,
+                            const double* d_prior_prec_sqrt, const double* d_y,
+                            const double* d_normals_n,
+                            const double* d_normals_P, double* d_coef_out);
+int bbx_woodbury_sample_scalar(bbx_design* h, double obs_prec,
+                               const double* prior_prec_sqrt, const double* y,
+                               const double* normals_n, const double* normals_P,
+                               double* coef_out);
+
 /* The hipStream_t (as void*) every kernel of this handle is launched on, and a
  * blocking wait on it. */
 int bbx_design_stream(bbx_design* h, void** stream);
@@ -513,6 +569,11 @@ int bbx_chain_set_gscale_update(bbx_chain* c, int mode);
  * 0 and no unconverged solves.  bbx_batch_create refuses such chains. */
 #define BBX_SAMPLER_CG 0
 #define BBX_SAMPLER_CHOLESKY 1
+/* BBX_SAMPLER_WOODBURY (dense designs only, refused by bbx_batch_create like
+ * BBX_SAMPLER_CHOLESKY): the draw of bbx_woodbury_sample; normals_n is the
+ * chain's eta1 stream and normals_P its eta2 stream (bbx_chain_eta), no
+ * running summary, n_cg_iter 0. */
+#define BBX_SAMPLER_WOODBURY 2
 int bbx_chain_set_coef_sampler(bbx_chain* c, int sampler);
 /*
  * Regenerates, on the device, the standard normals the chain's CG draw
