@@ -40,6 +40,7 @@ HMC_INFO_KEYS = ('stepsize', 'n_hessian_matvec', 'n_grad_evals',
                  'stability_limit_est', 'stability_adjustment_factor',
                  'instability_detected', 'n_integrator_step', 'accepted',
                  'accept_prob')
+NUTS_INFO_KEYS = HMC_INFO_KEYS[:6] + ('tree_height', 'ave_accept_prob')
 
 
 def _ptr(a):
@@ -51,15 +52,17 @@ class SamplerOptions():
 
     def __init__(self, coef_sampler_type='cg', global_scale_update='sample',
                  hmc_curvature_est_stabilized=False, rng=None):
-        if coef_sampler_type not in ('cholesky', 'cg', 'hmc', 'woodbury'):
+        if coef_sampler_type not in ('cholesky', 'cg', 'hmc', 'nuts',
+                                     'woodbury'):
             raise ValueError("Unsupported regression coefficient sampler.")
+        hamiltonian = coef_sampler_type in ('hmc', 'nuts')
         if rng is None:
-            rng = 'reference' if coef_sampler_type == 'hmc' else 'device'
-        if coef_sampler_type == 'hmc' and rng != 'reference':
-            # the HMC draw takes its momentum, step size and accept uniform
+            rng = 'reference' if hamiltonian else 'device'
+        if hamiltonian and rng != 'reference':
+            # the HMC / NUTS draw takes its momentum, step size and uniforms
             # from the global NumPy stream, as the reference does
-            raise ValueError("The 'hmc' sampler (Cox model) runs with "
-                             "rng='reference' only.")
+            raise ValueError("The '%s' sampler (Cox model) runs with "
+                             "rng='reference' only." % coef_sampler_type)
         if rng not in ('device', 'reference'):
             raise ValueError("rng must be 'device' or 'reference'")
         if global_scale_update not in ('sample', 'optimize', None):
@@ -85,15 +88,18 @@ class SamplerOptions():
                 warn("Duplicate specification of method for sampling "
                      "regression coefficient. Will use the dictionary one.")
             coef_sampler_type = options['coef_sampler_type']
-        if coef_sampler_type not in (None, 'cholesky', 'cg', 'hmc',
+        if coef_sampler_type not in (None, 'cholesky', 'cg', 'hmc', 'nuts',
                                      'woodbury'):
             raise ValueError("Unsupported sampler type.")
         if model_name == 'cox':
-            # gibbs_util.py:76-81: only HMC draws the Cox coefficients
-            if coef_sampler_type not in (None, 'hmc'):
+            # gibbs_util.py:76-81: only HMC draws the Cox coefficients -- and
+            # 'nuts', which the reference's loop dispatches
+            # (bayesbridge.py:387-389) but its option check never lets through
+            if coef_sampler_type not in (None, 'hmc', 'nuts'):
                 warn("Specified sampler type is not supported for the cox "
                      "model. Will use HMC instead.")
-            options['coef_sampler_type'] = 'hmc'
+                coef_sampler_type = None
+            options['coef_sampler_type'] = coef_sampler_type or 'hmc'
             return SamplerOptions(**options)
         if coef_sampler_type not in (None, 'cg') and not (
                 coef_sampler_type in ('cholesky', 'woodbury')
@@ -208,7 +214,8 @@ class BayesBridge():
             if not _is_hip_dense(self.model.design):
                 raise ValueError(
                     "Only 'cg' sampler supported with HIP matrices.")
-        if options.coef_sampler_type == 'hmc' and self.model.name != 'cox':
+        if options.coef_sampler_type in ('hmc', 'nuts') \
+                and self.model.name != 'cox':
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
         if params_to_save == 'all':
             params_to_save = ('coef', 'local_scale', 'global_scale', 'logp')
@@ -561,7 +568,8 @@ class BayesBridge():
         bridge_exp = prior.bridge_exp
         if self.rg is None:
             self.rg = ReferenceRandom()
-        if options.coef_sampler_type == 'hmc':
+        hamiltonian = options.coef_sampler_type in ('hmc', 'nuts')
+        if hamiltonian:
             sampler = HipHMCCoefficientSampler(
                 self.n_pred, self.prior_sd_for_unshrunk,
                 options.curvature_est_stabilized, prior.slab_size)
@@ -654,14 +662,19 @@ class BayesBridge():
             n_iter - n_burnin, thin, params_to_save)
         if options.coef_sampler_type in ('cholesky', 'woodbury'):
             sampling_info = {}       # gibbs_util.py:147-160: no n_cg_iter
-        info_keys = HMC_INFO_KEYS if options.coef_sampler_type == 'hmc' \
-            else ('n_cg_iter',)
+        info_keys = {'hmc': HMC_INFO_KEYS, 'nuts': NUTS_INFO_KEYS}.get(
+            options.coef_sampler_type, ('n_cg_iter',))
+        if options.coef_sampler_type == 'nuts':  # gibbs_util.py:150-159
+            sampling_info = {key: np.zeros_like(sampling_info['stepsize'])
+                             for key in NUTS_INFO_KEYS}
         n_status_update = min(n_iter, n_status_update)
         stamp = time.time()
         for mcmc_iter in range(1, n_iter + 1):
             # beta | rest (bayesbridge.py:372-395)
-            if options.coef_sampler_type == 'hmc':
-                coef, info = sampler.sample_by_hmc(coef, gscale, lscale, model)
+            if hamiltonian:
+                coef, info = sampler.sample_by_hmc(
+                    coef, gscale, lscale, model,
+                    method=options.coef_sampler_type)
             elif model.name == 'linear':
                 coef, info = sampler.sample_gaussian_posterior(
                     model.y, design, obs_prec * np.ones(self.n_obs), gscale,

@@ -10,8 +10,8 @@ host synchronisation per trajectory).  The largest Hessian eigenvalue comes
 from SciPy's ARPACK on the host, as in the reference, with the device Hessian
 matvec behind it.  Every random number (the first eigenvector guess, dt, the
 integration time, the momentum, the accept uniform) comes from the global
-NumPy stream in the reference's order.  NUTS is not restated: the reference's
-Gibbs sampler never reaches it."""
+NumPy stream in the reference's order.  method='nuts' replaces the trajectory
+and the accept step by the No-U-Turn draw of nuts.py."""
 import math
 from math import copysign, exp, log, log10
 from warnings import warn
@@ -20,6 +20,7 @@ import numpy as np
 import scipy.sparse.linalg
 import scipy.stats
 
+from . import nuts
 from .reg_coef_sampler import (HipRegressionCoefficientSampler,
                                RegressionCoeffficientPosteriorSummarizer,
                                compute_prior_shrunk_scale)
@@ -269,8 +270,11 @@ class HipHMCCoefficientSampler():
         self.regcoef_summarizer.update_precond_hessian_pc(np.squeeze(eigvec))
         return 2 / np.sqrt(max_curvature), counter[0]
 
-    def sample_by_hmc(self, coef, gscale, lscale, model, max_step=512):
-        """reg_coef_sampler.py:105-172, method 'hmc'."""
+    def sample_by_hmc(self, coef, gscale, lscale, model, method='hmc',
+                      max_step=512):
+        """reg_coef_sampler.py:105-172, methods 'hmc' and 'nuts'."""
+        if method not in ('hmc', 'nuts'):
+            raise NotImplementedError()
         post_sd = self.regcoef_summarizer.estimate_coef_precond_scale_sd()
         precond_scale, precond_prior_prec = \
             self.compute_preconditioning_scale(gscale, lscale, post_sd)
@@ -285,6 +289,11 @@ class HipHMCCoefficientSampler():
             self.stability_adjustment_adapter.get_current_stepsize()
         dt = np.random.uniform(.5, 1) * (adjustment_factor * stability_limit)
         coef_precond = coef / precond_scale
+        if method == 'nuts':
+            return self._finish_nuts(
+                coef_precond, dt, model, precond_scale, precond_prior_prec,
+                int(math.log2(max_step)), gscale, lscale, n_hessian_matvec,
+                stability_limit, adjustment_factor)
         integration_time = np.pi / 2 * np.random.uniform(.8, 1.)
         n_step = min(int(np.ceil(integration_time / dt)), max_step)
         # f(q0) (hmc.py:95-97): the log-density and gradient in the
@@ -313,4 +322,26 @@ class HipHMCCoefficientSampler():
         info['stability_adjustment_factor'] = adjustment_factor
         info['momentum'] = hmc_info['momentum']
         info['hamiltonian_error'] = hmc_info['hamiltonian_error']
+        return coef, info
+
+    def _finish_nuts(self, coef_precond, dt, model, precond_scale,
+                     precond_prior_prec, max_height, gscale, lscale,
+                     n_hessian_matvec, stability_limit, adjustment_factor):
+        """reg_coef_sampler.py:149-172."""
+        coef_precond, nuts_info = nuts.generate_next_state(
+            model, dt, coef_precond, precond_scale, precond_prior_prec,
+            max_height=max_height)
+        info = {key: nuts_info[key] for key in (
+            'ave_accept_prob', 'n_grad_evals', 'tree_height',
+            'instability_detected')}
+        coef = coef_precond * precond_scale
+        self.regcoef_summarizer.update(coef, gscale, lscale)
+        self.stability_adjustment_adapter.adapt_stepsize(
+            nuts_info['ave_hamiltonian_error'])
+        info['n_hessian_matvec'] = n_hessian_matvec
+        info['stepsize'] = dt
+        info['stability_limit_est'] = stability_limit
+        info['stability_adjustment_factor'] = adjustment_factor
+        info['momentum'] = nuts_info['momentum']
+        info['hamiltonian_error'] = nuts_info['ave_hamiltonian_error']
         return coef, info

@@ -314,6 +314,50 @@ class CoxModel(_Model):
                 'n_steps': n_steps.value, 'instability': bool(instab.value),
                 'hamiltonian': ham}
 
+    def nuts_begin(self, precond_scale, prior_prec, q0, p0, logp0, grad0,
+                   joint_logp0, joint_logp_threshold, hamiltonian_tol=100.):
+        """Installs the single-state trajectory tree of a NUTS draw on the
+        handle (bbx_cox_nuts_begin; see nuts.py)."""
+        P = self.n_pred
+        arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in (
+            precond_scale, prior_prec, q0, p0, grad0)]
+        if any(a.shape != (P,) for a in arrays):
+            raise ValueError("trajectory vectors must have length %d" % P)
+        _lib.check(self._lib.bbx_cox_nuts_begin(
+            self._cox, *[_ptr(a) for a in arrays[:4]], float(logp0),
+            _ptr(arrays[4]), float(joint_logp0), float(joint_logp_threshold),
+            float(hamiltonian_tol)))
+
+    def nuts_doubling(self, dt, direction, height, uniforms):
+        """Doubles the tree by a half-tree of 2^height leapfrog steps in
+        `direction` (bbx_cox_nuts_doubling: one enqueue, one host wait).
+        uniforms: the 2^height numbers the merges may consume."""
+        uniforms = np.ascontiguousarray(uniforms, dtype=np.float64)
+        if height < 0 or uniforms.shape != (2 ** height,):
+            raise ValueError("a half-tree of height h takes 2^h uniforms")
+        n_unif, n_steps = c_int(), c_int()
+        flags, tree = np.zeros(3, np.int32), np.zeros(2, np.int32)
+        ave = np.zeros(2)
+        _lib.check(self._lib.bbx_cox_nuts_doubling(
+            self._cox, float(dt), int(direction), int(height), _ptr(uniforms),
+            byref(n_unif), byref(n_steps), _ptr(flags), _ptr(tree),
+            _ptr(ave)))
+        return {'n_uniform': n_unif.value, 'n_steps': n_steps.value,
+                'u_turn_detected': bool(flags[0]),
+                'instability_detected': bool(flags[1]),
+                'doubling_rejected': bool(flags[2]),
+                'height': int(tree[0]), 'n_acceptable_state': int(tree[1]),
+                'ave_hamiltonian_error': float(ave[0]),
+                'ave_accept_prob': float(ave[1])}
+
+    def nuts_sample(self):
+        """(q, logp, grad) of the tree's sample (bbx_cox_nuts_sample)."""
+        q, grad = np.empty(self.n_pred), np.empty(self.n_pred)
+        logp = c_double()
+        _lib.check(self._lib.bbx_cox_nuts_sample(
+            self._cox, _ptr(q), byref(logp), _ptr(grad)))
+        return q, logp.value, grad
+
     @staticmethod
     def simulate_outcome(X, beta, censoring_frac=.9, seed=None):
         """cox_model.py:275-298: exponential event times under a constant

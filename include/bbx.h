@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-/* 106: + bbx_design_transposed_fisher_info, bbx_woodbury_sample (the n-space
+/* 107: + the No-U-Turn sampler on the Cox model (bbx_cox_nuts_*).
+ * 106: + bbx_design_transposed_fisher_info, bbx_woodbury_sample (the n-space
  *      draw for dense designs with more columns than rows; the reference leaves
  *      it as a TODO, gibbs_util.py:66-68), BBX_SAMPLER_WOODBURY; dense designs
  *      of more than 19 200 columns.
@@ -45,7 +46,7 @@ extern "C" {
  *      bbx_setup_lock_acquire/_release, bbx_design_useful_bytes.  A binding
  *      compares bbx_version() with the BBX_VERSION it was written against
  *      (bayesbridge_amd/_lib.py does) instead of calling with a stale arity. */
-#define BBX_VERSION 106 /* 0.1.6 */
+#define BBX_VERSION 107 /* 0.1.7 */
 
 /* status codes */
 #define BBX_OK 0
@@ -753,6 +754,41 @@ int bbx_cox_hmc_trajectory(bbx_cox* cox, double dt, int n_step,
                            double hamiltonian_tol, double* q, double* p,
                            double* logp, double* grad, int* n_grad_evals,
                            int* instability, double* hamiltonian);
+
+/* The No-U-Turn sampler of hamiltonian_monte_carlo/nuts.py on the same f and
+ * integrator, one draw as  begin, doubling ..., sample.  The trajectory tree
+ * lives on the handle; no P-vector leaves the device before `sample`.
+ *
+ * begin: installs the tree of the single state q0, p0 (logp0 = f(q0), grad0 =
+ * grad f(q0)) with joint_logp0 = -(Hamiltonian at q0, p0), the slice
+ * threshold joint_logp0 - Exp(1) and the tolerance on max H - min H.
+ *
+ * doubling: _TrajectoryTree.double_trajectory (nuts.py:230-236): builds the
+ * next half-tree of 2^height leapfrog steps from the tree's end in
+ * `direction` (1 or -1; 0 <= height <= 10) and merges it.  The whole doubling
+ * is enqueued at once and the host waits once.  uniforms[2^height]: the
+ * numbers of np.random.uniform() in the order the reference would draw them;
+ * *n_uniform_used of them are consumed (one per merge that happens, the
+ * top-level one included; fewer when the half-tree ends early).  A half-tree
+ * ends at the first merged subtree that detects a U-turn or whose max H -
+ * min H exceeds the tolerance; *n_steps < 2^height then, and the doubling is
+ * rejected.  Outputs (each may be NULL), of the tree after the merge:
+ * flags[3] = {u_turn_detected, instability_detected, doubling rejected},
+ * tree[2] = {height, n_acceptable_state}, averages[2] =
+ * {ave_hamiltonian_error, ave_accept_prob}.
+ *
+ * sample: the tree's sample q, logp, grad (each may be NULL; grad is
+ * unspecified if logp is -inf).  Host pointers, synchronous. */
+int bbx_cox_nuts_begin(bbx_cox* cox, const double* precond_scale,
+                       const double* prior_prec, const double* q0,
+                       const double* p0, double logp0, const double* grad0,
+                       double joint_logp0, double joint_logp_threshold,
+                       double hamiltonian_tol);
+int bbx_cox_nuts_doubling(bbx_cox* cox, double dt, int direction, int height,
+                          const double* uniforms, int* n_uniform_used,
+                          int* n_steps, int* flags, int* tree,
+                          double* averages);
+int bbx_cox_nuts_sample(bbx_cox* cox, double* q, double* logp, double* grad);
 
 /* ----------------------- host-side reference-stream samplers (libbbx_hostrng)
  * Exported by the separate, HIP-free libbbx_hostrng.so.  `bitgen` is the

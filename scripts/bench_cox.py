@@ -1,7 +1,7 @@
-"""Cox model with the HMC coefficient sampler on the device:
+"""Cox model with the HMC or the NUTS coefficient sampler on the device:
 
     python scripts/bench_cox.py --shapes binary:1000000x50000 dense:100000x2000 \
-        --steps 5 --warmup 2
+        --steps 5 --warmup 2 [--sampler nuts]
 
 For each shape: a simulated Cox outcome (cox_model.py:275-298, demo
 coefficients, 90 % censored), then
@@ -15,6 +15,13 @@ coefficients, 90 % censored), then
   `warmup` (gibbs_resume), from global_scale .1, unit local scales and
   small random coefficients (no mode search).
 One JSON line per shape.
+
+--sampler nuts: leapfrog_us is one step of a 64-step half-tree (one doubling
+of height 6: the leaf and merge kernels included, one host wait), the Gibbs
+chain draws with 'nuts' from the same seeded start, mean_n_step is the mean
+number of leapfrog steps per draw, and mean_tree_height / mean_accept_prob
+replace accept_rate.  --profile-steps N then runs one half-tree of N steps
+(N a power of two up to 1024).
 
 --profile-steps N: only the trajectory and the products, for a kernel trace:
 
@@ -78,7 +85,21 @@ def products_us(design, reps):
     return (time.perf_counter() - tic) / reps * 1e6
 
 
-def run(kind, n, p, steps, warmup, seed=0, profile_steps=0):
+def nuts_half_tree(model, dt, height, scale, pp, q0, p0, logp0, grad0):
+    """One doubling of 2^height steps from a fresh tree; the step size is
+    far too small for a U-turn, so every step and every merge runs."""
+    joint = -(-logp0 + 0.5 * np.dot(p0, p0))
+    model.nuts_begin(scale, pp, q0, p0, logp0, grad0, joint, joint - 1., 1e300)
+    uniforms = np.random.RandomState(2).rand(2 ** height)
+    model.design.synchronize()
+    tic = time.perf_counter()
+    out = model.nuts_doubling(dt, 1, height, uniforms)
+    elapsed = time.perf_counter() - tic
+    assert out['n_steps'] == 2 ** height and not out['doubling_rejected'], out
+    return elapsed
+
+
+def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc'):
     X = make_X(kind, n, p, seed)
     beta = simulate.demo_beta(p)
     et, ct = CoxModel.simulate_outcome(X, beta, seed=seed)
@@ -119,15 +140,25 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0):
     logp0 = ll - np.sum(q0 ** 2) / 2
     grad0 = scale * g - q0
     n_traj = profile_steps or 64
-    model.hmc_trajectory(1e-3, 4, scale, pp, q0, p0, logp0, grad0, 1e300)
-    tic = time.perf_counter()
-    tr = model.hmc_trajectory(1e-3, n_traj, scale, pp, q0, p0, logp0, grad0,
-                              1e300)
-    leap_us = (time.perf_counter() - tic) / n_traj * 1e6
-    assert tr['n_steps'] == n_traj
+    if sampler == 'nuts':
+        height = n_traj.bit_length() - 1
+        if n_traj != 2 ** height or height > 10:
+            raise SystemExit("--profile-steps must be a power of two <= 1024 "
+                             "with --sampler nuts")
+        nuts_half_tree(model, 1e-3, 2, scale, pp, q0, p0, logp0, grad0)
+        leap_us = nuts_half_tree(model, 1e-3, height, scale, pp, q0, p0,
+                                 logp0, grad0) / n_traj * 1e6
+    else:
+        model.hmc_trajectory(1e-3, 4, scale, pp, q0, p0, logp0, grad0, 1e300)
+        tic = time.perf_counter()
+        tr = model.hmc_trajectory(1e-3, n_traj, scale, pp, q0, p0, logp0,
+                                  grad0, 1e300)
+        leap_us = (time.perf_counter() - tic) / n_traj * 1e6
+        assert tr['n_steps'] == n_traj
     prod_us = products_us(design, profile_steps or 50)
     if profile_steps:
-        return {'shape': '%s:%dx%d' % (kind, n, p), 'profile_steps': n_traj,
+        return {'shape': '%s:%dx%d' % (kind, n, p), 'sampler': sampler,
+                'profile_steps': n_traj,
                 'leapfrog_us': round(leap_us, 1),
                 'products_us': round(prod_us, 1)}
     prior = RegressionCoefPrior(bridge_exponent=.25,
@@ -137,21 +168,29 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0):
             'coef': rs.randn(P) * .01}
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        _, info = bridge.gibbs(warmup, init=init, seed=0)
+        _, info = bridge.gibbs(warmup, init=init, seed=0,
+                               coef_sampler_type=sampler)
         tic = time.perf_counter()
         _, info = bridge.gibbs_resume(info, steps)
     it_s = steps / (time.perf_counter() - tic)
     si = info['_reg_coef_sampling_info']
-    return {'shape': '%s:%dx%d' % (kind, n, p), 'n_event': model.n_event,
+    if sampler == 'nuts':
+        tail = {'mean_n_step': float(np.mean(si['n_grad_evals'] - 1)),
+                'mean_dt': float(np.mean(si['stepsize'])),
+                'mean_tree_height': float(np.mean(si['tree_height'])),
+                'mean_accept_prob': float(np.mean(si['ave_accept_prob']))}
+    else:
+        tail = {'mean_n_step': float(np.mean(si['n_integrator_step'])),
+                'mean_dt': float(np.mean(si['stepsize'])),
+                'accept_rate': float(np.mean(si['accepted']))}
+    return {'shape': '%s:%dx%d' % (kind, n, p), 'sampler': sampler,
+            'n_event': model.n_event,
             'preprocess_s': round(preprocess_s, 2),
             'grad_us': round(grad_us, 1), 'hvp_us': round(hvp_us, 1),
             'leapfrog_us': round(leap_us, 1),
             'products_us': round(prod_us, 1),
             'ratio': round(leap_us / prod_us, 3),
-            'gibbs_it_s': round(it_s, 3),
-            'mean_n_step': float(np.mean(si['n_integrator_step'])),
-            'mean_dt': float(np.mean(si['stepsize'])),
-            'accept_rate': float(np.mean(si['accepted']))}
+            'gibbs_it_s': round(it_s, 3), **tail}
 
 
 def main():
@@ -161,12 +200,14 @@ def main():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--profile-steps', type=int, default=0)
+    ap.add_argument('--sampler', choices=['hmc', 'nuts'], default='hmc')
     a = ap.parse_args()
     for s in a.shapes:
         kind, size = s.split(':')
         n, p = (int(x) for x in size.split('x'))
         print(json.dumps(run(kind, n, p, a.steps, a.warmup,
-                             profile_steps=a.profile_steps)), flush=True)
+                             profile_steps=a.profile_steps,
+                             sampler=a.sampler)), flush=True)
 
 
 if __name__ == '__main__':
