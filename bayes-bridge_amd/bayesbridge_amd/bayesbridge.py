@@ -48,7 +48,15 @@ def _ptr(a):
 
 
 class SamplerOptions():
-    """gibbs_util.py:7-84 restricted to what a HIP design supports."""
+    """gibbs_util.py:7-84 restricted to what a HIP design supports.
+
+    rng: 'device' or 'reference'; None takes 'reference' for 'hmc' / 'nuts'
+    (they draw from the reference's host streams only) and 'device' otherwise.
+    An instance handed to `BayesBridge.gibbs` counts as stating the choice:
+    SamplerOptions('hmc') on a logit model runs the whole chain, its
+    Polya-Gamma draws included, on the host streams.  The name-and-dictionary
+    route (`pick_default_and_create`) asks a logit chain for an explicit
+    rng='reference' instead."""
 
     def __init__(self, coef_sampler_type='cg', global_scale_update='sample',
                  hmc_curvature_est_stabilized=False, rng=None):
@@ -61,8 +69,8 @@ class SamplerOptions():
         if hamiltonian and rng != 'reference':
             # the HMC / NUTS draw takes its momentum, step size and uniforms
             # from the global NumPy stream, as the reference does
-            raise ValueError("The '%s' sampler (Cox model) runs with "
-                             "rng='reference' only." % coef_sampler_type)
+            raise ValueError("The '%s' sampler (Cox and logit models) runs "
+                             "with rng='reference' only." % coef_sampler_type)
         if rng not in ('device', 'reference'):
             raise ValueError("rng must be 'device' or 'reference'")
         if global_scale_update not in ('sample', 'optimize', None):
@@ -100,6 +108,18 @@ class SamplerOptions():
                      "model. Will use HMC instead.")
                 coef_sampler_type = None
             options['coef_sampler_type'] = coef_sampler_type or 'hmc'
+            return SamplerOptions(**options)
+        if model_name == 'logit' and coef_sampler_type in ('hmc', 'nuts'):
+            # gibbs_util.py:52-75 lets 'hmc' through for the logit model.  Its
+            # draw exists on the reference's host streams only, and a logit
+            # chain's default is the device RNG: the caller has to say so,
+            # a chain is not moved to host-side Polya-Gamma draws silently
+            if options.get('rng') != 'reference':
+                raise ValueError(
+                    "The '%s' sampler of the logit model draws from the "
+                    "reference's host streams: pass options={'rng': "
+                    "'reference'} to select it." % coef_sampler_type)
+            options['coef_sampler_type'] = coef_sampler_type
             return SamplerOptions(**options)
         if coef_sampler_type not in (None, 'cg') and not (
                 coef_sampler_type in ('cholesky', 'woodbury')
@@ -206,7 +226,11 @@ class BayesBridge():
         _device_out (device-RNG mode; chains.run_chains): {name: torch CUDA
         tensor, float64, contiguous, SAMPLE-major [n_sample, dim]} for names
         out of 'coef', 'local_scale', 'obs_prec' -- those samples are left in
-        HBM (ready for the RCCL gather) and are absent from `samples`."""
+        HBM (ready for the RCCL gather) and are absent from `samples`.
+
+        coef_sampler_type 'hmc' / 'nuts' on a logit model needs
+        options={'rng': 'reference'} (a SamplerOptions instance states its rng
+        itself: see SamplerOptions)."""
         if not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
                 coef_sampler_type, options, self.model.name, self.model.design)
@@ -215,7 +239,9 @@ class BayesBridge():
                 raise ValueError(
                     "Only 'cg' sampler supported with HIP matrices.")
         if options.coef_sampler_type in ('hmc', 'nuts') \
-                and self.model.name != 'cox':
+                and self.model.name not in ('cox', 'logit'):
+            # the reference's sample_by_hmc never passes obs_prec to the
+            # linear model's likelihood
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
         if params_to_save == 'all':
             params_to_save = ('coef', 'local_scale', 'global_scale', 'logp')
@@ -440,7 +466,8 @@ class BayesBridge():
                                  init, params_to_save, options, batch=batch)
 
     # ------------------------------------------------- shared initialisation
-    def _pre_allocate(self, n_post_burnin, thin, params_to_save):
+    def _pre_allocate(self, n_post_burnin, thin, params_to_save,
+                      coef_sampler_type='cg'):
         n_sample = math.floor(n_post_burnin / thin)        # gibbs_util.py:122
         samples = {}
         if 'coef' in params_to_save:
@@ -457,9 +484,10 @@ class BayesBridge():
                 samples['obs_prec'] = np.zeros((self.n_obs, n_sample))
         if 'logp' in params_to_save:
             samples['logp'] = np.zeros(n_sample)
-        if self.model.name == 'cox':                 # gibbs_util.py:141-160
-            return samples, {key: np.zeros(n_sample) for key in HMC_INFO_KEYS}
-        return samples, {'n_cg_iter': np.zeros(n_sample)}
+        info_keys = {'hmc': HMC_INFO_KEYS, 'nuts': NUTS_INFO_KEYS,
+                     'cg': ('n_cg_iter',)}.get(coef_sampler_type, ())
+        return samples, {key: np.zeros(n_sample)      # gibbs_util.py:141-160
+                         for key in info_keys}
 
     def _initial_obs_prec(self, init, coef):
         if self.model.name == 'cox':                    # bayesbridge.py:355-370
@@ -659,14 +687,9 @@ class BayesBridge():
                                    update_obs_precision, update_global_scale,
                                    sampler)
         samples, sampling_info = self._pre_allocate(
-            n_iter - n_burnin, thin, params_to_save)
-        if options.coef_sampler_type in ('cholesky', 'woodbury'):
-            sampling_info = {}       # gibbs_util.py:147-160: no n_cg_iter
-        info_keys = {'hmc': HMC_INFO_KEYS, 'nuts': NUTS_INFO_KEYS}.get(
-            options.coef_sampler_type, ('n_cg_iter',))
-        if options.coef_sampler_type == 'nuts':  # gibbs_util.py:150-159
-            sampling_info = {key: np.zeros_like(sampling_info['stepsize'])
-                             for key in NUTS_INFO_KEYS}
+            n_iter - n_burnin, thin, params_to_save,
+            options.coef_sampler_type)
+        info_keys = tuple(sampling_info) or ('n_cg_iter',)
         n_status_update = min(n_iter, n_status_update)
         stamp = time.time()
         for mcmc_iter in range(1, n_iter + 1):

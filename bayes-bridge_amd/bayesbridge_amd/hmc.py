@@ -1,12 +1,12 @@
 """HMC draw of the regression coefficients, the reference's only sampler for
-the Cox model: `sample_by_hmc` and its stability-limit estimate
+the Cox model and one it also accepts for the logit model: `sample_by_hmc` and its stability-limit estimate
 (reg_coef_sampler.py:105-240), the trajectory and accept step (hmc.py:88-174),
 the step-size adapter (stepsize_adapter.py:6-131), the stability-estimate
 stabilizer (reg_coef_sampler.py:394-429) and the Hessian principal-component
 summary (reg_coef_posterior_summarizer.py:22-67).
 
-The trajectory runs on the device in one call (bbx_cox_hmc_trajectory: one
-host synchronisation per trajectory).  The largest Hessian eigenvalue comes
+The trajectory runs on the device in one call (bbx_cox_hmc_trajectory /
+bbx_logit_hmc_trajectory: one host synchronisation per trajectory).  The largest Hessian eigenvalue comes
 from SciPy's ARPACK on the host, as in the reference, with the device Hessian
 matvec behind it.  Every random number (the first eigenvector guess, dt, the
 integration time, the momentum, the accept uniform) comes from the global
@@ -192,7 +192,7 @@ def generate_next_state(model, dt, n_step, q0, logp0, grad0, precond_scale,
 
 class HipHMCCoefficientSampler():
     """The 'hmc' branch of SparseRegressionCoefficientSampler
-    (reg_coef_sampler.py:20-58,105-279) on a device Cox model."""
+    (reg_coef_sampler.py:20-58,105-279) on a device Cox or logit model."""
 
     _sampling_info_attributes = ('regcoef_summarizer',
                                  'stability_adjustment_adapter',
@@ -298,7 +298,7 @@ class HipHMCCoefficientSampler():
         n_step = min(int(np.ceil(integration_time / dt)), max_step)
         # f(q0) (hmc.py:95-97): the log-density and gradient in the
         # preconditioned coordinates (reg_coef_sampler.py:259-279)
-        loglik, grad = model.compute_loglik_and_gradient(
+        loglik, grad = model.hamiltonian_loglik_and_gradient(
             coef_precond * precond_scale)
         logp0 = loglik + np.sum(-precond_prior_prec * coef_precond ** 2) / 2
         if math.isfinite(logp0):

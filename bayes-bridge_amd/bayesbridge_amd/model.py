@@ -2,7 +2,8 @@
 (model/factory.py:10-68, linear_model.py:6-45, logistic_model.py:6-116,
 cox_model.py:7-303).  The Cox likelihood, its gradient and its Hessian-vector
 products run on the device (csrc/cox.hip); its coefficients are drawn by HMC
-(hmc.py)."""
+(hmc.py).  The logit model has the same device path (csrc/logit.hip) for the
+'hmc' and 'nuts' coefficient samplers."""
 import math
 from ctypes import byref, c_double, c_int, c_void_p
 from warnings import warn
@@ -59,7 +60,119 @@ class LinearModel(_Model):
         return X.dot(beta) + noise_sd * np.random.randn(X.shape[0])
 
 
-class LogisticModel(_Model):
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(c_void_p)
+
+
+class _DeviceHamiltonian():
+    """The device trajectory and No-U-Turn tree of a likelihood handle
+    (csrc/hamiltonian.hpp): the same calls on bbx_cox_* and bbx_logit_*.  A
+    model names its family in `_ham_prefix` and gives its handle as
+    `handle`."""
+
+    def _ham_fn(self, name):
+        return getattr(_lib.load(), self._ham_prefix + name)
+
+    def _hessian_operator(self, beta):
+        """The handle holds one location: an operator stops working once a
+        later call has moved it."""
+        beta = np.ascontiguousarray(beta, dtype=np.float64)
+        if beta.shape != (self.n_pred,):
+            raise ValueError("beta must have length %d" % self.n_pred)
+        st = self._ham_fn('set_location')(self.handle, _ptr(beta))
+        self._location_serial += 1
+        if st == _lib.ERR_NUMERIC:
+            raise ValueError(
+                'Hessian operator cannot be computed likely due to an '
+                'unreasonable value of regression coefficients. This could '
+                'be caused by the likelihood and prior both being too weak '
+                'or by a poor initialization of the Markov chain.')
+        _lib.check(st)
+        serial = self._location_serial
+        matvec, handle = self._ham_fn('hessian_matvec'), self.handle
+
+        def hessian_op(v):
+            if serial != self._location_serial:
+                raise RuntimeError("the Hessian location has moved since this "
+                                   "operator was made")
+            v = np.ascontiguousarray(np.ravel(v), dtype=np.float64)
+            if v.shape != (self.n_pred,):
+                raise ValueError("v must have length %d" % self.n_pred)
+            out = np.empty(self.n_pred)
+            _lib.check(matvec(handle, _ptr(v), _ptr(out)))
+            return out
+
+        return hessian_op
+
+    def hmc_trajectory(self, dt, n_step, precond_scale, prior_prec, q0, p0,
+                       logp0, grad0, hamiltonian_tol=100.):
+        """n_step velocity-Verlet steps on the device (bbx_<family>_hmc_trajectory,
+        one host synchronisation).  Returns a dict: q, p, logp, grad (None if
+        logp is not finite), n_steps (steps taken), instability and
+        hamiltonian = [H at the start, H at the end]."""
+        P = self.n_pred
+        arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in (
+            precond_scale, prior_prec, q0, p0, grad0)]
+        if any(a.shape != (P,) for a in arrays):
+            raise ValueError("trajectory vectors must have length %d" % P)
+        q, p, grad, ham = np.empty(P), np.empty(P), np.empty(P), np.empty(2)
+        logp, n_steps, instab = c_double(), c_int(), c_int()
+        _lib.check(self._ham_fn('hmc_trajectory')(
+            self.handle, float(dt), int(n_step), *[_ptr(a) for a in arrays[:4]],
+            float(logp0), _ptr(arrays[4]), float(hamiltonian_tol), _ptr(q),
+            _ptr(p), byref(logp), _ptr(grad), byref(n_steps), byref(instab),
+            _ptr(ham)))
+        return {'q': q, 'p': p, 'logp': logp.value,
+                'grad': grad if math.isfinite(logp.value) else None,
+                'n_steps': n_steps.value, 'instability': bool(instab.value),
+                'hamiltonian': ham}
+
+    def nuts_begin(self, precond_scale, prior_prec, q0, p0, logp0, grad0,
+                   joint_logp0, joint_logp_threshold, hamiltonian_tol=100.):
+        """Installs the single-state trajectory tree of a NUTS draw on the
+        handle (bbx_<family>_nuts_begin; see nuts.py)."""
+        P = self.n_pred
+        arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in (
+            precond_scale, prior_prec, q0, p0, grad0)]
+        if any(a.shape != (P,) for a in arrays):
+            raise ValueError("trajectory vectors must have length %d" % P)
+        _lib.check(self._ham_fn('nuts_begin')(
+            self.handle, *[_ptr(a) for a in arrays[:4]], float(logp0),
+            _ptr(arrays[4]), float(joint_logp0), float(joint_logp_threshold),
+            float(hamiltonian_tol)))
+
+    def nuts_doubling(self, dt, direction, height, uniforms):
+        """Doubles the tree by a half-tree of 2^height leapfrog steps in
+        `direction` (bbx_<family>_nuts_doubling: one enqueue, one host wait).
+        uniforms: the 2^height numbers the merges may consume."""
+        uniforms = np.ascontiguousarray(uniforms, dtype=np.float64)
+        if height < 0 or uniforms.shape != (2 ** height,):
+            raise ValueError("a half-tree of height h takes 2^h uniforms")
+        n_unif, n_steps = c_int(), c_int()
+        flags, tree = np.zeros(3, np.int32), np.zeros(2, np.int32)
+        ave = np.zeros(2)
+        _lib.check(self._ham_fn('nuts_doubling')(
+            self.handle, float(dt), int(direction), int(height), _ptr(uniforms),
+            byref(n_unif), byref(n_steps), _ptr(flags), _ptr(tree),
+            _ptr(ave)))
+        return {'n_uniform': n_unif.value, 'n_steps': n_steps.value,
+                'u_turn_detected': bool(flags[0]),
+                'instability_detected': bool(flags[1]),
+                'doubling_rejected': bool(flags[2]),
+                'height': int(tree[0]), 'n_acceptable_state': int(tree[1]),
+                'ave_hamiltonian_error': float(ave[0]),
+                'ave_accept_prob': float(ave[1])}
+
+    def nuts_sample(self):
+        """(q, logp, grad) of the tree's sample (bbx_<family>_nuts_sample)."""
+        q, grad = np.empty(self.n_pred), np.empty(self.n_pred)
+        logp = c_double()
+        _lib.check(self._ham_fn('nuts_sample')(
+            self.handle, _ptr(q), byref(logp), _ptr(grad)))
+        return q, logp.value, grad
+
+
+class LogisticModel(_DeviceHamiltonian, _Model):
 
     def __init__(self, n_success, n_trial, design):
         """Outcome checks of logistic_model.py:10-47: counts must line up with
@@ -91,6 +204,28 @@ class LogisticModel(_Model):
         self.n_trial = n_trial
         self.design = design
         self.name = 'logit'
+        # the device likelihood of the 'hmc' / 'nuts' samplers: one bbx_logit
+        # handle, made by the first call that needs it
+        self._ham_prefix = 'bbx_logit_'
+        self._logit = c_void_p()
+        self._location_serial = 0
+
+    def __del__(self):
+        h = getattr(self, '_logit', None)
+        if h and not _lib.finalizing:
+            _lib.load().bbx_logit_destroy(h)
+        self._logit = c_void_p()
+
+    @property
+    def handle(self):
+        if not self._logit:
+            if not getattr(self.design, 'use_hip', False):
+                raise TypeError("the device likelihood needs a HipDesignMatrix")
+            y = np.ascontiguousarray(self.n_success, dtype=np.float64)
+            m = np.ascontiguousarray(self.n_trial, dtype=np.float64)
+            _lib.check(_lib.load().bbx_logit_create(
+                self.design.handle, _ptr(y), _ptr(m), byref(self._logit)))
+        return self._logit
 
     def compute_loglik_and_gradient(self, beta, loglik_only=False):
         logit_prob = self.design.dot(beta)           # logistic_model.py:49-60
@@ -101,6 +236,24 @@ class LogisticModel(_Model):
             prob = 1 / (1 + np.exp(-logit_prob))
             grad = self.design.Tdot(self.n_success - self.n_trial * prob)
         return loglik, grad
+
+    def hamiltonian_loglik_and_gradient(self, beta, loglik_only=False):
+        """The same likelihood on the device (bbx_logit_loglik_grad: fixed
+        summation orders, the gradient's X~^T product without a host round
+        trip): what the 'hmc' and 'nuts' samplers evaluate.  The other
+        samplers keep compute_loglik_and_gradient."""
+        beta = np.ascontiguousarray(beta, dtype=np.float64)
+        if beta.shape != (self.n_pred,):
+            raise ValueError("beta must have length %d" % self.n_pred)
+        loglik = c_double()
+        grad = None if loglik_only else np.empty(self.n_pred)
+        _lib.check(self._ham_fn('loglik_grad')(
+            self.handle, _ptr(beta), byref(loglik), _ptr(grad)))
+        return loglik.value, grad
+
+    def get_hessian_matvec_operator(self, beta):
+        """logistic_model.py:68-74 on the device."""
+        return self._hessian_operator(beta)
 
     def calc_intercept_mle(self):
         p_hat = self.n_success.mean() / self.n_trial.mean()
@@ -121,10 +274,6 @@ class LogisticModel(_Model):
         if seed is not None:
             np.random.seed(seed)
         return np.random.binomial(n_trial, prob)
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(c_void_p)
 
 
 def cox_sort_permutation(event_time, censoring_time):
@@ -208,7 +357,7 @@ def cox_risk_sets(event_time, censoring_time):
     return n_event, start, end, n_app
 
 
-class CoxModel(_Model):
+class CoxModel(_DeviceHamiltonian, _Model):
     """cox_model.py:7-303 on a HIP design whose rows are already in the
     model's order (RegressionModel(..., family='cox') sorts them).  The
     likelihood, its gradient and the Hessian-vector products run on the device
@@ -229,6 +378,7 @@ class CoxModel(_Model):
         self.n_appearance_in_risk_set = n_app
         self.design = design
         self.name = 'cox'
+        self._ham_prefix = 'bbx_cox_'
         self._lib = _lib.load()
         self._cox = c_void_p()
         self._location_serial = 0
@@ -267,96 +417,10 @@ class CoxModel(_Model):
     def get_hessian_matvec_operator(self, beta):
         """cox_model.py:251-273.  The handle holds one location: an operator
         stops working once a later call has moved it."""
-        beta = np.ascontiguousarray(beta, dtype=np.float64)
-        st = self._lib.bbx_cox_set_location(self._cox, _ptr(beta))
-        self._location_serial += 1
-        if st == _lib.ERR_NUMERIC:
-            raise ValueError(
-                'Hessian operator cannot be computed likely due to an '
-                'unreasonable value of regression coefficients. This could '
-                'be caused by the likelihood and prior both being too weak '
-                'or by a poor initialization of the Markov chain.')
-        _lib.check(st)
-        serial = self._location_serial
+        return self._hessian_operator(beta)
 
-        def hessian_op(v):
-            if serial != self._location_serial:
-                raise RuntimeError("the Hessian location has moved since this "
-                                   "operator was made")
-            v = np.ascontiguousarray(np.ravel(v), dtype=np.float64)
-            out = np.empty(self.n_pred)
-            _lib.check(self._lib.bbx_cox_hessian_matvec(
-                self._cox, _ptr(v), _ptr(out)))
-            return out
-
-        return hessian_op
-
-    def hmc_trajectory(self, dt, n_step, precond_scale, prior_prec, q0, p0,
-                       logp0, grad0, hamiltonian_tol=100.):
-        """n_step velocity-Verlet steps on the device (bbx_cox_hmc_trajectory,
-        one host synchronisation).  Returns a dict: q, p, logp, grad (None if
-        logp is not finite), n_steps (steps taken), instability and
-        hamiltonian = [H at the start, H at the end]."""
-        P = self.n_pred
-        arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in (
-            precond_scale, prior_prec, q0, p0, grad0)]
-        if any(a.shape != (P,) for a in arrays):
-            raise ValueError("trajectory vectors must have length %d" % P)
-        q, p, grad, ham = np.empty(P), np.empty(P), np.empty(P), np.empty(2)
-        logp, n_steps, instab = c_double(), c_int(), c_int()
-        _lib.check(self._lib.bbx_cox_hmc_trajectory(
-            self._cox, float(dt), int(n_step), *[_ptr(a) for a in arrays[:4]],
-            float(logp0), _ptr(arrays[4]), float(hamiltonian_tol), _ptr(q),
-            _ptr(p), byref(logp), _ptr(grad), byref(n_steps), byref(instab),
-            _ptr(ham)))
-        return {'q': q, 'p': p, 'logp': logp.value,
-                'grad': grad if math.isfinite(logp.value) else None,
-                'n_steps': n_steps.value, 'instability': bool(instab.value),
-                'hamiltonian': ham}
-
-    def nuts_begin(self, precond_scale, prior_prec, q0, p0, logp0, grad0,
-                   joint_logp0, joint_logp_threshold, hamiltonian_tol=100.):
-        """Installs the single-state trajectory tree of a NUTS draw on the
-        handle (bbx_cox_nuts_begin; see nuts.py)."""
-        P = self.n_pred
-        arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in (
-            precond_scale, prior_prec, q0, p0, grad0)]
-        if any(a.shape != (P,) for a in arrays):
-            raise ValueError("trajectory vectors must have length %d" % P)
-        _lib.check(self._lib.bbx_cox_nuts_begin(
-            self._cox, *[_ptr(a) for a in arrays[:4]], float(logp0),
-            _ptr(arrays[4]), float(joint_logp0), float(joint_logp_threshold),
-            float(hamiltonian_tol)))
-
-    def nuts_doubling(self, dt, direction, height, uniforms):
-        """Doubles the tree by a half-tree of 2^height leapfrog steps in
-        `direction` (bbx_cox_nuts_doubling: one enqueue, one host wait).
-        uniforms: the 2^height numbers the merges may consume."""
-        uniforms = np.ascontiguousarray(uniforms, dtype=np.float64)
-        if height < 0 or uniforms.shape != (2 ** height,):
-            raise ValueError("a half-tree of height h takes 2^h uniforms")
-        n_unif, n_steps = c_int(), c_int()
-        flags, tree = np.zeros(3, np.int32), np.zeros(2, np.int32)
-        ave = np.zeros(2)
-        _lib.check(self._lib.bbx_cox_nuts_doubling(
-            self._cox, float(dt), int(direction), int(height), _ptr(uniforms),
-            byref(n_unif), byref(n_steps), _ptr(flags), _ptr(tree),
-            _ptr(ave)))
-        return {'n_uniform': n_unif.value, 'n_steps': n_steps.value,
-                'u_turn_detected': bool(flags[0]),
-                'instability_detected': bool(flags[1]),
-                'doubling_rejected': bool(flags[2]),
-                'height': int(tree[0]), 'n_acceptable_state': int(tree[1]),
-                'ave_hamiltonian_error': float(ave[0]),
-                'ave_accept_prob': float(ave[1])}
-
-    def nuts_sample(self):
-        """(q, logp, grad) of the tree's sample (bbx_cox_nuts_sample)."""
-        q, grad = np.empty(self.n_pred), np.empty(self.n_pred)
-        logp = c_double()
-        _lib.check(self._lib.bbx_cox_nuts_sample(
-            self._cox, _ptr(q), byref(logp), _ptr(grad)))
-        return q, logp.value, grad
+    # the trajectory's f(q0) (hmc.py:95-97) is the model's own likelihood
+    hamiltonian_loglik_and_gradient = compute_loglik_and_gradient
 
     @staticmethod
     def simulate_outcome(X, beta, censoring_frac=.9, seed=None):

@@ -1,6 +1,7 @@
 """The No-U-Turn draw of the regression coefficients:
 NoUTurnSampler.generate_next_state (hamiltonian_monte_carlo/nuts.py:108-188)
-with the trajectory tree on the device (csrc/cox.hip, bbx_cox_nuts_*).
+with the trajectory tree on the device (csrc/hamiltonian.hpp; bbx_cox_nuts_*,
+bbx_logit_nuts_*).
 
 One doubling is one device call and one host wait.  Every random number comes
 from the global NumPy stream in the reference's order: the momentum, the
@@ -15,7 +16,7 @@ from warnings import warn
 
 import numpy as np
 
-MAX_HEIGHT = 10          # NUTS_MAXH of csrc/cox.hip
+MAX_HEIGHT = 10          # NUTS_MAXH of csrc/hamiltonian.hpp
 
 
 def draw_ahead(n):
@@ -35,7 +36,7 @@ def generate_next_state(model, dt, q, precond_scale, precond_prior_prec,
                         logp=None, grad=None, p=None, max_height=10,
                         hamiltonian_error_tol=100., warning_requested=True):
     """nuts.py:108-151 on f(q) = loglik(precond_scale q) - 1/2
-    sum(precond_prior_prec q^2) of a device Cox model.  Returns (q, info);
+    sum(precond_prior_prec q^2) of a device Cox or logit model.  Returns (q, info);
     info has the reference's keys plus 'directions', 'n_uniform' (uniforms
     consumed by the merges) and 'momentum'."""
     if not 1 <= max_height <= MAX_HEIGHT:
@@ -43,7 +44,7 @@ def generate_next_state(model, dt, q, precond_scale, precond_prior_prec,
     q = np.ascontiguousarray(q, dtype=np.float64)
     n_grad_evals = 0
     if logp is None or grad is None:
-        loglik, g = model.compute_loglik_and_gradient(q * precond_scale)
+        loglik, g = model.hamiltonian_loglik_and_gradient(q * precond_scale)
         logp = loglik + np.sum(-precond_prior_prec * q ** 2) / 2
         if math.isfinite(logp):
             grad = precond_scale * g

@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-/* 107: + the No-U-Turn sampler on the Cox model (bbx_cox_nuts_*).
+/* 108: + the logit likelihood with the HMC trajectory and the No-U-Turn
+ *      sampler of the Cox handle (bbx_logit_*).
+ * 107: + the No-U-Turn sampler on the Cox model (bbx_cox_nuts_*).
  * 106: + bbx_design_transposed_fisher_info, bbx_woodbury_sample (the n-space
  *      draw for dense designs with more columns than rows; the reference leaves
  *      it as a TODO, gibbs_util.py:66-68), BBX_SAMPLER_WOODBURY; dense designs
@@ -46,7 +48,7 @@ extern "C" {
  *      bbx_setup_lock_acquire/_release, bbx_design_useful_bytes.  A binding
  *      compares bbx_version() with the BBX_VERSION it was written against
  *      (bayesbridge_amd/_lib.py does) instead of calling with a stale arity. */
-#define BBX_VERSION 107 /* 0.1.7 */
+#define BBX_VERSION 108 /* 0.1.8 */
 
 /* status codes */
 #define BBX_OK 0
@@ -789,6 +791,59 @@ int bbx_cox_nuts_doubling(bbx_cox* cox, double dt, int direction, int height,
                           int* n_steps, int* flags, int* tree,
                           double* averages);
 int bbx_cox_nuts_sample(bbx_cox* cox, double* q, double* logp, double* grad);
+
+/* ----------------------------------------------------------- logit model
+ * The binomial-logit likelihood of model/logistic_model.py:49-74 on a design
+ * (intercept column and centred predictors included), with the trajectory and
+ * the No-U-Turn draw of the Cox handle on it (csrc/logit.hip; the leapfrog
+ * and tree kernels are the Cox handle's, csrc/hamiltonian.hpp).  Every entry
+ * point has the argument list, the status codes and the synchronisation of
+ * its bbx_cox_* counterpart above.  The handle borrows the design (it must
+ * outlive the handle) and runs on its stream.  Every sum has a fixed order:
+ * the same inputs give the same bits on every call.
+ *
+ * create: n_success[n], n_trial[n] (host).  BBX_ERR_INVALID for a NULL
+ * pointer, a destroyed or foreign design, a count that is not finite,
+ * n_success < 0, n_trial <= 0 or n_success > n_trial. */
+typedef struct bbx_logit bbx_logit;
+int bbx_logit_create(bbx_design* design, const double* n_success,
+                     const double* n_trial, bbx_logit** out);
+int bbx_logit_destroy(bbx_logit* logit);
+/* loglik = sum_i y_i eta_i - m_i logaddexp(0, eta_i), eta = X~ beta (y =
+ * n_success, m = n_trial); grad[P] = X~^T (y - m p), p = 1 / (1 + exp(-eta)).
+ * loglik is not finite only where an eta is not.  grad may be NULL. */
+int bbx_logit_loglik_grad(bbx_logit* logit, const double* beta, double* loglik,
+                          double* grad);
+int bbx_logit_loglik_grad_dev(bbx_logit* logit, const double* d_beta,
+                              double* loglik, double* d_grad);
+/* Hessian-vector products at a fixed beta (logistic_model.py:68-74):
+ * set_location stores d = m (p (1 - p)) at beta; hessian_matvec gives
+ * out = -X~^T (d .* (X~ v)) (BBX_ERR_STATE before a set_location). */
+int bbx_logit_set_location(bbx_logit* logit, const double* beta);
+int bbx_logit_hessian_matvec(bbx_logit* logit, const double* v, double* out);
+int bbx_logit_hessian_matvec_dev(bbx_logit* logit, const double* d_v,
+                                 double* d_out);
+/* bbx_cox_hmc_trajectory on the logit f. */
+int bbx_logit_hmc_trajectory(bbx_logit* logit, double dt, int n_step,
+                             const double* precond_scale,
+                             const double* prior_prec, const double* q0,
+                             const double* p0, double logp0,
+                             const double* grad0, double hamiltonian_tol,
+                             double* q, double* p, double* logp, double* grad,
+                             int* n_grad_evals, int* instability,
+                             double* hamiltonian);
+/* bbx_cox_nuts_begin / _doubling / _sample on the logit f. */
+int bbx_logit_nuts_begin(bbx_logit* logit, const double* precond_scale,
+                         const double* prior_prec, const double* q0,
+                         const double* p0, double logp0, const double* grad0,
+                         double joint_logp0, double joint_logp_threshold,
+                         double hamiltonian_tol);
+int bbx_logit_nuts_doubling(bbx_logit* logit, double dt, int direction,
+                            int height, const double* uniforms,
+                            int* n_uniform_used, int* n_steps, int* flags,
+                            int* tree, double* averages);
+int bbx_logit_nuts_sample(bbx_logit* logit, double* q, double* logp,
+                          double* grad);
 
 /* ----------------------- host-side reference-stream samplers (libbbx_hostrng)
  * Exported by the separate, HIP-free libbbx_hostrng.so.  `bitgen` is the
