@@ -8,12 +8,13 @@ from .cg_sampler import HipCGSampler
 from .device_chain import HipChainBatch, HipGibbsChain
 from .design_matrix import (HipDenseDesignMatrix, HipDesignMatrix,
                             HipSparseDesignMatrix)
-from .model import CoxModel, LinearModel, LogisticModel, RegressionModel
+from .model import (CoxModel, LinearModel, LogisticModel, PoissonModel,
+                    RegressionModel)
 from .prior import RegressionCoefPrior
 
 __all__ = [
     "BayesBridge", "RegressionModel", "RegressionCoefPrior", "SamplerOptions",
     "HipDesignMatrix", "HipSparseDesignMatrix", "HipDenseDesignMatrix",
-    "HipCGSampler", "HipGibbsChain", "HipChainBatch", "LinearModel", "LogisticModel", "CoxModel", "BbxError",
+    "HipCGSampler", "HipGibbsChain", "HipChainBatch", "LinearModel", "LogisticModel", "CoxModel", "PoissonModel", "BbxError",
     "device_count",
 ]

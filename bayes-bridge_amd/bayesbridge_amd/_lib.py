@@ -12,7 +12,7 @@ from ctypes import (POINTER, byref, c_char_p, c_double, c_int, c_int32,
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libbbx.so")
 
-ABI_VERSION = 108          # BBX_VERSION of include/bbx.h
+ABI_VERSION = 109          # BBX_VERSION of include/bbx.h
 FORMAT_AUTO, FORMAT_CSR, FORMAT_TILED = 0, 1, 2
 F64, F32 = 0, 1
 MODEL_LINEAR, MODEL_LOGIT = 0, 1
@@ -244,6 +244,28 @@ def _declare(lib):
             [hp, c_double, c_int, c_int, c_void_p, POINTER(c_int),
              POINTER(c_int), c_void_p, c_void_p, c_void_p], c_int),
         "bbx_logit_nuts_sample": (
+            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
+        "bbx_poisson_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
+        "bbx_poisson_destroy": ([hp], c_int),
+        "bbx_poisson_loglik_grad": (
+            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
+        "bbx_poisson_loglik_grad_dev": (
+            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
+        "bbx_poisson_set_location": ([hp, c_void_p], c_int),
+        "bbx_poisson_hessian_matvec": ([hp, c_void_p, c_void_p], c_int),
+        "bbx_poisson_hessian_matvec_dev": ([hp, c_void_p, c_void_p], c_int),
+        "bbx_poisson_hmc_trajectory": (
+            [hp, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_double, c_void_p, c_double, c_void_p, c_void_p,
+             POINTER(c_double), c_void_p, POINTER(c_int), POINTER(c_int),
+             c_void_p], c_int),
+        "bbx_poisson_nuts_begin": (
+            [hp, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
+             c_double, c_double, c_double], c_int),
+        "bbx_poisson_nuts_doubling": (
+            [hp, c_double, c_int, c_int, c_void_p, POINTER(c_int),
+             POINTER(c_int), c_void_p, c_void_p, c_void_p], c_int),
+        "bbx_poisson_nuts_sample": (
             [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
     }
     for name, (argtypes, restype) in sigs.items():

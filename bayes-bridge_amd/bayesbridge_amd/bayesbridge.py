@@ -41,6 +41,9 @@ HMC_INFO_KEYS = ('stepsize', 'n_hessian_matvec', 'n_grad_evals',
                  'instability_detected', 'n_integrator_step', 'accepted',
                  'accept_prob')
 NUTS_INFO_KEYS = HMC_INFO_KEYS[:6] + ('tree_height', 'ave_accept_prob')
+# models without an observation precision (or Polya-Gamma) parameter: their
+# chains carry no 'obs_prec' and draw the coefficients by 'hmc' / 'nuts' only
+NO_OBS_PREC = ('cox', 'poisson')
 
 
 def _ptr(a):
@@ -69,7 +72,7 @@ class SamplerOptions():
         if hamiltonian and rng != 'reference':
             # the HMC / NUTS draw takes its momentum, step size and uniforms
             # from the global NumPy stream, as the reference does
-            raise ValueError("The '%s' sampler (Cox and logit models) runs "
+            raise ValueError("The '%s' sampler (Cox, logit and Poisson models) runs "
                              "with rng='reference' only." % coef_sampler_type)
         if rng not in ('device', 'reference'):
             raise ValueError("rng must be 'device' or 'reference'")
@@ -107,6 +110,17 @@ class SamplerOptions():
                 warn("Specified sampler type is not supported for the cox "
                      "model. Will use HMC instead.")
                 coef_sampler_type = None
+            options['coef_sampler_type'] = coef_sampler_type or 'hmc'
+            return SamplerOptions(**options)
+        if model_name == 'poisson':
+            # no Polya-Gamma form: there is no Gaussian conditional for 'cg',
+            # 'cholesky' or 'woodbury' to draw from, and a chain that was
+            # asked for one of them is not run with another sampler
+            if coef_sampler_type not in (None, 'hmc', 'nuts'):
+                raise ValueError(
+                    "The Poisson model draws its coefficients with 'hmc' or "
+                    "'nuts' only; '%s' needs a Gaussian conditional."
+                    % coef_sampler_type)
             options['coef_sampler_type'] = coef_sampler_type or 'hmc'
             return SamplerOptions(**options)
         if model_name == 'logit' and coef_sampler_type in ('hmc', 'nuts'):
@@ -238,14 +252,18 @@ class BayesBridge():
             if not _is_hip_dense(self.model.design):
                 raise ValueError(
                     "Only 'cg' sampler supported with HIP matrices.")
+        if self.model.name == 'poisson' \
+                and options.coef_sampler_type not in ('hmc', 'nuts'):
+            raise ValueError("The Poisson model draws its coefficients with "
+                             "'hmc' or 'nuts' only.")
         if options.coef_sampler_type in ('hmc', 'nuts') \
-                and self.model.name not in ('cox', 'logit'):
+                and self.model.name not in ('cox', 'logit', 'poisson'):
             # the reference's sample_by_hmc never passes obs_prec to the
             # linear model's likelihood
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
         if params_to_save == 'all':
             params_to_save = ('coef', 'local_scale', 'global_scale', 'logp')
-            if self.model.name != 'cox':              # bayesbridge.py:187-191
+            if self.model.name not in NO_OBS_PREC:    # bayesbridge.py:187-191
                 params_to_save += ('obs_prec',)
         start_time = time.time()
         if options.rng == 'reference':
@@ -317,7 +335,7 @@ class BayesBridge():
 
     def _pack_state(self, coef, obs_prec, lscale, gscale):
         state = {'coef': coef, 'local_scale': lscale, 'global_scale': gscale}
-        if self.model.name != 'cox':                   # gibbs_util.py:197-205
+        if self.model.name not in NO_OBS_PREC:         # gibbs_util.py:197-205
             state['obs_prec'] = obs_prec
         return state
 
@@ -398,7 +416,8 @@ class BayesBridge():
         if not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
                 None, options, self.model.name, self.model.design)
-        if options.coef_sampler_type != 'cg' or self.model.name == 'cox':
+        if options.coef_sampler_type != 'cg' \
+                or self.model.name in NO_OBS_PREC:
             raise ValueError("batched chains draw the coefficients with 'cg' "
                              "only")
         if options.rng != 'device':
@@ -451,7 +470,7 @@ class BayesBridge():
         samples[name] shaped (n_chain, ..., n_sample) on rank 0.  `batch`:
         False (default; chain k's samples do not depend on the number of
         ranks), 'auto' or a width -- see chains.run_chains."""
-        if self.model.name == 'cox':
+        if self.model.name in NO_OBS_PREC:
             raise ValueError("gibbs_multichain draws the coefficients with "
                              "'cg' only; the Cox model needs 'hmc'")
         if options is not None:
@@ -477,7 +496,8 @@ class BayesBridge():
                 (self.n_pred - self.n_unshrunk, n_sample))
         if 'global_scale' in params_to_save:
             samples['global_scale'] = np.zeros(n_sample)
-        if 'obs_prec' in params_to_save and self.model.name != 'cox':
+        if 'obs_prec' in params_to_save \
+                and self.model.name not in NO_OBS_PREC:
             if self.model.name == 'linear':
                 samples['obs_prec'] = np.zeros(n_sample)
             else:
@@ -490,7 +510,7 @@ class BayesBridge():
                          for key in info_keys}
 
     def _initial_obs_prec(self, init, coef):
-        if self.model.name == 'cox':                    # bayesbridge.py:355-370
+        if self.model.name in NO_OBS_PREC:              # bayesbridge.py:355-370
             return None
         if 'obs_prec' in init:                          # bayesbridge.py:355-370
             obs_prec = np.array(init['obs_prec'], dtype=np.float64, copy=True,
@@ -616,7 +636,7 @@ class BayesBridge():
         nu = self.n_unshrunk
 
         def update_obs_precision(coef):                  # bayesbridge.py:397-410
-            if model.name == 'cox':
+            if model.name in NO_OBS_PREC:
                 return None
             if model.name == 'linear':
                 resid = model.y - design.dot(coef)

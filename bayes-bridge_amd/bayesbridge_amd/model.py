@@ -3,7 +3,8 @@
 cox_model.py:7-303).  The Cox likelihood, its gradient and its Hessian-vector
 products run on the device (csrc/cox.hip); its coefficients are drawn by HMC
 (hmc.py).  The logit model has the same device path (csrc/logit.hip) for the
-'hmc' and 'nuts' coefficient samplers."""
+'hmc' and 'nuts' coefficient samplers, and the Poisson model (csrc/poisson.hip)
+has no other."""
 import math
 from ctypes import byref, c_double, c_int, c_void_p
 from warnings import warn
@@ -66,9 +67,9 @@ def _ptr(a):
 
 class _DeviceHamiltonian():
     """The device trajectory and No-U-Turn tree of a likelihood handle
-    (csrc/hamiltonian.hpp): the same calls on bbx_cox_* and bbx_logit_*.  A
-    model names its family in `_ham_prefix` and gives its handle as
-    `handle`."""
+    (csrc/hamiltonian.hpp): the same calls on bbx_cox_*, bbx_logit_* and
+    bbx_poisson_*.  A model names its family in `_ham_prefix` and gives its
+    handle as `handle`."""
 
     def _ham_fn(self, name):
         return getattr(_lib.load(), self._ham_prefix + name)
@@ -276,6 +277,95 @@ class LogisticModel(_DeviceHamiltonian, _Model):
         return np.random.binomial(n_trial, prob)
 
 
+class PoissonModel(_DeviceHamiltonian, _Model):
+    """Incidence-rate regression: counts y_i with mean exposure_i exp(eta_i).
+    The likelihood, its gradient and the Hessian-vector products run on the
+    device through one bbx_poisson handle (csrc/poisson.hip); the coefficients
+    are drawn by 'hmc' or 'nuts', as the Cox model's are."""
+
+    def __init__(self, y, exposure, design):
+        """Counts must line up with the rows of the design and be
+        non-negative integers (integer-valued floats are accepted); exposure
+        (None: 1 for every row) must be strictly positive and finite."""
+        n_row = design.shape[0]
+        y = np.asarray(y, dtype=np.float64)
+        if exposure is None:
+            exposure = np.ones(y.shape)
+        else:
+            exposure = np.asarray(exposure, dtype=np.float64)
+        if not (y.shape == exposure.shape == (n_row,)):
+            raise ValueError(
+                "Outcome vectors and design matrix have incompatible sizes: "
+                "%s counts, %s exposures, %d rows."
+                % (y.shape, exposure.shape, n_row))
+        if not np.all(np.isfinite(y)) or (y < 0).any() \
+                or (y != np.floor(y)).any():
+            raise ValueError("Every count must be a non-negative integer.")
+        if not np.all(np.isfinite(exposure)) or (exposure <= 0).any():
+            raise ValueError(
+                "Every exposure must be strictly positive and finite.")
+        self.y = y
+        self.exposure = exposure
+        self.log_exposure = np.log(exposure)
+        self.design = design
+        self.name = 'poisson'
+        # one bbx_poisson handle, made by the first call that needs it
+        self._ham_prefix = 'bbx_poisson_'
+        self._poisson = c_void_p()
+        self._location_serial = 0
+
+    def __del__(self):
+        h = getattr(self, '_poisson', None)
+        if h and not _lib.finalizing:
+            _lib.load().bbx_poisson_destroy(h)
+        self._poisson = c_void_p()
+
+    @property
+    def handle(self):
+        if not self._poisson:
+            if not getattr(self.design, 'use_hip', False):
+                raise TypeError("the device likelihood needs a HipDesignMatrix")
+            y = np.ascontiguousarray(self.y, dtype=np.float64)
+            o = np.ascontiguousarray(self.log_exposure, dtype=np.float64)
+            _lib.check(_lib.load().bbx_poisson_create(
+                self.design.handle, _ptr(y), _ptr(o), byref(self._poisson)))
+        return self._poisson
+
+    def compute_loglik_and_gradient(self, beta, loglik_only=False):
+        """sum y eta - mu and X~^T (y - mu), mu = exposure exp(eta) (the terms
+        constant in beta are dropped); (-inf, None) where a mean overflows."""
+        beta = np.ascontiguousarray(beta, dtype=np.float64)
+        if beta.shape != (self.n_pred,):
+            raise ValueError("beta must have length %d" % self.n_pred)
+        loglik = c_double()
+        grad = None if loglik_only else np.empty(self.n_pred)
+        _lib.check(self._ham_fn('loglik_grad')(
+            self.handle, _ptr(beta), byref(loglik), _ptr(grad)))
+        if loglik.value == -float('inf'):
+            return -float('inf'), None
+        return loglik.value, grad
+
+    # the trajectory's f(q0) (hmc.py:95-97) is the model's own likelihood
+    hamiltonian_loglik_and_gradient = compute_loglik_and_gradient
+
+    def get_hessian_matvec_operator(self, beta):
+        """v -> -X~^T (mu .* (X~ v)) at beta.  The handle holds one location:
+        an operator stops working once a later call has moved it."""
+        return self._hessian_operator(beta)
+
+    def calc_intercept_mle(self):
+        return np.log(self.y.sum() / self.exposure.sum())
+
+    @staticmethod
+    def simulate_outcome(X, beta, exposure=None, seed=None):
+        rate = np.exp(np.asarray(X.dot(beta), dtype=np.float64).ravel())
+        if exposure is not None:
+            rate = rate * np.asarray(exposure, dtype=np.float64)
+        if seed is not None:
+            np.random.seed(seed)
+        return np.random.poisson(rate)
+
+
 def cox_sort_permutation(event_time, censoring_time):
     """The row order of cox_model.py:70-121 (None: already in order): events
     by increasing time, then censored rows by decreasing censoring time.  The
@@ -449,7 +539,7 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     For family='cox', outcome = (event_time, censoring_time): the rows are
     sorted into the model's order (and uninformative ones dropped) before the
     design goes to the GPU; a prebuilt HipDesignMatrix must already be in that
-    order."""
+    order.  For family='poisson', outcome = y or (y, exposure)."""
     if add_intercept is None:
         add_intercept = (family != 'cox')
     if family == 'cox':
@@ -495,4 +585,10 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         return LogisticModel(n_success, n_trial, design)
     if family == 'cox':
         return CoxModel(event_time, censoring_time, design)
+    if family == 'poisson':
+        if isinstance(outcome, tuple):
+            y, exposure = outcome
+        else:
+            y, exposure = outcome, None
+        return PoissonModel(y, exposure, design)
     raise NotImplementedError()

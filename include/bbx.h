@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-/* 108: + the logit likelihood with the HMC trajectory and the No-U-Turn
+/* 109: + the Poisson likelihood (log link, exposure offset) with the HMC
+ *      trajectory and the No-U-Turn sampler of the Cox handle (bbx_poisson_*).
+ * 108: + the logit likelihood with the HMC trajectory and the No-U-Turn
  *      sampler of the Cox handle (bbx_logit_*).
  * 107: + the No-U-Turn sampler on the Cox model (bbx_cox_nuts_*).
  * 106: + bbx_design_transposed_fisher_info, bbx_woodbury_sample (the n-space
@@ -48,7 +50,7 @@ extern "C" {
  *      bbx_setup_lock_acquire/_release, bbx_design_useful_bytes.  A binding
  *      compares bbx_version() with the BBX_VERSION it was written against
  *      (bayesbridge_amd/_lib.py does) instead of calling with a stale arity. */
-#define BBX_VERSION 108 /* 0.1.8 */
+#define BBX_VERSION 109 /* 0.1.9 */
 
 /* status codes */
 #define BBX_OK 0
@@ -844,6 +846,65 @@ int bbx_logit_nuts_doubling(bbx_logit* logit, double dt, int direction,
                             int* tree, double* averages);
 int bbx_logit_nuts_sample(bbx_logit* logit, double* q, double* logp,
                           double* grad);
+
+/* --------------------------------------------------------- Poisson model
+ * Incidence-rate regression on a design (intercept column and centred
+ * predictors included): counts y_i >= 0 with mean mu_i = exp(eta_i + o_i),
+ * eta = X~ beta, o = log(exposure), with the trajectory and the No-U-Turn
+ * draw of the Cox handle on it (csrc/poisson.hip; the leapfrog and tree
+ * kernels are the Cox handle's, csrc/hamiltonian.hpp).  Every entry point but
+ * create has the argument list, the status codes and the synchronisation of
+ * its bbx_logit_* counterpart above.  The handle borrows the design (it must
+ * outlive the handle) and runs on its stream.  Every sum has a fixed order:
+ * the same inputs give the same bits on every call.
+ *
+ * create: y[n], log_exposure[n] (host; log_exposure may be NULL: all 0).
+ * BBX_ERR_INVALID for a NULL y or output pointer, a destroyed or foreign
+ * design, a count that is negative or not finite, an offset that is not
+ * finite. */
+typedef struct bbx_poisson bbx_poisson;
+int bbx_poisson_create(bbx_design* design, const double* y,
+                       const double* log_exposure, bbx_poisson** out);
+int bbx_poisson_destroy(bbx_poisson* poisson);
+/* loglik = sum_i y_i eta_i - mu_i (the terms constant in beta, sum_i y_i o_i -
+ * log y_i!, are dropped); grad[P] = X~^T (y - mu).  Where eta_i + o_i is past
+ * exp's range loglik is -inf and grad is not meaningful; a NaN in beta gives
+ * NaN.  grad may be NULL. */
+int bbx_poisson_loglik_grad(bbx_poisson* poisson, const double* beta,
+                            double* loglik, double* grad);
+int bbx_poisson_loglik_grad_dev(bbx_poisson* poisson, const double* d_beta,
+                                double* loglik, double* d_grad);
+/* Hessian-vector products at a fixed beta: set_location stores mu at beta;
+ * hessian_matvec gives out = -X~^T (mu .* (X~ v)) (BBX_ERR_STATE before a
+ * set_location). */
+int bbx_poisson_set_location(bbx_poisson* poisson, const double* beta);
+int bbx_poisson_hessian_matvec(bbx_poisson* poisson, const double* v,
+                               double* out);
+int bbx_poisson_hessian_matvec_dev(bbx_poisson* poisson, const double* d_v,
+                                   double* d_out);
+/* bbx_cox_hmc_trajectory on the Poisson f.  A step at which the likelihood
+ * overflows is the last one: logp = -inf, *instability = 1. */
+int bbx_poisson_hmc_trajectory(bbx_poisson* poisson, double dt, int n_step,
+                               const double* precond_scale,
+                               const double* prior_prec, const double* q0,
+                               const double* p0, double logp0,
+                               const double* grad0, double hamiltonian_tol,
+                               double* q, double* p, double* logp,
+                               double* grad, int* n_grad_evals,
+                               int* instability, double* hamiltonian);
+/* bbx_cox_nuts_begin / _doubling / _sample on the Poisson f.  An overflow
+ * ends the half-tree as an empty risk-set sum ends the Cox handle's. */
+int bbx_poisson_nuts_begin(bbx_poisson* poisson, const double* precond_scale,
+                           const double* prior_prec, const double* q0,
+                           const double* p0, double logp0, const double* grad0,
+                           double joint_logp0, double joint_logp_threshold,
+                           double hamiltonian_tol);
+int bbx_poisson_nuts_doubling(bbx_poisson* poisson, double dt, int direction,
+                              int height, const double* uniforms,
+                              int* n_uniform_used, int* n_steps, int* flags,
+                              int* tree, double* averages);
+int bbx_poisson_nuts_sample(bbx_poisson* poisson, double* q, double* logp,
+                            double* grad);
 
 /* ----------------------- host-side reference-stream samplers (libbbx_hostrng)
  * Exported by the separate, HIP-free libbbx_hostrng.so.  `bitgen` is the

@@ -1,0 +1,616 @@
+"""GPU: the Poisson model (csrc/poisson.hip on csrc/hamiltonian.hpp) -- the
+likelihood, its gradient and Hessian matvec against the NumPy oracle
+(tests/poisson_oracle.py) at the row counts where the row kernel changes
+path, the overflow rule, the trajectory against a host velocity Verlet,
+No-U-Turn doublings against tests/nuts_oracle.py, whole seeded chains against
+the same driver on the oracle model, the refusals and one statistical check.
+There is no reference implementation of this family: the oracle is the
+yardstick throughout."""
+import os
+import re
+import warnings
+from ctypes import byref, c_double, c_int, c_void_p
+
+import numpy as np
+import pytest
+import scipy.sparse as sparse
+
+import logit_oracle as lo
+import nuts_oracle as no
+import poisson_oracle as po
+from conftest import ROOT
+
+pytestmark = pytest.mark.gpu
+
+RTOL, ATOL = 1e-6, 1e-9          # the seeded Hamiltonian chains' tolerance
+
+
+def _constant(name, src):
+    text = open(os.path.join(ROOT, 'bayes-bridge_amd', 'csrc', src)).read()
+    return int(re.search(r'constexpr int %s = (\d+);' % name, text).group(1))
+
+
+# the row kernel's geometry: row i belongs to workgroup (i / VEC_BLOCK) %
+# NPART, a thread keeps U rows of consecutive laps in flight
+VEC_BLOCK = _constant('VEC_BLOCK', 'common.hpp')
+NPART = _constant('NPART', 'common.hpp')
+U = _constant('POISSON_U', 'poisson.hip')
+LAP = NPART * VEC_BLOCK
+ROWS = (1, VEC_BLOCK - 1, VEC_BLOCK + 1, LAP + 1, U * LAP + 3)
+KINDS = ('tiled_binary', 'csr_valued', 'dense64', 'dense32', 'mixed')
+
+
+def _design_and_matrix(kind, n, p, intercept, center, seed):
+    """A device design and the host matrix the oracle multiplies with."""
+    from bayesbridge_amd import (HipDenseDesignMatrix, HipSparseDesignMatrix,
+                                 simulate)
+    rs = np.random.RandomState(seed)
+    if kind == 'tiled_binary':
+        X = simulate.simulate_binary_csr_fast(n, p, .2, seed=seed)
+    elif kind == 'csr_valued':
+        X = sparse.random(n, p, density=.3, format='csr', random_state=rs)
+    elif kind == 'mixed':
+        X = simulate.simulate_design_csr(n, p, binary_frac=.8, seed=seed)
+    else:
+        X = rs.randn(n, p)
+    if kind in ('tiled_binary', 'mixed'):
+        dsn = HipSparseDesignMatrix(X, add_intercept=intercept,
+                                    center_predictor=center, storage='tiled')
+    elif kind == 'csr_valued':
+        dsn = HipSparseDesignMatrix(X, add_intercept=intercept,
+                                    center_predictor=center, storage='csr')
+    else:
+        dtype = 'float32' if kind == 'dense32' else 'float64'
+        dsn = HipDenseDesignMatrix(X, add_intercept=intercept,
+                                   center_predictor=center,
+                                   storage_dtype=dtype)
+    assert dsn.shape == (n, p + int(intercept))
+    if kind == 'dense32':
+        # float32 storage holds the CENTRED entries rounded to float32
+        if center:
+            X = X - dsn.column_offset
+        X = X.astype(np.float32).astype(np.float64)
+        return dsn, lo.design(X, False, intercept)
+    return dsn, lo.design(X, center, intercept,
+                          offset=dsn.column_offset if center else None)
+
+
+def _poisson_data(kind, n, p, intercept=True, center=True, exposure=True,
+                  seed=0):
+    """A device Poisson model, the oracle's design, the counts and the
+    offset."""
+    from bayesbridge_amd import RegressionModel
+    dsn, D = _design_and_matrix(kind, n, p, intercept, center, seed)
+    rs = np.random.RandomState(seed + 1)
+    beta = rs.randn(p) * .3
+    e = rs.uniform(.5, 2., n) if exposure else None
+    rate = np.exp(.2 + np.asarray(D[0].dot(beta)).ravel())
+    y = rs.poisson(rate * (e if exposure else 1.)).astype(np.float64)
+    model = RegressionModel((y, e) if exposure else y, dsn, 'poisson')
+    assert model.name == 'poisson' and model.design is dsn
+    return model, D, y, (np.log(e) if exposure else np.zeros(n))
+
+
+# (kind, n, p, add_intercept, center_predictor, exposure)
+CASES = [(kind, n, 7 if n > LAP else 23, True, True, True)
+         for kind in KINDS for n in ROWS] + [
+    (kind, VEC_BLOCK + 1, 23) + flags for kind in KINDS for flags in (
+        (False, True, True), (True, False, True), (False, False, True),
+        (True, True, False), (False, False, False))]
+
+
+@pytest.mark.parametrize('case', range(len(CASES)))
+def test_likelihood_gradient_hessian_match_the_oracle(case, monkeypatch):
+    kind, n, p, intercept, center, exposure = CASES[case]
+    if n == 1:
+        # every column of a single row is "constant", and the design classes
+        # drop constant columns as hand-made intercepts: keep them, the row
+        # kernel is what this case is about
+        from bayesbridge_amd import design_matrix
+        monkeypatch.setattr(design_matrix, 'remove_intercept_indicator',
+                            lambda X: X)
+    model, D, y, o = _poisson_data(kind, n, p, intercept, center, exposure,
+                                   seed=case)
+    assert (o != 0).any() == exposure
+    P = p + int(intercept)
+    rs = np.random.RandomState(1)
+    for k, beta in enumerate((rs.randn(P) * .1, rs.randn(P) * .4)):
+        v = rs.randn(P)
+        ll, grad = model.compute_loglik_and_gradient(beta)
+        oll, ograd = po.loglik_grad(D, y, o, beta)
+        print(kind, n, p, 'beta', k, 'max eta+o %.3g'
+              % (lo.dot(D, beta) + o).max(), 'loglik', ll, oll,
+              'grad max|d| %.2e of %.3g' % (np.abs(grad - ograd).max(),
+                                            np.abs(ograd).max()))
+        assert np.isfinite(oll)
+        np.testing.assert_allclose(ll, oll, rtol=RTOL, atol=ATOL)
+        np.testing.assert_allclose(grad, ograd, rtol=RTOL, atol=ATOL)
+        ll2, grad2 = model.compute_loglik_and_gradient(beta)
+        assert ll2 == ll and np.array_equal(grad2, grad)
+        hv = model.get_hessian_matvec_operator(beta)(v)
+        ohv = po.hessian_matvec(D, y, o, beta, v)
+        print('   hessian max|d| %.2e of %.3g' % (np.abs(hv - ohv).max(),
+                                                  np.abs(ohv).max()))
+        np.testing.assert_allclose(hv, ohv, rtol=RTOL, atol=ATOL)
+        hv2 = model.get_hessian_matvec_operator(beta)(v)
+        assert np.array_equal(hv2, hv)
+    ll, none = model.compute_loglik_and_gradient(beta, loglik_only=True)
+    assert none is None and ll == ll2
+    assert model.hamiltonian_loglik_and_gradient(beta)[0] == ll2
+
+
+def test_an_operator_stops_once_the_location_has_moved():
+    model, D, y, o = _poisson_data('dense64', 100, 20)
+    rs = np.random.RandomState(2)
+    op = model.get_hessian_matvec_operator(rs.randn(21) * .1)
+    op(rs.randn(21))
+    model.get_hessian_matvec_operator(rs.randn(21) * .1)
+    with pytest.raises(RuntimeError, match='location has moved'):
+        op(rs.randn(21))
+    with pytest.raises(ValueError):
+        model.compute_loglik_and_gradient(np.zeros(20))
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(c_void_p)
+
+
+def _traj_inputs(D, y, o, seed=0, near_mode=True):
+    """f of the preconditioned coordinates and a start.  near_mode: next to
+    the maximum of the likelihood -- far from it the force decides the
+    direction of travel (a random momentum "turns round" within a step or
+    two) and the Hamiltonian's range passes any tolerance."""
+    P = D[0].shape[1] + int(D[2])
+    rs = np.random.RandomState(seed)
+    scale = np.exp(rs.randn(P) * .3) * .3
+    prior_prec = np.ones(P)
+    f = po.precond_f(D, y, o, scale, prior_prec)
+    q0 = rs.randn(P) * .1
+    if near_mode:
+        q0 = po.newton_mle(D, y, o)[0] / scale + q0 * .2
+    p0 = rs.randn(P)
+    logp0, grad0 = f(q0)
+    return f, scale, prior_prec, q0, p0, logp0, grad0
+
+
+def _stability_limit(D, y, o, scale, pp, q0):
+    """2 / sqrt(largest curvature of -f at q0), by power iteration on the
+    oracle's Hessian."""
+    v = np.ones(len(q0))
+    for _ in range(30):
+        hv = pp * v - scale * po.hessian_matvec(D, y, o, q0 * scale, scale * v)
+        curvature = np.linalg.norm(hv) / np.linalg.norm(v)
+        v = hv / np.linalg.norm(hv)
+    return 2 / np.sqrt(curvature)
+
+
+@pytest.mark.parametrize('kind', ['tiled_binary', 'dense64'])
+def test_overflow_gives_minus_infinity_and_a_nan_offset_is_refused(kind):
+    from bayesbridge_amd import _lib
+    n, p = LAP + 1, 7
+    model, D, y, o = _poisson_data(kind, n, p)
+    rs = np.random.RandomState(3)
+    b = rs.randn(p + 1)
+    # exp overflows past 709.78: the largest eta + o is 720, so some rows
+    # are over and most are not
+    beta = b * (720. / lo.dot(D, b).max())
+    beta = beta * ((720. - o[np.argmax(lo.dot(D, beta) + o)])
+                   / lo.dot(D, beta).max())
+    over = (lo.dot(D, beta) + o) > 709.79
+    print('rows over exp range:', over.sum(), 'of', n)
+    assert 0 < over.sum() < n
+    assert po.loglik_grad(D, y, o, beta)[0] == -np.inf
+    assert model.compute_loglik_and_gradient(beta) == (-np.inf, None)
+    assert model.compute_loglik_and_gradient(beta, loglik_only=True) \
+        == (-np.inf, None)
+    # a NaN comes out as a NaN
+    bad = beta * .001
+    bad[1] = np.nan
+    assert np.isnan(model.compute_loglik_and_gradient(bad)[0])
+    # the flags were that evaluation's only
+    small = beta * .001
+    ll, grad = model.compute_loglik_and_gradient(small)
+    oll, ograd = po.loglik_grad(D, y, o, small)
+    np.testing.assert_allclose(ll, oll, rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(grad, ograd, rtol=RTOL, atol=ATOL)
+    # a trajectory whose first step overflows: no HIP error, instability
+    f, scale, pp, q0, p0, logp0, grad0 = _traj_inputs(D, y, o,
+                                                      near_mode=False)
+    p0 = p0 * 1e4
+    want = lo.trajectory(f, 1., 10, q0, p0, logp0, grad0)
+    got = model.hmc_trajectory(1., 10, scale, pp, q0, p0, logp0, grad0)
+    assert want[5] and want[4] == 1 and want[2] == -np.inf
+    assert got['instability'] is True and got['n_steps'] == 1
+    assert got['logp'] == -np.inf and got['grad'] is None
+    np.testing.assert_allclose(got['q'], want[0], rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(got['p'], want[1], rtol=RTOL, atol=ATOL)
+    assert got['hamiltonian'][1] == np.inf
+    np.testing.assert_allclose(got['hamiltonian'][0], want[6], rtol=RTOL)
+    ll2, grad2 = model.compute_loglik_and_gradient(small)
+    assert ll2 == ll and np.array_equal(grad2, grad)
+    v = rs.randn(p + 1)
+    np.testing.assert_allclose(model.design.dot(v), lo.dot(D, v), rtol=RTOL,
+                               atol=ATOL)
+    # creation refuses a NaN offset
+    h = c_void_p()
+    nan_o = o.copy()
+    nan_o[n // 2] = np.nan
+    assert _lib.load().bbx_poisson_create(
+        model.design.handle, _ptr(y), _ptr(nan_o), byref(h)) < 0
+    assert not h.value and 'log_exposure' in _lib.last_error()
+
+
+@pytest.mark.parametrize('kind', ['tiled_binary', 'dense64'])
+def test_trajectory_matches_host_velocity_verlet(kind):
+    """The intercept column, the centring and the offset are live here."""
+    model, D, y, o = _poisson_data(kind, 3 * VEC_BLOCK + 5, 23)
+    f, scale, pp, q0, p0, logp0, grad0 = _traj_inputs(D, y, o)
+    limit = _stability_limit(D, y, o, scale, pp, q0)
+    dt = limit / 4
+    print('stability limit', limit)
+    want = lo.trajectory(f, dt, 25, q0, p0, logp0, grad0)
+    got = model.hmc_trajectory(dt, 25, scale, pp, q0, p0, logp0, grad0)
+    assert not want[5] and not got['instability']
+    assert got['n_steps'] == want[4] == 25
+    for key, ref in (('q', want[0]), ('p', want[1]), ('grad', want[3])):
+        print(key, np.abs(got[key] - ref).max() / np.abs(ref).max())
+        np.testing.assert_allclose(got[key], ref, rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(got['logp'], want[2], rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(got['hamiltonian'], [want[6], want[7]],
+                               rtol=RTOL, atol=ATOL)
+    again = model.hmc_trajectory(dt, 25, scale, pp, q0, p0, logp0, grad0)
+    for key in ('q', 'p', 'grad', 'hamiltonian'):
+        assert np.array_equal(again[key], got[key])
+    assert again['logp'] == got['logp']
+    # a tolerance on the Hamiltonian's range that a larger step exceeds:
+    # both stop at the same step
+    tol = .5
+    want = lo.trajectory(f, dt * 3, 200, q0, p0, logp0, grad0, tol=tol)
+    got = model.hmc_trajectory(dt * 3, 200, scale, pp, q0, p0, logp0, grad0,
+                               tol)
+    print('small tol: steps', got['n_steps'], want[4])
+    assert want[5] and 1 <= want[4] < 200 and np.isfinite(want[2])
+    assert got['instability'] and got['n_steps'] == want[4]
+    np.testing.assert_allclose(got['q'], want[0], rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(got['p'], want[1], rtol=RTOL, atol=ATOL)
+
+
+def _compare_doublings(model, oracle, scale, pp, q0, p0, logp0, grad0, dt,
+                       directions, tol, seed):
+    """The same doublings on the device and on the oracle, with the same
+    uniforms; returns the device's outputs."""
+    joint = logp0 - .5 * np.dot(p0, p0)
+    rs = np.random.RandomState(seed)
+    for m in (model, oracle):
+        m.nuts_begin(scale, pp, q0, p0, logp0, grad0, joint, joint - 1., tol)
+    outs = []
+    for height, direction in enumerate(directions):
+        uniforms = rs.rand(2 ** height)
+        with np.errstate(all='ignore'):
+            want = oracle.nuts_doubling(dt, direction, height, uniforms)
+        got = model.nuts_doubling(dt, direction, height, uniforms)
+        print('height', height, 'dir', direction, got)
+        for key in want:
+            if isinstance(want[key], float):
+                np.testing.assert_allclose(got[key], want[key], rtol=RTOL,
+                                           atol=ATOL, err_msg=key)
+            else:
+                assert got[key] == want[key], (key, got, want)
+        q, logp, grad = model.nuts_sample()
+        wq, wlogp, wgrad = oracle.nuts_sample()
+        np.testing.assert_allclose(q, wq, rtol=RTOL, atol=ATOL)
+        np.testing.assert_allclose(logp, wlogp, rtol=RTOL, atol=ATOL)
+        np.testing.assert_allclose(grad, wgrad, rtol=RTOL, atol=ATOL)
+        outs.append(got)
+        if got['u_turn_detected'] or got['instability_detected']:
+            break
+    return outs
+
+
+@pytest.mark.parametrize('kind', ['tiled_binary', 'dense64'])
+def test_nuts_doublings_match_the_oracle(kind):
+    model, D, y, o = _poisson_data(kind, 3 * VEC_BLOCK + 5, 23)
+    oracle = po.OracleModel(D, y, o)
+    f, scale, pp, q0, p0, logp0, grad0 = _traj_inputs(D, y, o)
+    limit = _stability_limit(D, y, o, scale, pp, q0)
+    args = (model, oracle, scale, pp, q0, p0, logp0, grad0)
+    # every height up to 4 in both directions: a step small enough for the
+    # 31 steps to make no U-turn
+    for first in (1, -1):
+        directions = [first * (-1) ** h for h in range(5)]
+        outs = _compare_doublings(*args, limit / 40, directions, 100., 5)
+        assert [out['height'] for out in outs] == [1, 2, 3, 4, 5]
+        assert sum(out['n_steps'] for out in outs) == 31
+        assert sum(out['n_uniform'] for out in outs) == 31
+        assert not any(out['doubling_rejected'] for out in outs)
+    # a step at which the tree turns round within 2^6 steps
+    outs = _compare_doublings(*args, limit / 4, [1, 1, -1, 1, -1, 1, 1], 100.,
+                              6)
+    assert outs[-1]['u_turn_detected']
+    assert not outs[-1]['instability_detected']
+    # a tolerance on the Hamiltonian's range that the steps exceed
+    outs = _compare_doublings(*args, limit * .75, [1, -1, 1, 1, -1, 1, 1],
+                              1e-3, 7)
+    assert outs[-1]['instability_detected']
+    # a first step that overflows inside a half-tree of four: the half-tree
+    # ends there, the doubling is rejected, the sample stays
+    big = p0 * 1e4
+    logp_joint = logp0 - .5 * np.dot(big, big)
+    for m in (model, oracle):
+        m.nuts_begin(scale, pp, q0, big, logp0, grad0, logp_joint,
+                     logp_joint - 1., 100.)
+    uniforms = np.random.RandomState(8).rand(4)
+    with np.errstate(all='ignore'):
+        want = oracle.nuts_doubling(1., 1, 2, uniforms)
+    got = model.nuts_doubling(1., 1, 2, uniforms)
+    print('overflow', got)
+    assert got == want
+    assert got['instability_detected'] and got['doubling_rejected']
+    assert got['n_steps'] == 1 and got['n_uniform'] == 0
+    assert np.array_equal(model.nuts_sample()[0], q0)
+    # the flags were the doubling's only
+    beta = q0 * scale
+    np.testing.assert_allclose(model.compute_loglik_and_gradient(beta)[0],
+                               po.loglik_grad(D, y, o, beta)[0], rtol=RTOL)
+
+
+# ------------------------------------------------------------ whole chains
+CHAIN_N, CHAIN_P = 300, 12
+# A chain multiplies a rounding difference from iteration to iteration (the
+# step size follows log10 of the Hamiltonian's error, a small difference of
+# sums of a few hundred).  The seeds are ones at which the oracle's own chain,
+# run again with its likelihood and gradient perturbed by 1e-15 relative (a
+# few ulp: what another summation order and another exp differ by), agrees
+# with itself to 1e-7 or better, three times out of three: 'hmc' the best of
+# seeds 0-319 (sparse 2e-8, dense 8e-8), 'nuts' 3e-9 and 7e-10 at 1e-14.
+CHAIN_SEED = {('hmc', 'sparse'): 230, ('hmc', 'dense'): 146,
+              ('nuts', 'sparse'): 10, ('nuts', 'dense'): 0}
+
+
+def _chain_problem(fmt):
+    rs = np.random.RandomState(11)
+    if fmt == 'sparse':
+        X = sparse.random(CHAIN_N, CHAIN_P, density=.3, format='csr',
+                          random_state=rs)
+        X.data[:] = 1.
+    else:
+        X = rs.randn(CHAIN_N, CHAIN_P) * .5
+    beta = np.zeros(CHAIN_P)
+    beta[:4] = (.8, -.6, .4, -.3)
+    e = rs.uniform(.5, 2., CHAIN_N)
+    y = rs.poisson(e * np.exp(.3 + np.asarray(X.dot(beta)).ravel()))
+    return X, y.astype(np.float64), e
+
+
+def _chain_start(fmt):
+    """The maximum-likelihood coefficients (Newton iterations on the oracle):
+    a chain started there has no long transient trajectories."""
+    X, y, e = _chain_problem(fmt)
+    return po.newton_mle(lo.design(X), y, np.log(e))[0]
+
+
+def _chain(fmt, method, seed, oracle=False, n_iter=12, resume=None):
+    """`n_iter` Gibbs iterations on the device model, or on the oracle model
+    behind the same design object.  The chain starts at given coefficients,
+    so no mode search runs."""
+    from bayesbridge_amd import BayesBridge, RegressionCoefPrior
+    from bayesbridge_amd import RegressionModel
+    X, y, e = _chain_problem(fmt)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        model = RegressionModel((y, e), X, 'poisson')
+    if oracle:
+        dsn = model.design
+        D = lo.design(X, True, True, offset=dsn.column_offset)
+        model = po.OracleModel(D, y, np.log(e), design=dsn)
+    prior = RegressionCoefPrior(bridge_exponent=.5, sd_for_intercept=2.,
+                                regularizing_slab_size=1.)
+    init = {'coef': _chain_start(fmt), 'global_scale': .1}
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        with np.errstate(all='ignore'):
+            samples, info = BayesBridge(model, prior).gibbs(
+                n_iter, init=init, seed=seed, params_to_save='all',
+                coef_sampler_type=method)
+            if resume:
+                samples, info = BayesBridge(model, prior).gibbs_resume(
+                    info, resume, merge=True, prev_samples=samples)
+    return samples, info
+
+
+@pytest.mark.parametrize('method,fmt', [('hmc', 'dense'), ('hmc', 'sparse'),
+                                        ('nuts', 'dense'), ('nuts', 'sparse')])
+def test_seeded_chain_matches_the_driver_on_the_oracle(method, fmt):
+    from bayesbridge_amd.bayesbridge import HMC_INFO_KEYS, NUTS_INFO_KEYS
+    seed = CHAIN_SEED[method, fmt]
+    samples, info = _chain(fmt, method, seed)
+    want, winfo = _chain(fmt, method, seed, oracle=True)
+    assert info['coef_sampler_type'] == method
+    assert info['options']['rng'] == 'reference'
+    assert set(samples) == {'coef', 'local_scale', 'global_scale', 'logp'}
+    assert 'obs_prec' not in info['_markov_chain_state']
+    assert samples['coef'].shape == (CHAIN_P + 1, 12)
+    si, wsi = (i['_reg_coef_sampling_info'] for i in (info, winfo))
+    assert set(si) == set(wsi) == set(HMC_INFO_KEYS if method == 'hmc'
+                                      else NUTS_INFO_KEYS)
+    steps = 'n_integrator_step' if method == 'hmc' else 'tree_height'
+    print(steps, si[steps], 'n_grad_evals', si['n_grad_evals'], 'max rel coef',
+          np.max(np.abs(samples['coef'] - want['coef'])
+                 / (np.abs(want['coef']) + 1e-3)))
+    for key in ('coef', 'global_scale', 'logp', 'local_scale'):
+        np.testing.assert_allclose(samples[key], want[key], rtol=RTOL,
+                                   atol=ATOL, err_msg=key)
+    for key in si:
+        np.testing.assert_allclose(si[key], wsi[key], rtol=RTOL, atol=ATOL,
+                                   err_msg=key)
+    assert np.all(si['n_grad_evals'] > 1)
+    # two halves through gibbs_resume against the straight run
+    resumed, rinfo = _chain(fmt, method, seed, n_iter=6, resume=6)
+    assert rinfo['n_iter'] == 12
+    for key in samples:
+        np.testing.assert_allclose(resumed[key], samples[key], rtol=RTOL,
+                                   atol=ATOL, err_msg=key)
+    for key in si:
+        np.testing.assert_allclose(rinfo['_reg_coef_sampling_info'][key],
+                                   si[key], rtol=RTOL, atol=ATOL, err_msg=key)
+
+
+def test_default_sampler_and_mode_search():
+    """No sampler named: 'hmc'; no coefficients given: the L-BFGS-B mode
+    search runs on the device likelihood, without obs_prec."""
+    from bayesbridge_amd import BayesBridge, RegressionCoefPrior
+    from bayesbridge_amd import RegressionModel
+    X, y, e = _chain_problem('dense')
+    model = RegressionModel((y, e), X, 'poisson')
+    assert model.intercept_added            # added by default, as for logit
+    D = lo.design(X, True, True, offset=model.design.column_offset)
+    prior = RegressionCoefPrior(bridge_exponent=.5, sd_for_intercept=2.,
+                                regularizing_slab_size=1.)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        samples, info = BayesBridge(model, prior).gibbs(
+            3, init={'global_scale': .1}, seed=1)
+    assert info['coef_sampler_type'] == 'hmc'
+    assert info['options']['rng'] == 'reference'
+    assert info['_init_optim_info']['is_success']
+    assert set(samples) == {'coef', 'global_scale', 'logp'}
+    assert np.all(np.isfinite(samples['coef']))
+    assert info['_init_optim_info']['n_iter'] > 0
+    # the search went uphill from its start (intercept-only coefficients)
+    start = np.zeros(CHAIN_P + 1)
+    start[0] = model.calc_intercept_mle()
+    assert po.loglik_grad(D, y, np.log(e), info['init']['coef'])[0] > \
+        po.loglik_grad(D, y, np.log(e), start)[0]
+    assert 'obs_prec' not in info['_markov_chain_state']
+
+
+def test_refusals_are_exceptions():
+    from bayesbridge_amd import BayesBridge, RegressionCoefPrior, SamplerOptions
+    model, D, y, o = _poisson_data('dense64', 100, 20)
+    bridge = BayesBridge(model, RegressionCoefPrior(bridge_exponent=.5))
+    init = {'global_scale': .1}
+    for method in ('cg', 'cholesky', 'woodbury'):
+        with pytest.raises(ValueError):
+            bridge.gibbs(2, init=init, seed=0, coef_sampler_type=method)
+        with pytest.raises(ValueError):
+            bridge.gibbs(2, init=init, seed=0, options=SamplerOptions(method))
+    with pytest.raises(ValueError):
+        bridge.gibbs(2, init=init, seed=0, options={'rng': 'device'})
+    with pytest.raises(ValueError, match="'cg'"):
+        bridge.gibbs_batch([0, 1], 2, init=init)
+    with pytest.raises(ValueError, match="'cg'"):
+        bridge.gibbs_batch([0, 1], 2, init=init,
+                           options={'coef_sampler_type': 'hmc'})
+    with pytest.raises(ValueError, match="'cg' only"):
+        bridge.gibbs_multichain(2, 2, init=init)
+
+
+def test_c_abi_errors_are_status_codes():
+    from bayesbridge_amd import HipDenseDesignMatrix, _lib
+    lib = _lib.load()
+    rs = np.random.RandomState(0)
+    n, p = 50, 4
+    design = HipDenseDesignMatrix(rs.randn(n, p))
+    P = p + 1
+    y, o = np.ones(n), np.full(n, .5)
+    vec, out = rs.randn(P) * .1, np.empty(P)
+    ll, k = c_double(), c_int()
+    # NULL handle
+    null = c_void_p()
+    assert lib.bbx_poisson_loglik_grad(null, _ptr(vec), byref(ll), None) < 0
+    assert lib.bbx_poisson_set_location(null, _ptr(vec)) < 0
+    assert lib.bbx_poisson_hessian_matvec(null, _ptr(vec), _ptr(out)) < 0
+    assert lib.bbx_poisson_nuts_sample(null, None, byref(ll), None) < 0
+    assert lib.bbx_poisson_destroy(null) == 0
+    # bad arguments at create
+    h = c_void_p()
+    assert lib.bbx_poisson_create(design.handle, _ptr(y), _ptr(o), None) < 0
+    assert lib.bbx_poisson_create(null, _ptr(y), _ptr(o), byref(h)) < 0
+    assert lib.bbx_poisson_create(design.handle, None, _ptr(o), byref(h)) < 0
+    at = np.arange(n)
+    for bad_y, bad_o in ((np.where(at == 7, -1., y), o),
+                         (np.where(at == 7, np.nan, y), o),
+                         (np.where(at == 7, np.inf, y), o),
+                         (y, np.where(at == 9, np.inf, o)),
+                         (y, np.where(at == 9, -np.inf, o)),
+                         (y, np.where(at == 9, np.nan, o))):
+        bad_y, bad_o = np.ascontiguousarray(bad_y), np.ascontiguousarray(bad_o)
+        assert lib.bbx_poisson_create(design.handle, _ptr(bad_y), _ptr(bad_o),
+                                      byref(h)) < 0
+        assert not h.value
+        assert _lib.last_error()
+    # no offset: log_exposure = NULL
+    h0 = c_void_p()
+    assert lib.bbx_poisson_create(design.handle, _ptr(y), None,
+                                  byref(h0)) == 0
+    assert lib.bbx_poisson_create(design.handle, _ptr(y), _ptr(o),
+                                  byref(h)) == 0
+    ll0 = c_double()
+    assert lib.bbx_poisson_loglik_grad(h0, _ptr(vec), byref(ll0), None) == 0
+    assert lib.bbx_poisson_destroy(h0) == 0
+    # order of calls
+    assert lib.bbx_poisson_hessian_matvec(h, _ptr(vec), _ptr(out)) < 0
+    assert 'set_location' in _lib.last_error()
+    u = rs.rand(1)
+    assert lib.bbx_poisson_nuts_doubling(h, .1, 1, 0, _ptr(u), byref(k),
+                                         byref(k), None, None, None) < 0
+    assert 'nuts_begin' in _lib.last_error()
+    assert lib.bbx_poisson_nuts_sample(h, None, byref(ll), None) < 0
+    assert lib.bbx_poisson_hmc_trajectory(
+        h, .1, -1, _ptr(vec), _ptr(vec), _ptr(vec), _ptr(vec), 0., _ptr(vec),
+        100., None, None, None, None, None, None, None) < 0
+    assert lib.bbx_poisson_loglik_grad(h, _ptr(vec), byref(ll), _ptr(out)) == 0
+    assert np.isfinite(ll.value)
+    # a positive offset enters the mean only: it lowers y eta - mu
+    assert ll.value < ll0.value
+    # use after the design is destroyed
+    design.__del__()
+    assert lib.bbx_poisson_loglik_grad(h, _ptr(vec), byref(ll), None) < 0
+    assert 'destroyed' in _lib.last_error()
+    assert lib.bbx_poisson_destroy(h) == 0
+
+
+def test_posterior_mean_is_near_the_maximum_likelihood_estimate():
+    """400 x 6 dense, unit exposure, a Gaussian prior (bridge exponent 2) of
+    fixed, large scale: the posterior is close to the likelihood, so each
+    posterior mean lies within 5 posterior sd of the maximum-likelihood
+    estimate (Newton iterations on the oracle)."""
+    # The same chain (seed 3, 500 'nuts' iterations, 100 of them burn-in) on
+    # poisson_oracle.OracleModel alone, on the CPU: the largest deviation is
+    # 0.089 posterior sd (the intercept; the six others 0.010 to 0.041).
+    from bayesbridge_amd import BayesBridge, RegressionCoefPrior
+    from bayesbridge_amd import RegressionModel
+    X, y, truth = _stat_problem()
+    model = RegressionModel(y, X, 'poisson')
+    D = lo.design(X, True, True, offset=model.design.column_offset)
+    mle, _ = po.newton_mle(D, y, np.zeros(len(y)))
+    samples = _stat_chain(BayesBridge, RegressionCoefPrior, model)
+    mean, sd = samples['coef'].mean(axis=1), samples['coef'].std(axis=1)
+    dev = np.abs(mean - mle) / sd
+    print('mle', mle, 'posterior mean', mean, 'sd', sd, 'deviation', dev)
+    assert np.all(np.abs(truth - mle) < 1.)
+    assert dev.max() < 5.
+
+
+def _stat_problem():
+    rs = np.random.RandomState(21)
+    X = rs.randn(400, 6) * .5
+    truth = np.array([.5, .6, -.4, .3, 0., -.2, .1])
+    y = rs.poisson(np.exp(truth[0] + X.dot(truth[1:]))).astype(np.float64)
+    return X, y, truth
+
+
+def _stat_chain(BayesBridge, RegressionCoefPrior, model):
+    prior = RegressionCoefPrior(bridge_exponent=2.,
+                                _global_scale_parametrization='raw')
+    coef = np.zeros(7)
+    coef[0] = model.calc_intercept_mle()
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        with np.errstate(all='ignore'):
+            samples, _ = BayesBridge(model, prior).gibbs(
+                500, n_burnin=100, seed=3, coef_sampler_type='nuts',
+                init={'coef': coef, 'global_scale': 100.},
+                options={'global_scale_update': None})
+    assert samples['coef'].shape == (7, 400)
+    return samples
