@@ -12,7 +12,7 @@ from ctypes import (POINTER, byref, c_char_p, c_double, c_int, c_int32,
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libbbx.so")
 
-ABI_VERSION = 109          # BBX_VERSION of include/bbx.h
+ABI_VERSION = 110          # BBX_VERSION of include/bbx.h
 FORMAT_AUTO, FORMAT_CSR, FORMAT_TILED = 0, 1, 2
 F64, F32 = 0, 1
 MODEL_LINEAR, MODEL_LOGIT = 0, 1
@@ -202,6 +202,9 @@ def _declare(lib):
             [c_int, c_uint64, c_uint64, c_int64, c_void_p], c_int),
         "bbx_cox_create": (
             [hp, c_int64, c_void_p, c_void_p, c_void_p, POINTER(hp)], c_int),
+        "bbx_cox_create_stratified": (
+            [hp, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+             POINTER(hp)], c_int),
         "bbx_cox_destroy": ([hp], c_int),
         "bbx_cox_loglik_grad": ([hp, c_void_p, POINTER(c_double), c_void_p],
                                 c_int),

@@ -7,7 +7,7 @@ products run on the device (csrc/cox.hip); its coefficients are drawn by HMC
 has no other."""
 import math
 from ctypes import byref, c_double, c_int, c_void_p
-from warnings import warn
+from warnings import catch_warnings, simplefilter, warn
 
 import numpy as np
 import scipy.sparse as sparse
@@ -447,36 +447,193 @@ def cox_risk_sets(event_time, censoring_time):
     return n_event, start, end, n_app
 
 
+def _stratum_codes(strata, n):
+    """(labels in np.unique order, the stratum number of every row)."""
+    strata = np.asarray(strata)
+    if strata.ndim != 1 or len(strata) != n:
+        raise ValueError("strata must be a 1-d array with one label for each "
+                         "observation.")
+    labels, codes = np.unique(strata, return_inverse=True)
+    return labels, np.asarray(codes, dtype=np.int64).ravel()
+
+
+def cox_preprocess_stratified(event_time, censoring_time, strata, X=None):
+    """cox_preprocess for a stratified model: the rows sorted stratum-major
+    (strata in np.unique order of their labels; inside a stratum the events by
+    increasing time, then the censored rows by decreasing censoring time; the
+    sort is stable, so tied rows keep their relative order), then without the
+    strata that have no event and without the rows censored before the first
+    event of their stratum.  Returns (event_time, censoring_time, strata, X,
+    keep): keep[i] is the original index of row i."""
+    event_time = np.asarray(event_time, dtype=np.float64)
+    censoring_time = np.asarray(censoring_time, dtype=np.float64)
+    if event_time.shape != censoring_time.shape or event_time.ndim != 1:
+        raise ValueError("event_time and censoring_time must be 1-d arrays of "
+                         "the same length.")
+    if not np.all(np.equal(event_time == float('inf'),
+                           censoring_time < float('inf'))):
+        raise ValueError("Either event or censoring time must be infinity for "
+                         "each observation.")
+    n = len(event_time)
+    strata = np.asarray(strata)
+    labels, codes = _stratum_codes(strata, n)
+    censored = event_time == float('inf')
+    key = np.where(censored, -censoring_time, event_time)
+    keep = np.lexsort((key, censored, codes))
+    if not np.array_equal(keep, np.arange(n)):
+        warn("The observations and design matrix will be sorted by stratum, "
+             "and within each stratum so that the event times are in the "
+             "ascending order and censoring times in the descending order.")
+    event_time, censoring_time = event_time[keep], censoring_time[keep]
+    strata, codes = strata[keep], codes[keep]
+    first_event = np.full(len(labels), float('inf'))
+    np.minimum.at(first_event, codes, event_time)
+    has_event = np.isfinite(first_event)[codes]
+    if not np.all(has_event):
+        warn("Some strata have no event and do not contribute to the "
+             "likelihood, so they are being removed.")
+    informative = ~(censoring_time < first_event[codes])
+    if not np.all(informative | ~has_event):
+        warn("Some observations do not contribute to the likelihood, so they "
+             "are being removed.")
+    ok = has_event & informative
+    if not np.all(ok):
+        keep, strata = keep[ok], strata[ok]
+        event_time, censoring_time = event_time[ok], censoring_time[ok]
+    if X is not None and not np.array_equal(keep, np.arange(X.shape[0])):
+        X = X.tocsr()[keep, :] if sparse.issparse(X) else X[keep, :]
+    return event_time, censoring_time, strata, X, keep
+
+
+def cox_stratified_risk_sets(event_time, censoring_time, strata):
+    """cox_risk_sets per stratum, in global indices, of rows already in
+    cox_preprocess_stratified's order.  Returns (stratum_ptr, stratum_n_event,
+    start, end, last_set): stratum s is rows stratum_ptr[s] ..
+    stratum_ptr[s + 1] - 1; events are numbered in row order across strata;
+    risk set k is rows start[k] .. end[k], inside the stratum of event k;
+    last_set[i] is the number of the last event whose risk set holds row i."""
+    event_time = np.asarray(event_time, dtype=np.float64)
+    censoring_time = np.asarray(censoring_time, dtype=np.float64)
+    n = len(event_time)
+    if event_time.shape != censoring_time.shape or event_time.ndim != 1:
+        raise ValueError("event_time and censoring_time must be 1-d arrays of "
+                         "the same length.")
+    labels, codes = _stratum_codes(strata, n)
+    if n == 0:
+        raise ValueError("The Cox model needs at least one event.")
+    if np.any(codes[:-1] > codes[1:]):
+        raise ValueError(
+            "The observations need to be sorted by stratum, the strata in the "
+            "increasing order of their labels.")
+    same = codes[:-1] == codes[1:]
+    if np.any(same & (event_time[:-1] > event_time[1:])):
+        raise ValueError(
+            "The observations of each stratum need to be sorted so that the "
+            "event times are in the increasing order, from the earliest to "
+            "last events.")
+    if np.any(same & (censoring_time[:-1] < censoring_time[1:])):
+        raise ValueError(
+            "The observations of each stratum need to be sorted so that the "
+            "censoring times are in the decreasing order, from uncensored, "
+            "last censored, to the earliest censored.")
+    n_strata = len(labels)
+    stratum_ptr = np.zeros(n_strata + 1, dtype=np.int64)
+    np.cumsum(np.bincount(codes, minlength=n_strata), out=stratum_ptr[1:])
+    is_event = np.isfinite(event_time)
+    stratum_n_event = np.bincount(codes[is_event], minlength=n_strata)
+    if np.any(stratum_n_event == 0):
+        raise ValueError(
+            "Some strata have no event. They have to be removed before using "
+            "the CoxModel class.")
+    event_ptr = np.zeros(n_strata + 1, dtype=np.int64)
+    np.cumsum(stratum_n_event, out=event_ptr[1:])
+    rows = np.flatnonzero(is_event)              # the row of every event
+    ev_time, ev_code = event_time[rows], codes[rows]
+    # start: the first event of the same stratum tied with event k
+    head = np.ones(len(rows), dtype=bool)
+    head[1:] = (ev_code[1:] != ev_code[:-1]) | (ev_time[1:] != ev_time[:-1])
+    start = np.maximum.accumulate(np.where(head, rows, 0))
+    # end: the stratum's last row minus its rows censored before t_k (a tied
+    # censoring time is in the risk set): merge events and censored rows by
+    # (stratum, time, events first) and count the censored rows ahead
+    cens_rows = np.flatnonzero(~is_event)
+    m_time = np.concatenate((ev_time, censoring_time[cens_rows]))
+    m_code = np.concatenate((ev_code, codes[cens_rows]))
+    m_cens = np.concatenate((np.zeros(len(rows), dtype=np.int64),
+                             np.ones(len(cens_rows), dtype=np.int64)))
+    order = np.lexsort((m_cens, m_time, m_code))
+    ahead = np.empty(len(order), dtype=np.int64)
+    ahead[order] = np.cumsum(m_cens[order])
+    cens_ptr = stratum_ptr - event_ptr           # censored rows before stratum s
+    end = (stratum_ptr[ev_code + 1] - 1
+           - (ahead[:len(rows)] - cens_ptr[ev_code]))
+    diff = np.zeros(n + 1, dtype=np.int64)
+    np.add.at(diff, start, 1)
+    np.add.at(diff, end + 1, -1)
+    n_app = np.cumsum(diff[:n])
+    if not np.all(n_app >= 1):
+        raise ValueError(
+            "Some individuals never appear in the risk set. They have to be "
+            "removed before using the CoxModel class.")
+    # the risk sets that hold row i are the first n_app[i] of its stratum
+    last_set = event_ptr[codes] + n_app - 1
+    return stratum_ptr, stratum_n_event, start, end, last_set
+
+
 class CoxModel(_DeviceHamiltonian, _Model):
     """cox_model.py:7-303 on a HIP design whose rows are already in the
     model's order (RegressionModel(..., family='cox') sorts them).  The
     likelihood, its gradient and the Hessian-vector products run on the device
-    through one bbx_cox handle."""
+    through one bbx_cox handle.  With `strata` (one label per row, the rows in
+    cox_preprocess_stratified's order) the likelihood is the stratified
+    partial likelihood: one risk-set structure and one baseline hazard per
+    stratum, shared coefficients."""
 
-    def __init__(self, event_time, censoring_time, design):
-        n_event, start, end, n_app = cox_risk_sets(event_time, censoring_time)
+    def __init__(self, event_time, censoring_time, design, strata=None):
+        self.strata = None
+        if strata is None:
+            n_event, start, end, n_app = cox_risk_sets(event_time,
+                                                       censoring_time)
+        else:
+            sptr, sne, start, end, last_set = cox_stratified_risk_sets(
+                event_time, censoring_time, strata)
+            n_event = int(np.sum(sne))
         if len(event_time) != design.shape[0]:
             raise ValueError(
                 "Incompatible sizes of the outcome and design matrix.")
         if n_event == 0:
             raise ValueError("The Cox model needs at least one event.")
+        if strata is None:
+            self.n_appearance_in_risk_set = n_app
+        else:
+            self.strata = np.asarray(strata)
+            self.stratum_ptr = sptr
+            self.stratum_n_event = sne
+            self.last_risk_set_index = last_set
         self.n_event = n_event
         self.event_time = np.asarray(event_time, dtype=np.float64)
         self.censoring_time = np.asarray(censoring_time, dtype=np.float64)
         self.risk_set_start_index = start
         self.risk_set_end_index = end
-        self.n_appearance_in_risk_set = n_app
         self.design = design
         self.name = 'cox'
         self._ham_prefix = 'bbx_cox_'
         self._lib = _lib.load()
         self._cox = c_void_p()
         self._location_serial = 0
-        i32 = [np.ascontiguousarray(a, dtype=np.int32)
-               for a in (start, end, n_app)]
-        _lib.check(self._lib.bbx_cox_create(
-            design.handle, n_event, _ptr(i32[0]), _ptr(i32[1]), _ptr(i32[2]),
-            byref(self._cox)))
+        if strata is None:
+            i32 = [np.ascontiguousarray(a, dtype=np.int32)
+                   for a in (start, end, n_app)]
+            _lib.check(self._lib.bbx_cox_create(
+                design.handle, n_event, _ptr(i32[0]), _ptr(i32[1]),
+                _ptr(i32[2]), byref(self._cox)))
+        else:
+            sptr = np.ascontiguousarray(sptr, dtype=np.int64)
+            i32 = [np.ascontiguousarray(a, dtype=np.int32)
+                   for a in (sne, start, end, last_set)]
+            _lib.check(self._lib.bbx_cox_create_stratified(
+                design.handle, len(sne), _ptr(sptr), *[_ptr(a) for a in i32],
+                byref(self._cox)))
 
     def __del__(self):
         h = getattr(self, '_cox', None)
@@ -536,7 +693,8 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
                     dense_storage_dtype='float64'):
     """model/factory.py:10-68 with the design placed on an MI355X.  `X` may be
     a SciPy sparse matrix, a NumPy array, or an already built HipDesignMatrix.
-    For family='cox', outcome = (event_time, censoring_time): the rows are
+    For family='cox', outcome = (event_time, censoring_time) or, for the
+    stratified model, (event_time, censoring_time, strata): the rows are
     sorted into the model's order (and uninformative ones dropped) before the
     design goes to the GPU; a prebuilt HipDesignMatrix must already be in that
     order.  For family='poisson', outcome = y or (y, exposure)."""
@@ -547,24 +705,41 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
             add_intercept = False
             warn("Intercept is not identifiable in Cox model and won't be "
                  "added.")
-        event_time, censoring_time = outcome
+        strata = None
+        if len(outcome) == 3:
+            event_time, censoring_time, strata = outcome
+        else:
+            event_time, censoring_time = outcome
         if isinstance(X, HipDesignMatrix):
             et = np.asarray(event_time, dtype=np.float64)
             ct = np.asarray(censoring_time, dtype=np.float64)
-            if cox_sort_permutation(et, ct) is not None \
-                    or np.any(ct < np.min(et)):
+            if strata is None:
+                in_order = cox_sort_permutation(et, ct) is None \
+                    and not np.any(ct < np.min(et))
+            else:
+                with catch_warnings():
+                    simplefilter('ignore')
+                    keep = cox_preprocess_stratified(et, ct, strata)[4]
+                in_order = np.array_equal(keep, np.arange(len(et)))
+            if not in_order:
                 raise ValueError(
                     "A prebuilt HipDesignMatrix must have its rows in the Cox "
                     "model's order (events by increasing time, then censored "
                     "rows by decreasing censoring time, none censored before "
-                    "the first event); pass X as a NumPy or SciPy matrix to "
-                    "have it sorted.")
+                    "the first event; with strata, stratum by stratum in the "
+                    "sorted order of the labels, each stratum in that order "
+                    "and with an event); pass X as a NumPy or SciPy matrix "
+                    "to have it sorted.")
             if X.intercept_added:
                 raise ValueError("The Cox model takes a design without an "
                                  "intercept column.")
-        else:
+        elif strata is None:
             event_time, censoring_time, X, _ = cox_preprocess(
                 event_time, censoring_time, X)
+        else:
+            event_time, censoring_time, strata, X, _ = \
+                cox_preprocess_stratified(event_time, censoring_time, strata,
+                                          X)
     if isinstance(X, HipDesignMatrix):
         design = X
     elif sparse.issparse(X):
@@ -584,7 +759,7 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
             n_success, n_trial = outcome, None
         return LogisticModel(n_success, n_trial, design)
     if family == 'cox':
-        return CoxModel(event_time, censoring_time, design)
+        return CoxModel(event_time, censoring_time, design, strata)
     if family == 'poisson':
         if isinstance(outcome, tuple):
             y, exposure = outcome

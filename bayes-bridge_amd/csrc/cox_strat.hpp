@@ -1,0 +1,333 @@
+// Stratified Cox partial likelihood: the kernels of a handle made by
+// bbx_cox_create_stratified (included by cox.hip, whose host code drives them).
+//
+// Rows are stratum-major; inside stratum s the model's order holds (events by
+// increasing time, then censored rows by decreasing censoring time).  Every
+// quantity of cox.hip's header restarts per stratum:
+//
+//   m_s    = max eta over stratum s,  h_i = exp(eta_i - m_s(i))
+//   scan_i = sum of h from i to the last event of i's stratum     (i an event)
+//          = sum of h from the stratum's first censored row to i  (i censored)
+//   H_k    = scan[start_k] + (end_k censored ? scan[end_k] : 0)
+//   c      = cumsum_k 1/H_k, restarted at the first event of every stratum
+//   w_i    = [i an event] - c[last_i] h_i
+//
+// The shift is per stratum: with one global max, a stratum whose eta lies 800
+// below another's has h == 0 in every row and H_k == 0, although its own
+// partial likelihood is perfectly finite (it is invariant to a shift of eta
+// within the stratum).
+//
+// Scans.  One segmented scan serves all of them: elements carry a head flag
+// and the operator on (flag, value) pairs is
+//   (f1, v1) o (f2, v2) = (f1 | f2, f2 ? v2 : v1 (+) v2),   (+) = sum or max,
+// associative, so the blocked two-pass scheme of cox.hip carries over.  The
+// partition is FIXED by the length alone: the row range [0, n) (forward, and
+// reversed for the suffix sums over events) and the event range [0, n_event)
+// are each cut into SCAN_G chunks; pass A leaves one (flag, value) aggregate
+// per chunk, pass B combines the aggregates of the chunks before its own in
+// order and scans its chunk in tiles of SCAN_BLOCK x SCAN_E.  Neither the
+// number nor the sizes of the strata enter the partition or the number of
+// launches.  No float atomics: the same inputs give the same bits.
+#pragma once
+
+namespace bbx {
+
+enum RowFlag : uint8_t {
+  RF_FWD = 1,     // forward head: first row or first censored row of a stratum
+  RF_BWD = 2,     // backward head: last event or last row of a stratum
+  RF_EVENT = 4,   // the row is an event
+  RF_SHEAD = 8,   // first row of a stratum
+  RF_SLAST = 16   // last row of a stratum
+};
+constexpr int EF_HEAD = 1;   // event flag: first event of a stratum
+
+enum SegOp { OP_SUM = 0, OP_MAX = 1 };
+
+struct FV {
+  int f;
+  double v;
+};
+
+template <int OP>
+__device__ inline FV seg_ident() {
+  FV r;
+  r.f = 0;
+  r.v = OP == OP_MAX ? -INFINITY : 0.;
+  return r;
+}
+
+template <int OP>
+__device__ inline double seg_op(double a, double b) {
+  return OP == OP_MAX ? nanmax(a, b) : a + b;
+}
+
+// a comes before b in scan order
+template <int OP>
+__device__ inline FV seg_comb(FV a, FV b) {
+  FV r;
+  r.f = a.f | b.f;
+  r.v = b.f ? b.v : seg_op<OP>(a.v, b.v);
+  return r;
+}
+
+template <int OP>
+__device__ inline FV wave_seg_incl(FV x, int lane) {
+#pragma unroll
+  for (int off = 1; off < WAVE; off <<= 1) {
+    FV y;
+    y.f = __shfl_up(x.f, off);
+    y.v = __shfl_up(x.v, off);
+    if (lane >= off) x = seg_comb<OP>(y, x);
+  }
+  return x;
+}
+
+// Block-wide segmented scan of one (flag, value) per thread, in thread order.
+// `pre`: everything before this thread (the exclusive prefix is the previous
+// lane's inclusive value, never a difference); `tot`: the whole block.
+template <int OP>
+__device__ inline void block_seg_scan(FV run, FV* s_wave, FV& pre, FV& tot) {
+  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+  const FV incl = wave_seg_incl<OP>(run, lane);
+  FV excl;
+  excl.f = __shfl_up(incl.f, 1);
+  excl.v = __shfl_up(incl.v, 1);
+  if (lane == 0) excl = seg_ident<OP>();
+  if (lane == WAVE - 1) s_wave[wid] = incl;
+  __syncthreads();
+  FV wpre = seg_ident<OP>();
+  tot = seg_ident<OP>();
+#pragma unroll
+  for (int k = 0; k < SCAN_BLOCK / WAVE; ++k) {
+    const FV w = s_wave[k];
+    if (k < wid) wpre = seg_comb<OP>(wpre, w);
+    tot = seg_comb<OP>(tot, w);
+  }
+  pre = seg_comb<OP>(wpre, excl);
+  __syncthreads();
+}
+
+// The aggregates of the chunks before chunk b of direction d, combined in
+// order (every wave computes the same value)
+template <int OP>
+__device__ inline FV chunk_prefix(const double* aggv, const int* aggf, int d,
+                                  int b) {
+  static_assert(SCAN_G % WAVE == 0, "SCAN_G / WAVE chunks per lane");
+  const int lane = threadIdx.x & (WAVE - 1);
+  FV acc = seg_ident<OP>();
+#pragma unroll
+  for (int k = 0; k < SCAN_G / WAVE; ++k) {
+    const int c = lane * (SCAN_G / WAVE) + k;
+    if (c < b) {
+      FV x;
+      x.f = aggf[d * SCAN_G + c];
+      x.v = aggv[d * SCAN_G + c];
+      acc = seg_comb<OP>(acc, x);
+    }
+  }
+  acc = wave_seg_incl<OP>(acc, lane);
+  FV r;
+  r.f = __shfl(acc.f, WAVE - 1);
+  r.v = __shfl(acc.v, WAVE - 1);
+  return r;
+}
+
+enum StratMode {
+  SS_MAX = 0,   // eta_i, max                               (rows, forward)
+  SS_H = 1,     // h_i = exp(eta_i - m_s(i))                (rows, both ways)
+  SS_HU = 2,    // h_i u_i                                  (rows, both ways)
+  SS_INVH = 3,  // 1 / H_k, and the loglik partials         (events, forward)
+  SS_WU = 4     // (1/H_k) ((1/H_k) S_k)                    (events, forward)
+};
+
+struct StratArgs {
+  int64_t len = 0;                  // n (rows) or n_event (events)
+  const uint8_t* flag = nullptr;    // RowFlag per row / EF_HEAD per event
+  const double* eta = nullptr;      // SS_MAX, SS_H, SS_INVH
+  const double* ms = nullptr;       // SS_H, SS_INVH: max eta per stratum
+  const int32_t* sid = nullptr;     // stratum of a row
+  const double* h = nullptr;        // SS_HU
+  const double* u = nullptr;        // SS_HU
+  const double* scan = nullptr;     // SS_INVH, SS_WU: risk scan per row
+  const double* inv = nullptr;      // SS_WU: 1 / H at the location
+  const int32_t* evrow = nullptr;   // SS_INVH: row of an event
+  const int32_t* start = nullptr;   // per event: row
+  const int32_t* endc = nullptr;    // per event: row if censored, else -1
+  double* val = nullptr;            // the per-element value, stored
+  double* llpart = nullptr;         // SS_INVH: SCAN_G loglik partials
+  CoxTraj* st = nullptr;            // SS_INVH: zero / skip flags
+  double* aggv = nullptr;           // (directions) x SCAN_G chunk aggregates
+  int* aggf = nullptr;
+};
+
+template <int MODE>
+__device__ inline int strat_mask(int d) {
+  if (MODE == SS_MAX) return RF_SHEAD;
+  if (MODE == SS_H || MODE == SS_HU) return d ? RF_BWD : RF_FWD;
+  return EF_HEAD;
+}
+
+// Pass A: the value of every element (stored in a.val) and one (flag, value)
+// aggregate per chunk.  Block d * SCAN_G + b: chunk b of direction d (d == 1:
+// the range read backwards).
+template <int MODE>
+__global__ __launch_bounds__(SCAN_BLOCK) void coxs_agg_kernel(
+    StratArgs a, const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  constexpr int OP = MODE == SS_MAX ? OP_MAX : OP_SUM;
+  __shared__ FV s_wave[SCAN_BLOCK / WAVE];
+  const int d = blockIdx.x / SCAN_G, b = blockIdx.x % SCAN_G;
+  const int mask = strat_mask<MODE>(d);
+  const int64_t len = a.len;
+  const int64_t L = (len + SCAN_G - 1) / SCAN_G;
+  const int64_t t0 = (int64_t)b * L, t1 = t0 + L < len ? t0 + L : len;
+  FV carry = seg_ident<OP>();
+  double ll = 0.;
+  bool zero = false;
+  for (int64_t tile = t0; tile < t1; tile += SCAN_TILE) {
+    const int64_t tb = tile + (int64_t)threadIdx.x * SCAN_E;
+    FV run = seg_ident<OP>();
+#pragma unroll
+    for (int e = 0; e < SCAN_E; ++e) {
+      const int64_t t = tb + e;
+      if (t >= t1) continue;
+      const int64_t i = d ? len - 1 - t : t;
+      FV x;
+      x.f = (a.flag[i] & mask) != 0;
+      if (MODE == SS_MAX) {
+        x.v = a.eta[i];
+      } else if (MODE == SS_H) {
+        x.v = exp(a.eta[i] - a.ms[a.sid[i]]);
+      } else if (MODE == SS_HU) {
+        x.v = a.h[i] * a.u[i];
+      } else {
+        const int32_t e1 = a.endc[i];
+        double H = a.scan[a.start[i]];
+        if (e1 >= 0) H += a.scan[e1];
+        if (MODE == SS_INVH) {
+          const int32_t r = a.evrow[i];
+          zero |= (H == 0.);
+          x.v = 1. / H;
+          ll += (a.eta[r] - a.ms[a.sid[r]]) - log(H);
+        } else {
+          const double iv = a.inv[i];
+          x.v = iv * (iv * H);
+        }
+      }
+      // both directions compute the same value; the forward one stores it
+      if (MODE != SS_MAX && d == 0) a.val[i] = x.v;
+      run = seg_comb<OP>(run, x);
+    }
+    FV pre, tot;
+    block_seg_scan<OP>(run, s_wave, pre, tot);
+    carry = seg_comb<OP>(carry, tot);
+  }
+  if (MODE == SS_INVH) {
+    ll = block_sum<SCAN_BLOCK>(ll);
+    if (zero) {
+      a.st->zero = 1;
+      a.st->skip = 1;
+    }
+  }
+  if (threadIdx.x == 0) {
+    a.aggv[blockIdx.x] = carry.v;
+    a.aggf[blockIdx.x] = carry.f;
+    if (MODE == SS_INVH) a.llpart[b] = ll;
+  }
+}
+
+enum StratOut {
+  SO_RISK = 0,  // rows, both ways: forward writes censored rows, backward events
+  SO_MAX = 1,   // rows, forward: the last row of stratum s writes ms[s]
+  SO_ALL = 2    // events, forward: every element
+};
+
+// Pass B: inclusive segmented scan of the stored values of each chunk, after
+// the aggregates of the chunks before it.
+template <int OUT>
+__global__ __launch_bounds__(SCAN_BLOCK) void coxs_out_kernel(
+    int64_t len, const uint8_t* __restrict__ flag,
+    const int32_t* __restrict__ sid, const double* __restrict__ val,
+    double* __restrict__ out, const double* __restrict__ aggv,
+    const int* __restrict__ aggf, const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  constexpr int OP = OUT == SO_MAX ? OP_MAX : OP_SUM;
+  __shared__ FV s_wave[SCAN_BLOCK / WAVE];
+  const int d = blockIdx.x / SCAN_G, b = blockIdx.x % SCAN_G;
+  const int mask = OUT == SO_MAX ? RF_SHEAD
+                   : OUT == SO_RISK ? (d ? RF_BWD : RF_FWD) : EF_HEAD;
+  const int64_t L = (len + SCAN_G - 1) / SCAN_G;
+  const int64_t t0 = (int64_t)b * L, t1 = t0 + L < len ? t0 + L : len;
+  if (t0 >= t1) return;
+  FV carry = chunk_prefix<OP>(aggv, aggf, d, b);
+  for (int64_t tile = t0; tile < t1; tile += SCAN_TILE) {
+    const int64_t tb = tile + (int64_t)threadIdx.x * SCAN_E;
+    double x[SCAN_E];
+    unsigned seen = 0, fl[SCAN_E];
+    FV run = seg_ident<OP>();
+#pragma unroll
+    for (int e = 0; e < SCAN_E; ++e) {
+      const int64_t t = tb + e;
+      fl[e] = 0;
+      if (t < t1) {
+        const int64_t i = d ? len - 1 - t : t;
+        fl[e] = flag[i];
+        FV y;
+        y.f = (fl[e] & mask) != 0;
+        y.v = val[i];
+        run = seg_comb<OP>(run, y);
+      }
+      x[e] = run.v;
+      if (run.f) seen |= 1u << e;
+    }
+    FV pre, tot;
+    block_seg_scan<OP>(run, s_wave, pre, tot);
+    const FV base = seg_comb<OP>(carry, pre);
+#pragma unroll
+    for (int e = 0; e < SCAN_E; ++e) {
+      const int64_t t = tb + e;
+      if (t >= t1) continue;
+      const int64_t i = d ? len - 1 - t : t;
+      const double r = (seen >> e) & 1u ? x[e] : seg_op<OP>(base.v, x[e]);
+      if (OUT == SO_MAX) {
+        if (fl[e] & RF_SLAST) out[sid[i]] = r;
+      } else if (OUT == SO_RISK) {
+        if (((fl[e] & RF_EVENT) != 0) == (d == 1)) out[i] = r;
+      } else {
+        out[i] = r;
+      }
+    }
+    carry = seg_comb<OP>(carry, tot);
+  }
+}
+
+// w = [i an event] - c[last_i] h_i                       (HESS = false)
+// w = -((c[last_i] h_i) u_i - h_i cz[last_i])            (HESS = true)
+// and the NPART partials of sum(w).
+template <bool HESS>
+__global__ __launch_bounds__(VEC_BLOCK) void coxs_weight_kernel(
+    int64_t n, const uint8_t* __restrict__ rflag, const double* __restrict__ h,
+    const double* __restrict__ c, const int32_t* __restrict__ last,
+    const double* __restrict__ u, const double* __restrict__ cz,
+    double* __restrict__ w, double* __restrict__ part,
+    const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  double acc = 0.;
+  for (int64_t i = (int64_t)blockIdx.x * VEC_BLOCK + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * VEC_BLOCK) {
+    const int32_t k = last[i];
+    const double rs = c[k] * h[i];
+    double v;
+    if (HESS) {
+      v = -(rs * u[i] - h[i] * cz[k]);
+    } else {
+      v = ((rflag[i] & RF_EVENT) ? 1. : 0.) - rs;
+    }
+    w[i] = v;
+    acc += v;
+  }
+  acc = block_sum<VEC_BLOCK>(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+}  // namespace bbx

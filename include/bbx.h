@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-/* 109: + the Poisson likelihood (log link, exposure offset) with the HMC
+/* 110: + strata in the Cox model (bbx_cox_create_stratified): one partial
+ *      likelihood per stratum on shared coefficients, through every other
+ *      bbx_cox_* entry point unchanged.
+ * 109: + the Poisson likelihood (log link, exposure offset) with the HMC
  *      trajectory and the No-U-Turn sampler of the Cox handle (bbx_poisson_*).
  * 108: + the logit likelihood with the HMC trajectory and the No-U-Turn
  *      sampler of the Cox handle (bbx_logit_*).
@@ -50,7 +53,7 @@ extern "C" {
  *      bbx_setup_lock_acquire/_release, bbx_design_useful_bytes.  A binding
  *      compares bbx_version() with the BBX_VERSION it was written against
  *      (bayesbridge_amd/_lib.py does) instead of calling with a stale arity. */
-#define BBX_VERSION 109 /* 0.1.9 */
+#define BBX_VERSION 110 /* 0.1.10 */
 
 /* status codes */
 #define BBX_OK 0
@@ -722,6 +725,31 @@ int bbx_device_normal(int device, uint64_t seed, uint64_t stream,
 typedef struct bbx_cox bbx_cox;
 int bbx_cox_create(bbx_design* design, int64_t n_event, const int32_t* start,
                    const int32_t* end, const int32_t* n_app, bbx_cox** out);
+/* The stratified partial likelihood: the product of one Cox partial likelihood
+ * per stratum, on shared coefficients (csrc/cox_strat.hpp).  Rows are
+ * stratum-major: stratum s is the row range [stratum_ptr[s], stratum_ptr[s+1])
+ * (n_strata + 1 increasing offsets from 0 to n), and inside it the order above
+ * holds -- its stratum_n_event[s] >= 1 events first by increasing time, then
+ * its censored rows by decreasing censoring time.  Events are numbered in row
+ * order across the strata (the events of stratum 0, then those of stratum 1,
+ * ...).  Risk set k is the row range [start[k], end[k]] in GLOBAL row ids,
+ * inside the stratum of event k (stratum first row <= start[k] <= the row of
+ * event k; the stratum's last event row <= end[k] <= its last row);
+ * last_set[i] is the global number of the last event whose risk set holds row
+ * i, an event of i's stratum.  Every index is checked: BBX_ERR_INVALID names
+ * the first bad stratum, risk set or row, and nothing is launched.  The shift
+ * m, the risk-set sums and the cumulative sums of every formula below restart
+ * per stratum (an offset of eta between strata cannot underflow a risk-set
+ * sum), so each value is the sum over the strata of the unstratified one.
+ * All other bbx_cox_* calls work on such a handle unchanged; their number of
+ * kernel launches does not depend on the number or the sizes of the strata.  A
+ * handle from bbx_cox_create runs the same kernels and gives the same bits as
+ * before this call existed. */
+int bbx_cox_create_stratified(bbx_design* design, int64_t n_strata,
+                              const int64_t* stratum_ptr,
+                              const int32_t* stratum_n_event,
+                              const int32_t* start, const int32_t* end,
+                              const int32_t* last_set, bbx_cox** out);
 int bbx_cox_destroy(bbx_cox* cox);
 /* loglik = sum_k (eta_k - m) - log H_k, eta = X~ beta, m = max eta,
  * H_k = sum over risk set k of exp(eta - m); grad[P] = X~^T w,

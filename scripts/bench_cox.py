@@ -33,6 +33,13 @@ runs one N-step trajectory and N X~ v + X~^T w pairs (after a 4-step warm-up
 trajectory); the design's product kernels then run 2N (+ a few) times, every
 Cox kernel N (+ a few) times, so per step: product kernels = their total / 2N,
 the Cox kernels = their total / N.
+
+--strata K: the stratified model (csrc/cox_strat.hpp) on K strata of equal
+expected size (labels drawn uniformly), the same outcome otherwise.
+--strata pairs: n / 2 matched pairs -- rows 2j and 2j + 1 form a stratum, the
+one with the earlier simulated event time is the event, the other is censored
+at its own later time, so no row is dropped.  Every figure above is then that
+of the stratified handle; `n_strata` is added to the JSON line.
 """
 import argparse
 import json
@@ -50,7 +57,8 @@ sys.path.insert(0, os.path.join(ROOT, "bayes-bridge_amd"))
 from bayesbridge_amd import (BayesBridge, HipDenseDesignMatrix,  # noqa: E402
                              HipSparseDesignMatrix, RegressionCoefPrior,
                              RegressionModel, _lib, simulate)
-from bayesbridge_amd.model import CoxModel, cox_preprocess  # noqa: E402
+from bayesbridge_amd.model import (CoxModel, cox_preprocess,  # noqa: E402
+                                   cox_preprocess_stratified)
 
 
 def make_X(kind, n, p, seed):
@@ -99,14 +107,40 @@ def nuts_half_tree(model, dt, height, scale, pp, q0, p0, logp0, grad0):
     return elapsed
 
 
-def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc'):
+def strata_outcome(X, beta, strata, seed):
+    """(event_time, censoring_time, labels) of --strata."""
+    n = X.shape[0]
+    if strata != 'pairs':
+        et, ct = CoxModel.simulate_outcome(X, beta, seed=seed)
+        labels = np.random.RandomState(seed + 1).randint(0, int(strata), n)
+        return et, ct, labels
+    eta = np.asarray(X.dot(beta), dtype=np.float64).ravel()
+    time_ = np.random.RandomState(seed).exponential(np.exp(eta.max() - eta))
+    m = n - n % 2                  # an odd last row: a stratum of one event
+    t = time_[:m].reshape(-1, 2)
+    first = t[:, 0] <= t[:, 1]
+    event = np.column_stack((first, ~first))
+    et = np.append(np.where(event, t, np.inf).ravel(), time_[m:])
+    ct = np.append(np.where(event, np.inf, t).ravel(), np.full(n - m, np.inf))
+    return et, ct, np.arange(n) // 2
+
+
+def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
+        strata=None):
     X = make_X(kind, n, p, seed)
     beta = simulate.demo_beta(p)
-    et, ct = CoxModel.simulate_outcome(X, beta, seed=seed)
+    labels = None
+    if strata is None:
+        et, ct = CoxModel.simulate_outcome(X, beta, seed=seed)
+    else:
+        et, ct, labels = strata_outcome(X, beta, strata, seed)
     tic = time.perf_counter()
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        et, ct, X, _ = cox_preprocess(et, ct, X)
+        if labels is None:
+            et, ct, X, _ = cox_preprocess(et, ct, X)
+        else:
+            et, ct, labels, X, _ = cox_preprocess_stratified(et, ct, labels, X)
     if kind == 'binary':
         design = HipSparseDesignMatrix(X, add_intercept=False,
                                        center_predictor=True)
@@ -117,7 +151,10 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc'):
     del X
     t_design = time.perf_counter() - tic
     tic = time.perf_counter()
-    model = RegressionModel((et, ct), design, 'cox')
+    outcome = (et, ct) if labels is None else (et, ct, labels)
+    model = RegressionModel(outcome, design, 'cox')
+    n_strata = {} if labels is None else {
+        'n_strata': len(model.stratum_n_event)}
     preprocess_s = t_design + time.perf_counter() - tic
     P = design.shape[1]
     rs = np.random.RandomState(1)
@@ -158,7 +195,7 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc'):
     prod_us = products_us(design, profile_steps or 50)
     if profile_steps:
         return {'shape': '%s:%dx%d' % (kind, n, p), 'sampler': sampler,
-                'profile_steps': n_traj,
+                'profile_steps': n_traj, **n_strata,
                 'leapfrog_us': round(leap_us, 1),
                 'products_us': round(prod_us, 1)}
     prior = RegressionCoefPrior(bridge_exponent=.25,
@@ -184,7 +221,7 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc'):
                 'mean_dt': float(np.mean(si['stepsize'])),
                 'accept_rate': float(np.mean(si['accepted']))}
     return {'shape': '%s:%dx%d' % (kind, n, p), 'sampler': sampler,
-            'n_event': model.n_event,
+            'n_event': model.n_event, **n_strata,
             'preprocess_s': round(preprocess_s, 2),
             'grad_us': round(grad_us, 1), 'hvp_us': round(hvp_us, 1),
             'leapfrog_us': round(leap_us, 1),
@@ -201,13 +238,18 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--profile-steps', type=int, default=0)
     ap.add_argument('--sampler', choices=['hmc', 'nuts'], default='hmc')
+    ap.add_argument('--strata', default=None,
+                    help="a number of strata, or 'pairs'")
     a = ap.parse_args()
+    if a.strata not in (None, 'pairs') and int(a.strata) < 1:
+        raise SystemExit("--strata takes a positive number or 'pairs'")
     for s in a.shapes:
         kind, size = s.split(':')
         n, p = (int(x) for x in size.split('x'))
         print(json.dumps(run(kind, n, p, a.steps, a.warmup,
                              profile_steps=a.profile_steps,
-                             sampler=a.sampler)), flush=True)
+                             sampler=a.sampler, strata=a.strata)),
+              flush=True)
 
 
 if __name__ == '__main__':
