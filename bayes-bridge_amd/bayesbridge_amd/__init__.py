@@ -9,12 +9,12 @@ from .device_chain import HipChainBatch, HipGibbsChain
 from .design_matrix import (HipDenseDesignMatrix, HipDesignMatrix,
                             HipSparseDesignMatrix)
 from .model import (CoxModel, LinearModel, LogisticModel, PoissonModel,
-                    RegressionModel)
+                    RegressionModel, cpoisson_preprocess)
 from .prior import RegressionCoefPrior
 
 __all__ = [
     "BayesBridge", "RegressionModel", "RegressionCoefPrior", "SamplerOptions",
     "HipDesignMatrix", "HipSparseDesignMatrix", "HipDenseDesignMatrix",
-    "HipCGSampler", "HipGibbsChain", "HipChainBatch", "LinearModel", "LogisticModel", "CoxModel", "PoissonModel", "BbxError",
+    "HipCGSampler", "HipGibbsChain", "HipChainBatch", "LinearModel", "LogisticModel", "CoxModel", "PoissonModel", "cpoisson_preprocess", "BbxError",
     "device_count",
 ]

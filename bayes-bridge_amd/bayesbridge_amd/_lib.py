@@ -12,7 +12,7 @@ from ctypes import (POINTER, byref, c_char_p, c_double, c_int, c_int32,
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libbbx.so")
 
-ABI_VERSION = 110          # BBX_VERSION of include/bbx.h
+ABI_VERSION = 111          # BBX_VERSION of include/bbx.h
 FORMAT_AUTO, FORMAT_CSR, FORMAT_TILED = 0, 1, 2
 F64, F32 = 0, 1
 MODEL_LINEAR, MODEL_LOGIT = 0, 1
@@ -269,6 +269,29 @@ def _declare(lib):
             [hp, c_double, c_int, c_int, c_void_p, POINTER(c_int),
              POINTER(c_int), c_void_p, c_void_p, c_void_p], c_int),
         "bbx_poisson_nuts_sample": (
+            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
+        "bbx_cpoisson_create": (
+            [hp, c_void_p, c_void_p, c_int64, c_void_p, POINTER(hp)], c_int),
+        "bbx_cpoisson_destroy": ([hp], c_int),
+        "bbx_cpoisson_loglik_grad": (
+            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
+        "bbx_cpoisson_loglik_grad_dev": (
+            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
+        "bbx_cpoisson_set_location": ([hp, c_void_p], c_int),
+        "bbx_cpoisson_hessian_matvec": ([hp, c_void_p, c_void_p], c_int),
+        "bbx_cpoisson_hessian_matvec_dev": ([hp, c_void_p, c_void_p], c_int),
+        "bbx_cpoisson_hmc_trajectory": (
+            [hp, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_double, c_void_p, c_double, c_void_p, c_void_p,
+             POINTER(c_double), c_void_p, POINTER(c_int), POINTER(c_int),
+             c_void_p], c_int),
+        "bbx_cpoisson_nuts_begin": (
+            [hp, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
+             c_double, c_double, c_double], c_int),
+        "bbx_cpoisson_nuts_doubling": (
+            [hp, c_double, c_int, c_int, c_void_p, POINTER(c_int),
+             POINTER(c_int), c_void_p, c_void_p, c_void_p], c_int),
+        "bbx_cpoisson_nuts_sample": (
             [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
     }
     for name, (argtypes, restype) in sigs.items():

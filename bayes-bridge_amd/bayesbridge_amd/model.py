@@ -3,8 +3,8 @@
 cox_model.py:7-303).  The Cox likelihood, its gradient and its Hessian-vector
 products run on the device (csrc/cox.hip); its coefficients are drawn by HMC
 (hmc.py).  The logit model has the same device path (csrc/logit.hip) for the
-'hmc' and 'nuts' coefficient samplers, and the Poisson model (csrc/poisson.hip)
-has no other."""
+'hmc' and 'nuts' coefficient samplers, and the Poisson model (csrc/poisson.hip;
+with strata the conditional Poisson model, csrc/cpoisson.hip) has no other."""
 import math
 from ctypes import byref, c_double, c_int, c_void_p
 from warnings import catch_warnings, simplefilter, warn
@@ -67,8 +67,8 @@ def _ptr(a):
 
 class _DeviceHamiltonian():
     """The device trajectory and No-U-Turn tree of a likelihood handle
-    (csrc/hamiltonian.hpp): the same calls on bbx_cox_*, bbx_logit_* and
-    bbx_poisson_*.  A model names its family in `_ham_prefix` and gives its
+    (csrc/hamiltonian.hpp): the same calls on bbx_cox_*, bbx_logit_*,
+    bbx_poisson_* and bbx_cpoisson_*.  A model names its family in `_ham_prefix` and gives its
     handle as `handle`."""
 
     def _ham_fn(self, name):
@@ -281,12 +281,19 @@ class PoissonModel(_DeviceHamiltonian, _Model):
     """Incidence-rate regression: counts y_i with mean exposure_i exp(eta_i).
     The likelihood, its gradient and the Hessian-vector products run on the
     device through one bbx_poisson handle (csrc/poisson.hip); the coefficients
-    are drawn by 'hmc' or 'nuts', as the Cox model's are."""
+    are drawn by 'hmc' or 'nuts', as the Cox model's are.  With `strata` (one
+    label per row, the rows in cpoisson_preprocess's order) the likelihood is
+    the conditional Poisson likelihood: one nuisance baseline rate per
+    stratum, conditioned on the stratum's total count, through one
+    bbx_cpoisson handle (csrc/cpoisson.hip) on a design without an intercept
+    column."""
 
-    def __init__(self, y, exposure, design):
+    def __init__(self, y, exposure, design, strata=None):
         """Counts must line up with the rows of the design and be
         non-negative integers (integer-valued floats are accepted); exposure
-        (None: 1 for every row) must be strictly positive and finite."""
+        (None: 1 for every row) must be strictly positive and finite.  With
+        strata the rows must be stratum-major, the strata in the sorted order
+        of their labels, and every stratum must hold a positive count."""
         n_row = design.shape[0]
         y = np.asarray(y, dtype=np.float64)
         if exposure is None:
@@ -309,15 +316,39 @@ class PoissonModel(_DeviceHamiltonian, _Model):
         self.log_exposure = np.log(exposure)
         self.design = design
         self.name = 'poisson'
-        # one bbx_poisson handle, made by the first call that needs it
+        self.strata = None
+        # one bbx_poisson (with strata: bbx_cpoisson) handle, made by the
+        # first call that needs it
         self._ham_prefix = 'bbx_poisson_'
+        if strata is not None:
+            if design.intercept_added:
+                raise ValueError("The conditional Poisson model takes a "
+                                 "design without an intercept column.")
+            labels, codes = _stratum_codes(strata, n_row)
+            if np.any(codes[:-1] > codes[1:]):
+                raise ValueError(
+                    "The observations need to be sorted by stratum, the "
+                    "strata in the increasing order of their labels.")
+            n_strata = len(labels)
+            stratum_ptr = np.zeros(n_strata + 1, dtype=np.int64)
+            np.cumsum(np.bincount(codes, minlength=n_strata),
+                      out=stratum_ptr[1:])
+            total = np.bincount(codes, weights=y, minlength=n_strata)
+            if n_strata == 0 or np.any(total <= 0):
+                raise ValueError(
+                    "Some strata have no positive count. They have to be "
+                    "removed before using the PoissonModel class.")
+            self.strata = np.asarray(strata)
+            self.stratum_ptr = stratum_ptr
+            self.stratum_total = total
+            self._ham_prefix = 'bbx_cpoisson_'
         self._poisson = c_void_p()
         self._location_serial = 0
 
     def __del__(self):
         h = getattr(self, '_poisson', None)
         if h and not _lib.finalizing:
-            _lib.load().bbx_poisson_destroy(h)
+            self._ham_fn('destroy')(h)
         self._poisson = c_void_p()
 
     @property
@@ -327,13 +358,23 @@ class PoissonModel(_DeviceHamiltonian, _Model):
                 raise TypeError("the device likelihood needs a HipDesignMatrix")
             y = np.ascontiguousarray(self.y, dtype=np.float64)
             o = np.ascontiguousarray(self.log_exposure, dtype=np.float64)
-            _lib.check(_lib.load().bbx_poisson_create(
-                self.design.handle, _ptr(y), _ptr(o), byref(self._poisson)))
+            if self.strata is None:
+                _lib.check(_lib.load().bbx_poisson_create(
+                    self.design.handle, _ptr(y), _ptr(o),
+                    byref(self._poisson)))
+            else:
+                sptr = np.ascontiguousarray(self.stratum_ptr, dtype=np.int64)
+                _lib.check(_lib.load().bbx_cpoisson_create(
+                    self.design.handle, _ptr(y), _ptr(o), len(sptr) - 1,
+                    _ptr(sptr), byref(self._poisson)))
         return self._poisson
 
     def compute_loglik_and_gradient(self, beta, loglik_only=False):
         """sum y eta - mu and X~^T (y - mu), mu = exposure exp(eta) (the terms
-        constant in beta are dropped); (-inf, None) where a mean overflows."""
+        constant in beta are dropped); (-inf, None) where a mean overflows.
+        With strata: sum y (a - L_s) and X~^T (y - N_s pi), a = eta +
+        log(exposure), L_s = log sum_s exp(a), pi = exp(a - L_s); finite for
+        every finite beta."""
         beta = np.ascontiguousarray(beta, dtype=np.float64)
         if beta.shape != (self.n_pred,):
             raise ValueError("beta must have length %d" % self.n_pred)
@@ -349,8 +390,10 @@ class PoissonModel(_DeviceHamiltonian, _Model):
     hamiltonian_loglik_and_gradient = compute_loglik_and_gradient
 
     def get_hessian_matvec_operator(self, beta):
-        """v -> -X~^T (mu .* (X~ v)) at beta.  The handle holds one location:
-        an operator stops working once a later call has moved it."""
+        """v -> -X~^T (mu .* (X~ v)) at beta (with strata: v -> -X~^T (N_s pi
+        .* (u - ubar_s)), u = X~ v, ubar_s = sum_s pi u).  The handle holds
+        one location: an operator stops working once a later call has moved
+        it."""
         return self._hessian_operator(beta)
 
     def calc_intercept_mle(self):
@@ -503,6 +546,48 @@ def cox_preprocess_stratified(event_time, censoring_time, strata, X=None):
     if X is not None and not np.array_equal(keep, np.arange(X.shape[0])):
         X = X.tocsr()[keep, :] if sparse.issparse(X) else X[keep, :]
     return event_time, censoring_time, strata, X, keep
+
+
+def cpoisson_preprocess(y, exposure, strata, X=None):
+    """The row order of the conditional Poisson model: the rows sorted
+    stratum-major (strata in np.unique order of their labels; the sort is
+    stable, so the rows of a stratum keep their relative order), then without
+    the strata whose counts sum to 0 and without the strata of a single row
+    -- both contribute a constant to the likelihood.  Returns (y, exposure,
+    strata, X, keep): keep[i] is the original index of row i; exposure stays
+    None if it was."""
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 1:
+        raise ValueError("y must be a 1-d array.")
+    n = len(y)
+    if exposure is not None:
+        exposure = np.asarray(exposure, dtype=np.float64)
+        if exposure.shape != y.shape:
+            raise ValueError("y and exposure must be 1-d arrays of the same "
+                             "length.")
+    strata = np.asarray(strata)
+    labels, codes = _stratum_codes(strata, n)
+    keep = np.argsort(codes, kind='stable')
+    if not np.array_equal(keep, np.arange(n)):
+        warn("The observations and design matrix will be sorted by stratum.")
+    codes = codes[keep]
+    total = np.bincount(codes, weights=y[keep], minlength=len(labels))
+    size = np.bincount(codes, minlength=len(labels))
+    has_count = (total > 0)[codes]
+    if not np.all(has_count):
+        warn("Some strata have no positive count and do not contribute to the "
+             "likelihood, so they are being removed.")
+    plural = (size > 1)[codes]
+    if not np.all(plural | ~has_count):
+        warn("Some strata have a single observation and do not contribute to "
+             "the likelihood, so they are being removed.")
+    keep = keep[has_count & plural]
+    y, strata = y[keep], strata[keep]
+    if exposure is not None:
+        exposure = exposure[keep]
+    if X is not None and not np.array_equal(keep, np.arange(X.shape[0])):
+        X = X.tocsr()[keep, :] if sparse.issparse(X) else X[keep, :]
+    return y, exposure, strata, X, keep
 
 
 def cox_stratified_risk_sets(event_time, censoring_time, strata):
@@ -697,9 +782,38 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     stratified model, (event_time, censoring_time, strata): the rows are
     sorted into the model's order (and uninformative ones dropped) before the
     design goes to the GPU; a prebuilt HipDesignMatrix must already be in that
-    order.  For family='poisson', outcome = y or (y, exposure)."""
+    order.  For family='poisson', outcome = y or (y, exposure) or, for the
+    conditional Poisson model, (y, exposure, strata) (exposure may be None):
+    the rows are sorted stratum-major and uninformative strata dropped
+    (cpoisson_preprocess) before the design goes to the GPU; a prebuilt
+    HipDesignMatrix must already be in that order."""
+    stratified_poisson = (family == 'poisson' and isinstance(outcome, tuple)
+                          and len(outcome) == 3)
     if add_intercept is None:
-        add_intercept = (family != 'cox')
+        add_intercept = (family != 'cox') and not stratified_poisson
+    if stratified_poisson:
+        if add_intercept:
+            add_intercept = False
+            warn("Intercept is not identifiable in the conditional Poisson "
+                 "model and won't be added.")
+        y, exposure, strata = outcome
+        if isinstance(X, HipDesignMatrix):
+            with catch_warnings():
+                simplefilter('ignore')
+                keep = cpoisson_preprocess(y, exposure, strata)[4]
+            if not np.array_equal(keep, np.arange(len(np.asarray(y)))):
+                raise ValueError(
+                    "A prebuilt HipDesignMatrix must have its rows in the "
+                    "conditional Poisson model's order (stratum by stratum "
+                    "in the sorted order of the labels, every stratum with "
+                    "a positive count and more than one row); pass X as a "
+                    "NumPy or SciPy matrix to have it sorted.")
+            if X.intercept_added:
+                raise ValueError("The conditional Poisson model takes a "
+                                 "design without an intercept column.")
+        else:
+            y, exposure, strata, X, _ = cpoisson_preprocess(
+                y, exposure, strata, X)
     if family == 'cox':
         if add_intercept:
             add_intercept = False
@@ -761,6 +875,8 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     if family == 'cox':
         return CoxModel(event_time, censoring_time, design, strata)
     if family == 'poisson':
+        if stratified_poisson:
+            return PoissonModel(y, exposure, design, strata)
         if isinstance(outcome, tuple):
             y, exposure = outcome
         else:

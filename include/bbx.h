@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-/* 110: + strata in the Cox model (bbx_cox_create_stratified): one partial
+/* 111: + the conditional Poisson likelihood (bbx_cpoisson_*): counts with one
+ *      nuisance baseline rate per stratum, conditioned on the stratum totals,
+ *      with the trajectory and the No-U-Turn sampler of the Cox handle.
+ * 110: + strata in the Cox model (bbx_cox_create_stratified): one partial
  *      likelihood per stratum on shared coefficients, through every other
  *      bbx_cox_* entry point unchanged.
  * 109: + the Poisson likelihood (log link, exposure offset) with the HMC
@@ -53,7 +56,7 @@ extern "C" {
  *      bbx_setup_lock_acquire/_release, bbx_design_useful_bytes.  A binding
  *      compares bbx_version() with the BBX_VERSION it was written against
  *      (bayesbridge_amd/_lib.py does) instead of calling with a stale arity. */
-#define BBX_VERSION 110 /* 0.1.10 */
+#define BBX_VERSION 111 /* 0.1.11 */
 
 /* status codes */
 #define BBX_OK 0
@@ -933,6 +936,73 @@ int bbx_poisson_nuts_doubling(bbx_poisson* poisson, double dt, int direction,
                               int* tree, double* averages);
 int bbx_poisson_nuts_sample(bbx_poisson* poisson, double* q, double* logp,
                             double* grad);
+
+/* ----------------------------------------------- conditional Poisson model
+ * Counts with one nuisance baseline rate per stratum (persons of a
+ * self-controlled case series, matched sets, sites), conditioned on every
+ * stratum's total N_s: the product over strata of multinomial probabilities
+ * pi_i = exp(a_i) / sum_{j in s} exp(a_j), a = X~ beta + log(exposure)
+ * (csrc/cpoisson.hip; the leapfrog and tree kernels are the Cox handle's,
+ * csrc/hamiltonian.hpp).  The design has no intercept column: it cancels
+ * inside every stratum.  Rows are stratum-major: stratum s is rows
+ * stratum_ptr[s] .. stratum_ptr[s + 1] - 1.  Every entry point but create has
+ * the argument list, the status codes and the synchronisation of its
+ * bbx_logit_* counterpart above.  The handle borrows the design (it must
+ * outlive the handle) and runs on its stream.  Neither the number of launches
+ * nor the partition of the rows depends on the strata; every sum has a fixed
+ * order: the same inputs give the same bits on every call.
+ *
+ * create: y[n], log_exposure[n] (host; log_exposure may be NULL: all 0),
+ * stratum_ptr[n_strata + 1].  BBX_ERR_INVALID, with a bbx_last_error() that
+ * names the argument, for a NULL y, stratum_ptr or output pointer, a destroyed
+ * or foreign design, a count that is negative or not finite, an offset that
+ * is not finite, a stratum_ptr that does not start at 0, end at n or strictly
+ * increase, and a stratum whose counts sum to 0. */
+typedef struct bbx_cpoisson bbx_cpoisson;
+int bbx_cpoisson_create(bbx_design* design, const double* y,
+                        const double* log_exposure, int64_t n_strata,
+                        const int64_t* stratum_ptr, bbx_cpoisson** out);
+int bbx_cpoisson_destroy(bbx_cpoisson* cpoisson);
+/* loglik = sum_i y_i (a_i - L_s(i)), L_s = log sum_{j in s} exp(a_j) (the
+ * multinomial coefficient is dropped; loglik <= 0); grad[P] = X~^T w,
+ * w_i = y_i - N_s pi_i.  The shift of the log-sum-exp is per stratum: loglik is
+ * finite for every finite beta; a NaN in beta gives NaN.  grad may be NULL. */
+int bbx_cpoisson_loglik_grad(bbx_cpoisson* cpoisson, const double* beta,
+                             double* loglik, double* grad);
+int bbx_cpoisson_loglik_grad_dev(bbx_cpoisson* cpoisson, const double* d_beta,
+                                 double* loglik, double* d_grad);
+/* Hessian-vector products at a fixed beta: set_location stores pi at beta;
+ * hessian_matvec gives out = X~^T (-(N_s pi_i (u_i - ubar_s))), u = X~ v,
+ * ubar_s = sum_{j in s} pi_j u_j (BBX_ERR_STATE before a set_location). */
+int bbx_cpoisson_set_location(bbx_cpoisson* cpoisson, const double* beta);
+int bbx_cpoisson_hessian_matvec(bbx_cpoisson* cpoisson, const double* v,
+                                double* out);
+int bbx_cpoisson_hessian_matvec_dev(bbx_cpoisson* cpoisson, const double* d_v,
+                                    double* d_out);
+/* bbx_cox_hmc_trajectory on the conditional Poisson f. */
+int bbx_cpoisson_hmc_trajectory(bbx_cpoisson* cpoisson, double dt, int n_step,
+                                const double* precond_scale,
+                                const double* prior_prec, const double* q0,
+                                const double* p0, double logp0,
+                                const double* grad0, double hamiltonian_tol,
+                                double* q, double* p, double* logp,
+                                double* grad, int* n_grad_evals,
+                                int* instability, double* hamiltonian);
+/* bbx_cox_nuts_begin / _doubling / _sample on the conditional Poisson f. */
+int bbx_cpoisson_nuts_begin(bbx_cpoisson* cpoisson,
+                            const double* precond_scale,
+                            const double* prior_prec, const double* q0,
+                            const double* p0, double logp0,
+                            const double* grad0, double joint_logp0,
+                            double joint_logp_threshold,
+                            double hamiltonian_tol);
+int bbx_cpoisson_nuts_doubling(bbx_cpoisson* cpoisson, double dt,
+                               int direction, int height,
+                               const double* uniforms, int* n_uniform_used,
+                               int* n_steps, int* flags, int* tree,
+                               double* averages);
+int bbx_cpoisson_nuts_sample(bbx_cpoisson* cpoisson, double* q, double* logp,
+                             double* grad);
 
 /* ----------------------- host-side reference-stream samplers (libbbx_hostrng)
  * Exported by the separate, HIP-free libbbx_hostrng.so.  `bitgen` is the

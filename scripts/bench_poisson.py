@@ -23,6 +23,12 @@ chain draws with 'nuts' from the same seeded start, mean_n_step is the mean
 number of leapfrog steps per draw, and mean_tree_height / mean_accept_prob
 replace accept_rate.
 
+--strata K | sccs: the conditional Poisson model on K strata of equal size
+(K must divide n) or, with `sccs`, on strata of 2 to 8 rows as in a
+self-controlled case series; the outcome is simulated with a baseline rate
+exp(alpha_s), alpha_s ~ N(0, 2^2), per stratum, and the design has no
+intercept column.  The output is the same.
+
 --profile-steps N: only the trajectory (--sampler nuts: one half-tree of N
 steps, N a power of two up to 1024) and N X~ v + X~^T w pairs after a short
 warm-up, for a kernel trace in a run of its own.
@@ -92,25 +98,59 @@ def nuts_half_tree(model, dt, height, scale, pp, q0, p0, logp0, grad0):
     return elapsed
 
 
-def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc'):
+def stratum_sizes(strata, n, seed):
+    """Row counts of the strata, stratum-major: K equal ones, or ('sccs')
+    2 to 8 rows each."""
+    if strata == 'sccs':
+        sizes = np.random.RandomState(seed + 7).randint(2, 9, n // 2)
+        sizes = sizes[:np.searchsorted(np.cumsum(sizes), n - 2, 'right')]
+        rest = n - sizes.sum()                   # 2 .. 9 rows are left
+        tail = [rest] if rest <= 8 else [rest // 2, rest - rest // 2]
+        return np.append(sizes, tail)
+    k = int(strata)
+    if k < 1 or n % k or n // k < 2:
+        raise SystemExit("--strata K: K must divide n into strata of 2 or "
+                         "more rows")
+    return np.full(k, n // k)
+
+
+def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
+        strata=None):
     X = make_X(kind, n, p, seed)
     # demo coefficients scaled down: a count model's mean is exp(eta)
     beta = simulate.demo_beta(p) * .25
     exposure = np.random.RandomState(seed).uniform(.5, 2., n)
-    y = PoissonModel.simulate_outcome(X, beta, exposure=exposure, seed=seed)
+    intercept = strata is None
+    if strata is None:
+        y = PoissonModel.simulate_outcome(X, beta, exposure=exposure,
+                                          seed=seed)
+        outcome = (y, exposure)
+    else:
+        sizes = stratum_sizes(strata, n, seed)
+        label = np.repeat(np.arange(len(sizes)), sizes)
+        alpha = np.random.RandomState(seed + 3).randn(len(sizes)) * 2.
+        y = PoissonModel.simulate_outcome(
+            X, beta, exposure=exposure * np.exp(alpha[label]), seed=seed)
+        # a prebuilt design takes no stratum without a count: give each such
+        # stratum one (the timing does not depend on the counts)
+        empty = np.add.reduceat(y, np.cumsum(sizes) - sizes) == 0
+        y[(np.cumsum(sizes) - sizes)[empty]] = 1
+        outcome = (y, exposure, label)
     if kind == 'binary':
-        design = HipSparseDesignMatrix(X, add_intercept=True,
+        design = HipSparseDesignMatrix(X, add_intercept=intercept,
                                        center_predictor=True)
     else:
-        design = HipDenseDesignMatrix(X, add_intercept=True,
+        design = HipDenseDesignMatrix(X, add_intercept=intercept,
                                       center_predictor=True,
                                       storage_dtype='float32')
     del X
-    model = RegressionModel((y, exposure), design, 'poisson')
+    model = RegressionModel(outcome, design, 'poisson')
     P = design.shape[1]
     rs = np.random.RandomState(1)
     b = rs.randn(P) * .01
     head = {'shape': '%s:%dx%d' % (kind, n, p), 'sampler': sampler}
+    if strata is not None:
+        head['strata'] = len(model.stratum_ptr) - 1
     model.compute_loglik_and_gradient(b)
     tic = time.perf_counter()
     for _ in range(10):
@@ -157,8 +197,10 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc'):
                                 regularizing_slab_size=1.)
     bridge = BayesBridge(model, prior)
     coef = rs.randn(P) * .01
-    coef[0] = model.calc_intercept_mle()
-    init = {'global_scale': .1, 'local_scale': np.ones(P - 1), 'coef': coef}
+    if intercept:
+        coef[0] = model.calc_intercept_mle()
+    init = {'global_scale': .1, 'local_scale': np.ones(P - int(intercept)),
+            'coef': coef}
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
         _, info = bridge.gibbs(warmup, init=init, seed=0,
@@ -187,13 +229,16 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--profile-steps', type=int, default=0)
     ap.add_argument('--sampler', choices=['hmc', 'nuts'], default='hmc')
+    ap.add_argument('--strata', default=None,
+                    help="K equal strata, or 'sccs': strata of 2 to 8 rows")
     a = ap.parse_args()
     for s in a.shapes:
         kind, size = s.split(':')
         n, p = (int(x) for x in size.split('x'))
         print(json.dumps(run(kind, n, p, a.steps, a.warmup,
                              profile_steps=a.profile_steps,
-                             sampler=a.sampler)), flush=True)
+                             sampler=a.sampler, strata=a.strata)),
+              flush=True)
 
 
 if __name__ == '__main__':
