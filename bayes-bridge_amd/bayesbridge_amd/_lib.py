@@ -205,95 +205,36 @@ def _declare(lib):
         "bbx_cox_create_stratified": (
             [hp, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
              POINTER(hp)], c_int),
-        "bbx_cox_destroy": ([hp], c_int),
-        "bbx_cox_loglik_grad": ([hp, c_void_p, POINTER(c_double), c_void_p],
-                                c_int),
-        "bbx_cox_loglik_grad_dev": (
-            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
-        "bbx_cox_set_location": ([hp, c_void_p], c_int),
-        "bbx_cox_hessian_matvec": ([hp, c_void_p, c_void_p], c_int),
-        "bbx_cox_hessian_matvec_dev": ([hp, c_void_p, c_void_p], c_int),
-        "bbx_cox_hmc_trajectory": (
-            [hp, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-             c_double, c_void_p, c_double, c_void_p, c_void_p,
-             POINTER(c_double), c_void_p, POINTER(c_int), POINTER(c_int),
-             c_void_p], c_int),
-        "bbx_cox_nuts_begin": (
-            [hp, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
-             c_double, c_double, c_double], c_int),
-        "bbx_cox_nuts_doubling": (
-            [hp, c_double, c_int, c_int, c_void_p, POINTER(c_int),
-             POINTER(c_int), c_void_p, c_void_p, c_void_p], c_int),
-        "bbx_cox_nuts_sample": (
-            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
         "bbx_logit_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
-        "bbx_logit_destroy": ([hp], c_int),
-        "bbx_logit_loglik_grad": ([hp, c_void_p, POINTER(c_double), c_void_p],
-                                c_int),
-        "bbx_logit_loglik_grad_dev": (
-            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
-        "bbx_logit_set_location": ([hp, c_void_p], c_int),
-        "bbx_logit_hessian_matvec": ([hp, c_void_p, c_void_p], c_int),
-        "bbx_logit_hessian_matvec_dev": ([hp, c_void_p, c_void_p], c_int),
-        "bbx_logit_hmc_trajectory": (
-            [hp, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-             c_double, c_void_p, c_double, c_void_p, c_void_p,
-             POINTER(c_double), c_void_p, POINTER(c_int), POINTER(c_int),
-             c_void_p], c_int),
-        "bbx_logit_nuts_begin": (
-            [hp, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
-             c_double, c_double, c_double], c_int),
-        "bbx_logit_nuts_doubling": (
-            [hp, c_double, c_int, c_int, c_void_p, POINTER(c_int),
-             POINTER(c_int), c_void_p, c_void_p, c_void_p], c_int),
-        "bbx_logit_nuts_sample": (
-            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
         "bbx_poisson_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
-        "bbx_poisson_destroy": ([hp], c_int),
-        "bbx_poisson_loglik_grad": (
-            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
-        "bbx_poisson_loglik_grad_dev": (
-            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
-        "bbx_poisson_set_location": ([hp, c_void_p], c_int),
-        "bbx_poisson_hessian_matvec": ([hp, c_void_p, c_void_p], c_int),
-        "bbx_poisson_hessian_matvec_dev": ([hp, c_void_p, c_void_p], c_int),
-        "bbx_poisson_hmc_trajectory": (
-            [hp, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-             c_double, c_void_p, c_double, c_void_p, c_void_p,
-             POINTER(c_double), c_void_p, POINTER(c_int), POINTER(c_int),
-             c_void_p], c_int),
-        "bbx_poisson_nuts_begin": (
-            [hp, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
-             c_double, c_double, c_double], c_int),
-        "bbx_poisson_nuts_doubling": (
-            [hp, c_double, c_int, c_int, c_void_p, POINTER(c_int),
-             POINTER(c_int), c_void_p, c_void_p, c_void_p], c_int),
-        "bbx_poisson_nuts_sample": (
-            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
         "bbx_cpoisson_create": (
             [hp, c_void_p, c_void_p, c_int64, c_void_p, POINTER(hp)], c_int),
-        "bbx_cpoisson_destroy": ([hp], c_int),
-        "bbx_cpoisson_loglik_grad": (
-            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
-        "bbx_cpoisson_loglik_grad_dev": (
-            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
-        "bbx_cpoisson_set_location": ([hp, c_void_p], c_int),
-        "bbx_cpoisson_hessian_matvec": ([hp, c_void_p, c_void_p], c_int),
-        "bbx_cpoisson_hessian_matvec_dev": ([hp, c_void_p, c_void_p], c_int),
-        "bbx_cpoisson_hmc_trajectory": (
-            [hp, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-             c_double, c_void_p, c_double, c_void_p, c_void_p,
-             POINTER(c_double), c_void_p, POINTER(c_int), POINTER(c_int),
-             c_void_p], c_int),
-        "bbx_cpoisson_nuts_begin": (
-            [hp, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
-             c_double, c_double, c_double], c_int),
-        "bbx_cpoisson_nuts_doubling": (
-            [hp, c_double, c_int, c_int, c_void_p, POINTER(c_int),
-             POINTER(c_int), c_void_p, c_void_p, c_void_p], c_int),
-        "bbx_cpoisson_nuts_sample": (
-            [hp, c_void_p, POINTER(c_double), c_void_p], c_int),
     }
+    # the ten entry points every Hamiltonian likelihood handle has
+    # (csrc/hamiltonian.hpp): the same argument lists in every family
+    shared = {
+        "destroy": [hp],
+        "loglik_grad": [hp, c_void_p, POINTER(c_double), c_void_p],
+        "loglik_grad_dev": [hp, c_void_p, POINTER(c_double), c_void_p],
+        "set_location": [hp, c_void_p],
+        "hessian_matvec": [hp, c_void_p, c_void_p],
+        "hessian_matvec_dev": [hp, c_void_p, c_void_p],
+        "hmc_trajectory": [
+            hp, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+            c_double, c_void_p, c_double, c_void_p, c_void_p,
+            POINTER(c_double), c_void_p, POINTER(c_int), POINTER(c_int),
+            c_void_p],
+        "nuts_begin": [
+            hp, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
+            c_double, c_double, c_double],
+        "nuts_doubling": [
+            hp, c_double, c_int, c_int, c_void_p, POINTER(c_int),
+            POINTER(c_int), c_void_p, c_void_p, c_void_p],
+        "nuts_sample": [hp, c_void_p, POINTER(c_double), c_void_p],
+    }
+    for family in ("cox", "logit", "poisson", "cpoisson"):
+        for entry, argtypes in shared.items():
+            sigs["bbx_%s_%s" % (family, entry)] = (list(argtypes), c_int)
     for name, (argtypes, restype) in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes

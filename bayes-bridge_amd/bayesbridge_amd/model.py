@@ -68,11 +68,33 @@ def _ptr(a):
 class _DeviceHamiltonian():
     """The device trajectory and No-U-Turn tree of a likelihood handle
     (csrc/hamiltonian.hpp): the same calls on bbx_cox_*, bbx_logit_*,
-    bbx_poisson_* and bbx_cpoisson_*.  A model names its family in `_ham_prefix` and gives its
-    handle as `handle`."""
+    bbx_poisson_* and bbx_cpoisson_*.  A model names its family in
+    `_ham_prefix`, gives its handle as `handle` and keeps it in the attribute
+    that `_handle_attr` names."""
 
     def _ham_fn(self, name):
         return getattr(_lib.load(), self._ham_prefix + name)
+
+    def __del__(self):
+        h = getattr(self, self._handle_attr, None)
+        if h and not _lib.finalizing:
+            self._ham_fn('destroy')(h)
+        setattr(self, self._handle_attr, c_void_p())
+
+    def _device_loglik_and_gradient(self, beta, loglik_only=False,
+                                    inf_has_no_gradient=True):
+        """bbx_<family>_loglik_grad at beta: (loglik, gradient or None);
+        (-inf, None) where the likelihood is -inf, unless told otherwise."""
+        beta = np.ascontiguousarray(beta, dtype=np.float64)
+        if beta.shape != (self.n_pred,):
+            raise ValueError("beta must have length %d" % self.n_pred)
+        loglik = c_double()
+        grad = None if loglik_only else np.empty(self.n_pred)
+        _lib.check(self._ham_fn('loglik_grad')(
+            self.handle, _ptr(beta), byref(loglik), _ptr(grad)))
+        if inf_has_no_gradient and loglik.value == -float('inf'):
+            return -float('inf'), None
+        return loglik.value, grad
 
     def _hessian_operator(self, beta):
         """The handle holds one location: an operator stops working once a
@@ -175,6 +197,8 @@ class _DeviceHamiltonian():
 
 class LogisticModel(_DeviceHamiltonian, _Model):
 
+    _handle_attr = '_logit'
+
     def __init__(self, n_success, n_trial, design):
         """Outcome checks of logistic_model.py:10-47: counts must line up with
         the rows of the design, 0 < n_trial, n_success <= n_trial; without
@@ -211,12 +235,6 @@ class LogisticModel(_DeviceHamiltonian, _Model):
         self._logit = c_void_p()
         self._location_serial = 0
 
-    def __del__(self):
-        h = getattr(self, '_logit', None)
-        if h and not _lib.finalizing:
-            _lib.load().bbx_logit_destroy(h)
-        self._logit = c_void_p()
-
     @property
     def handle(self):
         if not self._logit:
@@ -243,14 +261,8 @@ class LogisticModel(_DeviceHamiltonian, _Model):
         summation orders, the gradient's X~^T product without a host round
         trip): what the 'hmc' and 'nuts' samplers evaluate.  The other
         samplers keep compute_loglik_and_gradient."""
-        beta = np.ascontiguousarray(beta, dtype=np.float64)
-        if beta.shape != (self.n_pred,):
-            raise ValueError("beta must have length %d" % self.n_pred)
-        loglik = c_double()
-        grad = None if loglik_only else np.empty(self.n_pred)
-        _lib.check(self._ham_fn('loglik_grad')(
-            self.handle, _ptr(beta), byref(loglik), _ptr(grad)))
-        return loglik.value, grad
+        return self._device_loglik_and_gradient(beta, loglik_only,
+                                                inf_has_no_gradient=False)
 
     def get_hessian_matvec_operator(self, beta):
         """logistic_model.py:68-74 on the device."""
@@ -287,6 +299,8 @@ class PoissonModel(_DeviceHamiltonian, _Model):
     stratum, conditioned on the stratum's total count, through one
     bbx_cpoisson handle (csrc/cpoisson.hip) on a design without an intercept
     column."""
+
+    _handle_attr = '_poisson'
 
     def __init__(self, y, exposure, design, strata=None):
         """Counts must line up with the rows of the design and be
@@ -345,12 +359,6 @@ class PoissonModel(_DeviceHamiltonian, _Model):
         self._poisson = c_void_p()
         self._location_serial = 0
 
-    def __del__(self):
-        h = getattr(self, '_poisson', None)
-        if h and not _lib.finalizing:
-            self._ham_fn('destroy')(h)
-        self._poisson = c_void_p()
-
     @property
     def handle(self):
         if not self._poisson:
@@ -375,16 +383,7 @@ class PoissonModel(_DeviceHamiltonian, _Model):
         With strata: sum y (a - L_s) and X~^T (y - N_s pi), a = eta +
         log(exposure), L_s = log sum_s exp(a), pi = exp(a - L_s); finite for
         every finite beta."""
-        beta = np.ascontiguousarray(beta, dtype=np.float64)
-        if beta.shape != (self.n_pred,):
-            raise ValueError("beta must have length %d" % self.n_pred)
-        loglik = c_double()
-        grad = None if loglik_only else np.empty(self.n_pred)
-        _lib.check(self._ham_fn('loglik_grad')(
-            self.handle, _ptr(beta), byref(loglik), _ptr(grad)))
-        if loglik.value == -float('inf'):
-            return -float('inf'), None
-        return loglik.value, grad
+        return self._device_loglik_and_gradient(beta, loglik_only)
 
     # the trajectory's f(q0) (hmc.py:95-97) is the model's own likelihood
     hamiltonian_loglik_and_gradient = compute_loglik_and_gradient
@@ -674,6 +673,8 @@ class CoxModel(_DeviceHamiltonian, _Model):
     partial likelihood: one risk-set structure and one baseline hazard per
     stratum, shared coefficients."""
 
+    _handle_attr = '_cox'
+
     def __init__(self, event_time, censoring_time, design, strata=None):
         self.strata = None
         if strata is None:
@@ -703,28 +704,21 @@ class CoxModel(_DeviceHamiltonian, _Model):
         self.design = design
         self.name = 'cox'
         self._ham_prefix = 'bbx_cox_'
-        self._lib = _lib.load()
         self._cox = c_void_p()
         self._location_serial = 0
         if strata is None:
             i32 = [np.ascontiguousarray(a, dtype=np.int32)
                    for a in (start, end, n_app)]
-            _lib.check(self._lib.bbx_cox_create(
+            _lib.check(self._ham_fn('create')(
                 design.handle, n_event, _ptr(i32[0]), _ptr(i32[1]),
                 _ptr(i32[2]), byref(self._cox)))
         else:
             sptr = np.ascontiguousarray(sptr, dtype=np.int64)
             i32 = [np.ascontiguousarray(a, dtype=np.int32)
                    for a in (sne, start, end, last_set)]
-            _lib.check(self._lib.bbx_cox_create_stratified(
+            _lib.check(self._ham_fn('create_stratified')(
                 design.handle, len(sne), _ptr(sptr), *[_ptr(a) for a in i32],
                 byref(self._cox)))
-
-    def __del__(self):
-        h = getattr(self, '_cox', None)
-        if h and not _lib.finalizing:
-            self._lib.bbx_cox_destroy(h)
-        self._cox = c_void_p()
 
     @property
     def handle(self):
@@ -732,16 +726,7 @@ class CoxModel(_DeviceHamiltonian, _Model):
 
     def compute_loglik_and_gradient(self, beta, loglik_only=False):
         """cox_model.py:180-204: (-inf, None) when a risk-set sum is 0."""
-        beta = np.ascontiguousarray(beta, dtype=np.float64)
-        if beta.shape != (self.n_pred,):
-            raise ValueError("beta must have length %d" % self.n_pred)
-        loglik = c_double()
-        grad = None if loglik_only else np.empty(self.n_pred)
-        _lib.check(self._lib.bbx_cox_loglik_grad(
-            self._cox, _ptr(beta), byref(loglik), _ptr(grad)))
-        if loglik.value == -float('inf'):
-            return -float('inf'), None
-        return loglik.value, grad
+        return self._device_loglik_and_gradient(beta, loglik_only)
 
     def compute_hessian(self, beta):
         raise NotImplementedError()

@@ -327,7 +327,6 @@ Segs event_segs(const bbx_cox* c) {
 using ham::cst;
 using ham::eta_of;
 using ham::read_state;
-using ham::with_p_stage;
 
 template <int MODE>
 int launch_scan_sum(bbx_cox* c, const Segs& sg, int nseg, const ScanArgs& a,
@@ -488,13 +487,6 @@ int likelihood_from_eta(bbx_cox* c, double* h_out, double* inv, double* cum,
   return launch_tdot(h, c->tmp.as<double>(), sumw, ep, grad);
 }
 
-int cox_check(const bbx_cox* c) {
-  if (!c) return fail(BBX_ERR_INVALID, "NULL cox handle");
-  if (!design_alive(c->h))
-    return fail(BBX_ERR_STATE, "the cox handle's design has been destroyed");
-  return BBX_OK;
-}
-
 // A handle with every buffer both kinds of handle use, the three index arrays
 // uploaded (n_event, n_event and n int32) and the device state zeroed; the
 // uploads are complete on return.
@@ -502,42 +494,21 @@ int cox_new(bbx_design* h, int64_t n_event, const int32_t* start,
             const int32_t* end, const int32_t* n_app, bbx_cox** out) {
   const int64_t n = h->n;
   bbx_cox* c = new bbx_cox;
-  c->h = h;
-  c->device = h->device;
-  c->n = n;
   c->ne = n_event;
-  c->P = h->P;
-  auto cleanup = [&](int st) {
-    if (c->host_st) (void)hipHostFree(c->host_st);
-    delete c;
-    return st;
-  };
-  if (hipSetDevice(h->device) != hipSuccess)
-    return cleanup(fail(BBX_ERR_HIP, "hipSetDevice"));
   const size_t d8 = sizeof(double), i4 = sizeof(int32_t);
-  int st = BBX_OK;
-  DevMem* nvec[] = {&c->eta, &c->hz, &c->scan, &c->tmp, &c->h_loc};
+  int st = ham::init_core(c, h, "cox");
+  DevMem* nvec[] = {&c->hz, &c->scan, &c->h_loc};
   for (DevMem* m : nvec)
     if (st == BBX_OK) st = m->alloc(d8 * n);
   DevMem* evec[] = {&c->inv, &c->cs, &c->inv_loc, &c->c_loc};
   for (DevMem* m : evec)
     if (st == BBX_OK) st = m->alloc(d8 * n_event);
-  DevMem* pvec[] = {&c->q, &c->p, &c->p2, &c->g, &c->gl, &c->v, &c->scale, &c->pp};
-  for (DevMem* m : pvec)
-    if (st == BBX_OK) st = m->alloc(d8 * c->P);
   if (st == BBX_OK) st = c->start.alloc(i4 * n_event);
   if (st == BBX_OK) st = c->end.alloc(i4 * n_event);
   if (st == BBX_OK) st = c->napp.alloc(i4 * n);
   if (st == BBX_OK) st = c->csum.alloc(d8 * 2 * SCAN_G);
   if (st == BBX_OK) st = c->maxp.alloc(d8 * NPART);
-  if (st == BBX_OK) st = c->llpart.alloc(d8 * SCAN_G);
-  if (st == BBX_OK) st = c->post.alloc(d8 * 3 * NPART);
-  if (st == BBX_OK) st = c->st.alloc(sizeof(CoxTraj));
-  if (st != BBX_OK) return cleanup(st);
-  if (hipHostMalloc((void**)&c->host_st, sizeof(CoxTraj)) != hipSuccess) {
-    c->host_st = nullptr;
-    return cleanup(fail(BBX_ERR_HIP, "hipHostMalloc"));
-  }
+  if (st != BBX_OK) return ham::discard(c, st);
   hipError_t e = hipMemcpyAsync(c->start.ptr, start, i4 * n_event,
                                 hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess)
@@ -546,11 +517,10 @@ int cox_new(bbx_design* h, int64_t n_event, const int32_t* start,
   if (e == hipSuccess)
     e = hipMemcpyAsync(c->napp.ptr, n_app, i4 * n, hipMemcpyHostToDevice,
                        h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(c->st.ptr, 0, sizeof(CoxTraj), h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess)
-    return cleanup(fail(BBX_ERR_HIP, std::string("cox upload: ") +
-                                         hipGetErrorString(e)));
+    return ham::discard(c, fail(BBX_ERR_HIP, std::string("cox upload: ") +
+                                                 hipGetErrorString(e)));
   *out = c;
   return BBX_OK;
 }
@@ -670,33 +640,40 @@ int cox_create_strat_impl(bbx_design* h, int64_t ns, const int64_t* sptr,
       st = fail(BBX_ERR_HIP, std::string("stratified cox upload: ") +
                                  hipGetErrorString(e));
   }
-  if (st != BBX_OK) {
-    ham::free_pinned(c);
-    delete c;
-    return st;
-  }
+  if (st != BBX_OK) return ham::discard(c, st);
   *out = c;
   return BBX_OK;
 }
 
-int cox_loglik_grad_dev(bbx_cox* c, const double* d_beta, double* loglik,
-                        double* d_grad) {
-  bbx_design* h = c->h;
-  BBX_LAUNCH(cox_reset_kernel, dim3(1), dim3(WAVE), 0, h->stream, cst(c));
-  BBX_TRY(eta_of(c, d_beta));
-  BBX_TRY(likelihood_from_eta(c, c->hz.as<double>(), c->inv.as<double>(),
-                              c->cs.as<double>(), d_grad));
-  BBX_LAUNCH(cox_loglik_kernel, dim3(1), dim3(WAVE), 0, h->stream,
-             c->llpart.as<const double>(), cst(c));
-  BBX_HIP(hipGetLastError());
-  BBX_TRY(read_state(c));
-  *loglik = c->host_st->logp;
-  return BBX_OK;
-}
+// The Cox block of a leapfrog step: everything from eta to X~^T w
+struct CoxLik {
+  bbx_cox* c;
+  int operator()(double* grad) const {
+    return likelihood_from_eta(c, c->hz.as<double>(), c->inv.as<double>(),
+                               c->cs.as<double>(), grad);
+  }
+};
 
-int cox_hessian_dev(bbx_cox* c, const double* d_v, double* d_out) {
-  if (!c->have_location)
-    return fail(BBX_ERR_STATE, "bbx_cox_set_location has not succeeded");
+struct CoxFamily {
+  static constexpr const char* name = "cox";
+  using Lik = CoxLik;
+  static int locate(bbx_cox* c, const double* d_in) {
+    BBX_LAUNCH(cox_reset_kernel, dim3(1), dim3(WAVE), 0, c->h->stream, cst(c));
+    BBX_TRY(eta_of(c, d_in));
+    BBX_TRY(likelihood_from_eta(c, c->h_loc.as<double>(),
+                                c->inv_loc.as<double>(), c->c_loc.as<double>(),
+                                nullptr));
+    BBX_TRY(read_state(c));
+    if (c->host_st->zero)
+      return fail(BBX_ERR_NUMERIC,
+                  "Hessian location: a risk-set sum of relative hazards is 0");
+    return BBX_OK;
+  }
+  static int hessian_from_v(bbx_cox* c, const double* d_v, double* d_out);
+};
+
+int CoxFamily::hessian_from_v(bbx_cox* c, const double* d_v,
+                              double* d_out) {
   bbx_design* h = c->h;
   BBX_LAUNCH(cox_reset_kernel, dim3(1), dim3(WAVE), 0, h->stream, cst(c));
   BBX_TRY(eta_of(c, d_v));   // u = X~ v, in c->eta
@@ -730,15 +707,6 @@ int cox_hessian_dev(bbx_cox* c, const double* d_v, double* d_out) {
   return launch_tdot(h, c->tmp.as<double>(), sumw, ep, d_out);
 }
 
-// The Cox block of a leapfrog step: everything from eta to X~^T w
-struct CoxLik {
-  bbx_cox* c;
-  int operator()(double* grad) const {
-    return likelihood_from_eta(c, c->hz.as<double>(), c->inv.as<double>(),
-                               c->cs.as<double>(), grad);
-  }
-};
-
 }  // namespace
 
 extern "C" {
@@ -761,140 +729,6 @@ int bbx_cox_create_stratified(bbx_design* design, int64_t n_strata,
   });
 }
 
-int bbx_cox_destroy(bbx_cox* c) {
-  if (!c) return BBX_OK;
-  if (design_alive(c->h)) {
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->h->stream);
-  }
-  ham::free_pinned(c);
-  delete c;
-  return BBX_OK;
-}
-
-int bbx_cox_loglik_grad_dev(bbx_cox* c, const double* d_beta, double* loglik,
-                            double* d_grad) {
-  BBX_TRY(cox_check(c));
-  if (!d_beta || !loglik) return fail(BBX_ERR_INVALID, "NULL argument");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] { return cox_loglik_grad_dev(c, d_beta, loglik, d_grad); });
-}
-
-int bbx_cox_loglik_grad(bbx_cox* c, const double* beta, double* loglik,
-                        double* grad) {
-  BBX_TRY(cox_check(c));
-  if (!beta || !loglik) return fail(BBX_ERR_INVALID, "NULL argument");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] {
-    double ll = 0.;
-    BBX_TRY(with_p_stage(c, beta, grad, [&](const double* d_in, double* d_out) {
-      return cox_loglik_grad_dev(c, d_in, &ll, d_out);
-    }));
-    *loglik = ll;
-    return BBX_OK;
-  });
-}
-
-int bbx_cox_set_location(bbx_cox* c, const double* beta) {
-  BBX_TRY(cox_check(c));
-  if (!beta) return fail(BBX_ERR_INVALID, "NULL argument");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] {
-    bbx_design* h = c->h;
-    c->have_location = false;
-    double* d_in = h->stage_P.as<double>();
-    BBX_HIP(hipMemcpyAsync(d_in, beta, sizeof(double) * c->P,
-                           hipMemcpyHostToDevice, h->stream));
-    BBX_LAUNCH(cox_reset_kernel, dim3(1), dim3(WAVE), 0, h->stream, cst(c));
-    BBX_TRY(eta_of(c, d_in));
-    BBX_TRY(likelihood_from_eta(c, c->h_loc.as<double>(),
-                                c->inv_loc.as<double>(), c->c_loc.as<double>(),
-                                nullptr));
-    BBX_TRY(read_state(c));
-    if (c->host_st->zero)
-      return fail(BBX_ERR_NUMERIC,
-                  "Hessian location: a risk-set sum of relative hazards is 0");
-    c->have_location = true;
-    return BBX_OK;
-  });
-}
-
-int bbx_cox_hessian_matvec_dev(bbx_cox* c, const double* d_v, double* d_out) {
-  BBX_TRY(cox_check(c));
-  if (!d_v || !d_out) return fail(BBX_ERR_INVALID, "NULL argument");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] { return cox_hessian_dev(c, d_v, d_out); });
-}
-
-int bbx_cox_hessian_matvec(bbx_cox* c, const double* v, double* out) {
-  BBX_TRY(cox_check(c));
-  if (!v || !out) return fail(BBX_ERR_INVALID, "NULL argument");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] {
-    return with_p_stage(c, v, out, [&](const double* d_in, double* d_out) {
-      return cox_hessian_dev(c, d_in, d_out);
-    });
-  });
-}
-
-int bbx_cox_hmc_trajectory(bbx_cox* c, double dt, int n_step,
-                           const double* precond_scale,
-                           const double* prior_prec, const double* q0,
-                           const double* p0, double logp0, const double* grad0,
-                           double hamiltonian_tol, double* q, double* p,
-                           double* logp, double* grad, int* n_grad_evals,
-                           int* instability, double* hamiltonian) {
-  BBX_TRY(cox_check(c));
-  if (!precond_scale || !prior_prec || !q0 || !p0 || !grad0)
-    return fail(BBX_ERR_INVALID, "NULL argument");
-  if (n_step < 0) return fail(BBX_ERR_INVALID, "n_step < 0");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] {
-    CoxLik lik{c};
-    return ham::trajectory_impl(c, lik, dt, n_step, precond_scale, prior_prec,
-                                q0, p0, logp0, grad0, hamiltonian_tol, q, p,
-                                logp, grad, n_grad_evals, instability,
-                                hamiltonian);
-  });
-}
-
-int bbx_cox_nuts_begin(bbx_cox* c, const double* precond_scale,
-                       const double* prior_prec, const double* q0,
-                       const double* p0, double logp0, const double* grad0,
-                       double joint_logp0, double joint_logp_threshold,
-                       double hamiltonian_tol) {
-  BBX_TRY(cox_check(c));
-  if (!precond_scale || !prior_prec || !q0 || !p0 || !grad0)
-    return fail(BBX_ERR_INVALID, "NULL argument");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] {
-    return ham::nuts_begin_impl(c, precond_scale, prior_prec, q0, p0, logp0,
-                                grad0, joint_logp0, joint_logp_threshold,
-                                hamiltonian_tol);
-  });
-}
-
-int bbx_cox_nuts_doubling(bbx_cox* c, double dt, int direction, int height,
-                          const double* uniforms, int* n_uniform_used,
-                          int* n_steps, int* flags, int* tree,
-                          double* averages) {
-  BBX_TRY(cox_check(c));
-  BBX_TRY(ham::nuts_doubling_args(c, "bbx_cox", uniforms, direction, height));
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] {
-    CoxLik lik{c};
-    BBX_TRY(ham::nuts_doubling_impl(c, lik, dt, direction, height, uniforms));
-    ham::nuts_doubling_out(c, n_uniform_used, n_steps, flags, tree, averages);
-    return BBX_OK;
-  });
-}
-
-int bbx_cox_nuts_sample(bbx_cox* c, double* q, double* logp, double* grad) {
-  BBX_TRY(cox_check(c));
-  if (!c->nuts_begun)
-    return fail(BBX_ERR_STATE, "bbx_cox_nuts_begin has not succeeded");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] { return ham::nuts_sample_impl(c, q, logp, grad); });
-}
-
 }  // extern "C"
+
+BBX_HAM_ENTRY_POINTS(cox, CoxFamily)

@@ -1,8 +1,9 @@
 // The preconditioned Hamiltonian trajectory shared by the likelihood families
-// (cox.hip, logit.hip): the leapfrog kernels, the No-U-Turn tree and their
-// drivers.  Velocity Verlet in preconditioned coordinates q = coef / scale,
-// f(q) = loglik(scale q) - 1/2 sum prior_prec q^2 (hmc.py:137-174,
-// dynamics.py, nuts.py).
+// (cox.hip, logit.hip, poisson.hip, cpoisson.hip): the leapfrog kernels, the
+// No-U-Turn tree, their drivers and the front of the C ABI (the ten entry
+// points every handle has).  Velocity Verlet in preconditioned coordinates
+// q = coef / scale, f(q) = loglik(scale q) - 1/2 sum prior_prec q^2
+// (hmc.py:137-174, dynamics.py, nuts.py).
 //
 // Per step (host enqueues, no synchronisation): step1 (half kick with the
 // previous gradient, drift, the dot input), X~ v, the family's likelihood
@@ -476,8 +477,9 @@ static __global__ __launch_bounds__(WAVE) void cox_nuts_merge_b_kernel(
   }
 }
 // ---------------------------------------------------------------- host side
-// What the trajectory and the tree need from a likelihood handle; bbx_cox and
-// bbx_logit derive from it (the design is borrowed: it must outlive them).
+// What the trajectory, the tree and the C ABI front need from a likelihood
+// handle; bbx_cox, bbx_logit, bbx_poisson and bbx_cpoisson derive from it (the
+// design is borrowed: it must outlive them).
 struct HamCore {
   bbx_design* h = nullptr;
   int device = 0;
@@ -756,14 +758,37 @@ int nuts_doubling_impl(HamCore* c, Lik& lik, double dt, int dir, int height,
   return BBX_OK;
 }
 
-// The C entry points' argument checks and read-backs, the same for every
-// family.  `what`: the family's prefix in messages ("bbx_cox", "bbx_logit").
-inline int nuts_doubling_args(const HamCore* c, const char* what,
+// ------------------------------------------------------------ the C ABI front
+// Everything of a handle's C entry points that does not depend on the family:
+// the checks, the HamCore part of `create`, `destroy` and one template per
+// shared entry point.  A family states a policy F:
+//   F::name                          "cox", "logit", ...: bbx_<name>_* and the
+//                                    messages
+//   F::Lik                           its likelihood block, built as Lik{c}
+//   F::locate(c, d_in)               set_location between the upload of beta
+//                                    (in d_in) and have_location = true; the
+//                                    host's beta is free when it returns
+//   F::hessian_from_v(c, d_v, d_out) the Hessian matvec at the location
+// and stamps its ten entry points with BBX_HAM_ENTRY_POINTS.
+inline int check(const HamCore* c, const char* family) {
+  if (!c)
+    return fail(BBX_ERR_INVALID, std::string("NULL ") + family + " handle");
+  if (!design_alive(c->h))
+    return fail(BBX_ERR_STATE, std::string("the ") + family +
+                                   " handle's design has been destroyed");
+  return BBX_OK;
+}
+
+// bbx_<family>_<entry> has to succeed before the call that was made
+inline int not_yet(const char* family, const char* entry) {
+  return fail(BBX_ERR_STATE, std::string("bbx_") + family + "_" + entry +
+                                 " has not succeeded");
+}
+
+inline int nuts_doubling_args(const HamCore* c, const char* family,
                               const double* uniforms, int direction,
                               int height) {
-  if (!c->nuts_begun)
-    return fail(BBX_ERR_STATE,
-                std::string(what) + "_nuts_begin has not succeeded");
+  if (!c->nuts_begun) return not_yet(family, "nuts_begin");
   if (!uniforms) return fail(BBX_ERR_INVALID, "NULL argument");
   if (direction != 1 && direction != -1)
     return fail(BBX_ERR_INVALID, "direction must be 1 or -1");
@@ -819,5 +844,261 @@ inline void free_pinned(HamCore* c) {
   c->host_nuts = nullptr;
 }
 
+// The HamCore part of a family's `create`, on a fresh handle: every buffer
+// HamCore declares but the NUTS ones, the pinned read-back and the device
+// state zeroed (queued on the design's stream: the family synchronises once,
+// after its own uploads).  After a failure the caller discards the handle.
+// (static, as the kernels are: a handle type's name in an exported symbol
+// would read as part of the C ABI.)
+static int init_core(HamCore* c, bbx_design* h, const char* family) {
+  c->h = h;
+  c->device = h->device;
+  c->n = h->n;
+  c->P = h->P;
+  if (hipSetDevice(h->device) != hipSuccess)
+    return fail(BBX_ERR_HIP, "hipSetDevice");
+  const size_t d8 = sizeof(double);
+  BBX_TRY(c->eta.alloc(d8 * c->n));
+  BBX_TRY(c->tmp.alloc(d8 * c->n));
+  DevMem* pvec[] = {&c->q, &c->p, &c->p2, &c->g, &c->gl, &c->v, &c->scale, &c->pp};
+  for (DevMem* m : pvec) BBX_TRY(m->alloc(d8 * c->P));
+  BBX_TRY(c->llpart.alloc(d8 * SCAN_G));
+  BBX_TRY(c->post.alloc(d8 * 3 * NPART));
+  BBX_TRY(c->st.alloc(sizeof(CoxTraj)));
+  if (hipHostMalloc((void**)&c->host_st, sizeof(CoxTraj)) != hipSuccess) {
+    c->host_st = nullptr;
+    return fail(BBX_ERR_HIP, "hipHostMalloc");
+  }
+  const hipError_t e = hipMemsetAsync(c->st.ptr, 0, sizeof(CoxTraj), h->stream);
+  if (e != hipSuccess)
+    return fail(BBX_ERR_HIP, std::string(family) + " upload: " +
+                                 hipGetErrorString(e));
+  return BBX_OK;
+}
+
+// Frees a handle and passes `st` on: the end of a `create` that failed
+template <class H>
+static int discard(H* c, int st) {
+  free_pinned(c);
+  delete c;
+  return st;
+}
+
+template <class H>
+static int destroy(H* c) {
+  if (!c) return BBX_OK;
+  if (design_alive(c->h)) {
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->h->stream);
+  }
+  return discard(c, BBX_OK);
+}
+
+// loglik (and, d_grad != null, its gradient) at a P-vector on the device
+template <class Lik>
+int loglik_grad_impl(HamCore* c, Lik& lik, const double* d_beta,
+                     double* loglik, double* d_grad) {
+  bbx_design* h = c->h;
+  // a trajectory that stopped early leaves its skip flag set
+  BBX_LAUNCH(cox_reset_kernel, dim3(1), dim3(WAVE), 0, h->stream, cst(c));
+  BBX_HIP(hipGetLastError());
+  BBX_TRY(eta_of(c, d_beta));
+  BBX_TRY(lik(d_grad));
+  BBX_LAUNCH(cox_loglik_kernel, dim3(1), dim3(WAVE), 0, h->stream,
+             c->llpart.as<const double>(), cst(c));
+  BBX_HIP(hipGetLastError());
+  BBX_TRY(read_state(c));
+  *loglik = c->host_st->logp;
+  return BBX_OK;
+}
+
+template <class F, class H>
+int hessian_impl(H* c, const double* d_v, double* d_out) {
+  if (!c->have_location) return not_yet(F::name, "set_location");
+  return F::hessian_from_v(c, d_v, d_out);
+}
+
+template <class F, class H>
+int loglik_grad_dev(H* c, const double* d_beta, double* loglik,
+                    double* d_grad) {
+  BBX_TRY(check(c, F::name));
+  if (!d_beta || !loglik) return fail(BBX_ERR_INVALID, "NULL argument");
+  BBX_HIP(hipSetDevice(c->device));
+  return no_throw([&] {
+    typename F::Lik lik{c};
+    return loglik_grad_impl(c, lik, d_beta, loglik, d_grad);
+  });
+}
+
+template <class F, class H>
+int loglik_grad(H* c, const double* beta, double* loglik, double* grad) {
+  BBX_TRY(check(c, F::name));
+  if (!beta || !loglik) return fail(BBX_ERR_INVALID, "NULL argument");
+  BBX_HIP(hipSetDevice(c->device));
+  return no_throw([&] {
+    typename F::Lik lik{c};
+    double ll = 0.;
+    BBX_TRY(with_p_stage(c, beta, grad, [&](const double* d_in, double* d_out) {
+      return loglik_grad_impl(c, lik, d_in, &ll, d_out);
+    }));
+    *loglik = ll;
+    return BBX_OK;
+  });
+}
+
+template <class F, class H>
+int set_location(H* c, const double* beta) {
+  BBX_TRY(check(c, F::name));
+  if (!beta) return fail(BBX_ERR_INVALID, "NULL argument");
+  BBX_HIP(hipSetDevice(c->device));
+  return no_throw([&] {
+    bbx_design* h = c->h;
+    c->have_location = false;
+    double* d_in = h->stage_P.as<double>();
+    BBX_HIP(hipMemcpyAsync(d_in, beta, sizeof(double) * c->P,
+                           hipMemcpyHostToDevice, h->stream));
+    BBX_TRY(F::locate(c, d_in));
+    c->have_location = true;
+    return BBX_OK;
+  });
+}
+
+template <class F, class H>
+int hessian_matvec_dev(H* c, const double* d_v, double* d_out) {
+  BBX_TRY(check(c, F::name));
+  if (!d_v || !d_out) return fail(BBX_ERR_INVALID, "NULL argument");
+  BBX_HIP(hipSetDevice(c->device));
+  return no_throw([&] { return hessian_impl<F>(c, d_v, d_out); });
+}
+
+template <class F, class H>
+int hessian_matvec(H* c, const double* v, double* out) {
+  BBX_TRY(check(c, F::name));
+  if (!v || !out) return fail(BBX_ERR_INVALID, "NULL argument");
+  BBX_HIP(hipSetDevice(c->device));
+  return no_throw([&] {
+    return with_p_stage(c, v, out, [&](const double* d_in, double* d_out) {
+      return hessian_impl<F>(c, d_in, d_out);
+    });
+  });
+}
+
+template <class F, class H>
+int hmc_trajectory(H* c, double dt, int n_step, const double* precond_scale,
+                   const double* prior_prec, const double* q0,
+                   const double* p0, double logp0, const double* grad0,
+                   double hamiltonian_tol, double* q, double* p, double* logp,
+                   double* grad, int* n_grad_evals, int* instability,
+                   double* hamiltonian) {
+  BBX_TRY(check(c, F::name));
+  if (!precond_scale || !prior_prec || !q0 || !p0 || !grad0)
+    return fail(BBX_ERR_INVALID, "NULL argument");
+  if (n_step < 0) return fail(BBX_ERR_INVALID, "n_step < 0");
+  BBX_HIP(hipSetDevice(c->device));
+  return no_throw([&] {
+    typename F::Lik lik{c};
+    return trajectory_impl(c, lik, dt, n_step, precond_scale, prior_prec, q0,
+                           p0, logp0, grad0, hamiltonian_tol, q, p, logp, grad,
+                           n_grad_evals, instability, hamiltonian);
+  });
+}
+
+template <class F, class H>
+int nuts_begin(H* c, const double* precond_scale, const double* prior_prec,
+               const double* q0, const double* p0, double logp0,
+               const double* grad0, double joint_logp0,
+               double joint_logp_threshold, double hamiltonian_tol) {
+  BBX_TRY(check(c, F::name));
+  if (!precond_scale || !prior_prec || !q0 || !p0 || !grad0)
+    return fail(BBX_ERR_INVALID, "NULL argument");
+  BBX_HIP(hipSetDevice(c->device));
+  return no_throw([&] {
+    return nuts_begin_impl(c, precond_scale, prior_prec, q0, p0, logp0, grad0,
+                           joint_logp0, joint_logp_threshold, hamiltonian_tol);
+  });
+}
+
+template <class F, class H>
+int nuts_doubling(H* c, double dt, int direction, int height,
+                  const double* uniforms, int* n_uniform_used, int* n_steps,
+                  int* flags, int* tree, double* averages) {
+  BBX_TRY(check(c, F::name));
+  BBX_TRY(nuts_doubling_args(c, F::name, uniforms, direction, height));
+  BBX_HIP(hipSetDevice(c->device));
+  return no_throw([&] {
+    typename F::Lik lik{c};
+    BBX_TRY(nuts_doubling_impl(c, lik, dt, direction, height, uniforms));
+    nuts_doubling_out(c, n_uniform_used, n_steps, flags, tree, averages);
+    return BBX_OK;
+  });
+}
+
+template <class F, class H>
+int nuts_sample(H* c, double* q, double* logp, double* grad) {
+  BBX_TRY(check(c, F::name));
+  if (!c->nuts_begun) return not_yet(F::name, "nuts_begin");
+  BBX_HIP(hipSetDevice(c->device));
+  return no_throw([&] { return nuts_sample_impl(c, q, logp, grad); });
+}
+
 }  // namespace ham
 }  // namespace bbx
+
+// The ten entry points that include/bbx.h declares for every family, on the
+// handle type bbx_<fam> under the policy F: one forwarding line each.
+#define BBX_HAM_ENTRY_POINTS(fam, F)                                           \
+  extern "C" {                                                                 \
+  int bbx_##fam##_destroy(bbx_##fam* c) { return ::bbx::ham::destroy(c); }     \
+  int bbx_##fam##_loglik_grad_dev(bbx_##fam* c, const double* d_beta,          \
+                                  double* loglik, double* d_grad) {            \
+    return ::bbx::ham::loglik_grad_dev<F>(c, d_beta, loglik, d_grad);          \
+  }                                                                            \
+  int bbx_##fam##_loglik_grad(bbx_##fam* c, const double* beta,                \
+                              double* loglik, double* grad) {                  \
+    return ::bbx::ham::loglik_grad<F>(c, beta, loglik, grad);                  \
+  }                                                                            \
+  int bbx_##fam##_set_location(bbx_##fam* c, const double* beta) {             \
+    return ::bbx::ham::set_location<F>(c, beta);                               \
+  }                                                                            \
+  int bbx_##fam##_hessian_matvec_dev(bbx_##fam* c, const double* d_v,          \
+                                     double* d_out) {                          \
+    return ::bbx::ham::hessian_matvec_dev<F>(c, d_v, d_out);                   \
+  }                                                                            \
+  int bbx_##fam##_hessian_matvec(bbx_##fam* c, const double* v,                \
+                                 double* out) {                                \
+    return ::bbx::ham::hessian_matvec<F>(c, v, out);                           \
+  }                                                                            \
+  int bbx_##fam##_hmc_trajectory(                                              \
+      bbx_##fam* c, double dt, int n_step, const double* precond_scale,        \
+      const double* prior_prec, const double* q0, const double* p0,            \
+      double logp0, const double* grad0, double hamiltonian_tol, double* q,    \
+      double* p, double* logp, double* grad, int* n_grad_evals,                \
+      int* instability, double* hamiltonian) {                                 \
+    return ::bbx::ham::hmc_trajectory<F>(                                      \
+        c, dt, n_step, precond_scale, prior_prec, q0, p0, logp0, grad0,        \
+        hamiltonian_tol, q, p, logp, grad, n_grad_evals, instability,          \
+        hamiltonian);                                                          \
+  }                                                                            \
+  int bbx_##fam##_nuts_begin(bbx_##fam* c, const double* precond_scale,        \
+                             const double* prior_prec, const double* q0,       \
+                             const double* p0, double logp0,                   \
+                             const double* grad0, double joint_logp0,          \
+                             double joint_logp_threshold,                      \
+                             double hamiltonian_tol) {                         \
+    return ::bbx::ham::nuts_begin<F>(c, precond_scale, prior_prec, q0, p0,     \
+                                     logp0, grad0, joint_logp0,                \
+                                     joint_logp_threshold, hamiltonian_tol);   \
+  }                                                                            \
+  int bbx_##fam##_nuts_doubling(bbx_##fam* c, double dt, int direction,        \
+                                int height, const double* uniforms,            \
+                                int* n_uniform_used, int* n_steps, int* flags, \
+                                int* tree, double* averages) {                 \
+    return ::bbx::ham::nuts_doubling<F>(c, dt, direction, height, uniforms,    \
+                                        n_uniform_used, n_steps, flags, tree,  \
+                                        averages);                             \
+  }                                                                            \
+  int bbx_##fam##_nuts_sample(bbx_##fam* c, double* q, double* logp,           \
+                              double* grad) {                                  \
+    return ::bbx::ham::nuts_sample<F>(c, q, logp, grad);                       \
+  }                                                                            \
+  }

@@ -132,16 +132,6 @@ namespace {
 
 using ham::cst;
 using ham::eta_of;
-using ham::read_state;
-using ham::with_p_stage;
-
-int poisson_check(const bbx_poisson* c) {
-  if (!c) return fail(BBX_ERR_INVALID, "NULL poisson handle");
-  if (!design_alive(c->h))
-    return fail(BBX_ERR_STATE,
-                "the poisson handle's design has been destroyed");
-  return BBX_OK;
-}
 
 template <int MODE>
 int launch_rows(bbx_poisson* c, const double* a, double* out, const int* skip) {
@@ -192,216 +182,48 @@ int poisson_create_impl(bbx_design* h, const double* y,
     yo[2 * i + 1] = oi;
   }
   bbx_poisson* c = new bbx_poisson;
-  c->h = h;
-  c->device = h->device;
-  c->n = n;
-  c->P = h->P;
-  auto cleanup = [&](int st) {
-    ham::free_pinned(c);
-    delete c;
-    return st;
-  };
-  if (hipSetDevice(h->device) != hipSuccess)
-    return cleanup(fail(BBX_ERR_HIP, "hipSetDevice"));
   const size_t d8 = sizeof(double);
-  int st = BBX_OK;
-  DevMem* nvec[] = {&c->eta, &c->tmp, &c->mu_loc};
-  for (DevMem* m : nvec)
-    if (st == BBX_OK) st = m->alloc(d8 * n);
+  int st = ham::init_core(c, h, "poisson");
+  if (st == BBX_OK) st = c->mu_loc.alloc(d8 * n);
   if (st == BBX_OK) st = c->yo.alloc(d8 * 2 * n);
-  DevMem* pvec[] = {&c->q, &c->p, &c->p2, &c->g, &c->gl, &c->v, &c->scale, &c->pp};
-  for (DevMem* m : pvec)
-    if (st == BBX_OK) st = m->alloc(d8 * c->P);
-  if (st == BBX_OK) st = c->llpart.alloc(d8 * SCAN_G);
-  if (st == BBX_OK) st = c->post.alloc(d8 * 3 * NPART);
-  if (st == BBX_OK) st = c->st.alloc(sizeof(CoxTraj));
-  if (st != BBX_OK) return cleanup(st);
-  if (hipHostMalloc((void**)&c->host_st, sizeof(CoxTraj)) != hipSuccess) {
-    c->host_st = nullptr;
-    return cleanup(fail(BBX_ERR_HIP, "hipHostMalloc"));
-  }
+  if (st != BBX_OK) return ham::discard(c, st);
   hipError_t e = hipMemcpyAsync(c->yo.ptr, yo.data(), d8 * 2 * n,
                                 hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(c->st.ptr, 0, sizeof(CoxTraj), h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess)
-    return cleanup(fail(BBX_ERR_HIP, std::string("poisson upload: ") +
-                                         hipGetErrorString(e)));
+    return ham::discard(c, fail(BBX_ERR_HIP, std::string("poisson upload: ") +
+                                                 hipGetErrorString(e)));
   *out = c;
   return BBX_OK;
 }
 
-int poisson_loglik_grad_dev(bbx_poisson* c, const double* d_beta,
-                            double* loglik, double* d_grad) {
-  bbx_design* h = c->h;
-  // a trajectory that stopped early leaves its skip flag set
-  BBX_LAUNCH(cox_reset_kernel, dim3(1), dim3(WAVE), 0, h->stream, cst(c));
-  BBX_HIP(hipGetLastError());
-  BBX_TRY(eta_of(c, d_beta));
-  BBX_TRY(likelihood_from_eta(c, d_grad));
-  BBX_LAUNCH(cox_loglik_kernel, dim3(1), dim3(WAVE), 0, h->stream,
-             c->llpart.as<const double>(), cst(c));
-  BBX_HIP(hipGetLastError());
-  BBX_TRY(read_state(c));
-  *loglik = c->host_st->logp;
-  return BBX_OK;
-}
-
-int poisson_hessian_dev(bbx_poisson* c, const double* d_v, double* d_out) {
-  if (!c->have_location)
-    return fail(BBX_ERR_STATE, "bbx_poisson_set_location has not succeeded");
-  bbx_design* h = c->h;
-  BBX_TRY(eta_of(c, d_v));   // u = X~ v, in c->eta
-  BBX_TRY(launch_rows<PM_HESS>(c, c->eta.as<const double>(),
-                               c->tmp.as<double>(), nullptr));
-  TdotEpilogue ep;
-  return launch_tdot(h, c->tmp.as<double>(), part_slot(h, PS_SUMW), ep, d_out);
-}
+struct PoissonFamily {
+  static constexpr const char* name = "poisson";
+  using Lik = PoissonLik;
+  static int locate(bbx_poisson* c, const double* d_in) {
+    BBX_TRY(eta_of(c, d_in));
+    BBX_TRY(launch_rows<PM_LOC>(c, c->eta.as<const double>(),
+                                c->mu_loc.as<double>(), nullptr));
+    BBX_HIP(hipStreamSynchronize(c->h->stream));   // beta is free again
+    return BBX_OK;
+  }
+  static int hessian_from_v(bbx_poisson* c, const double* d_v, double* d_out) {
+    bbx_design* h = c->h;
+    BBX_TRY(eta_of(c, d_v));   // u = X~ v, in c->eta
+    BBX_TRY(launch_rows<PM_HESS>(c, c->eta.as<const double>(),
+                                 c->tmp.as<double>(), nullptr));
+    TdotEpilogue ep;
+    return launch_tdot(h, c->tmp.as<double>(), part_slot(h, PS_SUMW), ep, d_out);
+  }
+};
 
 }  // namespace
 
-extern "C" {
-
-int bbx_poisson_create(bbx_design* design, const double* y,
-                       const double* log_exposure, bbx_poisson** out) {
+extern "C" int bbx_poisson_create(bbx_design* design, const double* y,
+                                  const double* log_exposure,
+                                  bbx_poisson** out) {
   return no_throw(
       [&] { return poisson_create_impl(design, y, log_exposure, out); });
 }
 
-int bbx_poisson_destroy(bbx_poisson* c) {
-  if (!c) return BBX_OK;
-  if (design_alive(c->h)) {
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->h->stream);
-  }
-  ham::free_pinned(c);
-  delete c;
-  return BBX_OK;
-}
-
-int bbx_poisson_loglik_grad_dev(bbx_poisson* c, const double* d_beta,
-                                double* loglik, double* d_grad) {
-  BBX_TRY(poisson_check(c));
-  if (!d_beta || !loglik) return fail(BBX_ERR_INVALID, "NULL argument");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw(
-      [&] { return poisson_loglik_grad_dev(c, d_beta, loglik, d_grad); });
-}
-
-int bbx_poisson_loglik_grad(bbx_poisson* c, const double* beta, double* loglik,
-                            double* grad) {
-  BBX_TRY(poisson_check(c));
-  if (!beta || !loglik) return fail(BBX_ERR_INVALID, "NULL argument");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] {
-    double ll = 0.;
-    BBX_TRY(with_p_stage(c, beta, grad, [&](const double* d_in, double* d_out) {
-      return poisson_loglik_grad_dev(c, d_in, &ll, d_out);
-    }));
-    *loglik = ll;
-    return BBX_OK;
-  });
-}
-
-int bbx_poisson_set_location(bbx_poisson* c, const double* beta) {
-  BBX_TRY(poisson_check(c));
-  if (!beta) return fail(BBX_ERR_INVALID, "NULL argument");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] {
-    bbx_design* h = c->h;
-    c->have_location = false;
-    double* d_in = h->stage_P.as<double>();
-    BBX_HIP(hipMemcpyAsync(d_in, beta, sizeof(double) * c->P,
-                           hipMemcpyHostToDevice, h->stream));
-    BBX_TRY(eta_of(c, d_in));
-    BBX_TRY(launch_rows<PM_LOC>(c, c->eta.as<const double>(),
-                                c->mu_loc.as<double>(), nullptr));
-    BBX_HIP(hipStreamSynchronize(h->stream));   // beta is free again
-    c->have_location = true;
-    return BBX_OK;
-  });
-}
-
-int bbx_poisson_hessian_matvec_dev(bbx_poisson* c, const double* d_v,
-                                   double* d_out) {
-  BBX_TRY(poisson_check(c));
-  if (!d_v || !d_out) return fail(BBX_ERR_INVALID, "NULL argument");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] { return poisson_hessian_dev(c, d_v, d_out); });
-}
-
-int bbx_poisson_hessian_matvec(bbx_poisson* c, const double* v, double* out) {
-  BBX_TRY(poisson_check(c));
-  if (!v || !out) return fail(BBX_ERR_INVALID, "NULL argument");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] {
-    return with_p_stage(c, v, out, [&](const double* d_in, double* d_out) {
-      return poisson_hessian_dev(c, d_in, d_out);
-    });
-  });
-}
-
-int bbx_poisson_hmc_trajectory(bbx_poisson* c, double dt, int n_step,
-                               const double* precond_scale,
-                               const double* prior_prec, const double* q0,
-                               const double* p0, double logp0,
-                               const double* grad0, double hamiltonian_tol,
-                               double* q, double* p, double* logp,
-                               double* grad, int* n_grad_evals,
-                               int* instability, double* hamiltonian) {
-  BBX_TRY(poisson_check(c));
-  if (!precond_scale || !prior_prec || !q0 || !p0 || !grad0)
-    return fail(BBX_ERR_INVALID, "NULL argument");
-  if (n_step < 0) return fail(BBX_ERR_INVALID, "n_step < 0");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] {
-    PoissonLik lik{c};
-    return ham::trajectory_impl(c, lik, dt, n_step, precond_scale, prior_prec,
-                                q0, p0, logp0, grad0, hamiltonian_tol, q, p,
-                                logp, grad, n_grad_evals, instability,
-                                hamiltonian);
-  });
-}
-
-int bbx_poisson_nuts_begin(bbx_poisson* c, const double* precond_scale,
-                           const double* prior_prec, const double* q0,
-                           const double* p0, double logp0, const double* grad0,
-                           double joint_logp0, double joint_logp_threshold,
-                           double hamiltonian_tol) {
-  BBX_TRY(poisson_check(c));
-  if (!precond_scale || !prior_prec || !q0 || !p0 || !grad0)
-    return fail(BBX_ERR_INVALID, "NULL argument");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] {
-    return ham::nuts_begin_impl(c, precond_scale, prior_prec, q0, p0, logp0,
-                                grad0, joint_logp0, joint_logp_threshold,
-                                hamiltonian_tol);
-  });
-}
-
-int bbx_poisson_nuts_doubling(bbx_poisson* c, double dt, int direction,
-                              int height, const double* uniforms,
-                              int* n_uniform_used, int* n_steps, int* flags,
-                              int* tree, double* averages) {
-  BBX_TRY(poisson_check(c));
-  BBX_TRY(ham::nuts_doubling_args(c, "bbx_poisson", uniforms, direction,
-                                  height));
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] {
-    PoissonLik lik{c};
-    BBX_TRY(ham::nuts_doubling_impl(c, lik, dt, direction, height, uniforms));
-    ham::nuts_doubling_out(c, n_uniform_used, n_steps, flags, tree, averages);
-    return BBX_OK;
-  });
-}
-
-int bbx_poisson_nuts_sample(bbx_poisson* c, double* q, double* logp,
-                            double* grad) {
-  BBX_TRY(poisson_check(c));
-  if (!c->nuts_begun)
-    return fail(BBX_ERR_STATE, "bbx_poisson_nuts_begin has not succeeded");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] { return ham::nuts_sample_impl(c, q, logp, grad); });
-}
-
-}  // extern "C"
+BBX_HAM_ENTRY_POINTS(poisson, PoissonFamily)
