@@ -2,6 +2,7 @@
 the matrix-core Gram against NumPy, the draw against the reference's recorded
 inputs and outputs, and exact-seed chains against the reference's fixtures."""
 import os
+import re
 import warnings
 
 import numpy as np
@@ -113,8 +114,11 @@ def test_chol_sample_indefinite_raises_and_design_stays_usable(golden_dir):
     args = (g['draw_prior_prec_sqrt'][0], g['draw_z'][0])
     w = g['draw_obs_prec'][0].copy()
     w[::2] *= -50.
-    with pytest.raises(np.linalg.LinAlgError, match="pivot"):
+    with pytest.raises(np.linalg.LinAlgError, match="pivot") as info:
         chol_sample(d, w, *args, normals=g['draw_normals'][0])
+    m = re.search(r"pivot (\d+)", str(info.value))
+    assert m, str(info.value)
+    assert 0 <= int(m.group(1)) < d.shape[1]
     coef = chol_sample(d, g['draw_obs_prec'][0], *args,
                        normals=g['draw_normals'][0])
     ref = g['draw_coef'][0]

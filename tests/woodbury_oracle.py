@@ -74,14 +74,19 @@ def case(name, seed=0):
     """The small problems of the tests: (Xt, obs_prec, prior_prec_sqrt, y).
     n < P and n > P; q = 0, 1, 3 flat coefficients; logit-like weights or one
     number (linear); one unshrunk coefficient with a finite sd; prior scales
-    over several decades as under the bridge prior."""
+    over several decades as under the bridge prior.  `name`: one of CASES, or
+    the shape itself, (n, P, q, linear)."""
     shapes = {
         'wide_q1_logit': (40, 130, 1, False), 'wide_q0_logit': (40, 130, 0, False),
         'wide_q3_linear': (70, 200, 3, True), 'tall_q1_logit': (150, 60, 1, False),
         'tall_q3_linear': (150, 60, 3, True), 'wide_q0_linear': (33, 97, 0, True),
     }
-    n, P, q, linear = shapes[name]
-    rng = np.random.default_rng(1000 + seed + len(name))
+    if isinstance(name, str):
+        n, P, q, linear = shapes[name]
+        rng = np.random.default_rng(1000 + seed + len(name))
+    else:
+        n, P, q, linear = name
+        rng = np.random.default_rng([2000 + seed, n, P, q, int(linear)])
     X = rng.normal(size=(n, P - 1))
     X[:, ::3] = (rng.random((n, len(range(0, P - 1, 3)))) < .3)
     X = X - X.mean(axis=0)
