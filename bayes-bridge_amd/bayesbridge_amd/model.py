@@ -4,7 +4,9 @@ cox_model.py:7-303).  The Cox likelihood, its gradient and its Hessian-vector
 products run on the device (csrc/cox.hip); its coefficients are drawn by HMC
 (hmc.py).  The logit model has the same device path (csrc/logit.hip) for the
 'hmc' and 'nuts' coefficient samplers, and the Poisson model (csrc/poisson.hip;
-with strata the conditional Poisson model, csrc/cpoisson.hip) has no other."""
+with strata the conditional Poisson model, csrc/cpoisson.hip) has no other.
+With entry times the Cox model is the counting-process form
+(csrc/cox_interval.hip)."""
 import math
 from ctypes import byref, c_double, c_int, c_void_p
 from warnings import catch_warnings, simplefilter, warn
@@ -489,6 +491,97 @@ def cox_risk_sets(event_time, censoring_time):
     return n_event, start, end, n_app
 
 
+def _interval_times(entry_time, event_time, censoring_time):
+    entry_time = np.asarray(entry_time, dtype=np.float64)
+    event_time = np.asarray(event_time, dtype=np.float64)
+    censoring_time = np.asarray(censoring_time, dtype=np.float64)
+    if not (entry_time.shape == event_time.shape == censoring_time.shape) \
+            or event_time.ndim != 1:
+        raise ValueError("entry_time, event_time and censoring_time must be "
+                         "1-d arrays of the same length.")
+    if not np.all(np.equal(event_time == float('inf'),
+                           censoring_time < float('inf'))):
+        raise ValueError("Either event or censoring time must be infinity for "
+                         "each observation.")
+    if np.any(np.isnan(entry_time)):
+        raise ValueError("An entry time must not be NaN.")
+    exit_time = np.minimum(event_time, censoring_time)
+    if not np.all(entry_time < exit_time):
+        raise ValueError("Every entry time must be strictly before the "
+                         "observation's event or censoring time.")
+    return entry_time, event_time, censoring_time, exit_time
+
+
+def _n_risk_sets(entry_time, exit_time, event_time):
+    """(p, q) of every row: the number of events at or before its exit time
+    and at or before its entry time; the row is in p - q risk sets."""
+    events = np.sort(event_time[np.isfinite(event_time)])
+    return (np.searchsorted(events, exit_time, side='right'),
+            np.searchsorted(events, entry_time, side='right'))
+
+
+def cox_preprocess_interval(entry_time, event_time, censoring_time, X=None):
+    """cox_preprocess for the counting-process form: row i is at risk on
+    (entry_time[i], min(event_time[i], censoring_time[i])].  The rows are
+    sorted by exit time ascending, events before censored rows at an equal
+    exit (a stable sort: tied rows keep their relative order), then without
+    the rows that are in no risk set.  Returns (entry_time, event_time,
+    censoring_time, X, keep): keep[i] is the original index of row i."""
+    entry_time, event_time, censoring_time, exit_time = _interval_times(
+        entry_time, event_time, censoring_time)
+    n = len(event_time)
+    censored = event_time == float('inf')
+    keep = np.lexsort((censored, exit_time))
+    if not np.array_equal(keep, np.arange(n)):
+        warn("The observations and design matrix will be sorted so that the "
+             "event and censoring times are in the ascending order, events "
+             "before the observations censored at the same time.")
+    p, q = _n_risk_sets(entry_time[keep], exit_time[keep], event_time)
+    informative = p > q
+    if not np.all(informative):
+        warn("Some observations do not contribute to the likelihood, so they "
+             "are being removed.")
+        keep = keep[informative]
+    entry_time, event_time = entry_time[keep], event_time[keep]
+    censoring_time = censoring_time[keep]
+    if X is not None and not np.array_equal(keep, np.arange(X.shape[0])):
+        X = X.tocsr()[keep, :] if sparse.issparse(X) else X[keep, :]
+    return entry_time, event_time, censoring_time, X, keep
+
+
+def cox_interval_risk_sets(entry_time, event_time, censoring_time):
+    """The index arrays of the counting-process Cox handle, of rows already in
+    cox_preprocess_interval's order, in O(n log n).  Returns (n_event, evrow,
+    a, b, p, q, entry_perm): evrow[k] is the row of event k in time order;
+    a[k] the first row whose exit time is >= t_k; entry_perm the rows in
+    ascending entry order (stable) and b[k] the first position in it whose
+    entry time is >= t_k (n if there is none), so that risk set k is the rows
+    from a[k] on minus the rows entry_perm[b[k]:]; p[i] = #{k : t_k <= exit_i}
+    and q[i] = #{k : t_k <= entry_i}."""
+    entry_time, event_time, censoring_time, exit_time = _interval_times(
+        entry_time, event_time, censoring_time)
+    censored = event_time == float('inf')
+    same = exit_time[:-1] == exit_time[1:]
+    if np.any(exit_time[:-1] > exit_time[1:]) \
+            or np.any(same & censored[:-1] & ~censored[1:]):
+        raise ValueError(
+            "The observations need to be sorted so that the event and "
+            "censoring times are in the increasing order, events before the "
+            "observations censored at the same time.")
+    evrow = np.flatnonzero(~censored)
+    n_event = len(evrow)
+    events = event_time[evrow]
+    p, q = _n_risk_sets(entry_time, exit_time, event_time)
+    if not np.all(p > q):
+        raise ValueError(
+            "Some individuals never appear in the risk set. They have to be "
+            "removed before using the CoxModel class.")
+    a = np.searchsorted(exit_time, events, side='left')
+    entry_perm = np.argsort(entry_time, kind='stable')
+    b = np.searchsorted(entry_time[entry_perm], events, side='left')
+    return n_event, evrow, a, b, p, q, entry_perm
+
+
 def _stratum_codes(strata, n):
     """(labels in np.unique order, the stratum number of every row)."""
     strata = np.asarray(strata)
@@ -671,12 +764,26 @@ class CoxModel(_DeviceHamiltonian, _Model):
     through one bbx_cox handle.  With `strata` (one label per row, the rows in
     cox_preprocess_stratified's order) the likelihood is the stratified
     partial likelihood: one risk-set structure and one baseline hazard per
-    stratum, shared coefficients."""
+    stratum, shared coefficients.  With `entry_time` (one per row, -inf where
+    a row is at risk from the start; the rows in cox_preprocess_interval's
+    order) the likelihood is the counting-process form, through one bbx_coxcp
+    handle (csrc/cox_interval.hip): row i is in the risk set of an event at t
+    iff entry_time[i] < t <= its event or censoring time, which covers delayed
+    entry and subjects written as several (start, stop] rows."""
 
     _handle_attr = '_cox'
 
-    def __init__(self, event_time, censoring_time, design, strata=None):
+    def __init__(self, event_time, censoring_time, design, strata=None,
+                 entry_time=None):
+        if entry_time is not None:
+            if strata is not None:
+                raise ValueError(
+                    "entry_time together with strata is not supported: the "
+                    "stratified counting-process model is not implemented.")
+            self._init_interval(entry_time, event_time, censoring_time, design)
+            return
         self.strata = None
+        self.entry_time = None
         if strata is None:
             n_event, start, end, n_app = cox_risk_sets(event_time,
                                                        censoring_time)
@@ -720,6 +827,36 @@ class CoxModel(_DeviceHamiltonian, _Model):
                 design.handle, len(sne), _ptr(sptr), *[_ptr(a) for a in i32],
                 byref(self._cox)))
 
+    def _init_interval(self, entry_time, event_time, censoring_time, design):
+        n_event, evrow, a, b, p, q, entry_perm = cox_interval_risk_sets(
+            entry_time, event_time, censoring_time)
+        if len(event_time) != design.shape[0]:
+            raise ValueError(
+                "Incompatible sizes of the outcome and design matrix.")
+        if n_event == 0:
+            raise ValueError("The Cox model needs at least one event.")
+        self.strata = None
+        self.n_event = n_event
+        self.entry_time = np.asarray(entry_time, dtype=np.float64)
+        self.event_time = np.asarray(event_time, dtype=np.float64)
+        self.censoring_time = np.asarray(censoring_time, dtype=np.float64)
+        self.event_row = evrow
+        self.risk_set_start_index = a
+        self.risk_set_entry_index = b
+        self.n_event_by_exit = p
+        self.n_event_by_entry = q
+        self.entry_order = entry_perm
+        self.design = design
+        self.name = 'cox'
+        self._ham_prefix = 'bbx_coxcp_'
+        self._cox = c_void_p()
+        self._location_serial = 0
+        i32 = [np.ascontiguousarray(v, dtype=np.int32)
+               for v in (evrow, a, b, p, q, entry_perm)]
+        _lib.check(self._ham_fn('create')(
+            design.handle, n_event, *[_ptr(v) for v in i32],
+            byref(self._cox)))
+
     @property
     def handle(self):
         return self._cox
@@ -760,18 +897,22 @@ class CoxModel(_DeviceHamiltonian, _Model):
 
 def RegressionModel(outcome, X, family='linear', add_intercept=None,
                     center_predictor=True, device=0, storage='auto',
-                    dense_storage_dtype='float64'):
+                    dense_storage_dtype='float64', entry_time=None):
     """model/factory.py:10-68 with the design placed on an MI355X.  `X` may be
     a SciPy sparse matrix, a NumPy array, or an already built HipDesignMatrix.
     For family='cox', outcome = (event_time, censoring_time) or, for the
     stratified model, (event_time, censoring_time, strata): the rows are
     sorted into the model's order (and uninformative ones dropped) before the
     design goes to the GPU; a prebuilt HipDesignMatrix must already be in that
-    order.  For family='poisson', outcome = y or (y, exposure) or, for the
+    order.  With `entry_time` (family='cox' without strata) the model is the
+    counting-process form: a row is at risk from its entry time on, and the
+    rows are sorted by cox_preprocess_interval.  For family='poisson', outcome = y or (y, exposure) or, for the
     conditional Poisson model, (y, exposure, strata) (exposure may be None):
     the rows are sorted stratum-major and uninformative strata dropped
     (cpoisson_preprocess) before the design goes to the GPU; a prebuilt
     HipDesignMatrix must already be in that order."""
+    if entry_time is not None and family != 'cox':
+        raise ValueError("entry_time is an argument of family='cox' only.")
     stratified_poisson = (family == 'poisson' and isinstance(outcome, tuple)
                           and len(outcome) == 3)
     if add_intercept is None:
@@ -809,7 +950,32 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
             event_time, censoring_time, strata = outcome
         else:
             event_time, censoring_time = outcome
-        if isinstance(X, HipDesignMatrix):
+        if entry_time is not None and strata is not None:
+            raise ValueError(
+                "entry_time together with strata is not supported: the "
+                "stratified counting-process model is not implemented.")
+        if entry_time is not None:
+            if isinstance(X, HipDesignMatrix):
+                with catch_warnings():
+                    simplefilter('ignore')
+                    keep = cox_preprocess_interval(
+                        entry_time, event_time, censoring_time)[4]
+                if not np.array_equal(keep, np.arange(X.shape[0])):
+                    raise ValueError(
+                        "A prebuilt HipDesignMatrix must have its rows in the "
+                        "counting-process Cox model's order (by increasing "
+                        "event or censoring time, events before the rows "
+                        "censored at the same time, every row in some risk "
+                        "set); pass X as a NumPy or SciPy matrix to have it "
+                        "sorted.")
+                if X.intercept_added:
+                    raise ValueError("The Cox model takes a design without "
+                                     "an intercept column.")
+            else:
+                entry_time, event_time, censoring_time, X, _ = \
+                    cox_preprocess_interval(entry_time, event_time,
+                                            censoring_time, X)
+        elif isinstance(X, HipDesignMatrix):
             et = np.asarray(event_time, dtype=np.float64)
             ct = np.asarray(censoring_time, dtype=np.float64)
             if strata is None:
@@ -858,7 +1024,8 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
             n_success, n_trial = outcome, None
         return LogisticModel(n_success, n_trial, design)
     if family == 'cox':
-        return CoxModel(event_time, censoring_time, design, strata)
+        return CoxModel(event_time, censoring_time, design, strata,
+                        entry_time)
     if family == 'poisson':
         if stratified_poisson:
             return PoissonModel(y, exposure, design, strata)

@@ -35,78 +35,14 @@
 
 #include "common.hpp"
 #include "hamiltonian.hpp"
+#include "cox_scan.hpp"
 
 #pragma clang fp contract(off)  // a + b * c rounded as NumPy rounds it
 
 namespace bbx {
 
-// SCAN_G (hamiltonian.hpp): chunks per segment
-constexpr int SCAN_BLOCK = 256;  // threads of the scan kernels
-constexpr int SCAN_E = 8;        // elements per thread and tile
-constexpr int SCAN_TILE = SCAN_BLOCK * SCAN_E;
-
-
-// Up to two segments of one scan: elements base .. base+len-1, read forward
-// or reversed (a suffix sum is a prefix sum of the reversed segment).
-struct Segs {
-  int64_t base[2];
-  int64_t len[2];
-  int rev[2];
-};
-
-__device__ inline int64_t seg_elem(const Segs& sg, int s, int64_t t) {
-  return sg.rev[s] ? sg.base[s] + sg.len[s] - 1 - t : sg.base[s] + t;
-}
-
-__device__ inline double nanmax(double a, double b) {
-  if (a != a) return a;
-  if (b != b) return b;
-  return a > b ? a : b;
-}
-
-__device__ inline double wave_max(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x = nanmax(x, __shfl_xor(x, off));
-  return x;
-}
-
-
-// the max over the NPART partials, in every thread
-__device__ inline double part_max(const double* part) {
-  __shared__ double s_m;
-  if (threadIdx.x < WAVE) {
-    double a = part[threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < NPART / WAVE; ++k)
-      a = nanmax(a, part[threadIdx.x + k * WAVE]);
-    a = wave_max(a);
-    if (threadIdx.x == 0) s_m = a;
-  }
-  __syncthreads();
-  const double r = s_m;
-  __syncthreads();
-  return r;
-}
-
-__global__ __launch_bounds__(VEC_BLOCK) void cox_max_kernel(
-    int64_t n, const double* __restrict__ eta, double* __restrict__ part,
-    const int* __restrict__ skip) {
-  if (skip && *skip) return;
-  __shared__ double s_w[VEC_BLOCK / WAVE];
-  double m = -INFINITY;
-  for (int64_t i = (int64_t)blockIdx.x * VEC_BLOCK + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * VEC_BLOCK)
-    m = nanmax(m, eta[i]);
-  m = wave_max(m);
-  if ((threadIdx.x & (WAVE - 1)) == 0) s_w[threadIdx.x / WAVE] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r = s_w[0];
-#pragma unroll
-    for (int k = 1; k < VEC_BLOCK / WAVE; ++k) r = nanmax(r, s_w[k]);
-    part[blockIdx.x] = r;
-  }
-}
+// SCAN_G, SCAN_BLOCK, SCAN_E, Segs, cox_max_kernel and pass B
+// (cox_scan_out_kernel): cox_scan.hpp
 
 enum ScanMode {
   SM_H = 0,     // h_i = exp(eta_i - m)                    (risk segments)
@@ -182,69 +118,6 @@ __global__ __launch_bounds__(SCAN_BLOCK) void cox_scan_sum_kernel(
   }
 }
 
-// Pass B: inclusive scan of the stored values of each chunk, offset by the
-// sums of the chunks before it.
-__global__ __launch_bounds__(SCAN_BLOCK) void cox_scan_out_kernel(
-    Segs sg, const double* __restrict__ val, double* __restrict__ out,
-    const double* __restrict__ csum, const int* __restrict__ skip) {
-  if (skip && *skip) return;
-  const int s = blockIdx.x / SCAN_G, b = blockIdx.x % SCAN_G;
-  const int64_t len = sg.len[s];
-  const int64_t L = (len + SCAN_G - 1) / SCAN_G;
-  const int64_t t0 = (int64_t)b * L, t1 = t0 + L < len ? t0 + L : len;
-  if (t0 >= t1) return;
-  __shared__ double s_off;
-  __shared__ double s_wave[SCAN_BLOCK / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  if (threadIdx.x < WAVE) {
-    double acc = 0.;
-    for (int c = lane; c < b; c += WAVE) acc += csum[s * SCAN_G + c];
-    acc = wave_allsum(acc);
-    if (lane == 0) s_off = acc;
-  }
-  __syncthreads();
-  double carry = s_off;
-  for (int64_t tile = t0; tile < t1; tile += SCAN_TILE) {
-    double x[SCAN_E];
-    const int64_t tb = tile + (int64_t)threadIdx.x * SCAN_E;
-    double run = 0.;
-#pragma unroll
-    for (int e = 0; e < SCAN_E; ++e) {
-      const int64_t t = tb + e;
-      run += t < t1 ? val[seg_elem(sg, s, t)] : 0.;
-      x[e] = run;
-    }
-    // inclusive scan of the thread totals across the wave
-    double incl = run;
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) {
-      const double y = __shfl_up(incl, off);
-      if (lane >= off) incl += y;
-    }
-    // the exclusive prefix is the previous lane's inclusive one, never
-    // incl - run: when a thread's run exceeds the lanes before it by more
-    // than 2^53 (1/H grows that fast across a few late risk sets) the
-    // difference loses them entirely
-    double excl = __shfl_up(incl, 1);
-    if (lane == 0) excl = 0.;
-    if (lane == WAVE - 1) s_wave[wid] = incl;
-    __syncthreads();
-    double wpre = 0., tot = 0.;
-#pragma unroll
-    for (int k = 0; k < SCAN_BLOCK / WAVE; ++k) {
-      if (k < wid) wpre += s_wave[k];
-      tot += s_wave[k];
-    }
-    const double base = carry + (wpre + excl);
-#pragma unroll
-    for (int e = 0; e < SCAN_E; ++e) {
-      const int64_t t = tb + e;
-      if (t < t1) out[seg_elem(sg, s, t)] = base + x[e];
-    }
-    carry += tot;
-    __syncthreads();
-  }
-}
 
 // w = [i < ne] - c[n_app_i - 1] h_i                 (HESS = false: gradient)
 // w = -((c[n_app_i - 1] h_i) u_i - h_i cz[n_app_i - 1])   (HESS = true)

@@ -1,7 +1,8 @@
 // The preconditioned Hamiltonian trajectory shared by the likelihood families
-// (cox.hip, logit.hip, poisson.hip, cpoisson.hip): the leapfrog kernels, the
-// No-U-Turn tree, their drivers and the front of the C ABI (the ten entry
-// points every handle has).  Velocity Verlet in preconditioned coordinates
+// (cox.hip, cox_interval.hip, logit.hip, poisson.hip, cpoisson.hip): the
+// leapfrog kernels, the No-U-Turn tree, their drivers and the front of the C
+// ABI (the ten entry points every handle has).  Velocity Verlet in
+// preconditioned coordinates
 // q = coef / scale, f(q) = loglik(scale q) - 1/2 sum prior_prec q^2
 // (hmc.py:137-174, dynamics.py, nuts.py).
 //

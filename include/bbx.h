@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-/* 111: + the conditional Poisson likelihood (bbx_cpoisson_*): counts with one
+/* 112: + the Cox model in counting-process form (bbx_coxcp_*): delayed entry
+ *      and (start, stop] rows, with the trajectory and the No-U-Turn sampler
+ *      of the Cox handle.
+ * 111: + the conditional Poisson likelihood (bbx_cpoisson_*): counts with one
  *      nuisance baseline rate per stratum, conditioned on the stratum totals,
  *      with the trajectory and the No-U-Turn sampler of the Cox handle.
  * 110: + strata in the Cox model (bbx_cox_create_stratified): one partial
@@ -56,7 +59,7 @@ extern "C" {
  *      bbx_setup_lock_acquire/_release, bbx_design_useful_bytes.  A binding
  *      compares bbx_version() with the BBX_VERSION it was written against
  *      (bayesbridge_amd/_lib.py does) instead of calling with a stale arity. */
-#define BBX_VERSION 111 /* 0.1.11 */
+#define BBX_VERSION 112 /* 0.1.12 */
 
 /* status codes */
 #define BBX_OK 0
@@ -824,6 +827,71 @@ int bbx_cox_nuts_doubling(bbx_cox* cox, double dt, int direction, int height,
                           int* n_steps, int* flags, int* tree,
                           double* averages);
 int bbx_cox_nuts_sample(bbx_cox* cox, double* q, double* logp, double* grad);
+
+/* --------------------------------- Cox model, counting-process form
+ * The Cox partial likelihood with an entry time per row: row i is at risk on
+ * (entry_i, exit_i], so a subject may enter late (left truncation) or be
+ * written as several (start, stop] rows whose covariates differ
+ * (csrc/cox_interval.hip; the leapfrog and tree kernels are the Cox handle's,
+ * csrc/hamiltonian.hpp).  Rows of the design are sorted by exit time
+ * ascending, events before censored rows at an equal exit.  Event k <
+ * n_event, in time order, is row evrow[k] (increasing); row i is in its risk
+ * set iff entry_i < t_k <= exit_i (Breslow ties).  entry_perm[n] lists the
+ * rows in ascending entry order; a[k] is the first row with exit >= t_k, b[k]
+ * the first position in entry order with entry >= t_k (n if there is none);
+ * p[i] = #{k : t_k <= exit_i} and q[i] = #{k : t_k <= entry_i} (q[i] < p[i]).
+ * Every index is checked: BBX_ERR_INVALID, with a bbx_last_error() that names
+ * the offender, for a NULL pointer, n_event outside [1, n], an index out of
+ * range, an entry_perm that is not a permutation, an a, b or p that
+ * decreases, a q that decreases in entry order, and a risk set that is empty
+ * by its indices (a[k] >= b[k]); nothing is launched then.  Every entry point
+ * but create has the argument list, the status codes and the synchronisation
+ * of its bbx_cox_* counterpart above.  The handle borrows the design (it must
+ * outlive the handle) and runs on its stream.  n < 2^31.  Every sum has a
+ * fixed order: the same inputs give the same bits on every call. */
+typedef struct bbx_coxcp bbx_coxcp;
+int bbx_coxcp_create(bbx_design* design, int64_t n_event,
+                     const int32_t* evrow, const int32_t* a, const int32_t* b,
+                     const int32_t* p, const int32_t* q,
+                     const int32_t* entry_perm, bbx_coxcp** out);
+int bbx_coxcp_destroy(bbx_coxcp* coxcp);
+/* loglik = sum_k (eta_k - m) - log H_k, H_k = E[a_k] - F[b_k]: E the suffix
+ * sums of h = exp(eta - m) in row order, F those in entry order (F[n] = 0);
+ * grad[P] = X~^T w, w_i = [i is an event] - h_i (c[p_i - 1] - c[q_i - 1]),
+ * c = cumsum(1/H), c[-1] = 0.  H_k is a difference of two sums: its relative
+ * error is about eps E / H, and H_k <= 0 counts as an empty risk-set sum
+ * (*loglik = -inf, grad unspecified).  Where no row enters late nothing is
+ * subtracted.  grad may be NULL. */
+int bbx_coxcp_loglik_grad(bbx_coxcp* coxcp, const double* beta, double* loglik,
+                          double* grad);
+int bbx_coxcp_loglik_grad_dev(bbx_coxcp* coxcp, const double* d_beta,
+                              double* loglik, double* d_grad);
+/* bbx_cox_set_location / _hessian_matvec on this likelihood. */
+int bbx_coxcp_set_location(bbx_coxcp* coxcp, const double* beta);
+int bbx_coxcp_hessian_matvec(bbx_coxcp* coxcp, const double* v, double* out);
+int bbx_coxcp_hessian_matvec_dev(bbx_coxcp* coxcp, const double* d_v,
+                                 double* d_out);
+/* bbx_cox_hmc_trajectory on this f. */
+int bbx_coxcp_hmc_trajectory(bbx_coxcp* coxcp, double dt, int n_step,
+                             const double* precond_scale,
+                             const double* prior_prec, const double* q0,
+                             const double* p0, double logp0,
+                             const double* grad0, double hamiltonian_tol,
+                             double* q, double* p, double* logp, double* grad,
+                             int* n_grad_evals, int* instability,
+                             double* hamiltonian);
+/* bbx_cox_nuts_begin / _doubling / _sample on this f. */
+int bbx_coxcp_nuts_begin(bbx_coxcp* coxcp, const double* precond_scale,
+                         const double* prior_prec, const double* q0,
+                         const double* p0, double logp0, const double* grad0,
+                         double joint_logp0, double joint_logp_threshold,
+                         double hamiltonian_tol);
+int bbx_coxcp_nuts_doubling(bbx_coxcp* coxcp, double dt, int direction,
+                            int height, const double* uniforms,
+                            int* n_uniform_used, int* n_steps, int* flags,
+                            int* tree, double* averages);
+int bbx_coxcp_nuts_sample(bbx_coxcp* coxcp, double* q, double* logp,
+                          double* grad);
 
 /* ----------------------------------------------------------- logit model
  * The binomial-logit likelihood of model/logistic_model.py:49-74 on a design

@@ -40,6 +40,13 @@ expected size (labels drawn uniformly), the same outcome otherwise.
 one with the earlier simulated event time is the event, the other is censored
 at its own later time, so no row is dropped.  Every figure above is then that
 of the stratified handle; `n_strata` is added to the JSON line.
+
+--entry FRAC: the counting-process model (csrc/cox_interval.hip): a fraction
+FRAC of the rows gets an entry time drawn uniformly below its exit time, the
+others are at risk from the start; the same outcome otherwise.  Every figure
+above is then that of the bbx_coxcp handle; `entry_frac` and `n_delayed` (rows
+with a finite entry time after preprocessing) are added to the JSON line.
+--entry 0 runs that handle without delayed entry.  Not together with --strata.
 """
 import argparse
 import json
@@ -58,6 +65,7 @@ from bayesbridge_amd import (BayesBridge, HipDenseDesignMatrix,  # noqa: E402
                              HipSparseDesignMatrix, RegressionCoefPrior,
                              RegressionModel, _lib, simulate)
 from bayesbridge_amd.model import (CoxModel, cox_preprocess,  # noqa: E402
+                                   cox_preprocess_interval,
                                    cox_preprocess_stratified)
 
 
@@ -125,8 +133,17 @@ def strata_outcome(X, beta, strata, seed):
     return et, ct, np.arange(n) // 2
 
 
+def entry_times(et, ct, frac, seed):
+    """Entry times of --entry: uniform on (0, exit) for a fraction of the
+    rows, -inf for the others."""
+    rs = np.random.RandomState(seed + 2)
+    x = np.minimum(et, ct)
+    entry = np.where(rs.rand(len(x)) < frac, x * rs.rand(len(x)), -np.inf)
+    return np.where(entry < x, entry, -np.inf)
+
+
 def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
-        strata=None):
+        strata=None, entry=None):
     X = make_X(kind, n, p, seed)
     beta = simulate.demo_beta(p)
     labels = None
@@ -134,10 +151,14 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
         et, ct = CoxModel.simulate_outcome(X, beta, seed=seed)
     else:
         et, ct, labels = strata_outcome(X, beta, strata, seed)
+    entry_time = None
     tic = time.perf_counter()
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        if labels is None:
+        if entry is not None:
+            entry_time, et, ct, X, _ = cox_preprocess_interval(
+                entry_times(et, ct, entry, seed), et, ct, X)
+        elif labels is None:
             et, ct, X, _ = cox_preprocess(et, ct, X)
         else:
             et, ct, labels, X, _ = cox_preprocess_stratified(et, ct, labels, X)
@@ -152,9 +173,12 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
     t_design = time.perf_counter() - tic
     tic = time.perf_counter()
     outcome = (et, ct) if labels is None else (et, ct, labels)
-    model = RegressionModel(outcome, design, 'cox')
+    model = RegressionModel(outcome, design, 'cox', entry_time=entry_time)
     n_strata = {} if labels is None else {
         'n_strata': len(model.stratum_n_event)}
+    if entry is not None:
+        n_strata = {'entry_frac': entry,
+                    'n_delayed': int(np.isfinite(entry_time).sum())}
     preprocess_s = t_design + time.perf_counter() - tic
     P = design.shape[1]
     rs = np.random.RandomState(1)
@@ -240,15 +264,23 @@ def main():
     ap.add_argument('--sampler', choices=['hmc', 'nuts'], default='hmc')
     ap.add_argument('--strata', default=None,
                     help="a number of strata, or 'pairs'")
+    ap.add_argument('--entry', type=float, default=None, metavar='FRAC',
+                    help="the counting-process model; the fraction of rows "
+                         "with a delayed entry time")
     a = ap.parse_args()
     if a.strata not in (None, 'pairs') and int(a.strata) < 1:
         raise SystemExit("--strata takes a positive number or 'pairs'")
+    if a.entry is not None and not 0. <= a.entry <= 1.:
+        raise SystemExit("--entry takes a fraction in [0, 1]")
+    if a.entry is not None and a.strata is not None:
+        raise SystemExit("--entry and --strata do not combine")
     for s in a.shapes:
         kind, size = s.split(':')
         n, p = (int(x) for x in size.split('x'))
         print(json.dumps(run(kind, n, p, a.steps, a.warmup,
                              profile_steps=a.profile_steps,
-                             sampler=a.sampler, strata=a.strata)),
+                             sampler=a.sampler, strata=a.strata,
+                             entry=a.entry)),
               flush=True)
 
 
