@@ -12,7 +12,7 @@ from ctypes import (POINTER, byref, c_char_p, c_double, c_int, c_int32,
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libbbx.so")
 
-ABI_VERSION = 112          # BBX_VERSION of include/bbx.h
+ABI_VERSION = 113         # BBX_VERSION of include/bbx.h
 FORMAT_AUTO, FORMAT_CSR, FORMAT_TILED = 0, 1, 2
 F64, F32 = 0, 1
 MODEL_LINEAR, MODEL_LOGIT = 0, 1
@@ -208,6 +208,8 @@ def _declare(lib):
         "bbx_coxcp_create": (
             [hp, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
              c_void_p, POINTER(hp)], c_int),
+        "bbx_coxef_create": (
+            [hp, c_int64, c_void_p, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_logit_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_poisson_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_cpoisson_create": (
@@ -235,7 +237,7 @@ def _declare(lib):
             POINTER(c_int), c_void_p, c_void_p, c_void_p],
         "nuts_sample": [hp, c_void_p, POINTER(c_double), c_void_p],
     }
-    for family in ("cox", "coxcp", "logit", "poisson", "cpoisson"):
+    for family in ("cox", "coxcp", "coxef", "logit", "poisson", "cpoisson"):
         for entry, argtypes in shared.items():
             sigs["bbx_%s_%s" % (family, entry)] = (list(argtypes), c_int)
     for name, (argtypes, restype) in sigs.items():

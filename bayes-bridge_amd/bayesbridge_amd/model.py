@@ -6,7 +6,8 @@ products run on the device (csrc/cox.hip); its coefficients are drawn by HMC
 'hmc' and 'nuts' coefficient samplers, and the Poisson model (csrc/poisson.hip;
 with strata the conditional Poisson model, csrc/cpoisson.hip) has no other.
 With entry times the Cox model is the counting-process form
-(csrc/cox_interval.hip)."""
+(csrc/cox_interval.hip); with ties='efron' tied event times take Efron's
+approximation (csrc/cox_efron.hip)."""
 import math
 from ctypes import byref, c_double, c_int, c_void_p
 from warnings import catch_warnings, simplefilter, warn
@@ -491,6 +492,23 @@ def cox_risk_sets(event_time, censoring_time):
     return n_event, start, end, n_app
 
 
+def cox_tie_groups(event_time):
+    """The tie group of every event of sorted observations: (gstart, gsize),
+    gstart[k] the row of the first event tied with event k (cox_risk_sets'
+    start_k) and gsize[k] = d the number of events that share its time.
+    Event k is number l = k - gstart[k] of its group, and Efron's
+    approximation leaves the fraction 1 - l/d of the group in its risk set."""
+    event_time = np.asarray(event_time, dtype=np.float64)
+    if np.any(event_time[:-1] > event_time[1:]):
+        raise ValueError(
+            "The observations need to be sorted so that the event times are "
+            "in the increasing order, from the earliest to last events.")
+    events = event_time[:len(event_time) - int(np.sum(np.isinf(event_time)))]
+    gstart = np.searchsorted(events, events, side='left')
+    gsize = np.searchsorted(events, events, side='right') - gstart
+    return gstart, gsize
+
+
 def _interval_times(entry_time, event_time, censoring_time):
     entry_time = np.asarray(entry_time, dtype=np.float64)
     event_time = np.asarray(event_time, dtype=np.float64)
@@ -757,6 +775,19 @@ def cox_stratified_risk_sets(event_time, censoring_time, strata):
     return stratum_ptr, stratum_n_event, start, end, last_set
 
 
+def _check_ties(ties, strata=None, entry_time=None):
+    if ties not in ('breslow', 'efron'):
+        raise ValueError("ties must be 'breslow' or 'efron', not %r." % (ties,))
+    if ties == 'efron' and strata is not None and entry_time is None:
+        raise ValueError(
+            "ties='efron' together with strata is not supported: Efron's "
+            "approximation in the stratified model is not built.")
+    if ties == 'efron' and entry_time is not None and strata is None:
+        raise ValueError(
+            "ties='efron' together with entry_time is not supported: Efron's "
+            "approximation in the counting-process model is not built.")
+
+
 class CoxModel(_DeviceHamiltonian, _Model):
     """cox_model.py:7-303 on a HIP design whose rows are already in the
     model's order (RegressionModel(..., family='cox') sorts them).  The
@@ -769,12 +800,19 @@ class CoxModel(_DeviceHamiltonian, _Model):
     order) the likelihood is the counting-process form, through one bbx_coxcp
     handle (csrc/cox_interval.hip): row i is in the risk set of an event at t
     iff entry_time[i] < t <= its event or censoring time, which covers delayed
-    entry and subjects written as several (start, stop] rows."""
+    entry and subjects written as several (start, stop] rows.  With
+    ties='efron' (without strata and without entry_time) tied event times are
+    handled by Efron's approximation instead of Breslow's rule, on the plain
+    model's rows through one bbx_coxef handle (csrc/cox_efron.hip);
+    `tie_group_size` then holds, for every event, the number of events that
+    share its time."""
 
     _handle_attr = '_cox'
 
     def __init__(self, event_time, censoring_time, design, strata=None,
-                 entry_time=None):
+                 entry_time=None, ties='breslow'):
+        _check_ties(ties, strata, entry_time)
+        self.ties = ties
         if entry_time is not None:
             if strata is not None:
                 raise ValueError(
@@ -811,6 +849,11 @@ class CoxModel(_DeviceHamiltonian, _Model):
         self.design = design
         self.name = 'cox'
         self._ham_prefix = 'bbx_cox_'
+        if ties == 'efron':
+            # the plain model's rows and arrays on the bbx_coxef handle
+            # (csrc/cox_efron.hip)
+            self.tie_group_size = cox_tie_groups(event_time)[1]
+            self._ham_prefix = 'bbx_coxef_'
         self._cox = c_void_p()
         self._location_serial = 0
         if strata is None:
@@ -897,7 +940,8 @@ class CoxModel(_DeviceHamiltonian, _Model):
 
 def RegressionModel(outcome, X, family='linear', add_intercept=None,
                     center_predictor=True, device=0, storage='auto',
-                    dense_storage_dtype='float64', entry_time=None):
+                    dense_storage_dtype='float64', entry_time=None,
+                    ties='breslow'):
     """model/factory.py:10-68 with the design placed on an MI355X.  `X` may be
     a SciPy sparse matrix, a NumPy array, or an already built HipDesignMatrix.
     For family='cox', outcome = (event_time, censoring_time) or, for the
@@ -906,13 +950,18 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     design goes to the GPU; a prebuilt HipDesignMatrix must already be in that
     order.  With `entry_time` (family='cox' without strata) the model is the
     counting-process form: a row is at risk from its entry time on, and the
-    rows are sorted by cox_preprocess_interval.  For family='poisson', outcome = y or (y, exposure) or, for the
+    rows are sorted by cox_preprocess_interval.  With ties='efron'
+    (family='cox' without strata and without entry_time) tied event times are
+    handled by Efron's approximation instead of Breslow's rule; the row order
+    is the same.  For family='poisson', outcome = y or (y, exposure) or, for the
     conditional Poisson model, (y, exposure, strata) (exposure may be None):
     the rows are sorted stratum-major and uninformative strata dropped
     (cpoisson_preprocess) before the design goes to the GPU; a prebuilt
     HipDesignMatrix must already be in that order."""
     if entry_time is not None and family != 'cox':
         raise ValueError("entry_time is an argument of family='cox' only.")
+    if ties != 'breslow' and family != 'cox':
+        raise ValueError("ties is an argument of family='cox' only.")
     stratified_poisson = (family == 'poisson' and isinstance(outcome, tuple)
                           and len(outcome) == 3)
     if add_intercept is None:
@@ -954,6 +1003,7 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
             raise ValueError(
                 "entry_time together with strata is not supported: the "
                 "stratified counting-process model is not implemented.")
+        _check_ties(ties, strata, entry_time)
         if entry_time is not None:
             if isinstance(X, HipDesignMatrix):
                 with catch_warnings():
@@ -1025,7 +1075,7 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         return LogisticModel(n_success, n_trial, design)
     if family == 'cox':
         return CoxModel(event_time, censoring_time, design, strata,
-                        entry_time)
+                        entry_time, ties)
     if family == 'poisson':
         if stratified_poisson:
             return PoissonModel(y, exposure, design, strata)

@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-/* 112: + the Cox model in counting-process form (bbx_coxcp_*): delayed entry
+/* 113: + Efron's approximation for tied event times in the Cox model
+ *      (bbx_coxef_*), on the plain handle's arrays, with the trajectory and
+ *      the No-U-Turn sampler of the Cox handle.
+ * 112: + the Cox model in counting-process form (bbx_coxcp_*): delayed entry
  *      and (start, stop] rows, with the trajectory and the No-U-Turn sampler
  *      of the Cox handle.
  * 111: + the conditional Poisson likelihood (bbx_cpoisson_*): counts with one
@@ -59,7 +62,7 @@ extern "C" {
  *      bbx_setup_lock_acquire/_release, bbx_design_useful_bytes.  A binding
  *      compares bbx_version() with the BBX_VERSION it was written against
  *      (bayesbridge_amd/_lib.py does) instead of calling with a stale arity. */
-#define BBX_VERSION 112 /* 0.1.12 */
+#define BBX_VERSION 113 /* 0.1.13 */
 
 /* status codes */
 #define BBX_OK 0
@@ -891,6 +894,66 @@ int bbx_coxcp_nuts_doubling(bbx_coxcp* coxcp, double dt, int direction,
                             int* n_uniform_used, int* n_steps, int* flags,
                             int* tree, double* averages);
 int bbx_coxcp_nuts_sample(bbx_coxcp* coxcp, double* q, double* logp,
+                          double* grad);
+
+/* ------------------------------------------- Cox model, Efron's tied events
+ * The Cox partial likelihood with Efron's approximation for tied event times
+ * (csrc/cox_efron.hip; the leapfrog and tree kernels are the Cox handle's,
+ * csrc/hamiltonian.hpp).  The rows and the three arrays are bbx_cox_create's:
+ * start[k] is the first event tied with event k, so events k and k' are tied
+ * iff start[k] == start[k'], and a tie group is the d rows s .. s+d-1 that
+ * share start == s.  Every index the kernels use is checked: BBX_ERR_INVALID,
+ * with a bbx_last_error() that names the array and the index, for a NULL
+ * pointer, n_event outside [1, n], start[k] outside [0, k], a start that
+ * decreases or is not the first row of a contiguous group, end[k] outside
+ * [n_event - 1, n) or increasing, n_app[i] outside [1, n_event] or not at the
+ * end of a tie group; nothing is launched then.  Every entry point but create
+ * has the argument list, the status codes and the synchronisation of its
+ * bbx_cox_* counterpart above, and a likelihood evaluation takes the same
+ * number of kernel launches.  The handle borrows the design (it must outlive
+ * the handle) and runs on its stream.  n < 2^31.  Every sum has a fixed order:
+ * the same inputs give the same bits on every call. */
+typedef struct bbx_coxef bbx_coxef;
+int bbx_coxef_create(bbx_design* design, int64_t n_event, const int32_t* start,
+                     const int32_t* end, const int32_t* n_app, bbx_coxef** out);
+int bbx_coxef_destroy(bbx_coxef* coxef);
+/* loglik = sum_k (eta_k - m) - log phi_k, phi_k = R_g + (1 - l/d) T_g for the
+ * l-th event (l = 0 .. d-1) of a tie group g: T_g the sum of h = exp(eta - m)
+ * over the group, R_g the sum over the rest of its risk set (Breslow's rule is
+ * R_g + T_g for every l).  grad[P] = X~^T w, w_i = [i < n_event] - h_i A_i,
+ * A_i = c[n_app_i - 1] - [i < n_event] (cb[s_i+d_i-1] - cb[s_i-1]),
+ * c = cumsum(1/phi), cb = cumsum((l/d) / phi), cb[-1] = 0.  phi_k <= 0 counts
+ * as an empty risk-set sum (*loglik = -inf, grad unspecified).  grad may be
+ * NULL. */
+int bbx_coxef_loglik_grad(bbx_coxef* coxef, const double* beta, double* loglik,
+                          double* grad);
+int bbx_coxef_loglik_grad_dev(bbx_coxef* coxef, const double* d_beta,
+                              double* loglik, double* d_grad);
+/* bbx_cox_set_location / _hessian_matvec on this likelihood. */
+int bbx_coxef_set_location(bbx_coxef* coxef, const double* beta);
+int bbx_coxef_hessian_matvec(bbx_coxef* coxef, const double* v, double* out);
+int bbx_coxef_hessian_matvec_dev(bbx_coxef* coxef, const double* d_v,
+                                 double* d_out);
+/* bbx_cox_hmc_trajectory on this f. */
+int bbx_coxef_hmc_trajectory(bbx_coxef* coxef, double dt, int n_step,
+                             const double* precond_scale,
+                             const double* prior_prec, const double* q0,
+                             const double* p0, double logp0,
+                             const double* grad0, double hamiltonian_tol,
+                             double* q, double* p, double* logp, double* grad,
+                             int* n_grad_evals, int* instability,
+                             double* hamiltonian);
+/* bbx_cox_nuts_begin / _doubling / _sample on this f. */
+int bbx_coxef_nuts_begin(bbx_coxef* coxef, const double* precond_scale,
+                         const double* prior_prec, const double* q0,
+                         const double* p0, double logp0, const double* grad0,
+                         double joint_logp0, double joint_logp_threshold,
+                         double hamiltonian_tol);
+int bbx_coxef_nuts_doubling(bbx_coxef* coxef, double dt, int direction,
+                            int height, const double* uniforms,
+                            int* n_uniform_used, int* n_steps, int* flags,
+                            int* tree, double* averages);
+int bbx_coxef_nuts_sample(bbx_coxef* coxef, double* q, double* logp,
                           double* grad);
 
 /* ----------------------------------------------------------- logit model

@@ -47,6 +47,18 @@ others are at risk from the start; the same outcome otherwise.  Every figure
 above is then that of the bbx_coxcp handle; `entry_frac` and `n_delayed` (rows
 with a finite entry time after preprocessing) are added to the JSON line.
 --entry 0 runs that handle without delayed entry.  Not together with --strata.
+
+--ties efron | breslow: the simulated times are rounded up to a grid of
+--grid points (default 3650: ten years of days) over the span of the observed
+times, so that events tie, and `mean_tie_group` (the mean over the events of
+the size of their tie group) and `n_tie_group` are added to the JSON line.
+efron: every figure above is that of the bbx_coxef handle
+(csrc/cox_efron.hip), and `plain_leapfrog_us` is the same trajectory on the
+plain handle (Breslow's rule) on the same design and rows, from the same
+library.  breslow: the plain handle on the gridded times.  With
+--profile-steps only the chosen handle runs, so that a kernel trace holds one
+handle's kernels: trace each in a run of its own.  Not together with --strata
+or --entry.
 """
 import argparse
 import json
@@ -66,7 +78,7 @@ from bayesbridge_amd import (BayesBridge, HipDenseDesignMatrix,  # noqa: E402
                              RegressionModel, _lib, simulate)
 from bayesbridge_amd.model import (CoxModel, cox_preprocess,  # noqa: E402
                                    cox_preprocess_interval,
-                                   cox_preprocess_stratified)
+                                   cox_preprocess_stratified, cox_tie_groups)
 
 
 def make_X(kind, n, p, seed):
@@ -142,8 +154,25 @@ def entry_times(et, ct, frac, seed):
     return np.where(entry < x, entry, -np.inf)
 
 
+def on_grid(et, ct, n_grid):
+    """Both times rounded up to a grid of n_grid points over the span of the
+    observed times (inf stays inf)."""
+    step = np.max(np.minimum(et, ct)) / n_grid
+    with np.errstate(invalid='ignore'):
+        return np.ceil(et / step) * step, np.ceil(ct / step) * step
+
+
+def leapfrog_us(model, n_traj, scale, pp, q0, p0, logp0, grad0):
+    model.hmc_trajectory(1e-3, 4, scale, pp, q0, p0, logp0, grad0, 1e300)
+    tic = time.perf_counter()
+    tr = model.hmc_trajectory(1e-3, n_traj, scale, pp, q0, p0, logp0, grad0,
+                              1e300)
+    assert tr['n_steps'] == n_traj
+    return (time.perf_counter() - tic) / n_traj * 1e6
+
+
 def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
-        strata=None, entry=None):
+        strata=None, entry=None, ties=None, n_grid=3650):
     X = make_X(kind, n, p, seed)
     beta = simulate.demo_beta(p)
     labels = None
@@ -151,6 +180,8 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
         et, ct = CoxModel.simulate_outcome(X, beta, seed=seed)
     else:
         et, ct, labels = strata_outcome(X, beta, strata, seed)
+    if ties is not None:
+        et, ct = on_grid(et, ct, n_grid)
     entry_time = None
     tic = time.perf_counter()
     with warnings.catch_warnings():
@@ -173,12 +204,17 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
     t_design = time.perf_counter() - tic
     tic = time.perf_counter()
     outcome = (et, ct) if labels is None else (et, ct, labels)
-    model = RegressionModel(outcome, design, 'cox', entry_time=entry_time)
+    model = RegressionModel(outcome, design, 'cox', entry_time=entry_time,
+                            ties=ties or 'breslow')
     n_strata = {} if labels is None else {
         'n_strata': len(model.stratum_n_event)}
     if entry is not None:
         n_strata = {'entry_frac': entry,
                     'n_delayed': int(np.isfinite(entry_time).sum())}
+    if ties is not None:
+        gstart, gsize = cox_tie_groups(et)
+        n_strata = {'ties': ties, 'mean_tie_group': round(gsize.mean(), 1),
+                    'n_tie_group': len(np.unique(gstart))}
     preprocess_s = t_design + time.perf_counter() - tic
     P = design.shape[1]
     rs = np.random.RandomState(1)
@@ -210,12 +246,15 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
         leap_us = nuts_half_tree(model, 1e-3, height, scale, pp, q0, p0,
                                  logp0, grad0) / n_traj * 1e6
     else:
-        model.hmc_trajectory(1e-3, 4, scale, pp, q0, p0, logp0, grad0, 1e300)
-        tic = time.perf_counter()
-        tr = model.hmc_trajectory(1e-3, n_traj, scale, pp, q0, p0, logp0,
-                                  grad0, 1e300)
-        leap_us = (time.perf_counter() - tic) / n_traj * 1e6
-        assert tr['n_steps'] == n_traj
+        leap_us = leapfrog_us(model, n_traj, scale, pp, q0, p0, logp0, grad0)
+        if ties == 'efron' and not profile_steps:
+            # the plain handle on the same design and rows: its own f(q0)
+            plain = RegressionModel(outcome, design, 'cox')
+            pll, pg = plain.compute_loglik_and_gradient(q0 * scale)
+            n_strata['plain_leapfrog_us'] = round(leapfrog_us(
+                plain, n_traj, scale, pp, q0, p0, pll - np.sum(q0 ** 2) / 2,
+                scale * pg - q0), 1)
+            del plain
     prod_us = products_us(design, profile_steps or 50)
     if profile_steps:
         return {'shape': '%s:%dx%d' % (kind, n, p), 'sampler': sampler,
@@ -267,7 +306,15 @@ def main():
     ap.add_argument('--entry', type=float, default=None, metavar='FRAC',
                     help="the counting-process model; the fraction of rows "
                          "with a delayed entry time")
+    ap.add_argument('--ties', choices=['breslow', 'efron'], default=None,
+                    help="times on a grid, tied events by this rule")
+    ap.add_argument('--grid', type=int, default=3650, metavar='N',
+                    help="grid points of --ties")
     a = ap.parse_args()
+    if a.ties is not None and (a.strata is not None or a.entry is not None):
+        raise SystemExit("--ties does not combine with --strata or --entry")
+    if a.grid < 1:
+        raise SystemExit("--grid takes a positive number")
     if a.strata not in (None, 'pairs') and int(a.strata) < 1:
         raise SystemExit("--strata takes a positive number or 'pairs'")
     if a.entry is not None and not 0. <= a.entry <= 1.:
@@ -280,7 +327,8 @@ def main():
         print(json.dumps(run(kind, n, p, a.steps, a.warmup,
                              profile_steps=a.profile_steps,
                              sampler=a.sampler, strata=a.strata,
-                             entry=a.entry)),
+                             entry=a.entry, ties=a.ties,
+                             n_grid=a.grid)),
               flush=True)
 
 
