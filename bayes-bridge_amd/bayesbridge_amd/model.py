@@ -7,7 +7,8 @@ products run on the device (csrc/cox.hip); its coefficients are drawn by HMC
 with strata the conditional Poisson model, csrc/cpoisson.hip) has no other.
 With entry times the Cox model is the counting-process form
 (csrc/cox_interval.hip); with ties='efron' tied event times take Efron's
-approximation (csrc/cox_efron.hip)."""
+approximation (csrc/cox_efron.hip); with weights= every row carries a case
+weight (the weighted partial likelihood, csrc/cox_weighted.hip)."""
 import math
 from ctypes import byref, c_double, c_int, c_void_p
 from warnings import catch_warnings, simplefilter, warn
@@ -788,6 +789,34 @@ def _check_ties(ties, strata=None, entry_time=None):
             "approximation in the counting-process model is not built.")
 
 
+def _check_weights(weights, n, strata=None, entry_time=None, ties='breslow'):
+    """The case weights of n rows as a float64 vector (None stays None)."""
+    if weights is None:
+        return None
+    if strata is not None:
+        raise ValueError(
+            "weights together with strata is not supported: case weights in "
+            "the stratified model are not built.")
+    if entry_time is not None:
+        raise ValueError(
+            "weights together with entry_time is not supported: case weights "
+            "in the counting-process model are not built.")
+    if ties == 'efron':
+        raise ValueError(
+            "weights together with ties='efron' is not supported: case "
+            "weights with Efron's approximation are not built.")
+    weights = np.array(weights, dtype=np.float64)
+    if weights.shape != (n,):
+        raise ValueError(
+            "weights must be a 1-d array with one weight for each "
+            "observation: shape %s, %d observations." % (weights.shape, n))
+    if not np.all(np.isfinite(weights)) or np.any(weights <= 0):
+        raise ValueError(
+            "Every weight must be strictly positive and finite (drop the "
+            "rows of weight 0 instead).")
+    return weights
+
+
 class CoxModel(_DeviceHamiltonian, _Model):
     """cox_model.py:7-303 on a HIP design whose rows are already in the
     model's order (RegressionModel(..., family='cox') sorts them).  The
@@ -805,14 +834,21 @@ class CoxModel(_DeviceHamiltonian, _Model):
     handled by Efron's approximation instead of Breslow's rule, on the plain
     model's rows through one bbx_coxef handle (csrc/cox_efron.hip);
     `tie_group_size` then holds, for every event, the number of events that
-    share its time."""
+    share its time.  With `weights` (one strictly positive weight per row, in
+    row order; without strata, entry_time and ties='efron') the likelihood is
+    the weighted partial likelihood, through one bbx_coxw handle
+    (csrc/cox_weighted.hip): with integer weights it is the plain likelihood
+    of the rows written that many times."""
 
     _handle_attr = '_cox'
 
     def __init__(self, event_time, censoring_time, design, strata=None,
-                 entry_time=None, ties='breslow'):
+                 entry_time=None, ties='breslow', weights=None):
         _check_ties(ties, strata, entry_time)
+        weights = _check_weights(weights, len(event_time), strata, entry_time,
+                                 ties)
         self.ties = ties
+        self.weights = weights
         if entry_time is not None:
             if strata is not None:
                 raise ValueError(
@@ -854,14 +890,20 @@ class CoxModel(_DeviceHamiltonian, _Model):
             # (csrc/cox_efron.hip)
             self.tie_group_size = cox_tie_groups(event_time)[1]
             self._ham_prefix = 'bbx_coxef_'
+        if weights is not None:
+            # the plain model's rows and arrays on the bbx_coxw handle
+            # (csrc/cox_weighted.hip)
+            self._ham_prefix = 'bbx_coxw_'
         self._cox = c_void_p()
         self._location_serial = 0
         if strata is None:
             i32 = [np.ascontiguousarray(a, dtype=np.int32)
                    for a in (start, end, n_app)]
+            # bbx_coxw_create takes the weights after the index arrays
+            more = () if weights is None else (_ptr(weights),)
             _lib.check(self._ham_fn('create')(
                 design.handle, n_event, _ptr(i32[0]), _ptr(i32[1]),
-                _ptr(i32[2]), byref(self._cox)))
+                _ptr(i32[2]), *more, byref(self._cox)))
         else:
             sptr = np.ascontiguousarray(sptr, dtype=np.int64)
             i32 = [np.ascontiguousarray(a, dtype=np.int32)
@@ -941,7 +983,7 @@ class CoxModel(_DeviceHamiltonian, _Model):
 def RegressionModel(outcome, X, family='linear', add_intercept=None,
                     center_predictor=True, device=0, storage='auto',
                     dense_storage_dtype='float64', entry_time=None,
-                    ties='breslow'):
+                    ties='breslow', weights=None):
     """model/factory.py:10-68 with the design placed on an MI355X.  `X` may be
     a SciPy sparse matrix, a NumPy array, or an already built HipDesignMatrix.
     For family='cox', outcome = (event_time, censoring_time) or, for the
@@ -953,8 +995,12 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     rows are sorted by cox_preprocess_interval.  With ties='efron'
     (family='cox' without strata and without entry_time) tied event times are
     handled by Efron's approximation instead of Breslow's rule; the row order
-    is the same.  For family='poisson', outcome = y or (y, exposure) or, for the
-    conditional Poisson model, (y, exposure, strata) (exposure may be None):
+    is the same.  With `weights` (family='cox' without strata, entry_time and
+    ties='efron'; one strictly positive case weight per row of X as given) the
+    likelihood is the weighted partial likelihood; the weights are sorted and
+    pruned with their rows.  For family='poisson', outcome = y or
+    (y, exposure) or, for the conditional Poisson model,
+    (y, exposure, strata) (exposure may be None):
     the rows are sorted stratum-major and uninformative strata dropped
     (cpoisson_preprocess) before the design goes to the GPU; a prebuilt
     HipDesignMatrix must already be in that order."""
@@ -962,6 +1008,8 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         raise ValueError("entry_time is an argument of family='cox' only.")
     if ties != 'breslow' and family != 'cox':
         raise ValueError("ties is an argument of family='cox' only.")
+    if weights is not None and family != 'cox':
+        raise ValueError("weights is an argument of family='cox' only.")
     stratified_poisson = (family == 'poisson' and isinstance(outcome, tuple)
                           and len(outcome) == 3)
     if add_intercept is None:
@@ -1004,6 +1052,8 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
                 "entry_time together with strata is not supported: the "
                 "stratified counting-process model is not implemented.")
         _check_ties(ties, strata, entry_time)
+        weights = _check_weights(weights, len(np.asarray(event_time)), strata,
+                                 entry_time, ties)
         if entry_time is not None:
             if isinstance(X, HipDesignMatrix):
                 with catch_warnings():
@@ -1049,8 +1099,10 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
                 raise ValueError("The Cox model takes a design without an "
                                  "intercept column.")
         elif strata is None:
-            event_time, censoring_time, X, _ = cox_preprocess(
+            event_time, censoring_time, X, keep = cox_preprocess(
                 event_time, censoring_time, X)
+            if weights is not None:
+                weights = weights[keep]
         else:
             event_time, censoring_time, strata, X, _ = \
                 cox_preprocess_stratified(event_time, censoring_time, strata,
@@ -1075,7 +1127,7 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         return LogisticModel(n_success, n_trial, design)
     if family == 'cox':
         return CoxModel(event_time, censoring_time, design, strata,
-                        entry_time, ties)
+                        entry_time, ties, weights)
     if family == 'poisson':
         if stratified_poisson:
             return PoissonModel(y, exposure, design, strata)

@@ -36,6 +36,10 @@ extern "C" {
 /* 113: + Efron's approximation for tied event times in the Cox model
  *      (bbx_coxef_*), on the plain handle's arrays, with the trajectory and
  *      the No-U-Turn sampler of the Cox handle.
+ *      + case weights in the Cox model (bbx_coxw_*: create, destroy and the
+ *      shared entry points of every likelihood handle).  New symbols and
+ *      nothing else, so the number stays 113: a binding written against 113
+ *      before them runs unchanged, one that needs them looks them up.
  * 112: + the Cox model in counting-process form (bbx_coxcp_*): delayed entry
  *      and (start, stop] rows, with the trajectory and the No-U-Turn sampler
  *      of the Cox handle.
@@ -955,6 +959,62 @@ int bbx_coxef_nuts_doubling(bbx_coxef* coxef, double dt, int direction,
                             int* tree, double* averages);
 int bbx_coxef_nuts_sample(bbx_coxef* coxef, double* q, double* logp,
                           double* grad);
+
+/* ------------------------------------------------ Cox model, case weights
+ * The Cox partial likelihood (Breslow's rule for ties) with one weight a_i > 0
+ * per row (csrc/cox_weighted.hip; the leapfrog and tree kernels are the Cox
+ * handle's, csrc/hamiltonian.hpp).  The rows and the three index arrays are
+ * bbx_cox_create's and are checked as it checks them; weights[n] (host,
+ * double) is in the same row order.  BBX_ERR_INVALID, with a bbx_last_error()
+ * that names the first offending row, for a NULL pointer or a weight that is
+ * NaN, infinite, zero or negative; nothing is launched then.  With integer
+ * weights the likelihood is the plain one of the rows written a_i times, with
+ * all weights 1 it is the plain one.  Every entry point but create has the
+ * argument list, the status codes and the synchronisation of its bbx_cox_*
+ * counterpart above, and a likelihood evaluation takes the same number of
+ * kernel launches.  The handle borrows the design (it must outlive the handle)
+ * and runs on its stream.  n < 2^31.  Every sum has a fixed order: the same
+ * inputs give the same bits on every call. */
+typedef struct bbx_coxw bbx_coxw;
+int bbx_coxw_create(bbx_design* design, int64_t n_event, const int32_t* start,
+                    const int32_t* end, const int32_t* n_app,
+                    const double* weights, bbx_coxw** out);
+int bbx_coxw_destroy(bbx_coxw* coxw);
+/* loglik = sum_k a_k ((eta_k - m) - log H_k), m = max eta, H_k the sum of
+ * g = a exp(eta - m) over risk set k.  grad[P] = X~^T w,
+ * w_i = [i < n_event] a_i - c[n_app_i - 1] g_i, c = cumsum(a_k (1/H_k)).
+ * H_k == 0 is an empty risk-set sum (*loglik = -inf, grad unspecified).  grad
+ * may be NULL. */
+int bbx_coxw_loglik_grad(bbx_coxw* coxw, const double* beta, double* loglik,
+                         double* grad);
+int bbx_coxw_loglik_grad_dev(bbx_coxw* coxw, const double* d_beta,
+                             double* loglik, double* d_grad);
+/* bbx_cox_set_location / _hessian_matvec on this likelihood. */
+int bbx_coxw_set_location(bbx_coxw* coxw, const double* beta);
+int bbx_coxw_hessian_matvec(bbx_coxw* coxw, const double* v, double* out);
+int bbx_coxw_hessian_matvec_dev(bbx_coxw* coxw, const double* d_v,
+                                double* d_out);
+/* bbx_cox_hmc_trajectory on this f. */
+int bbx_coxw_hmc_trajectory(bbx_coxw* coxw, double dt, int n_step,
+                            const double* precond_scale,
+                            const double* prior_prec, const double* q0,
+                            const double* p0, double logp0,
+                            const double* grad0, double hamiltonian_tol,
+                            double* q, double* p, double* logp, double* grad,
+                            int* n_grad_evals, int* instability,
+                            double* hamiltonian);
+/* bbx_cox_nuts_begin / _doubling / _sample on this f. */
+int bbx_coxw_nuts_begin(bbx_coxw* coxw, const double* precond_scale,
+                        const double* prior_prec, const double* q0,
+                        const double* p0, double logp0, const double* grad0,
+                        double joint_logp0, double joint_logp_threshold,
+                        double hamiltonian_tol);
+int bbx_coxw_nuts_doubling(bbx_coxw* coxw, double dt, int direction,
+                           int height, const double* uniforms,
+                           int* n_uniform_used, int* n_steps, int* flags,
+                           int* tree, double* averages);
+int bbx_coxw_nuts_sample(bbx_coxw* coxw, double* q, double* logp,
+                         double* grad);
 
 /* ----------------------------------------------------------- logit model
  * The binomial-logit likelihood of model/logistic_model.py:49-74 on a design

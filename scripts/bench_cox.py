@@ -59,6 +59,20 @@ library.  breslow: the plain handle on the gridded times.  With
 --profile-steps only the chosen handle runs, so that a kernel trace holds one
 handle's kernels: trace each in a run of its own.  Not together with --strata
 or --entry.
+
+--weights iptw: the weighted model (csrc/cox_weighted.hip) with stabilised
+inverse-probability-of-treatment weights: a treatment is drawn for every row
+from a simulated propensity e_i = expit(x_i . gamma - c) (gamma on the first
+five columns, c set so that the mean propensity is about 0.3), and a_i =
+P(z = z_i) / P(z = z_i | x_i).  `weight_min`, `weight_max` and `weight_mean`
+are added to the JSON line.  Every figure above is then that of the bbx_coxw
+handle, and `plain_leapfrog_us` is the same trajectory on the plain handle
+(no weights) on the same design and rows, from the same library, in the same
+process -- with --profile-steps too: in a kernel trace the two handles' own
+kernels have different names (coxw_* against cox_scan_sum_kernel and
+cox_weight_kernel), and cox_max_kernel and cox_scan_out_kernel are the same
+code on the same sizes in both, so their per-call average is either handle's.
+Not together with --strata, --entry or --ties.
 """
 import argparse
 import json
@@ -162,6 +176,18 @@ def on_grid(et, ct, n_grid):
         return np.ceil(et / step) * step, np.ceil(ct / step) * step
 
 
+def iptw_weights(X, seed):
+    """Stabilised inverse-probability-of-treatment weights of --weights."""
+    rs = np.random.RandomState(seed + 3)
+    k = min(5, X.shape[1])
+    gamma = rs.randn(k)
+    score = np.asarray(X[:, :k].dot(gamma), dtype=np.float64).ravel()
+    score = (score - score.mean()) / (score.std() or 1.)
+    e = 1. / (1. + np.exp(-(score + np.log(.3 / .7))))
+    z = rs.rand(len(e)) < e
+    return np.where(z, z.mean() / e, (1. - z.mean()) / (1. - e))
+
+
 def leapfrog_us(model, n_traj, scale, pp, q0, p0, logp0, grad0):
     model.hmc_trajectory(1e-3, 4, scale, pp, q0, p0, logp0, grad0, 1e300)
     tic = time.perf_counter()
@@ -172,7 +198,7 @@ def leapfrog_us(model, n_traj, scale, pp, q0, p0, logp0, grad0):
 
 
 def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
-        strata=None, entry=None, ties=None, n_grid=3650):
+        strata=None, entry=None, ties=None, n_grid=3650, weights=None):
     X = make_X(kind, n, p, seed)
     beta = simulate.demo_beta(p)
     labels = None
@@ -183,6 +209,8 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
     if ties is not None:
         et, ct = on_grid(et, ct, n_grid)
     entry_time = None
+    if weights is not None:
+        weights = iptw_weights(X, seed)
     tic = time.perf_counter()
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
@@ -190,7 +218,9 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
             entry_time, et, ct, X, _ = cox_preprocess_interval(
                 entry_times(et, ct, entry, seed), et, ct, X)
         elif labels is None:
-            et, ct, X, _ = cox_preprocess(et, ct, X)
+            et, ct, X, keep = cox_preprocess(et, ct, X)
+            if weights is not None:
+                weights = weights[keep]
         else:
             et, ct, labels, X, _ = cox_preprocess_stratified(et, ct, labels, X)
     if kind == 'binary':
@@ -205,7 +235,7 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
     tic = time.perf_counter()
     outcome = (et, ct) if labels is None else (et, ct, labels)
     model = RegressionModel(outcome, design, 'cox', entry_time=entry_time,
-                            ties=ties or 'breslow')
+                            ties=ties or 'breslow', weights=weights)
     n_strata = {} if labels is None else {
         'n_strata': len(model.stratum_n_event)}
     if entry is not None:
@@ -215,6 +245,11 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
         gstart, gsize = cox_tie_groups(et)
         n_strata = {'ties': ties, 'mean_tie_group': round(gsize.mean(), 1),
                     'n_tie_group': len(np.unique(gstart))}
+    if weights is not None:
+        n_strata = {'weights': 'iptw',
+                    'weight_min': float('%.4g' % weights.min()),
+                    'weight_max': float('%.4g' % weights.max()),
+                    'weight_mean': float('%.4g' % weights.mean())}
     preprocess_s = t_design + time.perf_counter() - tic
     P = design.shape[1]
     rs = np.random.RandomState(1)
@@ -247,7 +282,7 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
                                  logp0, grad0) / n_traj * 1e6
     else:
         leap_us = leapfrog_us(model, n_traj, scale, pp, q0, p0, logp0, grad0)
-        if ties == 'efron' and not profile_steps:
+        if (ties == 'efron' and not profile_steps) or weights is not None:
             # the plain handle on the same design and rows: its own f(q0)
             plain = RegressionModel(outcome, design, 'cox')
             pll, pg = plain.compute_loglik_and_gradient(q0 * scale)
@@ -308,11 +343,17 @@ def main():
                          "with a delayed entry time")
     ap.add_argument('--ties', choices=['breslow', 'efron'], default=None,
                     help="times on a grid, tied events by this rule")
+    ap.add_argument('--weights', choices=['iptw'], default=None,
+                    help="the weighted model, stabilised IPT weights")
     ap.add_argument('--grid', type=int, default=3650, metavar='N',
                     help="grid points of --ties")
     a = ap.parse_args()
     if a.ties is not None and (a.strata is not None or a.entry is not None):
         raise SystemExit("--ties does not combine with --strata or --entry")
+    if a.weights is not None and (a.strata is not None or a.entry is not None
+                                  or a.ties is not None):
+        raise SystemExit("--weights does not combine with --strata, --entry "
+                         "or --ties")
     if a.grid < 1:
         raise SystemExit("--grid takes a positive number")
     if a.strata not in (None, 'pairs') and int(a.strata) < 1:
@@ -328,7 +369,7 @@ def main():
                              profile_steps=a.profile_steps,
                              sampler=a.sampler, strata=a.strata,
                              entry=a.entry, ties=a.ties,
-                             n_grid=a.grid)),
+                             n_grid=a.grid, weights=a.weights)),
               flush=True)
 
 
