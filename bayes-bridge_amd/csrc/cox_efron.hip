@@ -27,6 +27,10 @@
 // rounding of c[n_app - 1] itself.  phi_k <= 0 is treated as the plain handle
 // treats H_k == 0: CoxTraj::zero and skip are raised.
 //
+// The kernels, their partition and reductions, the six launches and the
+// family are cox_family.hpp's; this file states the formulae above as its
+// policy (CoxEfron), the index checks and the C entry points.
+//
 // Scans: the fixed partition and pass B of cox_scan.hpp.  inv and (l/d) inv
 // are elements k and ne + k of one buffer of 2 ne values: the event pass A
 // gathers once per event and leaves the chunk sums of both halves, and one
@@ -39,260 +43,78 @@
 #include <vector>
 
 #include "common.hpp"
-#include "cox_scan.hpp"
-#include "hamiltonian.hpp"
+#include "cox_family.hpp"
 
 #pragma clang fp contract(off)  // a + b * c rounded as NumPy rounds it
 
-namespace bbx {
+using namespace bbx;
 
-// Pass A over the risk segments: h = exp(eta - m) (HU = false) or h u, stored
-// in val, and one sum per chunk.
-template <bool HU>
-__global__ __launch_bounds__(SCAN_BLOCK) void coxef_risk_sum_kernel(
-    Segs sg, const double* __restrict__ eta, const double* __restrict__ maxp,
-    const double* __restrict__ h, const double* __restrict__ u,
-    double* __restrict__ val, double* __restrict__ csum,
-    const int* __restrict__ skip) {
-  if (skip && *skip) return;
-  const int s = blockIdx.x / SCAN_G, b = blockIdx.x % SCAN_G;
-  const int64_t len = sg.len[s];
-  const int64_t L = (len + SCAN_G - 1) / SCAN_G;
-  const int64_t t0 = (int64_t)b * L, t1 = t0 + L < len ? t0 + L : len;
-  double m = 0.;
-  if (!HU) m = part_max(maxp);
-  double acc = 0.;
-  for (int64_t t = t0 + threadIdx.x; t < t1; t += SCAN_BLOCK) {
-    const int64_t i = seg_elem(sg, s, t);
-    const double v = HU ? h[i] * u[i] : exp(eta[i] - m);
-    val[i] = v;
-    acc += v;
-  }
-  acc = block_sum<SCAN_BLOCK>(acc);
-  if (threadIdx.x == 0) csum[blockIdx.x] = acc;
-}
-
-struct EfArgs {
-  const double* eta = nullptr;    // likelihood mode
-  const double* maxp = nullptr;   // NPART partials of max eta
-  const double* scan = nullptr;   // E in [0, ne), C in [ne, n)
-  const double* inv = nullptr;    // Hessian mode: 1 / phi at the location
-  const int2* grp = nullptr;      // (s - 1, s + d - 1) of every event
-  const int32_t* end = nullptr;
-  int64_t ne = 0;
-  double* val = nullptr;          // 2 ne: the value, (l/d) times the value
-  double* llpart = nullptr;       // likelihood mode: SCAN_G loglik partials
-  CoxTraj* st = nullptr;          // likelihood mode: zero / skip flags
+// One Cox likelihood with Efron ties on a design (borrowed: the design must
+// outlive it).  The event-length buffers of CoxCore hold 2 ne values: (1/phi,
+// l/d 1/phi) or z, and their cumsums (c, cb).
+struct bbx_coxef : CoxCore {
+  DevMem grp, end, napp;                 // int2 ne, int32 ne, int32 n
+  // out of line, as it has been since the handle was added: libbbx.so's
+  // dynamic symbols name it
+  __attribute__((noinline)) ~bbx_coxef() {}
 };
 
-// Pass A over the events, SCAN_G blocks: phi_k = R_g + a_k T_g from one
-// gather, 1/phi_k (HESS: inv_k (inv_k S_k)) into element k and l/d times it
-// into element ne + k, and the chunk sums of both halves.
-template <bool HESS>
-__global__ __launch_bounds__(SCAN_BLOCK) void coxef_event_sum_kernel(
-    EfArgs a, double* __restrict__ csum, const int* __restrict__ skip) {
-  if (skip && *skip) return;
-  const int b = blockIdx.x;
-  const int64_t len = a.ne;
-  const int64_t L = (len + SCAN_G - 1) / SCAN_G;
-  const int64_t t0 = (int64_t)b * L, t1 = t0 + L < len ? t0 + L : len;
-  double m = 0.;
-  if (!HESS) m = part_max(a.maxp);
-  double acc = 0., accb = 0., ll = 0.;
-  bool zero = false;
-  for (int64_t k = t0 + threadIdx.x; k < t1; k += SCAN_BLOCK) {
-    const int2 g = a.grp[k];
-    const int32_t e = a.end[k];
-    const int64_t s = (int64_t)g.x + 1, next = (int64_t)g.y + 1;
-    const double En = next < a.ne ? a.scan[next] : 0.;
-    const double T = a.scan[s] - En;
-    double R = En;
-    if (e >= a.ne) R += a.scan[e];
-    const double lf = (double)(k - s) / (double)(next - s);
-    const double phi = R + (1. - lf) * T;
-    double v;
-    if (!HESS) {
-      zero |= (phi <= 0.);
-      v = 1. / phi;
-      ll += (a.eta[k] - m) - log(phi);
-    } else {
-      const double iv = a.inv[k];
-      v = iv * (iv * phi);
-    }
-    const double vb = lf * v;
-    a.val[k] = v;
-    a.val[a.ne + k] = vb;
-    acc += v;
-    accb += vb;
-  }
-  acc = block_sum<SCAN_BLOCK>(acc);
-  accb = block_sum<SCAN_BLOCK>(accb);
-  if (!HESS) {
-    ll = block_sum<SCAN_BLOCK>(ll);
-    if (zero) {
-      a.st->zero = 1;
-      a.st->skip = 1;
-    }
-  }
-  if (threadIdx.x == 0) {
-    csum[b] = acc;
-    csum[SCAN_G + b] = accb;
-    if (!HESS) a.llpart[b] = ll;
-  }
-}
+namespace {
 
-// A_i = c[n_app_i - 1] - [i < ne] (cb[s_i + d_i - 1] - cb[s_i - 1]), c in
-// cum[0, ne) and cb in cum[ne, 2 ne):
-// w = [i < ne] - h_i A_i                              (HESS = false: gradient)
-// w = -((h_i A_i) u_i - h_i Z_i), Z as A from cz      (HESS = true)
-// and the NPART partials of sum(w).  grp: (s - 1, s + d - 1), one 8-byte load.
-template <bool HESS>
-__global__ __launch_bounds__(VEC_BLOCK) void coxef_weight_kernel(
-    int64_t n, int64_t ne, const double* __restrict__ h,
-    const double* __restrict__ c, const int32_t* __restrict__ napp,
-    const int2* __restrict__ grp, const double* __restrict__ u,
-    const double* __restrict__ cz, double* __restrict__ w,
-    double* __restrict__ part, const int* __restrict__ skip) {
-  if (skip && *skip) return;
-  double acc = 0.;
-  for (int64_t i = (int64_t)blockIdx.x * VEC_BLOCK + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * VEC_BLOCK) {
+// The header's formulae as cox_family.hpp's kernels ask for them
+struct CoxEfron {
+  using Handle = bbx_coxef;
+  static constexpr const char* name = "coxef";
+  static constexpr int halves = 2;       // inv and (l/d) inv; c and cb
+  static constexpr bool keeps_inv = false;
+  const int2* grp;                       // (s - 1, s + d - 1) of every event
+  const int32_t* end;
+  const int32_t* napp;
+  int64_t ne;
+  static CoxEfron make(const bbx_coxef* c) {
+    return {c->grp.as<const int2>(), c->end.as<const int32_t>(),
+            c->napp.as<const int32_t>(), c->ne};
+  }
+  // E: the events reversed; C: the censored rows forward
+  static void risk_layout(const bbx_coxef* c, int* nseg, int64_t* len,
+                          int* rev) {
+    *nseg = 2;
+    len[0] = c->ne, rev[0] = 1;
+    len[1] = c->n - c->ne, rev[1] = 0;
+  }
+  static double* hu(bbx_coxef* c) { return c->tmp.as<double>(); }
+  __device__ int64_t row(int, int64_t i) const { return i; }
+  __device__ double h_of(int64_t, double e) const { return e; }
+  // phi_k = R_g + a_k T_g from one gather; lf = l/d
+  __device__ double H(const double* scan, int64_t k, double& lf) const {
+    const int2 g = grp[k];
+    const int32_t e = end[k];
+    const int64_t s = (int64_t)g.x + 1, next = (int64_t)g.y + 1;
+    const double En = next < ne ? scan[next] : 0.;
+    const double T = scan[s] - En;
+    double R = En;
+    if (e >= ne) R += scan[e];
+    lf = (double)(k - s) / (double)(next - s);
+    return R + (1. - lf) * T;
+  }
+  __device__ bool empty(double phi) const { return phi <= 0.; }
+  __device__ int64_t event_row(int64_t k) const { return k; }
+  __device__ double scaled(double x, double) const { return x; }
+  // c in cum[0, ne) and cb in cum[ne, 2 ne)
+  template <bool HESS>
+  __device__ void AZ(const double* c, const double* cz, int64_t i, double& A,
+                     double& Z) const {
     const int32_t k = napp[i] - 1;
-    const double hi = h[i];
-    double A = c[k], Z = HESS ? cz[k] : 0.;
+    A = c[k];
+    if (HESS) Z = cz[k];
     if (i < ne) {
       const int2 g = grp[i];
       A = A - (c[ne + g.y] - (g.x >= 0 ? c[ne + g.x] : 0.));
       if (HESS) Z = Z - (cz[ne + g.y] - (g.x >= 0 ? cz[ne + g.x] : 0.));
     }
-    const double rs = hi * A;
-    double v;
-    if (HESS) {
-      v = -(rs * u[i] - hi * Z);
-    } else {
-      v = (i < ne ? 1. : 0.) - rs;
-    }
-    w[i] = v;
-    acc += v;
   }
-  acc = block_sum<VEC_BLOCK>(acc);
-  if (threadIdx.x == 0) part[blockIdx.x] = acc;
-}
-
-}  // namespace bbx
-
-using namespace bbx;
-
-// One Cox likelihood with Efron ties on a design (borrowed: the design must
-// outlive it).
-struct bbx_coxef : HamCore {
-  int64_t ne = 0;
-  DevMem grp, end, napp;                 // int2 ne, int32 ne, int32 n
-  DevMem hz, scan;                       // n: h, risk scan (tmp: w / h u)
-  DevMem inv, cs;                        // 2 ne: (1/phi, l/d 1/phi) or z; cumsums
-  DevMem h_loc, inv_loc, c_loc;          // the Hessian's location: n, 2 ne, 2 ne
-  DevMem csum, maxp;                     // 2 SCAN_G, NPART
+  __device__ double indicator(int64_t i) const { return i < ne ? 1. : 0.; }
 };
-
-namespace {
-
-using ham::cst;
-using ham::eta_of;
-using ham::read_state;
-
-// E: the events reversed; C: the censored rows forward
-Segs risk_segs(const bbx_coxef* c) {
-  Segs sg;
-  sg.base[0] = 0;
-  sg.len[0] = c->ne;
-  sg.rev[0] = 1;
-  sg.base[1] = c->ne;
-  sg.len[1] = c->n - c->ne;
-  sg.rev[1] = 0;
-  return sg;
-}
-
-// c: elements 0 .. ne - 1; cb: elements ne .. 2 ne - 1, both forward
-Segs event_segs(const bbx_coxef* c) {
-  Segs sg;
-  sg.base[0] = 0;
-  sg.len[0] = c->ne;
-  sg.rev[0] = 0;
-  sg.base[1] = c->ne;
-  sg.len[1] = c->ne;
-  sg.rev[1] = 0;
-  return sg;
-}
-
-template <bool HU>
-int launch_risk_sum(bbx_coxef* c, const Segs& sg, const double* eta,
-                    const double* h, const double* u, double* val,
-                    const int* skip) {
-  BBX_LAUNCH(coxef_risk_sum_kernel<HU>, dim3(2 * SCAN_G), dim3(SCAN_BLOCK), 0,
-             c->h->stream, sg, eta, c->maxp.as<const double>(), h, u, val,
-             c->csum.as<double>(), skip);
-  BBX_HIP(hipGetLastError());
-  return BBX_OK;
-}
-
-template <bool HESS>
-int launch_event_sum(bbx_coxef* c, const EfArgs& a, const int* skip) {
-  BBX_LAUNCH(coxef_event_sum_kernel<HESS>, dim3(SCAN_G), dim3(SCAN_BLOCK), 0,
-             c->h->stream, a, c->csum.as<double>(), skip);
-  BBX_HIP(hipGetLastError());
-  return BBX_OK;
-}
-
-int launch_scan_out(bbx_coxef* c, const Segs& sg, const double* val,
-                    double* out, const int* skip) {
-  BBX_LAUNCH(cox_scan_out_kernel, dim3(2 * SCAN_G), dim3(SCAN_BLOCK), 0,
-             c->h->stream, sg, val, out, c->csum.as<const double>(), skip);
-  BBX_HIP(hipGetLastError());
-  return BBX_OK;
-}
-
-EfArgs event_args(const bbx_coxef* c) {
-  EfArgs b;
-  b.scan = c->scan.as<double>();
-  b.grp = c->grp.as<int2>();
-  b.end = c->end.as<int32_t>();
-  b.ne = c->ne;
-  return b;
-}
-
-// From eta (already in c->eta, complete in stream order): h, phi, the loglik
-// partials, (1/phi, l/d 1/phi) into `inv` and their cumsums (c, cb) into
-// `cum`, then (grad != null) w and grad = X~^T w.  `h_out`: where h goes
-// (c->hz or the location's).
-int likelihood_from_eta(bbx_coxef* c, double* h_out, double* inv, double* cum,
-                        double* grad) {
-  bbx_design* h = c->h;
-  const int* skip = &cst(c)->skip;
-  BBX_LAUNCH(cox_max_kernel, dim3(NPART), dim3(VEC_BLOCK), 0, h->stream, c->n,
-             c->eta.as<const double>(), c->maxp.as<double>(), skip);
-  BBX_HIP(hipGetLastError());
-  const Segs rs = risk_segs(c), es = event_segs(c);
-  BBX_TRY(launch_risk_sum<false>(c, rs, c->eta.as<const double>(), nullptr,
-                                 nullptr, h_out, skip));
-  BBX_TRY(launch_scan_out(c, rs, h_out, c->scan.as<double>(), skip));
-  EfArgs b = event_args(c);
-  b.eta = c->eta.as<double>();
-  b.maxp = c->maxp.as<double>();
-  b.val = inv;
-  b.llpart = c->llpart.as<double>();
-  b.st = cst(c);
-  BBX_TRY(launch_event_sum<false>(c, b, skip));
-  BBX_TRY(launch_scan_out(c, es, inv, cum, skip));
-  if (!grad) return BBX_OK;
-  double* sumw = part_slot(h, PS_SUMW);
-  BBX_LAUNCH(coxef_weight_kernel<false>, dim3(NPART), dim3(VEC_BLOCK), 0,
-             h->stream, c->n, c->ne, h_out, cum, c->napp.as<const int32_t>(),
-             c->grp.as<const int2>(), nullptr, nullptr, c->tmp.as<double>(),
-             sumw, skip);
-  BBX_HIP(hipGetLastError());
-  TdotEpilogue ep;
-  return launch_tdot(h, c->tmp.as<double>(), sumw, ep, grad);
-}
 
 std::string at(const char* name, int64_t i) {
   return std::string(name) + "[" + std::to_string(i) + "]";
@@ -301,16 +123,9 @@ std::string at(const char* name, int64_t i) {
 int coxef_create_impl(bbx_design* h, int64_t n_event, const int32_t* start,
                       const int32_t* end, const int32_t* n_app,
                       bbx_coxef** out) {
-  if (!out) return fail(BBX_ERR_INVALID, "NULL output pointer");
-  *out = nullptr;
-  if (!h || !design_alive(h)) return fail(BBX_ERR_INVALID, "invalid design");
-  if (!start || !end || !n_app)
-    return fail(BBX_ERR_INVALID, "NULL index array");
+  BBX_TRY(cox_create_head(
+      h, n_event, start && end && n_app ? nullptr : "NULL index array", out));
   const int64_t n = h->n;
-  if (n >= (int64_t(1) << 31))
-    return fail(BBX_ERR_INVALID, "the Cox model needs fewer than 2^31 rows");
-  if (n_event < 1 || n_event > n)
-    return fail(BBX_ERR_INVALID, "n_event must be in [1, n]");
   const int64_t ne = n_event;
   // the kernels index scan[s], scan[s + d], scan[end], c[n_app - 1],
   // cb[s - 1] and cb[s + d - 1]: check what is given, derive the tie groups
@@ -343,89 +158,16 @@ int coxef_create_impl(bbx_design* h, int64_t n_event, const int32_t* start,
   }
 
   bbx_coxef* c = new bbx_coxef;
-  c->ne = ne;
-  const size_t d8 = sizeof(double), i4 = sizeof(int32_t);
-  int st = ham::init_core(c, h, "coxef");
-  DevMem* nvec[] = {&c->hz, &c->scan, &c->h_loc};
-  for (DevMem* m : nvec)
-    if (st == BBX_OK) st = m->alloc(d8 * n);
-  DevMem* evec[] = {&c->inv, &c->cs, &c->inv_loc, &c->c_loc};
-  for (DevMem* m : evec)
-    if (st == BBX_OK) st = m->alloc(d8 * 2 * ne);
-  if (st == BBX_OK) st = c->grp.alloc(i4 * 2 * ne);
-  if (st == BBX_OK) st = c->end.alloc(i4 * ne);
-  if (st == BBX_OK) st = c->napp.alloc(i4 * n);
-  if (st == BBX_OK) st = c->csum.alloc(d8 * 2 * SCAN_G);
-  if (st == BBX_OK) st = c->maxp.alloc(d8 * NPART);
+  const char* fam = CoxEfron::name;
+  int st = cox_alloc(c, h, fam, ne, n, 2 * ne);
+  if (st == BBX_OK)
+    st = cox_upload(c, fam, c->grp, (const int2*)grp.data(), ne);
+  if (st == BBX_OK) st = cox_upload(c, fam, c->end, end, ne);
+  if (st == BBX_OK) st = cox_upload(c, fam, c->napp, n_app, n);
+  if (st == BBX_OK) st = cox_uploaded(c, fam);
   if (st != BBX_OK) return ham::discard(c, st);
-  const hipMemcpyKind H2D = hipMemcpyHostToDevice;
-  hipError_t e = hipMemcpyAsync(c->grp.ptr, grp.data(), i4 * 2 * ne, H2D,
-                                h->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(c->end.ptr, end, i4 * ne, H2D, h->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(c->napp.ptr, n_app, i4 * n, H2D, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess)
-    return ham::discard(c, fail(BBX_ERR_HIP, std::string("coxef upload: ") +
-                                                 hipGetErrorString(e)));
   *out = c;
   return BBX_OK;
-}
-
-// The Cox block of a leapfrog step: everything from eta to X~^T w
-struct CoxEfLik {
-  bbx_coxef* c;
-  int operator()(double* grad) const {
-    return likelihood_from_eta(c, c->hz.as<double>(), c->inv.as<double>(),
-                               c->cs.as<double>(), grad);
-  }
-};
-
-struct CoxEfFamily {
-  static constexpr const char* name = "coxef";
-  using Lik = CoxEfLik;
-  static int locate(bbx_coxef* c, const double* d_in) {
-    BBX_LAUNCH(cox_reset_kernel, dim3(1), dim3(WAVE), 0, c->h->stream, cst(c));
-    BBX_TRY(eta_of(c, d_in));
-    BBX_TRY(likelihood_from_eta(c, c->h_loc.as<double>(),
-                                c->inv_loc.as<double>(), c->c_loc.as<double>(),
-                                nullptr));
-    BBX_TRY(read_state(c));
-    if (c->host_st->zero)
-      return fail(BBX_ERR_NUMERIC,
-                  "Hessian location: a risk-set sum of relative hazards is 0");
-    return BBX_OK;
-  }
-  static int hessian_from_v(bbx_coxef* c, const double* d_v, double* d_out);
-};
-
-int CoxEfFamily::hessian_from_v(bbx_coxef* c, const double* d_v,
-                                double* d_out) {
-  bbx_design* h = c->h;
-  BBX_LAUNCH(cox_reset_kernel, dim3(1), dim3(WAVE), 0, h->stream, cst(c));
-  BBX_TRY(eta_of(c, d_v));   // u = X~ v, in c->eta
-  const Segs rs = risk_segs(c), es = event_segs(c);
-  BBX_TRY(launch_risk_sum<true>(c, rs, nullptr, c->h_loc.as<const double>(),
-                                c->eta.as<const double>(), c->tmp.as<double>(),
-                                nullptr));
-  BBX_TRY(launch_scan_out(c, rs, c->tmp.as<double>(), c->scan.as<double>(),
-                          nullptr));
-  EfArgs b = event_args(c);
-  b.inv = c->inv_loc.as<double>();
-  b.val = c->inv.as<double>();
-  BBX_TRY(launch_event_sum<true>(c, b, nullptr));
-  BBX_TRY(launch_scan_out(c, es, c->inv.as<double>(), c->cs.as<double>(),
-                          nullptr));
-  double* sumw = part_slot(h, PS_SUMW);
-  BBX_LAUNCH(coxef_weight_kernel<true>, dim3(NPART), dim3(VEC_BLOCK), 0,
-             h->stream, c->n, c->ne, c->h_loc.as<const double>(),
-             c->c_loc.as<const double>(), c->napp.as<const int32_t>(),
-             c->grp.as<const int2>(), c->eta.as<const double>(),
-             c->cs.as<const double>(), c->tmp.as<double>(), sumw, nullptr);
-  BBX_HIP(hipGetLastError());
-  TdotEpilogue ep;
-  return launch_tdot(h, c->tmp.as<double>(), sumw, ep, d_out);
 }
 
 }  // namespace
@@ -438,4 +180,4 @@ extern "C" int bbx_coxef_create(bbx_design* design, int64_t n_event,
   });
 }
 
-BBX_HAM_ENTRY_POINTS(coxef, CoxEfFamily)
+BBX_HAM_ENTRY_POINTS(coxef, CoxFamilyT<CoxEfron>)

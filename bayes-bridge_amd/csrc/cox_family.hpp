@@ -1,0 +1,409 @@
+// What the Cox likelihood handles share (cox.hip, cox_interval.hip,
+// cox_efron.hip, cox_weighted.hip): the handle base, the three kernels that
+// form values, the six-launch driver and the family that hamiltonian.hpp's
+// entry points take.  A handle states a policy V, a small struct of device
+// pointers that is passed to the kernels by value:
+//
+//   device side (the per-element expressions; everything else is written once)
+//     row(s, i)         the row behind element i of risk segment s
+//     h_of(r, e)        the relative hazard of row r from e = exp(eta_r - m)
+//     H(scan, k, f)     the risk-set sum of event k from the risk scan; f: a
+//                       factor of event k the policy wants back (weight, l/d)
+//     empty(H)          the test that raises CoxTraj::zero and skip
+//     event_row(k)      the row of event k
+//     scaled(x, f)      x, or x times the event's weight
+//     AZ<HESS>(c, cz, i, A, Z)   A_i of row i from the cumulative sum c and,
+//                       HESS, Z_i from cz the same way (one walk of the row's
+//                       indices serves both)
+//     indicator(i)      the event indicator (or event weight) of row i
+//     halves            1, or 2: f times the value goes to element ne + k and
+//                       its chunk sums to csum[SCAN_G + b]
+//     keeps_inv         1/H is stored beside the (scaled) value
+//   host side
+//     Handle, name      the C ABI's struct and "cox", "coxcp", ...
+//     make(c)           the policy of handle c
+//     risk_layout(c, nseg, len, rev)   the risk segments: how many are
+//                       launched, their lengths and directions (segment 1
+//                       starts where segment 0 ends)
+//     hu(c)             where the Hessian's h u goes
+//
+// A policy method is the expression of its handle's file header, with that
+// association and rounding order; the kernels below only add, reduce and
+// store.  Policies live in the unnamed namespace of their file: no two
+// translation units instantiate a kernel with the same arguments, and no
+// handle type's name reaches an exported symbol.
+#pragma once
+#include <math.h>
+
+#include <string>
+
+#include "common.hpp"
+#include "cox_scan.hpp"
+#include "hamiltonian.hpp"
+
+#pragma clang fp contract(off)  // a + b * c rounded as NumPy rounds it
+
+namespace bbx {
+
+// The buffers of every Cox handle.  "n" below is the handle's row length (n,
+// or nseg n of the interval handle), "ne" its event length (ne, or 2 ne of
+// the Efron handle).
+struct CoxCore : HamCore {
+  int64_t ne = 0;
+  DevMem hz, scan;                       // n: h, risk scan
+  DevMem inv, cs;                        // ne: 1/H (or z), cumsum
+  DevMem h_loc, inv_loc, c_loc;          // the Hessian's location: n, ne, ne
+  DevMem csum, maxp;                     // 2 SCAN_G, NPART
+};
+
+// Pass A over the risk segments: h (HU = false) or h u, stored in val, and
+// one sum per chunk.
+template <class V, bool HU>
+__global__ __launch_bounds__(SCAN_BLOCK) void cox_risk_sum_kernel(
+    Segs sg, V v, const double* __restrict__ eta,
+    const double* __restrict__ maxp, const double* __restrict__ h,
+    const double* __restrict__ u, double* __restrict__ val,
+    double* __restrict__ csum, const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  const int s = blockIdx.x / SCAN_G, b = blockIdx.x % SCAN_G;
+  const int64_t len = sg.len[s];
+  const int64_t L = (len + SCAN_G - 1) / SCAN_G;
+  const int64_t t0 = (int64_t)b * L, t1 = t0 + L < len ? t0 + L : len;
+  double m = 0.;
+  if (!HU) m = part_max(maxp);
+  double acc = 0.;
+  for (int64_t t = t0 + threadIdx.x; t < t1; t += SCAN_BLOCK) {
+    const int64_t i = seg_elem(sg, s, t);
+    const int64_t r = v.row(s, i);
+    const double x = HU ? h[r] * u[r] : v.h_of(r, exp(eta[r] - m));
+    val[i] = x;
+    acc += x;
+  }
+  acc = block_sum<SCAN_BLOCK>(acc);
+  if (threadIdx.x == 0) csum[blockIdx.x] = acc;
+}
+
+struct CoxEventArgs {
+  const double* eta = nullptr;    // likelihood mode
+  const double* maxp = nullptr;   // likelihood mode: NPART partials of max eta
+  const double* scan = nullptr;   // the risk scan
+  const double* inv = nullptr;    // Hessian mode: 1 / H at the location
+  int64_t ne = 0;
+  double* val = nullptr;          // the value (halves == 2: and f times it)
+  double* inv_out = nullptr;      // keeps_inv, optional: 1 / H
+  double* llpart = nullptr;       // likelihood mode: SCAN_G loglik partials
+  CoxTraj* st = nullptr;          // likelihood mode: zero / skip flags
+};
+
+// Pass A over the events, SCAN_G blocks: H_k (HESS: S_k) from the risk scan,
+// 1/H_k (HESS: inv_k (inv_k S_k)), scaled, stored in val, and one sum per
+// chunk and half.
+template <class V, bool HESS>
+__global__ __launch_bounds__(SCAN_BLOCK) void cox_event_sum_kernel(
+    V v, CoxEventArgs a, double* __restrict__ csum,
+    const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  const int b = blockIdx.x;
+  const int64_t len = a.ne;
+  const int64_t L = (len + SCAN_G - 1) / SCAN_G;
+  const int64_t t0 = (int64_t)b * L, t1 = t0 + L < len ? t0 + L : len;
+  double m = 0.;
+  if (!HESS) m = part_max(a.maxp);
+  double acc = 0., accb = 0., ll = 0.;
+  bool zero = false;
+  for (int64_t k = t0 + threadIdx.x; k < t1; k += SCAN_BLOCK) {
+    double f;
+    const double H = v.H(a.scan, k, f);
+    double x;
+    if (!HESS) {
+      zero |= v.empty(H);
+      const double iv = 1. / H;
+      if (V::keeps_inv && a.inv_out) a.inv_out[k] = iv;
+      x = v.scaled(iv, f);
+      ll += v.scaled((a.eta[v.event_row(k)] - m) - log(H), f);
+    } else {
+      const double iv = a.inv[k];
+      x = v.scaled(iv * (iv * H), f);
+    }
+    a.val[k] = x;
+    acc += x;
+    if (V::halves == 2) {
+      const double xb = f * x;
+      a.val[a.ne + k] = xb;
+      accb += xb;
+    }
+  }
+  acc = block_sum<SCAN_BLOCK>(acc);
+  if (V::halves == 2) accb = block_sum<SCAN_BLOCK>(accb);
+  if (!HESS) {
+    ll = block_sum<SCAN_BLOCK>(ll);
+    if (zero) {
+      a.st->zero = 1;
+      a.st->skip = 1;
+    }
+  }
+  if (threadIdx.x == 0) {
+    csum[b] = acc;
+    if (V::halves == 2) csum[SCAN_G + b] = accb;
+    if (!HESS) a.llpart[b] = ll;
+  }
+}
+
+// w = indicator_i - h_i A_i                           (HESS = false: gradient)
+// w = -((h_i A_i) u_i - h_i Z_i), Z as A from cz      (HESS = true)
+// and the NPART partials of sum(w) (the Tdot's intercept / centring term).
+template <class V, bool HESS>
+__global__ __launch_bounds__(VEC_BLOCK) void cox_row_weight_kernel(
+    V v, int64_t n, const double* __restrict__ h, const double* __restrict__ c,
+    const double* __restrict__ u, const double* __restrict__ cz,
+    double* __restrict__ w, double* __restrict__ part,
+    const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  double acc = 0.;
+  for (int64_t i = (int64_t)blockIdx.x * VEC_BLOCK + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * VEC_BLOCK) {
+    const double hi = h[i];
+    double A, Z = 0.;
+    v.template AZ<HESS>(c, cz, i, A, Z);
+    const double rs = hi * A;
+    double x;
+    if (HESS) {
+      x = -(rs * u[i] - hi * Z);
+    } else {
+      x = v.indicator(i) - rs;
+    }
+    w[i] = x;
+    acc += x;
+  }
+  acc = block_sum<VEC_BLOCK>(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+namespace {  // host side: internal, as the handle types appear in the names
+
+using ham::cst;
+using ham::eta_of;
+using ham::read_state;
+
+// The shared head of a `create`.  `missing`: the message for the first NULL
+// array argument, or null where every array is given.
+template <class H>
+int cox_create_head(bbx_design* h, int64_t n_event, const char* missing,
+                    H** out) {
+  if (!out) return fail(BBX_ERR_INVALID, "NULL output pointer");
+  *out = nullptr;
+  if (!h || !design_alive(h)) return fail(BBX_ERR_INVALID, "invalid design");
+  if (missing) return fail(BBX_ERR_INVALID, missing);
+  if (h->n >= (int64_t(1) << 31))
+    return fail(BBX_ERR_INVALID, "the Cox model needs fewer than 2^31 rows");
+  if (n_event < 1 || n_event > h->n)
+    return fail(BBX_ERR_INVALID, "n_event must be in [1, n]");
+  return BBX_OK;
+}
+
+// HamCore's part of a fresh handle and the buffers of CoxCore: `rows` doubles
+// in each row-length buffer, `events` in each event-length one.
+int cox_alloc(CoxCore* c, bbx_design* h, const char* family, int64_t n_event,
+              int64_t rows, int64_t events) {
+  c->ne = n_event;
+  const size_t d8 = sizeof(double);
+  BBX_TRY(ham::init_core(c, h, family));
+  for (DevMem* m : {&c->hz, &c->scan, &c->h_loc}) BBX_TRY(m->alloc(d8 * rows));
+  for (DevMem* m : {&c->inv, &c->cs, &c->inv_loc, &c->c_loc})
+    BBX_TRY(m->alloc(d8 * events));
+  BBX_TRY(c->csum.alloc(d8 * 2 * SCAN_G));
+  return c->maxp.alloc(d8 * NPART);
+}
+
+int cox_upload_failed(const char* family, hipError_t e) {
+  return fail(BBX_ERR_HIP, std::string(family) + " upload: " +
+                               hipGetErrorString(e));
+}
+
+// Allocates `m` for `count` values and queues their upload from the host
+template <class T>
+int cox_upload(CoxCore* c, const char* family, DevMem& m, const T* src,
+               size_t count) {
+  BBX_TRY(m.alloc(sizeof(T) * count));
+  const hipError_t e = hipMemcpyAsync(m.ptr, src, sizeof(T) * count,
+                                      hipMemcpyHostToDevice, c->h->stream);
+  return e == hipSuccess ? BBX_OK : cox_upload_failed(family, e);
+}
+
+// The end of a `create`: the uploads are complete on return
+int cox_uploaded(CoxCore* c, const char* family) {
+  const hipError_t e = hipStreamSynchronize(c->h->stream);
+  return e == hipSuccess ? BBX_OK : cox_upload_failed(family, e);
+}
+
+// Two segments, the second after the first
+Segs cox_segs(int64_t len0, int rev0, int64_t len1, int rev1) {
+  Segs sg;
+  sg.base[0] = 0;
+  sg.len[0] = len0;
+  sg.rev[0] = rev0;
+  sg.base[1] = len0;
+  sg.len[1] = len1;
+  sg.rev[1] = rev1;
+  return sg;
+}
+
+template <class V>
+Segs risk_segs(const typename V::Handle* c, int* nseg) {
+  int64_t len[2];
+  int rev[2];
+  V::risk_layout(c, nseg, len, rev);
+  return cox_segs(len[0], rev[0], len[1], rev[1]);
+}
+
+// The cumulative sums over the events, forward: one per half
+template <class V>
+Segs event_segs(const typename V::Handle* c) {
+  return cox_segs(c->ne, 0, V::halves == 2 ? c->ne : 0, 0);
+}
+
+int launch_scan_out(CoxCore* c, const Segs& sg, int nseg, const double* val,
+                    double* out, const int* skip) {
+  BBX_LAUNCH(cox_scan_out_kernel, dim3(nseg * SCAN_G), dim3(SCAN_BLOCK), 0,
+             c->h->stream, sg, val, out, c->csum.as<const double>(), skip);
+  BBX_HIP(hipGetLastError());
+  return BBX_OK;
+}
+
+// Risk pass A / B: the values into `val`, their scan into c->scan
+template <class V, bool HU>
+int launch_risk(typename V::Handle* c, const double* h, double* val,
+                const int* skip) {
+  int nseg;
+  const Segs rs = risk_segs<V>(c, &nseg);
+  BBX_LAUNCH((cox_risk_sum_kernel<V, HU>), dim3(nseg * SCAN_G),
+             dim3(SCAN_BLOCK), 0, c->h->stream, rs, V::make(c),
+             c->eta.template as<const double>(),
+             c->maxp.template as<const double>(), h,
+             c->eta.template as<const double>(), val,
+             c->csum.template as<double>(), skip);
+  BBX_HIP(hipGetLastError());
+  return launch_scan_out(c, rs, nseg, val, c->scan.template as<double>(),
+                         skip);
+}
+
+// Event pass A / B: the values into a.val, their cumsums into `cum`
+template <class V, bool HESS>
+int launch_event(typename V::Handle* c, CoxEventArgs a, double* cum,
+                 const int* skip) {
+  a.scan = c->scan.template as<const double>();
+  a.ne = c->ne;
+  BBX_LAUNCH((cox_event_sum_kernel<V, HESS>), dim3(SCAN_G), dim3(SCAN_BLOCK),
+             0, c->h->stream, V::make(c), a, c->csum.template as<double>(),
+             skip);
+  BBX_HIP(hipGetLastError());
+  return launch_scan_out(c, event_segs<V>(c), V::halves, a.val, cum, skip);
+}
+
+// Row pass and X~^T w into `out`
+template <class V, bool HESS>
+int launch_rows(typename V::Handle* c, const double* h_at, const double* cum,
+                const double* cz, double* out, const int* skip) {
+  bbx_design* h = c->h;
+  double* w = c->tmp.template as<double>();
+  double* sumw = part_slot(h, PS_SUMW);
+  BBX_LAUNCH((cox_row_weight_kernel<V, HESS>), dim3(NPART), dim3(VEC_BLOCK), 0,
+             h->stream, V::make(c), c->n, h_at, cum,
+             HESS ? c->eta.template as<const double>() : nullptr, cz, w, sumw,
+             skip);
+  BBX_HIP(hipGetLastError());
+  TdotEpilogue ep;
+  return launch_tdot(h, w, sumw, ep, out);
+}
+
+// From eta (already in c->eta, complete in stream order): h, H, the loglik
+// partials, the event values into `inv` (keeps_inv: and 1/H into `inv1` where
+// given) and their cumsums into `cum`, then (grad != null) w and
+// grad = X~^T w.  `h_out`: where h goes (c->hz or the location's).  Six
+// launches: max, risk pass A / B, event pass A / B, rows.
+template <class V>
+int likelihood_from_eta(typename V::Handle* c, double* h_out, double* inv,
+                        double* inv1, double* cum, double* grad) {
+  const int* skip = &cst(c)->skip;
+  BBX_LAUNCH(cox_max_kernel, dim3(NPART), dim3(VEC_BLOCK), 0, c->h->stream,
+             c->n, c->eta.template as<const double>(),
+             c->maxp.template as<double>(), skip);
+  BBX_HIP(hipGetLastError());
+  BBX_TRY((launch_risk<V, false>(c, nullptr, h_out, skip)));
+  CoxEventArgs b;
+  b.eta = c->eta.template as<const double>();
+  b.maxp = c->maxp.template as<const double>();
+  b.val = inv;
+  b.inv_out = inv1;
+  b.llpart = c->llpart.template as<double>();
+  b.st = cst(c);
+  BBX_TRY((launch_event<V, false>(c, b, cum, skip)));
+  if (!grad) return BBX_OK;
+  return launch_rows<V, false>(c, h_out, cum, nullptr, grad, skip);
+}
+
+// The Hessian matvec at the location, after u = X~ v is in c->eta
+template <class V>
+int hessian_from_u(typename V::Handle* c, double* d_out) {
+  const double* h_loc = c->h_loc.template as<const double>();
+  BBX_TRY((launch_risk<V, true>(c, h_loc, V::hu(c), nullptr)));
+  CoxEventArgs b;
+  b.inv = c->inv_loc.template as<const double>();
+  b.val = c->inv.template as<double>();
+  BBX_TRY((launch_event<V, true>(c, b, c->cs.template as<double>(), nullptr)));
+  return launch_rows<V, true>(c, h_loc, c->c_loc.template as<const double>(),
+                              c->cs.template as<const double>(), d_out,
+                              nullptr);
+}
+
+// The two blocks above as a family calls them; cox.hip states its own, which
+// sends a stratified handle to its own algorithm
+template <class V>
+struct CoxDriverT {
+  using H = typename V::Handle;
+  static int likelihood(H* c, double* h_out, double* inv, double* inv1,
+                        double* cum, double* grad) {
+    return likelihood_from_eta<V>(c, h_out, inv, inv1, cum, grad);
+  }
+  static int hessian(H* c, double* d_out) { return hessian_from_u<V>(c, d_out); }
+};
+
+// The policy hamiltonian.hpp's entry points take
+template <class V, class D = CoxDriverT<V>>
+struct CoxFamilyT {
+  using H = typename V::Handle;
+  static constexpr const char* name = V::name;
+  // The Cox block of a leapfrog step: everything from eta to X~^T w
+  struct Lik {
+    H* c;
+    int operator()(double* grad) const {
+      return D::likelihood(c, c->hz.template as<double>(),
+                           c->inv.template as<double>(), nullptr,
+                           c->cs.template as<double>(), grad);
+    }
+  };
+  static int locate(H* c, const double* d_in) {
+    BBX_LAUNCH(cox_reset_kernel, dim3(1), dim3(WAVE), 0, c->h->stream, cst(c));
+    BBX_TRY(eta_of(c, d_in));
+    // keeps_inv: the location keeps 1/H itself; the scaled value is only the
+    // scan's input and goes to the scratch c->inv
+    double* inv_loc = c->inv_loc.template as<double>();
+    BBX_TRY(D::likelihood(c, c->h_loc.template as<double>(),
+                          V::keeps_inv ? c->inv.template as<double>() : inv_loc,
+                          V::keeps_inv ? inv_loc : nullptr,
+                          c->c_loc.template as<double>(), nullptr));
+    BBX_TRY(read_state(c));
+    if (c->host_st->zero)
+      return fail(BBX_ERR_NUMERIC,
+                  "Hessian location: a risk-set sum of relative hazards is 0");
+    return BBX_OK;
+  }
+  static int hessian_from_v(H* c, const double* d_v, double* d_out) {
+    BBX_LAUNCH(cox_reset_kernel, dim3(1), dim3(WAVE), 0, c->h->stream, cst(c));
+    BBX_TRY(eta_of(c, d_v));   // u = X~ v, in c->eta
+    return D::hessian(c, d_out);
+  }
+};
+
+}  // namespace
+}  // namespace bbx

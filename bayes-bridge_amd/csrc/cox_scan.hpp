@@ -1,7 +1,7 @@
-// The blocked two-pass scan of the Cox handles (cox.hip, cox_interval.hip): the
-// segment descriptor, the max of eta and pass B.  Every scan runs over a FIXED
-// partition: each segment is cut into SCAN_G chunks; a pass A (the handle's
-// own: it forms the values) writes one sum per chunk, pass B re-adds the sums
+// The blocked two-pass scan of the Cox handles (cox_family.hpp): the segment
+// descriptor, the max of eta and pass B.  Every scan runs over a FIXED
+// partition: each segment is cut into SCAN_G chunks; a pass A (cox_family.hpp's:
+// it forms the values) writes one sum per chunk, pass B re-adds the sums
 // of the chunks before its own in a fixed order and scans its chunk in tiles
 // of SCAN_BLOCK x SCAN_E.  No float atomics: the same inputs give the same
 // bits on every run.  The kernels are static, as hamiltonian.hpp's are: each

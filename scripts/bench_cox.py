@@ -69,9 +69,11 @@ are added to the JSON line.  Every figure above is then that of the bbx_coxw
 handle, and `plain_leapfrog_us` is the same trajectory on the plain handle
 (no weights) on the same design and rows, from the same library, in the same
 process -- with --profile-steps too: in a kernel trace the two handles' own
-kernels have different names (coxw_* against cox_scan_sum_kernel and
-cox_weight_kernel), and cox_max_kernel and cox_scan_out_kernel are the same
-code on the same sizes in both, so their per-call average is either handle's.
+kernels differ in their policy argument (cox_risk_sum_kernel<CoxWeighted, ..>
+against cox_risk_sum_kernel<CoxPlain, ..>, and so on for cox_event_sum_kernel
+and cox_row_weight_kernel), and cox_max_kernel and cox_scan_out_kernel are the
+same code on the same sizes in both, so their per-call average is either
+handle's.
 Not together with --strata, --entry or --ties.
 """
 import argparse

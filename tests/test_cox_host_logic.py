@@ -305,12 +305,15 @@ def test_step_size_adapter_and_direction_summary():
 def test_cox_kernels_do_not_spill(tmp_path):
     table = _resource_table(
         os.path.join(ROOT, "bayes-bridge_amd", "csrc", "cox.hip"), tmp_path)
-    for k in ("cox_max_kernel", "cox_scan_sum_kernel", "cox_scan_out_kernel",
-              "cox_weight_kernel", "cox_loglik_kernel", "cox_reset_kernel",
+    for k in ("cox_max_kernel", "cox_risk_sum_kernel", "cox_event_sum_kernel",
+              "cox_scan_out_kernel", "cox_row_weight_kernel",
+              "cox_loglik_kernel", "cox_reset_kernel",
               "cox_step1_kernel", "cox_post_a_kernel", "cox_post_b_kernel",
               "cox_sumsq_kernel", "cox_traj_init_kernel", "cox_finish_kernel"):
         assert any(k in name for name in table), (k, sorted(table))
-    assert sum("cox_scan_sum_kernel" in k for k in table) == 4
+    for k in ("cox_risk_sum_kernel", "cox_event_sum_kernel",
+              "cox_row_weight_kernel"):
+        assert sum(k in name for name in table) == 2, (k, sorted(table))
     for name, res in table.items():
         assert res["VGPRs Spill"] == 0, (name, res)
         assert res["SGPRs Spill"] == 0, (name, res)

@@ -1,7 +1,7 @@
 """CPU (hipcc cross-compile): no kernel of the weighted Cox handle
-(cox_weighted.hip: its own pass A and weight kernels, its copies of the shared
-scan kernels of cox_scan.hpp and of the trajectory kernels of hamiltonian.hpp)
-uses scratch or spills registers."""
+(cox_weighted.hip: its instantiations of cox_family.hpp's three kernels,
+its copies of the scan kernels of cox_scan.hpp and of the trajectory kernels
+of hamiltonian.hpp) uses scratch or spills registers."""
 import os
 
 import pytest
@@ -9,9 +9,9 @@ import pytest
 from conftest import ROOT
 from test_cholesky_kernel_resources import HIPCC, _resource_table
 
-OWN = {"coxw_risk_sum_kernel": 2,       # g, g u
-       "coxw_event_sum_kernel": 2,      # a/H, z
-       "coxw_weight_kernel": 2}         # gradient, Hessian
+OWN = {"cox_risk_sum_kernel": 2,        # g, g u
+       "cox_event_sum_kernel": 2,       # a/H, z
+       "cox_row_weight_kernel": 2}      # gradient, Hessian
 SHARED = ("cox_max_kernel", "cox_scan_out_kernel", "cox_loglik_kernel",
           "cox_reset_kernel", "cox_step1_kernel", "cox_post_a_kernel",
           "cox_post_b_kernel", "cox_nuts_leaf_kernel",
