@@ -1,0 +1,133 @@
+"""Sequential host replay of the device chain's Philox draws
+(`bbx_replay_*` of libbbx_hostrng.so, csrc/replay_impl.hpp): what the tests
+pin the sampler kernels to, draw by draw.  NumPy marshalling only.
+
+`stream` is the kernel's stream word: `iter_stream(STREAM_PG, it)` for the
+chain's iteration `it`, the bare stream id for the stand-alone
+`bbx_device_*` entry points.  `variant` 0 is the reference's arithmetic, 1 the
+kernels' forms evaluated by the host's libm."""
+import ctypes
+from ctypes import c_double, c_int, c_int64, c_uint32, c_uint64, c_void_p
+
+import numpy as np
+
+from . import hostrng
+
+# csrc/philox.hpp PhiloxStream
+STREAM_ETA1, STREAM_ETA2, STREAM_PG, STREAM_GSCALE, STREAM_LSCALE, \
+    STREAM_OBSVAR = 1, 2, 3, 4, 5, 6
+
+_SIGS = {
+    "bbx_replay_philox_block": [c_void_p, c_void_p, c_void_p],
+    "bbx_replay_philox_counter": [c_uint64, c_uint64, c_uint64, c_uint32,
+                                  c_void_p, c_void_p],
+    "bbx_replay_uniform": [c_uint64, c_uint64, c_uint64, c_uint32, c_int64,
+                           c_void_p],
+    "bbx_replay_normal": [c_uint64, c_uint64, c_int64, c_void_p],
+    "bbx_replay_polya_gamma": [c_uint64, c_uint64, c_int64, c_int, c_void_p,
+                               c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    "bbx_replay_tilted_stable": [c_uint64, c_uint64, c_int64, c_double,
+                                 c_void_p, c_int, c_void_p, c_void_p],
+    "bbx_replay_gamma": [c_uint64, c_uint64, c_uint64, c_int64, c_double,
+                         c_void_p],
+}
+_declared = False
+
+
+def _lib():
+    global _declared
+    lib = hostrng.load()
+    if not _declared:
+        for name, argtypes in _SIGS.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+        _declared = True
+    return lib
+
+
+def _check(status, what):
+    if status != 0:
+        raise ValueError("invalid arguments to the %s replay" % what)
+
+
+def _p(a):
+    return a.ctypes.data_as(c_void_p)
+
+
+def iter_stream(stream, iteration):
+    """The stream word of chain iteration `iteration` (csrc/chain.hip)."""
+    return (int(stream) | (int(iteration) << 8)) & 0xFFFFFFFFFFFFFFFF
+
+
+def philox_block(counter, key):
+    """One Philox4x32-10 block: counter[4], key[2] -> four 32-bit words."""
+    c = np.ascontiguousarray(counter, dtype=np.uint32)
+    k = np.ascontiguousarray(key, dtype=np.uint32)
+    assert c.shape == (4,) and k.shape == (2,)
+    out = np.empty(4, dtype=np.uint32)
+    _check(_lib().bbx_replay_philox_block(_p(c), _p(k), _p(out)), 'Philox')
+    return out
+
+
+def philox_counter(seed, stream, index, trial=0):
+    """(counter[4], key[2]) of a freshly made Philox(seed, stream, index,
+    trial)."""
+    c, k = np.empty(4, dtype=np.uint32), np.empty(2, dtype=np.uint32)
+    _check(_lib().bbx_replay_philox_counter(seed, stream, index, trial,
+                                            _p(c), _p(k)), 'Philox')
+    return c, k
+
+
+def uniform(seed, stream, index, trial, n):
+    out = np.empty(n)
+    _check(_lib().bbx_replay_uniform(seed, stream, index, trial, n, _p(out)),
+           'uniform')
+    return out
+
+
+def normal(seed, stream, n):
+    out = np.empty(n)
+    _check(_lib().bbx_replay_normal(seed, stream, n, _p(out)), 'normal')
+    return out
+
+
+def polya_gamma(seed, stream, shape, tilt, variant=0, trace=False):
+    """Draws; with trace, (draws, attempts, restarts): the inverse-Gaussian
+    proposals each element took and whether its series test made it start
+    over.  `shape`: an integer array (int32, as bbx_device_polya_gamma takes
+    it) or a float one (double, as the chain holds n_trial)."""
+    shape = np.asarray(shape)
+    is_double = not np.issubdtype(shape.dtype, np.integer)
+    shape = np.ascontiguousarray(
+        shape, dtype=np.float64 if is_double else np.int32)
+    tilt = np.ascontiguousarray(tilt, dtype=np.float64)
+    assert shape.shape == tilt.shape and tilt.ndim == 1
+    out = np.empty(tilt.size)
+    att = np.zeros(tilt.size, dtype=np.int32)
+    rst = np.zeros(tilt.size, dtype=np.int32)
+    _check(_lib().bbx_replay_polya_gamma(
+        seed, stream, tilt.size, int(is_double), _p(shape), _p(tilt),
+        int(variant), _p(out), _p(att), _p(rst)), 'Polya-Gamma')
+    return (out, att, rst) if trace else out
+
+
+def tilted_stable(seed, stream, char_exp, tilt, variant=0, trace=False):
+    """Draws; with trace, (draws, winner): the number of the accepted
+    candidate of each element."""
+    tilt = np.ascontiguousarray(tilt, dtype=np.float64)
+    assert tilt.ndim == 1
+    out = np.empty(tilt.size)
+    win = np.zeros(tilt.size, dtype=np.int32)
+    _check(_lib().bbx_replay_tilted_stable(
+        seed, stream, tilt.size, float(char_exp), _p(tilt), int(variant),
+        _p(out), _p(win)), 'tilted-stable')
+    return (out, win) if trace else out
+
+
+def gamma(seed, stream, shape, n=1, index=0):
+    """gamma_draw on Philox(seed, stream, index + k), k < n."""
+    out = np.empty(n)
+    _check(_lib().bbx_replay_gamma(seed, stream, index, n, float(shape),
+                                   _p(out)), 'Gamma')
+    return out

@@ -1217,6 +1217,42 @@ int bbx_host_pg_right_mass(int64_t n, const double* z, double* log_form,
 int bbx_host_pg_series_accept(int64_t n, const double* x, const double* u,
                               int32_t* sequential, int32_t* direct);
 
+/* ---------------------- sequential replay of the device draws (libbbx_hostrng)
+ * Every draw of the device chain is a function of (seed, stream, element,
+ * inputs): these walk the same Philox sub-streams on the host, one element
+ * after the other, with none of the kernels' structure (csrc/replay_impl.hpp).
+ * `stream` is the kernel's stream word, e.g. STREAM_PG | iteration << 8.
+ * `variant` 0: the reference's arithmetic (pow, the log forms of the
+ * Polya-Gamma pieces); 1: the kernels' forms (roots and integer powers,
+ * right_mass_direct, series_accept_direct) in the host's libm. */
+/* One Philox4x32-10 block, and the counter / key words of a generator. */
+int bbx_replay_philox_block(const uint32_t* counter, const uint32_t* key,
+                            uint32_t* out);
+int bbx_replay_philox_counter(uint64_t seed, uint64_t stream, uint64_t index,
+                              uint32_t trial, uint32_t* counter, uint32_t* key);
+/* The first n uniforms of Philox(seed, stream, index, trial). */
+int bbx_replay_uniform(uint64_t seed, uint64_t stream, uint64_t index,
+                       uint32_t trial, int64_t n, double* out);
+/* out[i] = the first normal of Philox(seed, stream, i) (bbx_device_normal). */
+int bbx_replay_normal(uint64_t seed, uint64_t stream, int64_t n, double* out);
+/* polya_gamma_block (csrc/pg_queue.hpp) restated; `shape`: int32 or, with
+ * shape_is_double, double entries.  Optional traces: attempts[i] = the
+ * inverse-Gaussian proposals element i took (0: none needed), restarts[i] = 1
+ * when its series test rejected and the draw started over. */
+int bbx_replay_polya_gamma(uint64_t seed, uint64_t stream, int64_t n,
+                           int shape_is_double, const void* shape,
+                           const double* tilt, int variant, double* out,
+                           int32_t* attempts, int32_t* restarts);
+/* tilted_stable_block (csrc/chain.hip) restated: candidates 0, 1, 2, ... in
+ * order, the first accepted one is the draw; winner[i] (optional) = its
+ * number.  Tilts must be finite and >= 0. */
+int bbx_replay_tilted_stable(uint64_t seed, uint64_t stream, int64_t n,
+                             double char_exp, const double* tilt, int variant,
+                             double* out, int32_t* winner);
+/* out[k] = gamma_draw on Philox(seed, stream, index + k). */
+int bbx_replay_gamma(uint64_t seed, uint64_t stream, uint64_t index, int64_t n,
+                     double shape, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,8 +11,15 @@ deterministic piece of an iteration comparable on identical inputs:
   chain_gscale_kernel    logp (+ 'optimize' / fixed tau)   bayesbridge.py:412-456,480-511
   fill_normal_kernel     eta1, eta2            cg_sampler.py:61-62 (distribution)
 
-The random draws themselves (Polya-Gamma, tilted stable, Gamma) are
-distribution-tested in test_hip_chain.py.
+The random draws themselves -- Omega (Polya-Gamma), the sampled global scale
+and the linear model's observation precision (Gamma), the local scales (tilted
+stable) -- are functions of (seed, stream | iteration << 8, element, inputs):
+each is compared with the sequential host replay of its Philox sub-streams
+(bayesbridge_amd.replay; `_check_draws_against_replay` below) from the
+device's new coefficient vector, with psi = X~ beta, sum |beta|^alpha and the
+residual sum of squares recomputed by the oracle.  The stand-alone kernels are
+pinned the same way in test_hip_sampler_replay.py; their distributions are
+tested in test_hip_chain.py.  Tolerances: tests/replay_cases.py.
 """
 import math
 import warnings
@@ -26,9 +33,61 @@ import oracle
 from oracle.gibbs import OracleGibbs, unit_bridge_magnitude
 from oracle.summarizer import CoefSummarizer, regularized_prior_scale
 
+import replay_cases as C
+from bayesbridge_amd import replay as R
+
 pytestmark = pytest.mark.gpu
 
 ALPHA, SLAB = .5, 2.
+
+
+def _check_draws_against_replay(what, seed, it, family, design_o, outcome,
+                                nu, shape0, rate0, coef, obs_prec, lscale,
+                                gscale, f32=False):
+    """The four random updates of iteration `it` (0-based, the value of
+    chain.iteration BEFORE the run) that led to (obs_prec, lscale, gscale),
+    replayed on the host from the new coefficient vector `coef`
+    (csrc/chain.hip chain_post_draw)."""
+    beta = coef[nu:]
+    psi = design_o.dot(coef)
+    # ---- tau | beta  (chain_gscale_kernel, gscale_update = 'sample')
+    pow_sum = np.sum(np.abs(beta) ** ALPHA)
+    gam = R.gamma(seed, R.iter_stream(R.STREAM_GSCALE, it),
+                  shape0 + beta.size / ALPHA)[0]
+    tau = 1. / (gam / (rate0 + pow_sum)) ** (1. / ALPHA)
+    tau = max(tau, .001 / unit_bridge_magnitude(ALPHA))
+    print("%s it %d: tau device %.17g replay %.17g (relative %.3g)"
+          % (what, it, gscale, tau, abs(gscale / tau - 1)))
+    assert abs(gscale - tau) <= C.CHAIN_SCALAR_TOL * tau
+    # ---- lambda | tau, beta  (chain_lscale_kernel), from the DEVICE's tau
+    ratio = beta / gscale
+    ts, win = R.tilted_stable(seed, R.iter_stream(R.STREAM_LSCALE, it),
+                              ALPHA / 2, ratio * ratio, 0, trace=True)
+    with np.errstate(divide='ignore'):
+        ls = np.sqrt(.5 / ts)
+    ls[ls == 0.] = 10e-16
+    ls[np.isinf(ls)] = 2. / gscale
+    C.compare("%s it %d local scales" % (what, it), lscale, ls,
+              C.tolerance(C.TS_VARIANT_SPREAD[ALPHA / 2]),
+              lambda j: "beta %.17g winner %d" % (beta[j], win[j]))
+    # ---- Omega | beta
+    if family == 'logit':
+        n_trial = np.asarray(outcome[1], dtype=np.float64)
+        om, att, rst = R.polya_gamma(seed, R.iter_stream(R.STREAM_PG, it),
+                                     n_trial, psi, 0, trace=True)
+        C.compare("%s it %d Omega" % (what, it), obs_prec, om,
+                  C.CHAIN_OMEGA_TOL,
+                  lambda i: "n_trial %g psi %.17g attempts %d restart %d"
+                  % (n_trial[i], psi[i], att[i], rst[i]))
+    else:
+        rss = np.sum((outcome - psi) ** 2)
+        gam = R.gamma(seed, R.iter_stream(R.STREAM_OBSVAR, it),
+                      len(psi) / 2.)[0]
+        want = 1. / ((rss / 2.) / gam)
+        print("%s it %d: obs_prec device %.17g replay %.17g (relative %.3g)"
+              % (what, it, obs_prec, want, abs(obs_prec / want - 1)))
+        assert abs(obs_prec - want) <= \
+            (C.CHAIN_F32_TOL if f32 else C.CHAIN_SCALAR_TOL) * want
 
 
 def _problem(family, kind, n=3000, p=200, seed=3, binary=False):
@@ -196,7 +255,106 @@ def test_device_chain_iteration_equals_oracle(family, kind, storage):
             assert np.all(obs_a > 0) and obs_a.shape == (n,)
         else:
             assert obs_a > 0
+        # ---- the random draws of this iteration, replayed
+        _check_draws_against_replay(
+            "%s/%s/%s" % (family, kind, storage), 17, it, family, ora.design,
+            outcome, nu, ora.shape0, ora.rate0, coef_a, obs_a, ls_a, g_a,
+            f32=storage == 'float32')
     chain.close()
+
+
+def _replay_chain(hip, X, outcome, n_iter, what, seed=23):
+    """`n_iter` iterations of a logit chain, each one's draws replayed."""
+    from bayesbridge_amd.device_chain import HipGibbsChain
+    n, P = hip.shape
+    ora = oracle.OracleSparseDesign(X, center_predictor=True,
+                                    add_intercept=True)
+    chain = HipGibbsChain(hip, 'logit', outcome[0], n_trial=outcome[1],
+                          sd_unshrunk=[2.], bridge_exponent=ALPHA,
+                          slab_size=SLAB, gscale_shape=1.5, gscale_rate=.3,
+                          seed=seed)
+    rng = np.random.default_rng(6)
+    chain.set_state(np.zeros(P), None, np.exp(rng.normal(0., 1., P - 1)), .07)
+    chain.init_obs_prec()
+    for it in range(n_iter):
+        assert chain.iteration == it
+        _, n_unconv = chain.run(1)
+        assert n_unconv == 0
+        coef_a, obs_a, ls_a, g_a = chain.get_state()
+        _check_draws_against_replay(what, seed, it, 'logit', ora, outcome, 1,
+                                    1.5, .3, coef_a, obs_a, ls_a, g_a)
+    chain.close()
+
+
+def test_binomial_rows_of_a_chain_equal_the_replay():
+    """n_trial > 1 on every third row: those rows take the sequential
+    Polya-Gamma sampler inside the chain's kernel (csrc/pg_queue.hpp), with the
+    shapes held as doubles."""
+    from bayesbridge_amd import simulate
+    X, _ = _problem('logit', 'sparse')
+    beta = np.zeros(X.shape[1])
+    beta[:5], beta[5:10] = 1.5, -1.
+    n_trial = np.ones(X.shape[0])
+    n_trial[::3] = np.random.default_rng(1).integers(2, 6, len(n_trial[::3]))
+    outcome = simulate.simulate_outcome(X, beta, 'logit', n_trial=n_trial,
+                                        seed=4)
+    assert outcome[1].max() == 5
+    _replay_chain(_designs(X, 'sparse', 'csr'), X, outcome, 2, 'binomial')
+
+
+def test_forked_chain_with_four_elements_per_lane_equals_the_replay():
+    """n = 50 048, 2 100 shrunk coefficients: the smallest shape at which the
+    chain draws Omega with four elements per lane (n >= 50 000; a last block
+    whose upper slots are past n) AND runs the tau / lambda branch on a second
+    stream beside it (n >= 50 000 and P - n_unshrunk >= 2 048: chain.hip
+    chain_post_draw)."""
+    from bayesbridge_amd import simulate
+    n, p = 50048, 2100
+    X = simulate.simulate_binary_csr_fast(n, p, .01, seed=5)
+    beta = np.zeros(p)
+    beta[:5], beta[5:10] = 1.5, -1.
+    outcome = simulate.simulate_outcome(X, beta, 'logit', seed=6)
+    hip = _designs(X, 'sparse', 'tiled')
+    assert hip.shape == (n, p + 1)
+    assert n >= 50000 and hip.shape[1] - 1 >= 2048        # `fork`
+    assert n % 1024 != 0 and n < 800000                   # E = 4, ragged
+    _replay_chain(hip, X, outcome, 2, 'forked 50048 x 2100')
+
+
+def test_member_of_a_batch_equals_the_replay(golden_dir):
+    """The second chain of a K = 2 batch (test_hip_batch_pin.py's set-up): its
+    draws come from its own key and iteration, whatever its companion does."""
+    from bayesbridge_amd import HipChainBatch, HipGibbsChain, \
+        HipSparseDesignMatrix
+    from helpers import config2_small_problem
+    _, X, outcome = config2_small_problem(golden_dir)     # 20 000 x 1 000
+    hip = HipSparseDesignMatrix(X, center_predictor=True, add_intercept=True,
+                                storage='tiled')
+    n, P = hip.shape
+    ora = oracle.OracleSparseDesign(X, center_predictor=True,
+                                    add_intercept=True)
+    chains = []
+    for c in range(2):
+        ch = HipGibbsChain(hip, 'logit', outcome[0], n_trial=outcome[1],
+                           sd_unshrunk=[2.], bridge_exponent=ALPHA,
+                           slab_size=SLAB, gscale_shape=1.5, gscale_rate=.3,
+                           seed=300 + 7 * c)
+        rng = np.random.default_rng(40 + c)
+        ch.set_state(np.zeros(P), None, np.exp(rng.normal(0., 1., P - 1)),
+                     (.02, .3)[c])
+        ch.init_obs_prec()
+        chains.append(ch)
+    batch = HipChainBatch(chains, allow_slow=True)
+    for it in range(2):
+        _, n_unconv = batch.run(1)
+        assert n_unconv == 0
+        coef_a, obs_a, ls_a, g_a = chains[1].get_state()
+        _check_draws_against_replay('batch member 1', 307, it, 'logit', ora,
+                                    outcome, 1, 1.5, .3, coef_a, obs_a, ls_a,
+                                    g_a)
+    batch.close()
+    for ch in chains:
+        ch.close()
 
 
 def test_gscale_update_modes_follow_the_reference():
