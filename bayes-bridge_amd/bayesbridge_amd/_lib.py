@@ -213,6 +213,9 @@ def _declare(lib):
         "bbx_coxw_create": (
             [hp, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(hp)],
             c_int),
+        "bbx_coxfg_create": (
+            [hp, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+             c_void_p, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_logit_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_poisson_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_cpoisson_create": (
@@ -240,7 +243,8 @@ def _declare(lib):
             POINTER(c_int), c_void_p, c_void_p, c_void_p],
         "nuts_sample": [hp, c_void_p, POINTER(c_double), c_void_p],
     }
-    for family in ("cox", "coxcp", "coxef", "coxw", "logit", "poisson", "cpoisson"):
+    for family in ("cox", "coxcp", "coxef", "coxw", "coxfg", "logit",
+                   "poisson", "cpoisson"):
         for entry, argtypes in shared.items():
             sigs["bbx_%s_%s" % (family, entry)] = (list(argtypes), c_int)
     for name, (argtypes, restype) in sigs.items():

@@ -601,6 +601,111 @@ def cox_interval_risk_sets(entry_time, event_time, censoring_time):
     return n_event, evrow, a, b, p, q, entry_perm
 
 
+def _finegray_times(event_time, censoring_time, competing_time):
+    """(event, censoring, competing times as float64, the observed time T,
+    the status: 0 event, 1 competing event, 2 censored)."""
+    event_time = np.asarray(event_time, dtype=np.float64)
+    censoring_time = np.asarray(censoring_time, dtype=np.float64)
+    competing_time = np.asarray(competing_time, dtype=np.float64)
+    if not (event_time.shape == censoring_time.shape == competing_time.shape) \
+            or event_time.ndim != 1:
+        raise ValueError("event_time, censoring_time and competing_time must "
+                         "be 1-d arrays of the same length.")
+    times = np.stack((event_time, competing_time, censoring_time))
+    if np.any(np.isnan(times)):
+        raise ValueError("A time must not be NaN.")
+    if not np.all(np.sum(times < float('inf'), axis=0) == 1) \
+            or np.any(times == -float('inf')):
+        raise ValueError("Exactly one of event, censoring and competing time "
+                         "must be finite for each observation (the others "
+                         "infinity).")
+    return (event_time, censoring_time, competing_time, np.min(times, axis=0),
+            np.argmin(times, axis=0))
+
+
+def cox_finegray_censoring_survivor(event_time, censoring_time,
+                                    competing_time):
+    """G(T_i-) of every row: the Kaplan-Meier estimate of the censoring
+    survivor function from the left, G(s-) = prod_{c < s} (1 - m_c / Y(c))
+    over the distinct censoring times c, m_c rows censored at c and
+    Y(c) = #{i : T_i >= c} rows of every status.  G(T_i-) > 0: row i is in
+    Y(c) for every c <= T_i."""
+    _, censoring_time, _, T, status = _finegray_times(
+        event_time, censoring_time, competing_time)
+    c, m = np.unique(T[status == 2], return_counts=True)
+    Y = len(T) - np.searchsorted(np.sort(T), c, side='left')
+    G = np.concatenate(([1.], np.cumprod(1. - m / Y)))
+    return G[np.searchsorted(c, T, side='left')]
+
+
+def cox_preprocess_finegray(event_time, censoring_time, competing_time,
+                            X=None):
+    """cox_preprocess for the Fine-Gray competing-risks model: every row has
+    exactly one finite time out of event, censoring and competing time.  G is
+    computed on all the rows as given (cox_finegray_censoring_survivor); the
+    rows are then sorted by their time ascending, at an equal time events,
+    then competing, then censored rows (a stable sort), and the rows censored
+    before the first event are dropped (a competing row stays in every later
+    risk set and is never dropped).  Returns (event_time, censoring_time,
+    competing_time, X, keep, event_g, comp_rinv): keep[i] is the original
+    index of row i, event_g[k] = G(t_k-) of the events in time order and
+    comp_rinv[j] = 1 / G(T-) of the competing rows in row order."""
+    event_time, censoring_time, competing_time, T, status = _finegray_times(
+        event_time, censoring_time, competing_time)
+    G = cox_finegray_censoring_survivor(event_time, censoring_time,
+                                        competing_time)
+    n = len(T)
+    keep = np.lexsort((status, T))
+    if not np.array_equal(keep, np.arange(n)):
+        warn("The observations and design matrix will be sorted so that the "
+             "event, competing and censoring times are in the ascending "
+             "order, events before competing events before the observations "
+             "censored at the same time.")
+    first = np.min(event_time) if n else float('inf')
+    informative = ~((status[keep] == 2) & (T[keep] < first))
+    if not np.all(informative):
+        warn("Some observations do not contribute to the likelihood, so they "
+             "are being removed.")
+        keep = keep[informative]
+    event_time, censoring_time = event_time[keep], censoring_time[keep]
+    competing_time = competing_time[keep]
+    if X is not None and not np.array_equal(keep, np.arange(X.shape[0])):
+        X = X.tocsr()[keep, :] if sparse.issparse(X) else X[keep, :]
+    G, status = G[keep], status[keep]
+    return (event_time, censoring_time, competing_time, X, keep,
+            G[status == 0], 1. / G[status == 1])
+
+
+def cox_finegray_risk_sets(event_time, censoring_time, competing_time):
+    """The index arrays of the Fine-Gray handle, of rows already in
+    cox_preprocess_finegray's order, in O(n log n).  Returns (n_event, evrow,
+    a, b, p, comp_row): evrow[k] is the row of event k in time order; a[k] the
+    first row whose time is >= t_k; comp_row the competing rows, ascending;
+    b[k] the number of competing rows before row a[k], so that risk set k is
+    the rows from a[k] on with weight 1 and the rows comp_row[:b[k]] with
+    weight G(t_k-) / G(T-); p[i] = #{k : t_k <= T_i}."""
+    event_time, censoring_time, competing_time, T, status = _finegray_times(
+        event_time, censoring_time, competing_time)
+    same = T[:-1] == T[1:]
+    if np.any(T[:-1] > T[1:]) or np.any(same & (status[:-1] > status[1:])):
+        raise ValueError(
+            "The observations need to be sorted so that the event, competing "
+            "and censoring times are in the increasing order, events before "
+            "competing events before the observations censored at the same "
+            "time.")
+    evrow = np.flatnonzero(status == 0)
+    comp_row = np.flatnonzero(status == 1)
+    events = event_time[evrow]
+    p = np.searchsorted(events, T, side='right')
+    if np.any((p == 0) & (status == 2)):
+        raise ValueError(
+            "Some individuals never appear in the risk set. They have to be "
+            "removed before using the CoxModel class.")
+    a = np.searchsorted(T, events, side='left')
+    b = np.searchsorted(comp_row, a, side='left')
+    return len(evrow), evrow, a, b, p, comp_row
+
+
 def _stratum_codes(strata, n):
     """(labels in np.unique order, the stratum number of every row)."""
     strata = np.asarray(strata)
@@ -817,6 +922,28 @@ def _check_weights(weights, n, strata=None, entry_time=None, ties='breslow'):
     return weights
 
 
+def _check_competing(competing_time, strata=None, entry_time=None,
+                     ties='breslow', weights=None):
+    if competing_time is None:
+        return
+    if strata is not None:
+        raise ValueError(
+            "competing_time together with strata is not supported: the "
+            "stratified Fine-Gray model is not built.")
+    if entry_time is not None:
+        raise ValueError(
+            "competing_time together with entry_time is not supported: the "
+            "Fine-Gray model with delayed entry is not built.")
+    if ties == 'efron':
+        raise ValueError(
+            "competing_time together with ties='efron' is not supported: "
+            "Efron's approximation in the Fine-Gray model is not built.")
+    if weights is not None:
+        raise ValueError(
+            "competing_time together with weights is not supported: case "
+            "weights in the Fine-Gray model are not built.")
+
+
 class CoxModel(_DeviceHamiltonian, _Model):
     """cox_model.py:7-303 on a HIP design whose rows are already in the
     model's order (RegressionModel(..., family='cox') sorts them).  The
@@ -838,17 +965,31 @@ class CoxModel(_DeviceHamiltonian, _Model):
     row order; without strata, entry_time and ties='efron') the likelihood is
     the weighted partial likelihood, through one bbx_coxw handle
     (csrc/cox_weighted.hip): with integer weights it is the plain likelihood
-    of the rows written that many times."""
+    of the rows written that many times.  With `competing_time` (one per row,
+    inf where the row had no competing event; exactly one of the three times
+    of a row is finite; the rows in cox_preprocess_finegray's order; without
+    strata, entry_time, ties='efron' and weights) the likelihood is the
+    Fine-Gray subdistribution-hazard likelihood, through one bbx_coxfg handle
+    (csrc/cox_finegray.hip): a row with a competing event stays in the later
+    risk sets with weight G(t-) / G(T_i-), G the left-continuous Kaplan-Meier
+    estimate of the censoring survivor function on the rows given."""
 
     _handle_attr = '_cox'
 
     def __init__(self, event_time, censoring_time, design, strata=None,
-                 entry_time=None, ties='breslow', weights=None):
+                 entry_time=None, ties='breslow', weights=None,
+                 competing_time=None):
+        _check_competing(competing_time, strata, entry_time, ties, weights)
         _check_ties(ties, strata, entry_time)
         weights = _check_weights(weights, len(event_time), strata, entry_time,
                                  ties)
         self.ties = ties
         self.weights = weights
+        self.competing_time = None
+        if competing_time is not None:
+            self._init_finegray(event_time, censoring_time, competing_time,
+                                design)
+            return
         if entry_time is not None:
             if strata is not None:
                 raise ValueError(
@@ -942,6 +1083,59 @@ class CoxModel(_DeviceHamiltonian, _Model):
             design.handle, n_event, *[_ptr(v) for v in i32],
             byref(self._cox)))
 
+    @classmethod
+    def _finegray(cls, event_time, censoring_time, competing_time, design,
+                  event_g, comp_rinv):
+        """The Fine-Gray model with G from the caller: RegressionModel's,
+        which computes it before it drops rows."""
+        self = cls.__new__(cls)
+        self.ties, self.weights = 'breslow', None
+        self._init_finegray(event_time, censoring_time, competing_time, design,
+                            event_g, comp_rinv)
+        return self
+
+    def _init_finegray(self, event_time, censoring_time, competing_time,
+                       design, event_g=None, comp_rinv=None):
+        n_event, evrow, a, b, p, comp_row = cox_finegray_risk_sets(
+            event_time, censoring_time, competing_time)
+        if len(event_time) != design.shape[0]:
+            raise ValueError(
+                "Incompatible sizes of the outcome and design matrix.")
+        if n_event == 0:
+            raise ValueError("The Cox model needs at least one event.")
+        if event_g is None:
+            # no row of these is dropped: they are all the data
+            G = cox_finegray_censoring_survivor(event_time, censoring_time,
+                                                competing_time)
+            event_g, comp_rinv = G[evrow], 1. / G[comp_row]
+        self.strata = None
+        self.entry_time = None
+        self.n_event = n_event
+        self.event_time = np.asarray(event_time, dtype=np.float64)
+        self.censoring_time = np.asarray(censoring_time, dtype=np.float64)
+        self.competing_time = np.asarray(competing_time, dtype=np.float64)
+        self.event_row = evrow
+        self.risk_set_start_index = a
+        self.n_competing_before = b
+        self.n_event_by_exit = p
+        self.competing_row = comp_row
+        self.event_censoring_survivor = np.ascontiguousarray(
+            event_g, dtype=np.float64)
+        self.competing_inverse_survivor = np.ascontiguousarray(
+            comp_rinv, dtype=np.float64)
+        self.design = design
+        self.name = 'cox'
+        self._ham_prefix = 'bbx_coxfg_'
+        self._cox = c_void_p()
+        self._location_serial = 0
+        i32 = [np.ascontiguousarray(v, dtype=np.int32)
+               for v in (evrow, a, b, p, comp_row)]
+        _lib.check(self._ham_fn('create')(
+            design.handle, n_event, *[_ptr(v) for v in i32[:4]],
+            len(comp_row), _ptr(i32[4]),
+            _ptr(self.event_censoring_survivor),
+            _ptr(self.competing_inverse_survivor), byref(self._cox)))
+
     @property
     def handle(self):
         return self._cox
@@ -983,7 +1177,7 @@ class CoxModel(_DeviceHamiltonian, _Model):
 def RegressionModel(outcome, X, family='linear', add_intercept=None,
                     center_predictor=True, device=0, storage='auto',
                     dense_storage_dtype='float64', entry_time=None,
-                    ties='breslow', weights=None):
+                    ties='breslow', weights=None, competing_time=None):
     """model/factory.py:10-68 with the design placed on an MI355X.  `X` may be
     a SciPy sparse matrix, a NumPy array, or an already built HipDesignMatrix.
     For family='cox', outcome = (event_time, censoring_time) or, for the
@@ -998,7 +1192,12 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     is the same.  With `weights` (family='cox' without strata, entry_time and
     ties='efron'; one strictly positive case weight per row of X as given) the
     likelihood is the weighted partial likelihood; the weights are sorted and
-    pruned with their rows.  For family='poisson', outcome = y or
+    pruned with their rows.  With `competing_time` (family='cox' without
+    strata, entry_time, ties='efron' and weights; inf where a row had no
+    competing event, and exactly one of the three times of a row finite) the
+    model is the Fine-Gray competing-risks model: the censoring survivor
+    function is estimated on the rows as given, then the rows are sorted and
+    pruned by cox_preprocess_finegray.  For family='poisson', outcome = y or
     (y, exposure) or, for the conditional Poisson model,
     (y, exposure, strata) (exposure may be None):
     the rows are sorted stratum-major and uninformative strata dropped
@@ -1010,6 +1209,8 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         raise ValueError("ties is an argument of family='cox' only.")
     if weights is not None and family != 'cox':
         raise ValueError("weights is an argument of family='cox' only.")
+    if competing_time is not None and family != 'cox':
+        raise ValueError("competing_time is an argument of family='cox' only.")
     stratified_poisson = (family == 'poisson' and isinstance(outcome, tuple)
                           and len(outcome) == 3)
     if add_intercept is None:
@@ -1047,6 +1248,7 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
             event_time, censoring_time, strata = outcome
         else:
             event_time, censoring_time = outcome
+        _check_competing(competing_time, strata, entry_time, ties, weights)
         if entry_time is not None and strata is not None:
             raise ValueError(
                 "entry_time together with strata is not supported: the "
@@ -1054,7 +1256,29 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         _check_ties(ties, strata, entry_time)
         weights = _check_weights(weights, len(np.asarray(event_time)), strata,
                                  entry_time, ties)
-        if entry_time is not None:
+        if competing_time is not None:
+            with catch_warnings():
+                if isinstance(X, HipDesignMatrix):
+                    simplefilter('ignore')
+                event_time, censoring_time, competing_time, sorted_X, keep, \
+                    event_g, comp_rinv = cox_preprocess_finegray(
+                        event_time, censoring_time, competing_time,
+                        None if isinstance(X, HipDesignMatrix) else X)
+            if isinstance(X, HipDesignMatrix):
+                if not np.array_equal(keep, np.arange(X.shape[0])):
+                    raise ValueError(
+                        "A prebuilt HipDesignMatrix must have its rows in the "
+                        "Fine-Gray model's order (by increasing event, "
+                        "competing or censoring time, at the same time "
+                        "events before competing events before censored "
+                        "rows, none censored before the first event); pass "
+                        "X as a NumPy or SciPy matrix to have it sorted.")
+                if X.intercept_added:
+                    raise ValueError("The Cox model takes a design without "
+                                     "an intercept column.")
+            else:
+                X = sorted_X
+        elif entry_time is not None:
             if isinstance(X, HipDesignMatrix):
                 with catch_warnings():
                     simplefilter('ignore')
@@ -1126,6 +1350,10 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
             n_success, n_trial = outcome, None
         return LogisticModel(n_success, n_trial, design)
     if family == 'cox':
+        if competing_time is not None:
+            return CoxModel._finegray(event_time, censoring_time,
+                                      competing_time, design, event_g,
+                                      comp_rinv)
         return CoxModel(event_time, censoring_time, design, strata,
                         entry_time, ties, weights)
     if family == 'poisson':

@@ -82,6 +82,7 @@ struct CoxPlain {
   static double* hu(bbx_cox* c) { return c->tmp.as<double>(); }
   __device__ int64_t row(int, int64_t i) const { return i; }
   __device__ double h_of(int64_t, double e) const { return e; }
+  __device__ double risk_term(int, int64_t, double x) const { return x; }
   __device__ double H(const double* scan, int64_t k, double&) const {
     const int32_t e = end[k];
     double H = scan[start[k]];

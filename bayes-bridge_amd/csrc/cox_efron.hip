@@ -66,6 +66,7 @@ struct CoxEfron {
   using Handle = bbx_coxef;
   static constexpr const char* name = "coxef";
   static constexpr int halves = 2;       // inv and (l/d) inv; c and cb
+  static constexpr int half_rev = 0;     // cb forward, as c
   static constexpr bool keeps_inv = false;
   const int2* grp;                       // (s - 1, s + d - 1) of every event
   const int32_t* end;
@@ -85,6 +86,7 @@ struct CoxEfron {
   static double* hu(bbx_coxef* c) { return c->tmp.as<double>(); }
   __device__ int64_t row(int, int64_t i) const { return i; }
   __device__ double h_of(int64_t, double e) const { return e; }
+  __device__ double risk_term(int, int64_t, double x) const { return x; }
   // phi_k = R_g + a_k T_g from one gather; lf = l/d
   __device__ double H(const double* scan, int64_t k, double& lf) const {
     const int2 g = grp[k];

@@ -1,12 +1,14 @@
 // What the Cox likelihood handles share (cox.hip, cox_interval.hip,
-// cox_efron.hip, cox_weighted.hip): the handle base, the three kernels that
-// form values, the six-launch driver and the family that hamiltonian.hpp's
-// entry points take.  A handle states a policy V, a small struct of device
-// pointers that is passed to the kernels by value:
+// cox_efron.hip, cox_weighted.hip, cox_finegray.hip): the handle base, the
+// three kernels that form values, the six-launch driver and the family that
+// hamiltonian.hpp's entry points take.  A handle states a policy V, a small
+// struct of device pointers that is passed to the kernels by value:
 //
 //   device side (the per-element expressions; everything else is written once)
 //     row(s, i)         the row behind element i of risk segment s
 //     h_of(r, e)        the relative hazard of row r from e = exp(eta_r - m)
+//     risk_term(s, i, x)   what element i of risk segment s adds to its scan:
+//                       x (h, or h u), or x times a factor of the element
 //     H(scan, k, f)     the risk-set sum of event k from the risk scan; f: a
 //                       factor of event k the policy wants back (weight, l/d)
 //     empty(H)          the test that raises CoxTraj::zero and skip
@@ -18,6 +20,9 @@
 //     indicator(i)      the event indicator (or event weight) of row i
 //     halves            1, or 2: f times the value goes to element ne + k and
 //                       its chunk sums to csum[SCAN_G + b]
+//     half_rev          halves == 2: 0, the second half's cumulative sum runs
+//                       forward as the first one's, or 2, it is a suffix sum
+//                       (cox_scan.hpp: over the same chunks)
 //     keeps_inv         1/H is stored beside the (scaled) value
 //   host side
 //     Handle, name      the C ABI's struct and "cox", "coxcp", ...
@@ -75,7 +80,8 @@ __global__ __launch_bounds__(SCAN_BLOCK) void cox_risk_sum_kernel(
   for (int64_t t = t0 + threadIdx.x; t < t1; t += SCAN_BLOCK) {
     const int64_t i = seg_elem(sg, s, t);
     const int64_t r = v.row(s, i);
-    const double x = HU ? h[r] * u[r] : v.h_of(r, exp(eta[r] - m));
+    const double x =
+        v.risk_term(s, i, HU ? h[r] * u[r] : v.h_of(r, exp(eta[r] - m)));
     val[i] = x;
     acc += x;
   }
@@ -256,10 +262,15 @@ Segs risk_segs(const typename V::Handle* c, int* nseg) {
   return cox_segs(len[0], rev[0], len[1], rev[1]);
 }
 
-// The cumulative sums over the events, forward: one per half
+// The cumulative sums over the events, one per half: the first forward, the
+// second as the policy says
 template <class V>
 Segs event_segs(const typename V::Handle* c) {
-  return cox_segs(c->ne, 0, V::halves == 2 ? c->ne : 0, 0);
+  if constexpr (V::halves == 2) {
+    return cox_segs(c->ne, 0, c->ne, V::half_rev);
+  } else {
+    return cox_segs(c->ne, 0, 0, 0);
+  }
 }
 
 int launch_scan_out(CoxCore* c, const Segs& sg, int nseg, const double* val,

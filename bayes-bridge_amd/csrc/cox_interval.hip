@@ -94,6 +94,7 @@ struct CoxEntry {
     return s == 0 ? i : (int64_t)perm[i - n];
   }
   __device__ double h_of(int64_t, double e) const { return e; }
+  __device__ double risk_term(int, int64_t, double x) const { return x; }
   __device__ double H(const double* scan, int64_t k, double&) const {
     const int32_t bk = b[k];
     double H = scan[a[k]];

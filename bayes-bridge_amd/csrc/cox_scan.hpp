@@ -23,7 +23,11 @@ constexpr int SCAN_TILE = SCAN_BLOCK * SCAN_E;
 
 
 // Up to two segments of one scan: elements base .. base+len-1, read forward
-// or reversed (a suffix sum is a prefix sum of the reversed segment).
+// (rev 0) or reversed (rev 1: a suffix sum is a prefix sum of the reversed
+// segment; the chunks are cut from the far end).  rev 2 (pass B only) is a
+// suffix sum over the FORWARD partition: chunk b of the scan is forward chunk
+// SCAN_G - 1 - b read from its far end, so that a pass A which walked the
+// segment forward for another scan has already left this one's chunk sums.
 struct Segs {
   int64_t base[2];
   int64_t len[2];
@@ -91,16 +95,23 @@ static __global__ __launch_bounds__(SCAN_BLOCK) void cox_scan_out_kernel(
     const double* __restrict__ csum, const int* __restrict__ skip) {
   if (skip && *skip) return;
   const int s = blockIdx.x / SCAN_G, b = blockIdx.x % SCAN_G;
+  const bool mirror = sg.rev[s] == 2;
+  const int fb = mirror ? SCAN_G - 1 - b : b;   // the chunk of the partition
   const int64_t len = sg.len[s];
   const int64_t L = (len + SCAN_G - 1) / SCAN_G;
-  const int64_t t0 = (int64_t)b * L, t1 = t0 + L < len ? t0 + L : len;
+  const int64_t t0 = (int64_t)fb * L, t1 = t0 + L < len ? t0 + L : len;
   if (t0 >= t1) return;
+  // position t of the chunk's walk -> element
+  auto elem = [&](int64_t t) {
+    return mirror ? sg.base[s] + (t0 + t1 - 1 - t) : seg_elem(sg, s, t);
+  };
   __shared__ double s_off;
   __shared__ double s_wave[SCAN_BLOCK / WAVE];
   const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
   if (threadIdx.x < WAVE) {
     double acc = 0.;
-    for (int c = lane; c < b; c += WAVE) acc += csum[s * SCAN_G + c];
+    for (int c = lane; c < b; c += WAVE)
+      acc += csum[s * SCAN_G + (mirror ? SCAN_G - 1 - c : c)];
     acc = wave_allsum(acc);
     if (lane == 0) s_off = acc;
   }
@@ -113,7 +124,7 @@ static __global__ __launch_bounds__(SCAN_BLOCK) void cox_scan_out_kernel(
 #pragma unroll
     for (int e = 0; e < SCAN_E; ++e) {
       const int64_t t = tb + e;
-      run += t < t1 ? val[seg_elem(sg, s, t)] : 0.;
+      run += t < t1 ? val[elem(t)] : 0.;
       x[e] = run;
     }
     // inclusive scan of the thread totals across the wave
@@ -141,7 +152,7 @@ static __global__ __launch_bounds__(SCAN_BLOCK) void cox_scan_out_kernel(
 #pragma unroll
     for (int e = 0; e < SCAN_E; ++e) {
       const int64_t t = tb + e;
-      if (t < t1) out[seg_elem(sg, s, t)] = base + x[e];
+      if (t < t1) out[elem(t)] = base + x[e];
     }
     carry += tot;
     __syncthreads();

@@ -87,6 +87,7 @@ struct CoxWeighted {
   static double* hu(bbx_coxw* c) { return c->tmp.as<double>(); }
   __device__ int64_t row(int, int64_t i) const { return i; }
   __device__ double h_of(int64_t r, double e) const { return a[r] * e; }
+  __device__ double risk_term(int, int64_t, double x) const { return x; }
   // a_k from the row vector: events are rows 0 .. ne - 1
   __device__ double H(const double* scan, int64_t k, double& ak) const {
     const int32_t e = end[k];

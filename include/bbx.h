@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-/* 113: + Efron's approximation for tied event times in the Cox model
+/* 113: + the Fine-Gray competing-risks model (bbx_coxfg_*: create, destroy and
+ *      the shared entry points of every likelihood handle).  New symbols and
+ *      nothing else, so the number stays 113.
+ *      + Efron's approximation for tied event times in the Cox model
  *      (bbx_coxef_*), on the plain handle's arrays, with the trajectory and
  *      the No-U-Turn sampler of the Cox handle.
  *      + case weights in the Cox model (bbx_coxw_*: create, destroy and the
@@ -1015,6 +1018,76 @@ int bbx_coxw_nuts_doubling(bbx_coxw* coxw, double dt, int direction,
                            int* tree, double* averages);
 int bbx_coxw_nuts_sample(bbx_coxw* coxw, double* q, double* logp,
                          double* grad);
+
+/* ------------------------------------------- Cox family, competing risks
+ * The Fine-Gray subdistribution-hazard likelihood (Breslow's rule for ties;
+ * csrc/cox_finegray.hip; the leapfrog and tree kernels are the Cox handle's,
+ * csrc/hamiltonian.hpp).  Every row has an observed time T and is an event of
+ * interest, a competing event or censored.  The rows are sorted by T
+ * ascending, at an equal T events, then competing, then censored rows.  Row i
+ * is in the risk set of an event at t with weight 1 iff T_i >= t, and with
+ * weight G(t-) / G(T_i-) iff it had a competing event at T_i < t, G(s-) being
+ * the caller's left-continuous Kaplan-Meier estimate of the censoring
+ * survivor function.  int32 arrays: evrow[n_event] the rows of the events in
+ * time order; a[n_event] the first row with T >= t_k; b[n_event] the number of
+ * competing rows before row a[k]; p[n] = #{k : t_k <= T_i} (0 only for a
+ * competing row); comp_row[n_comp] the competing rows, ascending.  double
+ * arrays: event_g[n_event] = G(t_k-), comp_rinv[n_comp] = 1 / G(T-) of
+ * competing row j.  comp_row and comp_rinv may be NULL where n_comp is 0.
+ * BBX_ERR_INVALID, with a bbx_last_error() that names the first offending
+ * element, for a NULL pointer, n_comp outside [0, n - n_event], an index out
+ * of range or out of order, a comp_row that is an event row, a b[k] that is
+ * not that count, an event_g outside (0, 1] or a comp_rinv that is not a
+ * finite number >= 1; nothing is launched then.  Without competing rows the
+ * likelihood is the plain one.  Every entry point but create has the argument
+ * list, the status codes and the synchronisation of its bbx_cox_* counterpart
+ * above, and a likelihood evaluation takes the same number of kernel
+ * launches.  The handle borrows the design (it must outlive the handle) and
+ * runs on its stream.  n < 2^31.  Every sum has a fixed order: the same
+ * inputs give the same bits on every call. */
+typedef struct bbx_coxfg bbx_coxfg;
+int bbx_coxfg_create(bbx_design* design, int64_t n_event, const int32_t* evrow,
+                     const int32_t* a, const int32_t* b, const int32_t* p,
+                     int64_t n_comp, const int32_t* comp_row,
+                     const double* event_g, const double* comp_rinv,
+                     bbx_coxfg** out);
+int bbx_coxfg_destroy(bbx_coxfg* coxfg);
+/* loglik = sum_k (eta_k - m) - log H_k, m = max eta, h = exp(eta - m),
+ * H_k = sum_{i >= a_k} h_i + g_k sum_{j < b_k} h_{comp_row[j]} r_j.
+ * grad[P] = X~^T w, w_i = [i is an event] - h_i A_i,
+ * A_i = c[p_i - 1] + [i = comp_row[j]] r_j sg[p_i], c = cumsum(1/H_k),
+ * sg[j] = sum_{k >= j} g_k (1/H_k).  H_k == 0 is an empty risk-set sum
+ * (*loglik = -inf, grad unspecified).  grad may be NULL. */
+int bbx_coxfg_loglik_grad(bbx_coxfg* coxfg, const double* beta, double* loglik,
+                          double* grad);
+int bbx_coxfg_loglik_grad_dev(bbx_coxfg* coxfg, const double* d_beta,
+                              double* loglik, double* d_grad);
+/* bbx_cox_set_location / _hessian_matvec on this likelihood. */
+int bbx_coxfg_set_location(bbx_coxfg* coxfg, const double* beta);
+int bbx_coxfg_hessian_matvec(bbx_coxfg* coxfg, const double* v, double* out);
+int bbx_coxfg_hessian_matvec_dev(bbx_coxfg* coxfg, const double* d_v,
+                                 double* d_out);
+/* bbx_cox_hmc_trajectory on this f. */
+int bbx_coxfg_hmc_trajectory(bbx_coxfg* coxfg, double dt, int n_step,
+                             const double* precond_scale,
+                             const double* prior_prec, const double* q0,
+                             const double* p0, double logp0,
+                             const double* grad0, double hamiltonian_tol,
+                             double* q, double* p, double* logp, double* grad,
+                             int* n_grad_evals, int* instability,
+                             double* hamiltonian);
+/* bbx_cox_nuts_begin / _doubling / _sample on this f. */
+int bbx_coxfg_nuts_begin(bbx_coxfg* coxfg, const double* precond_scale,
+                         const double* prior_prec, const double* q0,
+                         const double* p0, double logp0, const double* grad0,
+                         double joint_logp0, double joint_logp_threshold,
+                         double hamiltonian_tol);
+int bbx_coxfg_nuts_doubling(bbx_coxfg* coxfg, double dt, int direction,
+                            int height, const double* uniforms,
+                            int* n_uniform_used, int* n_steps, int* flags,
+                            int* tree, double* averages);
+int bbx_coxfg_nuts_sample(bbx_coxfg* coxfg, double* q, double* logp,
+                          double* grad);
 
 /* ----------------------------------------------------------- logit model
  * The binomial-logit likelihood of model/logistic_model.py:49-74 on a design

@@ -75,6 +75,19 @@ and cox_row_weight_kernel), and cox_max_kernel and cox_scan_out_kernel are the
 same code on the same sizes in both, so their per-call average is either
 handle's.
 Not together with --strata, --entry or --ties.
+
+--competing FRAC: the Fine-Gray competing-risks model (csrc/cox_finegray.hip):
+a fraction FRAC of the censored rows is recoded as competing events at their
+censoring times; the same outcome otherwise.  `competing_frac`, `n_competing`
+and `n_censored` (after preprocessing) are added to the JSON line.  Every
+figure above is then that of the bbx_coxfg handle, and `plain_leapfrog_us` is
+the same trajectory on the plain handle that censors at the competing event,
+on the same rows (in its own row order, so on a second design), from the same
+library, in the same process -- with --profile-steps too: in a kernel trace
+the two handles' own kernels differ in their policy argument (CoxFineGray
+against CoxPlain).  `launches` and `plain_launches` count the kernel launches
+of one loglik + gradient call of either handle.
+Not together with --strata, --entry, --ties or --weights.
 """
 import argparse
 import json
@@ -93,6 +106,7 @@ from bayesbridge_amd import (BayesBridge, HipDenseDesignMatrix,  # noqa: E402
                              HipSparseDesignMatrix, RegressionCoefPrior,
                              RegressionModel, _lib, simulate)
 from bayesbridge_amd.model import (CoxModel, cox_preprocess,  # noqa: E402
+                                   cox_preprocess_finegray,
                                    cox_preprocess_interval,
                                    cox_preprocess_stratified, cox_tie_groups)
 
@@ -190,6 +204,32 @@ def iptw_weights(X, seed):
     return np.where(z, z.mean() / e, (1. - z.mean()) / (1. - e))
 
 
+def competing_times(ct, frac, seed):
+    """(censoring, competing) times of --competing: a fraction of the censored
+    rows becomes competing events at the same times."""
+    recode = np.isfinite(ct) & (np.random.RandomState(seed + 4).rand(len(ct))
+                                < frac)
+    return np.where(recode, np.inf, ct), np.where(recode, ct, np.inf)
+
+
+def launches(model, beta):
+    """Kernel launches of one loglik + gradient call."""
+    from ctypes import c_uint64
+    lib = _lib.load()
+    lib.bbx_launch_count.restype = c_uint64
+    before = lib.bbx_launch_count()
+    model.compute_loglik_and_gradient(beta)
+    return int(lib.bbx_launch_count() - before)
+
+
+def make_design(kind, X):
+    if kind == 'binary':
+        return HipSparseDesignMatrix(X, add_intercept=False,
+                                     center_predictor=True)
+    return HipDenseDesignMatrix(X, add_intercept=False, center_predictor=True,
+                                storage_dtype='float32')
+
+
 def leapfrog_us(model, n_traj, scale, pp, q0, p0, logp0, grad0):
     model.hmc_trajectory(1e-3, 4, scale, pp, q0, p0, logp0, grad0, 1e300)
     tic = time.perf_counter()
@@ -200,7 +240,8 @@ def leapfrog_us(model, n_traj, scale, pp, q0, p0, logp0, grad0):
 
 
 def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
-        strata=None, entry=None, ties=None, n_grid=3650, weights=None):
+        strata=None, entry=None, ties=None, n_grid=3650, weights=None,
+        competing=None):
     X = make_X(kind, n, p, seed)
     beta = simulate.demo_beta(p)
     labels = None
@@ -213,10 +254,15 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
     entry_time = None
     if weights is not None:
         weights = iptw_weights(X, seed)
+    comp = plain_outcome = plain_design = None
+    if competing is not None:
+        ct, comp = competing_times(ct, competing, seed)
     tic = time.perf_counter()
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
-        if entry is not None:
+        if comp is not None:
+            et, ct, comp, X, _, _, _ = cox_preprocess_finegray(et, ct, comp, X)
+        elif entry is not None:
             entry_time, et, ct, X, _ = cox_preprocess_interval(
                 entry_times(et, ct, entry, seed), et, ct, X)
         elif labels is None:
@@ -225,19 +271,21 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
                 weights = weights[keep]
         else:
             et, ct, labels, X, _ = cox_preprocess_stratified(et, ct, labels, X)
-    if kind == 'binary':
-        design = HipSparseDesignMatrix(X, add_intercept=False,
-                                       center_predictor=True)
-    else:
-        design = HipDenseDesignMatrix(X, add_intercept=False,
-                                      center_predictor=True,
-                                      storage_dtype='float32')
-    del X
+    design = make_design(kind, X)
     t_design = time.perf_counter() - tic
+    if comp is not None:
+        # the plain handle censors at the competing event; its own row order
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            pet, pct, Xp, _ = cox_preprocess(et, np.minimum(ct, comp), X)
+        plain_outcome, plain_design = (pet, pct), make_design(kind, Xp)
+        del Xp
+    del X
     tic = time.perf_counter()
     outcome = (et, ct) if labels is None else (et, ct, labels)
     model = RegressionModel(outcome, design, 'cox', entry_time=entry_time,
-                            ties=ties or 'breslow', weights=weights)
+                            ties=ties or 'breslow', weights=weights,
+                            competing_time=comp)
     n_strata = {} if labels is None else {
         'n_strata': len(model.stratum_n_event)}
     if entry is not None:
@@ -252,6 +300,10 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
                     'weight_min': float('%.4g' % weights.min()),
                     'weight_max': float('%.4g' % weights.max()),
                     'weight_mean': float('%.4g' % weights.mean())}
+    if comp is not None:
+        n_strata = {'competing_frac': competing,
+                    'n_competing': int(np.isfinite(comp).sum()),
+                    'n_censored': int(np.isfinite(ct).sum())}
     preprocess_s = t_design + time.perf_counter() - tic
     P = design.shape[1]
     rs = np.random.RandomState(1)
@@ -291,6 +343,15 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
             n_strata['plain_leapfrog_us'] = round(leapfrog_us(
                 plain, n_traj, scale, pp, q0, p0, pll - np.sum(q0 ** 2) / 2,
                 scale * pg - q0), 1)
+            del plain
+        if comp is not None:
+            plain = RegressionModel(plain_outcome, plain_design, 'cox')
+            pll, pg = plain.compute_loglik_and_gradient(q0 * scale)
+            n_strata['plain_leapfrog_us'] = round(leapfrog_us(
+                plain, n_traj, scale, pp, q0, p0, pll - np.sum(q0 ** 2) / 2,
+                scale * pg - q0), 1)
+            n_strata['launches'] = launches(model, b)
+            n_strata['plain_launches'] = launches(plain, b)
             del plain
     prod_us = products_us(design, profile_steps or 50)
     if profile_steps:
@@ -347,6 +408,9 @@ def main():
                     help="times on a grid, tied events by this rule")
     ap.add_argument('--weights', choices=['iptw'], default=None,
                     help="the weighted model, stabilised IPT weights")
+    ap.add_argument('--competing', type=float, default=None, metavar='FRAC',
+                    help="the Fine-Gray model; the fraction of the censored "
+                         "rows recoded as competing events")
     ap.add_argument('--grid', type=int, default=3650, metavar='N',
                     help="grid points of --ties")
     a = ap.parse_args()
@@ -356,6 +420,13 @@ def main():
                                   or a.ties is not None):
         raise SystemExit("--weights does not combine with --strata, --entry "
                          "or --ties")
+    if a.competing is not None and (
+            a.strata is not None or a.entry is not None or a.ties is not None
+            or a.weights is not None):
+        raise SystemExit("--competing does not combine with --strata, "
+                         "--entry, --ties or --weights")
+    if a.competing is not None and not 0. <= a.competing <= 1.:
+        raise SystemExit("--competing takes a fraction in [0, 1]")
     if a.grid < 1:
         raise SystemExit("--grid takes a positive number")
     if a.strata not in (None, 'pairs') and int(a.strata) < 1:
@@ -371,7 +442,8 @@ def main():
                              profile_steps=a.profile_steps,
                              sampler=a.sampler, strata=a.strata,
                              entry=a.entry, ties=a.ties,
-                             n_grid=a.grid, weights=a.weights)),
+                             n_grid=a.grid, weights=a.weights,
+                             competing=a.competing)),
               flush=True)
 
 
