@@ -19,6 +19,7 @@ MODEL_LINEAR, MODEL_LOGIT = 0, 1
 GSCALE_SAMPLE, GSCALE_OPTIMIZE, GSCALE_FIXED = 0, 1, 2
 BATCH_ALLOW_SLOW = 1
 ERR_NUMERIC = -4           # BBX_ERR_NUMERIC
+COX_FAMILIES = ("cox", "coxcp", "coxef", "coxw", "coxfg")
 SAMPLER_CG, SAMPLER_CHOLESKY, SAMPLER_WOODBURY = 0, 1, 2
 # Philox stream ids of the chain's draws (csrc/philox.hpp)
 STREAM_ETA1, STREAM_ETA2 = 1, 2
@@ -216,6 +217,9 @@ def _declare(lib):
         "bbx_coxfg_create": (
             [hp, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
              c_void_p, c_void_p, c_void_p, POINTER(hp)], c_int),
+        "bbx_cox_survival_summary": (
+            [c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+             c_void_p, c_void_p, c_void_p, c_void_p], c_int),
         "bbx_logit_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_poisson_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_cpoisson_create": (
@@ -251,6 +255,19 @@ def _declare(lib):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype
+    # the two prediction entry points of every Cox handle type.  The header
+    # declares them through one macro (BBX_COX_PREDICT_DECL), not name by
+    # name, so they are bound here and not listed among the header's names.
+    predict = {
+        "baseline_hazard": [hp, c_void_p, c_int64, c_int64, c_void_p,
+                            c_void_p],
+        "residuals": [hp, c_void_p, c_void_p],
+    }
+    for family in COX_FAMILIES:
+        for entry, argtypes in predict.items():
+            fn = getattr(lib, "bbx_%s_%s" % (family, entry))
+            fn.argtypes = list(argtypes)
+            fn.restype = c_int
     return sigs
 
 

@@ -8,7 +8,10 @@ with strata the conditional Poisson model, csrc/cpoisson.hip) has no other.
 With entry times the Cox model is the counting-process form
 (csrc/cox_interval.hip); with ties='efron' tied event times take Efron's
 approximation (csrc/cox_efron.hip); with weights= every row carries a case
-weight (the weighted partial likelihood, csrc/cox_weighted.hip)."""
+weight (the weighted partial likelihood, csrc/cox_weighted.hip).  Every Cox
+model also gives its cumulative baseline hazard, its martingale residuals and
+the posterior survival of new rows (csrc/cox_family.hpp,
+csrc/cox_predict.hip)."""
 import math
 from ctypes import byref, c_double, c_int, c_void_p
 from warnings import catch_warnings, simplefilter, warn
@@ -944,6 +947,54 @@ def _check_competing(competing_time, strata=None, entry_time=None,
             "weights in the Fine-Gray model are not built.")
 
 
+def _cox_event_times(model):
+    """The event times of a CoxModel as the handle numbers them: a list with
+    one (number of the first event, event times ascending) per stratum (one
+    entry without strata)."""
+    t = model.event_time
+    if getattr(model, 'strata', None) is not None:
+        out, first = [], 0
+        for s, ne in enumerate(model.stratum_n_event):
+            r0 = int(model.stratum_ptr[s])
+            out.append((first, t[r0:r0 + int(ne)]))
+            first += int(ne)
+        return out
+    if hasattr(model, 'event_row'):       # counting-process and Fine-Gray rows
+        return [(0, t[model.event_row])]
+    return [(0, t[:model.n_event])]
+
+
+def cox_hazard_grid(model, times=None):
+    """The time grid of a baseline hazard and, for every grid point, the
+    number of the last event at or before it (-1: none), as the handle numbers
+    its events: (times, grid_event), grid_event int32 of shape (T,), or
+    (n_strata, T) for a stratified model (every stratum indexed on its own,
+    in global event numbers).  A grid point on an event time takes the last
+    event tied there.  times=None: the model's distinct event times; a
+    stratified model needs a grid.  Pure NumPy: no device call."""
+    events = _cox_event_times(model)
+    stratified = getattr(model, 'strata', None) is not None
+    if times is None:
+        if stratified:
+            raise ValueError(
+                "A stratified model has one set of event times per stratum: "
+                "a grid of times is required.")
+        times = np.unique(events[0][1])
+    else:
+        times = np.array(times, dtype=np.float64)
+        if times.ndim != 1 or len(times) == 0:
+            raise ValueError("times must be a non-empty 1-d array.")
+        if not np.all(np.isfinite(times)):
+            raise ValueError("Every grid time must be finite.")
+        if np.any(times[:-1] > times[1:]):
+            raise ValueError("The grid times must be in the ascending order.")
+    grid = np.empty((len(events), len(times)), dtype=np.int32)
+    for s, (first, t) in enumerate(events):
+        k = np.searchsorted(t, times, side='right') - 1
+        grid[s] = np.where(k >= 0, first + k, -1)
+    return times, (grid if stratified else grid[0])
+
+
 class CoxModel(_DeviceHamiltonian, _Model):
     """cox_model.py:7-303 on a HIP design whose rows are already in the
     model's order (RegressionModel(..., family='cox') sorts them).  The
@@ -1154,6 +1205,185 @@ class CoxModel(_DeviceHamiltonian, _Model):
 
     # the trajectory's f(q0) (hmc.py:95-97) is the model's own likelihood
     hamiltonian_loglik_and_gradient = compute_loglik_and_gradient
+
+    # ------------------------------------------------------ prediction
+    def _coef_draws(self, coef):
+        """coef (P,) or (P, S) as (the draws (S, P) C-contiguous, whether a
+        draw axis was given)."""
+        coef = np.asarray(coef, dtype=np.float64)
+        if coef.ndim not in (1, 2) or coef.shape[0] != self.n_pred \
+                or coef.size == 0:
+            raise ValueError(
+                "coef must have shape (%d,) or (%d, n_draw): %s."
+                % (self.n_pred, self.n_pred, coef.shape))
+        return (np.ascontiguousarray(coef.reshape(self.n_pred, -1).T),
+                coef.ndim == 2)
+
+    def _log_baseline_hazard(self, draws, grid_event):
+        """bbx_<family>_baseline_hazard: (n_draw, grid_event.size)."""
+        grid = np.ascontiguousarray(grid_event, dtype=np.int32).ravel()
+        out = np.empty((len(draws), len(grid)))
+        st = self._ham_fn('baseline_hazard')(
+            self.handle, _ptr(draws), len(draws), len(grid), _ptr(grid),
+            _ptr(out))
+        if st == _lib.ERR_NUMERIC:
+            raise ValueError(
+                "The baseline hazard cannot be computed: %s."
+                % _lib.last_error())
+        _lib.check(st)
+        return out
+
+    def cumulative_baseline_hazard(self, coef, times=None, log=False):
+        """Breslow's cumulative baseline hazard Lambda0 at `times` (None: the
+        distinct event times) for coef of shape (P,) or (P, S) -- what
+        samples['coef'] is: (times, value), value of shape (T,) or (T, S);
+        for a stratified model (n_strata, T[, S]), the strata in np.unique
+        order of their labels.  It is the hazard of a subject at the column
+        means of the training rows (the design's centred columns); with
+        ties='efron' the jump at a tied time is the sum of the group's
+        1/phi_l, with weights a_k / H_k, with entry times H_k is the interval
+        risk set's sum, and with competing_time Lambda0 is the cumulative
+        baseline subdistribution hazard.  log=True returns log Lambda0 (-inf
+        before the first event), which stays finite where Lambda0 itself
+        under- or overflows.  One device call for all the draws.  ValueError
+        if a draw has an empty risk-set sum."""
+        draws, many = self._coef_draws(coef)
+        times, grid = cox_hazard_grid(self, times)
+        value = self._log_baseline_hazard(draws, grid)
+        value = np.moveaxis(value.reshape((len(draws),) + grid.shape), 0, -1)
+        if not many:
+            value = value[..., 0]
+        value = np.ascontiguousarray(value)
+        return times, (value if log else np.exp(value))
+
+    def martingale_residuals(self, coef):
+        """delta_i - exp(eta_i) Lambda_i of every row at coef (P,), in the
+        model's row order: the w of the gradient's row pass, Lambda_i the
+        baseline hazard accumulated over the risk sets that hold row i.  With
+        case weights it is a_i times that.  ValueError if a risk-set sum is
+        empty."""
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if coef.shape != (self.n_pred,):
+            raise ValueError("coef must have length %d" % self.n_pred)
+        out = np.empty(self.n_obs)
+        st = self._ham_fn('residuals')(self.handle, _ptr(coef), _ptr(out))
+        if st == _lib.ERR_NUMERIC:
+            raise ValueError(
+                "The residuals cannot be computed: %s." % _lib.last_error())
+        _lib.check(st)
+        return out
+
+    def _new_design(self, X_new):
+        """X_new (raw columns) as a design centred with the TRAINING design's
+        column offsets, by the constructors that keep constant columns."""
+        train = self.design
+        offset = train.column_offset if train.centered else None
+        if sparse.issparse(X_new):
+            X_new = X_new.tocsr().copy()
+            X_new.sort_indices()
+            return HipSparseDesignMatrix.from_csr_arrays(
+                X_new.shape, X_new.indptr, X_new.indices, X_new.data,
+                column_offset=offset, add_intercept=False,
+                device=train.device)
+        import torch
+        dev = 'cuda:%d' % train.device
+        X_dev = torch.from_numpy(
+            np.ascontiguousarray(X_new, dtype=np.float64)).to(dev)
+        off_dev = None
+        if offset is not None:
+            off_dev = torch.from_numpy(
+                np.ascontiguousarray(offset, dtype=np.float64)).to(dev)
+        torch.cuda.synchronize(train.device)
+        # (the arrays are copied: the tensors may go once it returns)
+        return HipDenseDesignMatrix.from_device_array(
+            X_new.shape[0], X_new.shape[1], X_dev.data_ptr(),
+            off_dev.data_ptr() if off_dev is not None else None,
+            add_intercept=False, device=train.device, in_dtype='float64',
+            storage_dtype=getattr(train, 'storage_dtype', 'float64'))
+
+    def predict_survival(self, coef, X_new=None, times=None, strata_new=None,
+                         linear_predictor=None, return_draws=False):
+        """Posterior survival S(t | x) = exp(-Lambda0(t) exp(x~ . beta)) of new
+        rows over the draws coef (P,) or (P, S): a dict with 'time' (T,),
+        'mean' and 'sd' (n_new, T) -- the mean and the population standard
+        deviation over the draws -- and, with return_draws, 'draws'
+        (n_new, T, S).  For the Fine-Gray model S is 1 - CIF.  Exactly one of
+        X_new (n_new rows of the model's n_pred raw columns, NumPy or SciPy;
+        centred with the training design's column means, never its own) and
+        linear_predictor ((n_new,) for one draw, else (n_new, S): x~ . beta
+        on the centred columns) is given.  With strata, strata_new holds the
+        training stratum of every new row and `times` is required."""
+        draws, many = self._coef_draws(coef)
+        n_draw = len(draws)
+        if (X_new is None) == (linear_predictor is None):
+            raise ValueError(
+                "Exactly one of X_new and linear_predictor must be given.")
+        if X_new is not None:
+            if not sparse.issparse(X_new):
+                X_new = np.asarray(X_new, dtype=np.float64)
+            if X_new.ndim != 2 or X_new.shape[1] != self.n_pred \
+                    or X_new.shape[0] == 0:
+                raise ValueError(
+                    "X_new must have at least one row and the model's %d "
+                    "columns: shape %s." % (self.n_pred, X_new.shape))
+            n_new = X_new.shape[0]
+            train = self.design
+            if train.centered and train.column_offset is None:
+                raise TypeError(
+                    "The training design was adopted from device pointers "
+                    "and keeps no host copy of its column offsets: pass "
+                    "linear_predictor instead of X_new.")
+        else:
+            lp = np.asarray(linear_predictor, dtype=np.float64)
+            if lp.ndim == 1 and not many:
+                lp = lp[:, None]
+            if lp.ndim != 2 or lp.shape[1] != n_draw or lp.shape[0] == 0:
+                raise ValueError(
+                    "linear_predictor must have shape (n_new,) for one draw "
+                    "or (n_new, %d): %s."
+                    % (n_draw, np.shape(linear_predictor)))
+            n_new = lp.shape[0]
+        group, n_group = None, 1
+        if self.strata is not None:
+            if strata_new is None:
+                raise ValueError(
+                    "The model is stratified: strata_new (the stratum of "
+                    "every new row) is required.")
+            strata_new = np.asarray(strata_new)
+            if strata_new.shape != (n_new,):
+                raise ValueError(
+                    "strata_new must be a 1-d array with one label for each "
+                    "new row.")
+            labels = np.unique(self.strata)
+            code = np.searchsorted(labels, strata_new)
+            code[code == len(labels)] = 0
+            if not np.all(labels[code] == strata_new):
+                raise ValueError(
+                    "Every label of strata_new must be a stratum of the "
+                    "training rows.")
+            group = np.ascontiguousarray(code, dtype=np.int32)
+            n_group = len(labels)
+        elif strata_new is not None:
+            raise ValueError("strata_new is an argument of a stratified "
+                             "model only.")
+        times, grid = cox_hazard_grid(self, times)
+        # every check is done: the device from here on
+        if X_new is not None:
+            new_design = self._new_design(X_new)
+            eta = np.stack([new_design.dot(b) for b in draws])
+        else:
+            eta = np.ascontiguousarray(lp.T)
+        log_hazard = self._log_baseline_hazard(draws, grid)
+        n_time = len(times)
+        mean, sd = np.empty((n_new, n_time)), np.empty((n_new, n_time))
+        out = np.empty((n_new, n_time, n_draw)) if return_draws else None
+        _lib.check(_lib.load().bbx_cox_survival_summary(
+            self.design.device, n_new, n_time, n_draw, n_group, _ptr(eta),
+            _ptr(log_hazard), _ptr(group), _ptr(mean), _ptr(sd), _ptr(out)))
+        res = {'time': times, 'mean': mean, 'sd': sd}
+        if return_draws:
+            res['draws'] = out
+        return res
 
     @staticmethod
     def simulate_outcome(X, beta, censoring_frac=.9, seed=None):

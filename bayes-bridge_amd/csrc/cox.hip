@@ -215,6 +215,16 @@ struct CoxDriver {
     if (c->strat) return strat_hessian_from_u(c, d_out);
     return hessian_from_u<CoxPlain>(c, d_out);
   }
+  // the shift of an event: max eta, or the max of the event's stratum
+  static CoxShift shift(const bbx_cox* c) {
+    CoxShift sh = CoxDriverT<CoxPlain>::shift(c);
+    if (c->strat) {
+      sh.ms = c->ms.as<const double>();
+      sh.sid = c->sid.as<const int32_t>();
+      sh.evrow = c->evrow.as<const int32_t>();
+    }
+    return sh;
+  }
 };
 
 using CoxFamily = CoxFamilyT<CoxPlain, CoxDriver>;
@@ -374,3 +384,4 @@ int bbx_cox_create_stratified(bbx_design* design, int64_t n_strata,
 }  // extern "C"
 
 BBX_HAM_ENTRY_POINTS(cox, CoxFamily)
+BBX_COX_PREDICT_ENTRY_POINTS(cox, CoxFamily)

@@ -183,3 +183,4 @@ extern "C" int bbx_coxef_create(bbx_design* design, int64_t n_event,
 }
 
 BBX_HAM_ENTRY_POINTS(coxef, CoxFamilyT<CoxEfron>)
+BBX_COX_PREDICT_ENTRY_POINTS(coxef, CoxFamilyT<CoxEfron>)

@@ -1,7 +1,9 @@
 // What the Cox likelihood handles share (cox.hip, cox_interval.hip,
 // cox_efron.hip, cox_weighted.hip, cox_finegray.hip): the handle base, the
-// three kernels that form values, the six-launch driver and the family that
-// hamiltonian.hpp's entry points take.  A handle states a policy V, a small
+// three kernels that form values, the six-launch driver, the family that
+// hamiltonian.hpp's entry points take and the prediction calls (the baseline
+// hazard read off the likelihood's cumulative sum, the residuals; at the end
+// of the file).  A handle states a policy V, a small
 // struct of device pointers that is passed to the kernels by value:
 //
 //   device side (the per-element expressions; everything else is written once)
@@ -41,6 +43,7 @@
 #include <math.h>
 
 #include <string>
+#include <vector>
 
 #include "common.hpp"
 #include "cox_scan.hpp"
@@ -183,6 +186,42 @@ __global__ __launch_bounds__(VEC_BLOCK) void cox_row_weight_kernel(
   }
   acc = block_sum<VEC_BLOCK>(acc);
   if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// Where the shift m of an event comes from: the NPART partials of max eta, or
+// (a stratified handle) the stratum's own max through the row of the event
+struct CoxShift {
+  const double* maxp = nullptr;
+  const double* ms = nullptr;      // per stratum; null: one shift, from maxp
+  const int32_t* sid = nullptr;    // stratum of a row
+  const int32_t* evrow = nullptr;  // row of an event
+};
+
+// log Lambda0 on a grid: out[j] = log(c[k_j]) - m, k_j = grid_event[j]; -inf
+// where k_j is -1 (no event at or before the grid point).  c is the first
+// event half of the likelihood's cumulative sum, complete in stream order.  A
+// draw whose likelihood raised skip (an empty risk-set sum) writes nothing
+// but its flag.  Static, as the scan kernels are: one copy per handle file.
+static __global__ __launch_bounds__(VEC_BLOCK) void cox_hazard_grid_kernel(
+    CoxShift sh, int64_t n_grid, const int32_t* __restrict__ grid_event,
+    const double* __restrict__ c, double* __restrict__ out,
+    int* __restrict__ bad, const CoxTraj* __restrict__ st) {
+  if (st->skip) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *bad = 1;
+    return;
+  }
+  double m = 0.;
+  if (!sh.ms) m = part_max(sh.maxp);
+  for (int64_t j = (int64_t)blockIdx.x * VEC_BLOCK + threadIdx.x; j < n_grid;
+       j += (int64_t)gridDim.x * VEC_BLOCK) {
+    const int32_t k = grid_event[j];
+    double v = -INFINITY;
+    if (k >= 0) {
+      if (sh.ms) m = sh.ms[sh.sid[sh.evrow[k]]];
+      v = log(c[k]) - m;
+    }
+    out[j] = v;
+  }
 }
 
 namespace {  // host side: internal, as the handle types appear in the names
@@ -377,6 +416,11 @@ struct CoxDriverT {
     return likelihood_from_eta<V>(c, h_out, inv, inv1, cum, grad);
   }
   static int hessian(H* c, double* d_out) { return hessian_from_u<V>(c, d_out); }
+  static CoxShift shift(const H* c) {
+    CoxShift sh;
+    sh.maxp = c->maxp.template as<const double>();
+    return sh;
+  }
 };
 
 // The policy hamiltonian.hpp's entry points take
@@ -414,7 +458,146 @@ struct CoxFamilyT {
     BBX_TRY(eta_of(c, d_v));   // u = X~ v, in c->eta
     return D::hessian(c, d_out);
   }
+  static CoxShift shift(const H* c) { return D::shift(c); }
 };
 
+// ------------------------------------------------- prediction
+// The two calls below evaluate the likelihood block at coefficients from the
+// host; they use the trajectory's scratch (eta, hz, inv, cs, tmp, gl) and
+// never the Hessian's location.  A No-U-Turn tree between nuts_begin and
+// nuts_sample keeps its state in the same scratch: refused.
+template <class F>
+int predict_head(const typename F::H* c, const char* entry) {
+  BBX_TRY(ham::check(c, F::name));
+  if (c->nuts_open)
+    return fail(BBX_ERR_STATE, std::string("bbx_") + F::name + "_" + entry +
+                                   ": a No-U-Turn tree is installed on the "
+                                   "handle (bbx_" + F::name +
+                                   "_nuts_sample ends the draw)");
+  return BBX_OK;
+}
+
+// log Lambda0 of n_draw coefficient vectors on one grid: per draw the flags
+// are reset, eta = X~ beta, the likelihood block without its gradient, the
+// gather; everything is enqueued before the one synchronisation.
+template <class F>
+int baseline_hazard_impl(typename F::H* c, const double* beta, int64_t n_draw,
+                         int64_t n_grid, const int32_t* grid_event,
+                         double* log_hazard) {
+  bbx_design* h = c->h;
+  hipStream_t s = h->stream;
+  const size_t pbytes = sizeof(double) * c->P;
+  DevMem d_beta, d_grid, d_out, d_bad;
+  BBX_TRY(d_beta.alloc(pbytes * n_draw));
+  BBX_TRY(d_grid.alloc(sizeof(int32_t) * n_grid));
+  BBX_TRY(d_out.alloc(sizeof(double) * n_draw * n_grid));
+  BBX_TRY(d_bad.alloc(sizeof(int) * n_draw));
+  std::vector<int> bad(n_draw);
+  BBX_HIP(hipMemcpyAsync(d_beta.ptr, beta, pbytes * n_draw,
+                         hipMemcpyHostToDevice, s));
+  BBX_HIP(hipMemcpyAsync(d_grid.ptr, grid_event, sizeof(int32_t) * n_grid,
+                         hipMemcpyHostToDevice, s));
+  BBX_HIP(hipMemsetAsync(d_bad.ptr, 0, sizeof(int) * n_draw, s));
+  const int blocks =
+      (int)((n_grid + VEC_BLOCK - 1) / VEC_BLOCK < NPART
+                ? (n_grid + VEC_BLOCK - 1) / VEC_BLOCK
+                : NPART);
+  typename F::Lik lik{c};
+  // the staging vector the one-draw calls use: the same eta, bit for bit
+  double* d_in = h->stage_P.template as<double>();
+  for (int64_t d = 0; d < n_draw; ++d) {
+    BBX_LAUNCH(cox_reset_kernel, dim3(1), dim3(WAVE), 0, s, cst(c));
+    BBX_HIP(hipGetLastError());
+    BBX_HIP(hipMemcpyAsync(d_in, d_beta.template as<double>() + d * c->P,
+                           pbytes, hipMemcpyDeviceToDevice, s));
+    BBX_TRY(eta_of(c, d_in));
+    BBX_TRY(lik(nullptr));
+    BBX_LAUNCH(cox_hazard_grid_kernel, dim3(blocks), dim3(VEC_BLOCK), 0, s,
+               F::shift(c), n_grid, d_grid.template as<const int32_t>(),
+               c->cs.template as<const double>(),
+               d_out.template as<double>() + d * n_grid,
+               d_bad.template as<int>() + d, cst(c));
+    BBX_HIP(hipGetLastError());
+  }
+  BBX_HIP(hipMemcpyAsync(log_hazard, d_out.ptr,
+                         sizeof(double) * n_draw * n_grid,
+                         hipMemcpyDeviceToHost, s));
+  BBX_HIP(hipMemcpyAsync(bad.data(), d_bad.ptr, sizeof(int) * n_draw,
+                         hipMemcpyDeviceToHost, s));
+  BBX_HIP(hipStreamSynchronize(s));
+  for (int64_t d = 0; d < n_draw; ++d) {
+    if (bad[d])
+      return fail(BBX_ERR_NUMERIC,
+                  "draw " + std::to_string(d) +
+                      ": a risk-set sum of relative hazards is 0");
+  }
+  return BBX_OK;
+}
+
+template <class F>
+int baseline_hazard(typename F::H* c, const double* beta, int64_t n_draw,
+                    int64_t n_grid, const int32_t* grid_event,
+                    double* log_hazard) {
+  BBX_TRY(predict_head<F>(c, "baseline_hazard"));
+  if (!beta || !grid_event || !log_hazard)
+    return fail(BBX_ERR_INVALID, "NULL argument");
+  if (n_draw < 1) return fail(BBX_ERR_INVALID, "n_draw must be at least 1");
+  if (n_grid < 1) return fail(BBX_ERR_INVALID, "n_grid must be at least 1");
+  // the kernel indexes c[grid_event]: check them all
+  for (int64_t j = 0; j < n_grid; ++j) {
+    if (grid_event[j] < -1 || grid_event[j] >= c->ne)
+      return fail(BBX_ERR_INVALID, "grid_event[" + std::to_string(j) +
+                                       "] outside [-1, n_event)");
+  }
+  BBX_HIP(hipSetDevice(c->device));
+  return no_throw([&] {
+    return baseline_hazard_impl<F>(c, beta, n_draw, n_grid, grid_event,
+                                   log_hazard);
+  });
+}
+
+// The row pass's w at beta (the martingale residuals): one gradient
+// evaluation; X~^T w goes to the scratch c->gl
+template <class F>
+int residuals(typename F::H* c, const double* beta, double* out) {
+  BBX_TRY(predict_head<F>(c, "residuals"));
+  if (!beta || !out) return fail(BBX_ERR_INVALID, "NULL argument");
+  BBX_HIP(hipSetDevice(c->device));
+  return no_throw([&] {
+    bbx_design* h = c->h;
+    typename F::Lik lik{c};
+    double* d_in = h->stage_P.template as<double>();
+    BBX_HIP(hipMemcpyAsync(d_in, beta, sizeof(double) * c->P,
+                           hipMemcpyHostToDevice, h->stream));
+    BBX_LAUNCH(cox_reset_kernel, dim3(1), dim3(WAVE), 0, h->stream, cst(c));
+    BBX_HIP(hipGetLastError());
+    BBX_TRY(eta_of(c, d_in));
+    BBX_TRY(lik(c->gl.template as<double>()));
+    BBX_HIP(hipMemcpyAsync(out, c->tmp.ptr, sizeof(double) * c->n,
+                           hipMemcpyDeviceToHost, h->stream));
+    BBX_TRY(read_state(c));
+    if (c->host_st->zero)
+      return fail(BBX_ERR_NUMERIC,
+                  "residuals: a risk-set sum of relative hazards is 0");
+    return BBX_OK;
+  });
+}
 }  // namespace
 }  // namespace bbx
+
+// The two prediction entry points include/bbx.h declares for every Cox handle
+// type (BBX_COX_PREDICT_DECL), on bbx_<fam> under the family F; stamped next
+// to BBX_HAM_ENTRY_POINTS, in the policy's own translation unit.
+#define BBX_COX_PREDICT_ENTRY_POINTS(fam, F)                                   \
+  extern "C" {                                                                 \
+  int bbx_##fam##_baseline_hazard(bbx_##fam* c, const double* beta,            \
+                                  int64_t n_draw, int64_t n_grid,              \
+                                  const int32_t* grid_event,                   \
+                                  double* log_hazard) {                        \
+    return ::bbx::baseline_hazard<F>(c, beta, n_draw, n_grid, grid_event,      \
+                                     log_hazard);                              \
+  }                                                                            \
+  int bbx_##fam##_residuals(bbx_##fam* c, const double* beta, double* out) {   \
+    return ::bbx::residuals<F>(c, beta, out);                                  \
+  }                                                                            \
+  }

@@ -258,3 +258,4 @@ extern "C" int bbx_coxfg_create(bbx_design* design, int64_t n_event,
 }
 
 BBX_HAM_ENTRY_POINTS(coxfg, CoxFamilyT<CoxFineGray>)
+BBX_COX_PREDICT_ENTRY_POINTS(coxfg, CoxFamilyT<CoxFineGray>)

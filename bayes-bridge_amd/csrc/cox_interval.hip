@@ -208,3 +208,4 @@ extern "C" int bbx_coxcp_create(bbx_design* design, int64_t n_event,
 }
 
 BBX_HAM_ENTRY_POINTS(coxcp, CoxFamilyT<CoxEntry>)
+BBX_COX_PREDICT_ENTRY_POINTS(coxcp, CoxFamilyT<CoxEntry>)

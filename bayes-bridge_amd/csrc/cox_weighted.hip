@@ -161,3 +161,4 @@ extern "C" int bbx_coxw_create(bbx_design* design, int64_t n_event,
 }
 
 BBX_HAM_ENTRY_POINTS(coxw, CoxFamilyT<CoxWeighted>)
+BBX_COX_PREDICT_ENTRY_POINTS(coxw, CoxFamilyT<CoxWeighted>)

@@ -496,6 +496,11 @@ struct HamCore {
   DevMem nuts_st, nuts_u;                // NutsState, 2^NUTS_MAXH uniforms
   NutsState* host_nuts = nullptr;        // pinned read-back
   bool nuts_begun = false;
+  // between nuts_begin and nuts_sample: the tree's draw is under way, and the
+  // calls that would reuse its scratch (cox_family.hpp's prediction) refuse.
+  // Only nuts_sample (valid at any time after nuts_begin) and the next
+  // nuts_begin change it: that is how an abandoned tree is closed.
+  bool nuts_open = false;
   // P-vector k of tree buffer b: 0 near q, 1 near p, 2 sample q, 3 sample grad
   double* nuts_tree_vec(int b, int k) const {
     return nuts_vec.as<double>() + (size_t)(4 * b + k) * P;
@@ -634,6 +639,7 @@ inline int nuts_begin_impl(HamCore* c, const double* scale,
   bbx_design* h = c->h;
   const size_t bytes = sizeof(double) * c->P;
   c->nuts_begun = false;
+  c->nuts_open = false;
   if (!c->nuts_vec.ptr) {
     BBX_TRY(c->nuts_vec.alloc(bytes * (4 * (NUTS_MAXH + 1) + 8)));
     BBX_TRY(c->nuts_st.alloc(sizeof(NutsState)));
@@ -659,6 +665,7 @@ inline int nuts_begin_impl(HamCore* c, const double* scale,
   BBX_HIP(hipGetLastError());
   BBX_HIP(hipStreamSynchronize(h->stream));   // the host arrays are free again
   c->nuts_begun = true;
+  c->nuts_open = true;
   return BBX_OK;
 }
 
@@ -835,6 +842,7 @@ inline int nuts_sample_impl(HamCore* c, double* q, double* logp,
                          hipMemcpyDeviceToHost, h->stream));
   BBX_HIP(hipStreamSynchronize(h->stream));
   if (logp) *logp = c->host_nuts->tree[NUTS_MAIN].logp;
+  c->nuts_open = false;
   return BBX_OK;
 }
 

@@ -33,7 +33,11 @@
 extern "C" {
 #endif
 
-/* 113: + the Fine-Gray competing-risks model (bbx_coxfg_*: create, destroy and
+/* 113: + prediction from the Cox handles: the cumulative baseline hazard and
+ *      the martingale residuals of every handle type (BBX_COX_PREDICT_DECL)
+ *      and bbx_cox_survival_summary.  New symbols and nothing else, so the
+ *      number stays 113.
+ *      + the Fine-Gray competing-risks model (bbx_coxfg_*: create, destroy and
  *      the shared entry points of every likelihood handle).  New symbols and
  *      nothing else, so the number stays 113.
  *      + Efron's approximation for tied event times in the Cox model
@@ -1088,6 +1092,92 @@ int bbx_coxfg_nuts_doubling(bbx_coxfg* coxfg, double dt, int direction,
                             int* tree, double* averages);
 int bbx_coxfg_nuts_sample(bbx_coxfg* coxfg, double* q, double* logp,
                           double* grad);
+
+/* ----------------------------------------------- prediction
+ * Two entry points per Cox handle type, bbx_<fam>_baseline_hazard and
+ * bbx_<fam>_residuals for <fam> = cox (plain and stratified), coxcp, coxef,
+ * coxw, coxfg, declared by the macro below.  With eta = X~ beta, m the shift
+ * of the handle (max eta; per stratum in a stratified handle) and c[k] the
+ * cumulative sum over the events, in time order, of the handle's own event
+ * value q_k (1/H_k; 1/phi_k with Efron ties; a_k/H_k with case weights;
+ * restarted at the first event of every stratum):
+ *
+ *   log Lambda0(t) = log c[k(t)] - m,  k(t) the last event with t_k <= t
+ *
+ * Breslow's cumulative baseline hazard on the centred columns, as a logarithm
+ * (m may be hundreds: exp(-m) alone underflows).  For bbx_coxfg it is the
+ * cumulative baseline subdistribution hazard.
+ *
+ * baseline_hazard: beta[n_draw][P] (host, draw-major), grid_event[n_grid]
+ * (host) with values in [-1, n_event): the handle's event number k(t_j) of
+ * grid point j, -1 where no event is at or before it (the result is -inf
+ * there); for a stratified handle the global event number, and the shift is
+ * that of the event's stratum.  log_hazard[n_draw][n_grid] (host).  Per draw:
+ * the flags are reset, eta = X~ beta, the likelihood's kernels (no gradient),
+ * one gather kernel: the launches of bbx_<fam>_loglik_grad without a
+ * gradient, whatever n_grid is.  All draws are enqueued back to back; ONE
+ * host synchronisation per call.  BBX_ERR_NUMERIC, naming the first such
+ * draw, if a draw has an empty risk-set sum (log_hazard is then unspecified);
+ * the draws after it are still evaluated on their own.
+ *
+ * residuals: out[n] (host) = w of the gradient's row pass at beta[P] (host),
+ * w_i = delta_i - exp(eta_i) Lambda0-sum of row i: the martingale residuals in
+ * the handle's row order (bbx_coxw: a_i times that).  One gradient evaluation,
+ * one synchronisation.  BBX_ERR_NUMERIC for an empty risk-set sum.
+ *
+ * Neither call moves the Hessian's location: an operator made by
+ * set_location before them gives the same bits after them.  Both use the
+ * trajectory's scratch: BBX_ERR_STATE between bbx_<fam>_nuts_begin and the
+ * bbx_<fam>_nuts_sample that ends the draw.  BBX_ERR_INVALID for a NULL
+ * handle or array, n_draw < 1, n_grid < 1 or a grid_event outside
+ * [-1, n_event); the handle stays usable.  Fixed reduction orders: draw d of a
+ * call has the bits of the same draw called alone.
+ *
+ * A tree that is abandoned between nuts_begin and nuts_sample (the caller
+ * stopped early) keeps refusing these two calls: bbx_<fam>_nuts_sample is valid
+ * at any time after nuts_begin and closes it, as the next complete draw does.
+ *
+ * "One synchronisation" counts the explicit ones: beta, grid_event, log_hazard
+ * and out are pageable host memory as far as the library knows, and the
+ * runtime may stage each such copy and hold the host while it does.
+ *
+ * Why a macro and not ten spelled-out prototypes: the per-family tests of the
+ * likelihood handles compare the set of names bbx_<fam>_* that this header
+ * spells out with the ten shared entry points plus create, exactly, so a
+ * name written here would fail them.  A binding therefore looks the ten
+ * symbols up by name (bayesbridge_amd/_lib.py binds them beside its table of
+ * header names), and tests/test_cox_predict_host_logic.py checks that every
+ * one is exported. */
+#define BBX_COX_PREDICT_DECL(fam)                                              \
+  int bbx_##fam##_baseline_hazard(                                             \
+      bbx_##fam* handle, const double* beta, int64_t n_draw, int64_t n_grid,   \
+      const int32_t* grid_event, double* log_hazard);                          \
+  int bbx_##fam##_residuals(bbx_##fam* handle, const double* beta, double* out);
+BBX_COX_PREDICT_DECL(cox)
+BBX_COX_PREDICT_DECL(coxcp)
+BBX_COX_PREDICT_DECL(coxef)
+BBX_COX_PREDICT_DECL(coxw)
+BBX_COX_PREDICT_DECL(coxfg)
+
+/* Posterior survival of new rows (csrc/cox_predict.hip; no handle, every
+ * pointer a host pointer): S[i][t][d] = exp(-exp(log_hazard[d][g_i][t] +
+ * eta[d][i])), the exponent formed as that one sum; a log_hazard of -inf
+ * gives exactly 1, an exponent past 709 exactly 0, a NaN stays a NaN.  For
+ * the Fine-Gray model S is 1 - CIF.
+ * eta[n_draw][n_row] (draw-major), log_hazard[n_draw][n_group][n_time],
+ * group[n_row] in [0, n_group) or NULL where n_group == 1.  mean[n_row][n_time]
+ * and sd[n_row][n_time]: the mean over the draws and the population standard
+ * deviation (two passes over the draws in index order; no atomics: the same
+ * inputs give the same bits).  draws[n_row][n_time][n_draw]: every S, or
+ * NULL.  The rows go through the device in slabs sized so that the call's
+ * device memory is bounded (64 MiB beside log_hazard itself).
+ * BBX_ERR_INVALID for a NULL array, n_row, n_time, n_draw or n_group < 1, or
+ * a group outside [0, n_group). */
+int bbx_cox_survival_summary(int device, int64_t n_row, int64_t n_time,
+                             int64_t n_draw, int64_t n_group,
+                             const double* eta, const double* log_hazard,
+                             const int32_t* group, double* mean, double* sd,
+                             double* draws);
 
 /* ----------------------------------------------------------- logit model
  * The binomial-logit likelihood of model/logistic_model.py:49-74 on a design

@@ -88,6 +88,16 @@ the two handles' own kernels differ in their policy argument (CoxFineGray
 against CoxPlain).  `launches` and `plain_launches` count the kernel launches
 of one loglik + gradient call of either handle.
 Not together with --strata, --entry, --ties or --weights.
+
+--predict S: prediction instead of sampling, on the handle the
+other options select: `hazard_us_per_draw`, the wall time per draw of one
+S-draw cumulative_baseline_hazard call on a 257-point grid (one host
+synchronisation for all the draws), against `loglik_only_us`, one synchronous
+loglik-only evaluation of the same handle in the same process (mean of 10);
+the launches of either per draw; `residuals_us`, one martingale_residuals
+call; `survival_ms`, three bbx_cox_survival_summary calls of 100 000 rows x 10
+times x 256 draws from host memory, uploads and read-back included, with the
+bytes in and out.  Not together with --strata.
 """
 import argparse
 import json
@@ -239,9 +249,65 @@ def leapfrog_us(model, n_traj, scale, pp, q0, p0, logp0, grad0):
     return (time.perf_counter() - tic) / n_traj * 1e6
 
 
+def predict_figures(model, n_draw, n_grid=257, seed=0):
+    """--predict: one n_draw-draw baseline-hazard call against the synchronous
+    loglik-only evaluation of the same handle, and the survival summary of
+    100 000 rows x 10 times x 256 draws."""
+    from ctypes import c_uint64, c_void_p
+    lib = _lib.load()
+    lib.bbx_launch_count.restype = c_uint64
+    P = model.n_pred
+    rs = np.random.RandomState(seed + 5)
+    coef = rs.randn(P, n_draw) * .01
+    ev = model.event_time[np.isfinite(model.event_time)]
+    grid = np.sort(rs.uniform(ev.min(), ev.max(), n_grid))
+    b = np.ascontiguousarray(coef[:, 0])
+    model.compute_loglik_and_gradient(b, loglik_only=True)
+    before = lib.bbx_launch_count()
+    tic = time.perf_counter()
+    for _ in range(10):
+        model.compute_loglik_and_gradient(b, loglik_only=True)
+    loglik_us = (time.perf_counter() - tic) / 10 * 1e6
+    loglik_launches = int(lib.bbx_launch_count() - before) // 10
+    model.cumulative_baseline_hazard(coef[:, :2], grid)
+    before = lib.bbx_launch_count()
+    tic = time.perf_counter()
+    model.cumulative_baseline_hazard(coef, grid, log=True)
+    hazard_us = (time.perf_counter() - tic) / n_draw * 1e6
+    hazard_launches = int(lib.bbx_launch_count() - before) / n_draw
+    tic = time.perf_counter()
+    model.martingale_residuals(b)
+    resid_us = (time.perf_counter() - tic) * 1e6
+    n_row, n_time, n_d = 100000, 10, 256
+    eta = np.ascontiguousarray(rs.randn(n_d, n_row))
+    lh = np.ascontiguousarray(np.sort(rs.randn(n_d, 1, n_time), axis=2) - 1.)
+    mean, sd = np.empty((n_row, n_time)), np.empty((n_row, n_time))
+
+    def ptr(a):
+        return a.ctypes.data_as(c_void_p)
+
+    surv_ms = []
+    for _ in range(3):
+        tic = time.perf_counter()
+        _lib.check(lib.bbx_cox_survival_summary(
+            model.design.device, n_row, n_time, n_d, 1, ptr(eta), ptr(lh),
+            None, ptr(mean), ptr(sd), None))
+        surv_ms.append((time.perf_counter() - tic) * 1e3)
+    return {'predict_draws': n_draw, 'n_grid': n_grid,
+            'hazard_us_per_draw': round(hazard_us, 1),
+            'loglik_only_us': round(loglik_us, 1),
+            'hazard_launches_per_draw': hazard_launches,
+            'loglik_only_launches': loglik_launches,
+            'residuals_us': round(resid_us, 1),
+            'survival_ms': [round(x, 2) for x in surv_ms],
+            'survival_shape': [n_row, n_time, n_d],
+            'survival_bytes_in': eta.nbytes + lh.nbytes,
+            'survival_bytes_out': mean.nbytes + sd.nbytes}
+
+
 def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
         strata=None, entry=None, ties=None, n_grid=3650, weights=None,
-        competing=None):
+        competing=None, predict=0):
     X = make_X(kind, n, p, seed)
     beta = simulate.demo_beta(p)
     labels = None
@@ -305,6 +371,9 @@ def run(kind, n, p, steps, warmup, seed=0, profile_steps=0, sampler='hmc',
                     'n_competing': int(np.isfinite(comp).sum()),
                     'n_censored': int(np.isfinite(ct).sum())}
     preprocess_s = t_design + time.perf_counter() - tic
+    if predict:
+        return {'shape': '%s:%dx%d' % (kind, n, p), 'n_event': model.n_event,
+                **n_strata, **predict_figures(model, predict, seed=seed)}
     P = design.shape[1]
     rs = np.random.RandomState(1)
     b = rs.randn(P) * .01
@@ -411,6 +480,10 @@ def main():
     ap.add_argument('--competing', type=float, default=None, metavar='FRAC',
                     help="the Fine-Gray model; the fraction of the censored "
                          "rows recoded as competing events")
+    ap.add_argument('--predict', type=int, default=0, metavar='S',
+                    help="prediction instead of sampling: one S-draw "
+                         "baseline-hazard call against a loglik-only "
+                         "evaluation, and the survival summary")
     ap.add_argument('--grid', type=int, default=3650, metavar='N',
                     help="grid points of --ties")
     a = ap.parse_args()
@@ -427,6 +500,9 @@ def main():
                          "--entry, --ties or --weights")
     if a.competing is not None and not 0. <= a.competing <= 1.:
         raise SystemExit("--competing takes a fraction in [0, 1]")
+    if a.predict < 0 or (a.predict and a.strata is not None):
+        raise SystemExit("--predict takes a number of draws and does not "
+                         "combine with --strata")
     if a.grid < 1:
         raise SystemExit("--grid takes a positive number")
     if a.strata not in (None, 'pairs') and int(a.strata) < 1:
@@ -443,7 +519,7 @@ def main():
                              sampler=a.sampler, strata=a.strata,
                              entry=a.entry, ties=a.ties,
                              n_grid=a.grid, weights=a.weights,
-                             competing=a.competing)),
+                             competing=a.competing, predict=a.predict)),
               flush=True)
 
 
