@@ -16,6 +16,7 @@ ABI_VERSION = 113         # BBX_VERSION of include/bbx.h
 FORMAT_AUTO, FORMAT_CSR, FORMAT_TILED = 0, 1, 2
 F64, F32 = 0, 1
 MODEL_LINEAR, MODEL_LOGIT = 0, 1
+PRED_LINEAR, PRED_LOGIT, PRED_POISSON = 0, 1, 2   # BBX_PRED_*
 GSCALE_SAMPLE, GSCALE_OPTIMIZE, GSCALE_FIXED = 0, 1, 2
 BATCH_ALLOW_SLOW = 1
 ERR_NUMERIC = -4           # BBX_ERR_NUMERIC
@@ -220,6 +221,10 @@ def _declare(lib):
         "bbx_cox_survival_summary": (
             [c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
              c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+        "bbx_design_predictive_summary": (
+            [hp, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+             c_void_p, c_void_p, c_void_p], c_int),
         "bbx_logit_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_poisson_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_cpoisson_create": (

@@ -11,7 +11,10 @@ approximation (csrc/cox_efron.hip); with weights= every row carries a case
 weight (the weighted partial likelihood, csrc/cox_weighted.hip).  Every Cox
 model also gives its cumulative baseline hazard, its martingale residuals and
 the posterior survival of new rows (csrc/cox_family.hpp,
-csrc/cox_predict.hip)."""
+csrc/cox_predict.hip).  The linear, logit and Poisson models predict from
+their draws -- posterior mean and spread, log pointwise predictive density,
+WAIC -- with the draws' linear predictors kept on the device
+(csrc/predict.hip)."""
 import math
 from ctypes import byref, c_double, c_int, c_void_p
 from warnings import catch_warnings, simplefilter, warn
@@ -39,7 +42,199 @@ class _Model():
         return self.design.intercept_added
 
 
-class LinearModel(_Model):
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(c_void_p)
+
+
+def _coef_draws(coef, n_pred):
+    """coef (P,) or (P, S) as (the draws (S, P) C-contiguous, whether a draw
+    axis was given)."""
+    coef = np.asarray(coef, dtype=np.float64)
+    if coef.ndim not in (1, 2) or coef.shape[0] != n_pred or coef.size == 0:
+        raise ValueError(
+            "coef must have shape (%d,) or (%d, n_draw): %s."
+            % (n_pred, n_pred, coef.shape))
+    many = coef.ndim == 2
+    coef = coef.reshape(n_pred, -1)
+    # draw-major, 256 coefficients at a time: a block stays in cache, which
+    # halves the time of the strided copy at 50 000 x 256
+    draws = np.empty(coef.shape[::-1])
+    for j in range(0, n_pred, 256):
+        draws[:, j:j + 256] = coef[j:j + 256].T
+    return draws, many
+
+
+def _new_design(train, X_new, add_intercept):
+    """X_new (raw columns) as a design centred with the TRAINING design's
+    column offsets, by the constructors that keep constant columns."""
+    offset = train.column_offset if train.centered else None
+    if sparse.issparse(X_new):
+        X_new = X_new.tocsr().copy()
+        X_new.sort_indices()
+        return HipSparseDesignMatrix.from_csr_arrays(
+            X_new.shape, X_new.indptr, X_new.indices, X_new.data,
+            column_offset=offset, add_intercept=add_intercept,
+            device=train.device)
+    import torch
+    dev = 'cuda:%d' % train.device
+    X_dev = torch.from_numpy(
+        np.ascontiguousarray(X_new, dtype=np.float64)).to(dev)
+    off_dev = None
+    if offset is not None:
+        off_dev = torch.from_numpy(
+            np.ascontiguousarray(offset, dtype=np.float64)).to(dev)
+    torch.cuda.synchronize(train.device)
+    # (the arrays are copied: the tensors may go once it returns)
+    return HipDenseDesignMatrix.from_device_array(
+        X_new.shape[0], X_new.shape[1], X_dev.data_ptr(),
+        off_dev.data_ptr() if off_dev is not None else None,
+        add_intercept=add_intercept, device=train.device, in_dtype='float64',
+        storage_dtype=getattr(train, 'storage_dtype', 'float64'))
+
+
+def _binomial_outcome(n_success, n_trial, n_row):
+    """The outcome checks of logistic_model.py:10-47 on n_row rows:
+    (n_success, n_trial, whether n_trial was left out)."""
+    n_success = np.asarray(n_success, dtype=np.float64)
+    binary_default = n_trial is None
+    if binary_default:
+        if n_success.size and n_success.max() > 1:
+            raise ValueError(
+                "n_trial is required when the outcome is not binary.")
+        n_trial = np.ones(n_success.shape)
+    else:
+        n_trial = np.asarray(n_trial, dtype=np.float64)
+    if not (n_success.shape == n_trial.shape == (n_row,)):
+        raise ValueError(
+            "Outcome vectors and design matrix have incompatible sizes: "
+            "%s successes, %s trials, %d rows."
+            % (n_success.shape, n_trial.shape, n_row))
+    if not binary_default:
+        if (n_trial <= 0).any():
+            raise ValueError("Every n_trial must be strictly positive.")
+        if (n_success > n_trial).any():
+            raise ValueError("n_success exceeds n_trial in some row.")
+    return n_success, n_trial, binary_default
+
+
+def _count_outcome(y, exposure, n_row):
+    """The outcome checks of the Poisson model on n_row rows: (y, exposure)."""
+    y = np.asarray(y, dtype=np.float64)
+    if exposure is None:
+        exposure = np.ones(y.shape)
+    else:
+        exposure = np.asarray(exposure, dtype=np.float64)
+    if not (y.shape == exposure.shape == (n_row,)):
+        raise ValueError(
+            "Outcome vectors and design matrix have incompatible sizes: "
+            "%s counts, %s exposures, %d rows."
+            % (y.shape, exposure.shape, n_row))
+    if not np.all(np.isfinite(y)) or (y < 0).any() \
+            or (y != np.floor(y)).any():
+        raise ValueError("Every count must be a non-negative integer.")
+    if not np.all(np.isfinite(exposure)) or (exposure <= 0).any():
+        raise ValueError(
+            "Every exposure must be strictly positive and finite.")
+    return y, exposure
+
+
+def _log_factorial(x):
+    """gammaln(x + 1).  Counts are small integers over and over: they take
+    the value from a table of gammaln itself (the same bits) instead of one
+    evaluation per row."""
+    from scipy.special import gammaln
+    x = np.asarray(x, dtype=np.float64)
+    if x.size and np.all(np.isfinite(x)) and 0 <= x.min() \
+            and x.max() <= 1 << 20:
+        k = x.astype(np.intp)
+        if np.array_equal(k, x):
+            return gammaln(np.arange(k.max() + 1) + 1.)[k]
+    return gammaln(x + 1.)
+
+
+class _Predictive():
+    """Posterior prediction and pointwise predictive scores of the linear,
+    logit and Poisson models (bbx_design_predictive_summary,
+    csrc/predict.hip): the draws' linear predictors stay on the device, one
+    kernel reduces them per row, n-vectors come back.  A model names its
+    family in `_pred_family` and checks its own outcome arguments in its
+    `predict`, which ends in `_predictive_summary`."""
+
+    def _predict_rows(self, coef, X_new):
+        """The shared checks of every predict: (draws (S, P), X_new as an
+        array or SciPy matrix or None, the number of rows)."""
+        draws, _ = _coef_draws(coef, self.n_pred)
+        if X_new is None:
+            return draws, None, self.n_obs
+        if not sparse.issparse(X_new):
+            X_new = np.asarray(X_new, dtype=np.float64)
+        n_col = self.n_pred - int(bool(self.intercept_added))
+        if X_new.ndim != 2 or X_new.shape[1] != n_col \
+                or X_new.shape[0] == 0:
+            raise ValueError(
+                "X_new must have at least one row and the model's %d "
+                "columns: shape %s." % (n_col, X_new.shape))
+        train = self.design
+        if train.centered and train.column_offset is None:
+            raise TypeError(
+                "The training design was adopted from device pointers "
+                "and keeps no host copy of its column offsets: X_new "
+                "cannot be centred with them.")
+        return draws, X_new, X_new.shape[0]
+
+    def _predictive_summary(self, draws, X_new, n_row, y=None, obs_prec=None,
+                            offset=None, n_trial=None, ll_const=None,
+                            return_draws=False, draws_per_pass=0):
+        """Every check is done: the device from here on."""
+        n_draw = len(draws)
+        if y is not None and n_draw < 2:
+            raise ValueError(
+                "Scoring an outcome needs at least 2 draws (loglik_var is a "
+                "variance over the draws): coef holds %d." % n_draw)
+        if X_new is None:
+            design = self.design
+        else:
+            design = _new_design(self.design, X_new,
+                                 bool(self.intercept_added))
+        if not getattr(design, 'use_hip', False):
+            raise TypeError("prediction needs a HipDesignMatrix")
+        arrays = [None if a is None
+                  else np.ascontiguousarray(a, dtype=np.float64)
+                  for a in (obs_prec, offset, y, n_trial, ll_const)]
+        mean, sd = np.empty(n_row), np.empty(n_row)
+        score = [np.empty(n_row) if y is not None else None for _ in range(3)]
+        out = np.empty((n_draw, n_row)) if return_draws else None
+        _lib.check(_lib.load().bbx_design_predictive_summary(
+            design.handle, self._pred_family, n_draw, _ptr(draws),
+            *[_ptr(a) for a in arrays], int(draws_per_pass), _ptr(mean),
+            _ptr(sd), *[_ptr(a) for a in score], _ptr(out)))
+        res = {'mean': mean, 'sd': sd}
+        if y is not None:
+            lpd, ll_mean, ll_var = score
+            lppd, p_waic = float(np.sum(lpd)), float(np.sum(ll_var))
+            res.update({'lpd': lpd, 'loglik_mean': ll_mean,
+                        'loglik_var': ll_var, 'lppd': lppd, 'p_waic': p_waic,
+                        'waic': -2. * (lppd - p_waic)})
+        if return_draws:
+            res['draws'] = out.T
+        return res
+
+
+def _training_rows_only(X_new, **given):
+    """With X_new=None the rows are the training rows and their outcome is
+    the model's own: no outcome argument may be given."""
+    if X_new is None:
+        for name, value in given.items():
+            if value is not None:
+                raise ValueError(
+                    "%s is an argument of new rows only: without X_new the "
+                    "training rows are predicted, with the model's own "
+                    "outcome." % name)
+
+
+class LinearModel(_Predictive, _Model):
+
+    _pred_family = _lib.PRED_LINEAR
 
     def __init__(self, y, design):
         self.y = np.asarray(y, dtype=np.float64)
@@ -61,15 +256,52 @@ class LinearModel(_Model):
     def calc_intercept_mle(self):
         return self.y.mean()
 
+    def predict(self, coef, X_new=None, y_new=None, obs_prec=None,
+                return_draws=False, _draws_per_pass=0):
+        """Posterior prediction over the draws coef (P,) or (P, S) -- what
+        samples['coef'] is -- with obs_prec (S,) -- samples['obs_prec'].
+        X_new=None: the training rows with the model's own outcome;
+        otherwise n_new rows of the model's raw columns (NumPy or SciPy),
+        centred with the TRAINING design's column means, with y_new or
+        without.  A dict: 'mean' and 'sd' (n,), the posterior mean of
+        E[y | x] and its population standard deviation over the draws; with
+        an outcome 'lpd' (the log pointwise predictive density of every
+        row), 'loglik_mean' and 'loglik_var' (n,) and the floats 'lppd' =
+        sum lpd, 'p_waic' = sum loglik_var and 'waic' = -2 (lppd - p_waic),
+        the log density being the normal's with precision obs_prec; with
+        return_draws 'draws' (n, S).  One device call for all the draws."""
+        draws, X_new, n_row = self._predict_rows(coef, X_new)
+        _training_rows_only(X_new, y_new=y_new)
+        y = self.y if X_new is None else y_new
+        if y is not None:
+            y = np.asarray(y, dtype=np.float64)
+            if y.shape != (n_row,):
+                raise ValueError(
+                    "Incompatible sizes of the outcome and design matrix.")
+        if obs_prec is None:
+            raise ValueError(
+                "obs_prec (one observation precision per draw, "
+                "samples['obs_prec']) is required.")
+        obs_prec = np.asarray(obs_prec, dtype=np.float64).reshape(-1)
+        if obs_prec.shape != (len(draws),):
+            raise ValueError(
+                "obs_prec must hold one value per draw: %d values, %d draws."
+                % (len(obs_prec), len(draws)))
+        if not np.all(np.isfinite(obs_prec)) or (obs_prec <= 0).any():
+            raise ValueError(
+                "Every obs_prec must be strictly positive and finite.")
+        ll_const = None
+        if y is not None:
+            ll_const = np.full(n_row, -.5 * math.log(2. * math.pi))
+        return self._predictive_summary(
+            draws, X_new, n_row, y=y, obs_prec=obs_prec, ll_const=ll_const,
+            return_draws=return_draws, draws_per_pass=_draws_per_pass)
+
     @staticmethod
     def simulate_outcome(X, beta, noise_sd, seed=None):
         if seed is not None:
             np.random.seed(seed)
         return X.dot(beta) + noise_sd * np.random.randn(X.shape[0])
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(c_void_p)
 
 
 class _DeviceHamiltonian():
@@ -202,35 +434,18 @@ class _DeviceHamiltonian():
         return q, logp.value, grad
 
 
-class LogisticModel(_DeviceHamiltonian, _Model):
+class LogisticModel(_DeviceHamiltonian, _Predictive, _Model):
 
     _handle_attr = '_logit'
+    _pred_family = _lib.PRED_LOGIT
 
     def __init__(self, n_success, n_trial, design):
         """Outcome checks of logistic_model.py:10-47: counts must line up with
         the rows of the design, 0 < n_trial, n_success <= n_trial; without
         n_trial the outcome has to be 0/1."""
-        n_row = design.shape[0]
-        n_success = np.asarray(n_success, dtype=np.float64)
-        binary_default = n_trial is None
+        n_success, n_trial, binary_default = _binomial_outcome(
+            n_success, n_trial, design.shape[0])
         if binary_default:
-            if n_success.size and n_success.max() > 1:
-                raise ValueError(
-                    "n_trial is required when the outcome is not binary.")
-            n_trial = np.ones(n_success.shape)
-        else:
-            n_trial = np.asarray(n_trial, dtype=np.float64)
-        if not (n_success.shape == n_trial.shape == (n_row,)):
-            raise ValueError(
-                "Outcome vectors and design matrix have incompatible sizes: "
-                "%s successes, %s trials, %d rows."
-                % (n_success.shape, n_trial.shape, n_row))
-        if not binary_default:
-            if (n_trial <= 0).any():
-                raise ValueError("Every n_trial must be strictly positive.")
-            if (n_success > n_trial).any():
-                raise ValueError("n_success exceeds n_trial in some row.")
-        else:
             warn("n_trial not given: treating the outcome as binary.")
         self.n_success = n_success
         self.n_trial = n_trial
@@ -279,6 +494,43 @@ class LogisticModel(_DeviceHamiltonian, _Model):
         p_hat = self.n_success.mean() / self.n_trial.mean()
         return np.log(p_hat / (1 - p_hat))
 
+    def predict(self, coef, X_new=None, y_new=None, n_trial_new=None,
+                return_draws=False, _draws_per_pass=0):
+        """Posterior prediction over the draws coef (P,) or (P, S) -- what
+        samples['coef'] is.  X_new=None: the training rows with the model's
+        own successes and trials; otherwise n_new rows of the model's raw
+        columns (NumPy or SciPy), centred with the TRAINING design's column
+        means, with y_new (successes; n_trial_new as in the constructor) or
+        without.  A dict: 'mean' and 'sd' (n,), the posterior mean of the
+        success probability per trial and its population standard deviation
+        over the draws; with an outcome 'lpd' (the log pointwise predictive
+        density of every row), 'loglik_mean' and 'loglik_var' (n,) and the
+        floats 'lppd' = sum lpd, 'p_waic' = sum loglik_var and 'waic' =
+        -2 (lppd - p_waic), the log density being the binomial's with its
+        coefficient; with return_draws 'draws' (n, S).  One device call for
+        all the draws."""
+        draws, X_new, n_row = self._predict_rows(coef, X_new)
+        _training_rows_only(X_new, y_new=y_new, n_trial_new=n_trial_new)
+        y = m = ll_const = None
+        if X_new is None:
+            y, m = self.n_success, self.n_trial
+        elif y_new is not None:
+            y, m, _ = _binomial_outcome(y_new, n_trial_new, n_row)
+            # (what bbx_logit_create refuses)
+            if not np.all(np.isfinite(y)) or not np.all(np.isfinite(m)) \
+                    or (y < 0).any():
+                raise ValueError(
+                    "Every count must be finite and non-negative.")
+        elif n_trial_new is not None:
+            raise ValueError("n_trial_new is an argument of scoring only: "
+                             "y_new is not given.")
+        if y is not None:
+            ll_const = (_log_factorial(m) - _log_factorial(y)
+                        - _log_factorial(m - y))
+        return self._predictive_summary(
+            draws, X_new, n_row, y=y, n_trial=m, ll_const=ll_const,
+            return_draws=return_draws, draws_per_pass=_draws_per_pass)
+
     @staticmethod
     def compute_polya_gamma_mean(shape, tilt):
         """logistic_model.py:80-87 (including its b/2 value at |tilt| <= 1e-5)."""
@@ -296,7 +548,7 @@ class LogisticModel(_DeviceHamiltonian, _Model):
         return np.random.binomial(n_trial, prob)
 
 
-class PoissonModel(_DeviceHamiltonian, _Model):
+class PoissonModel(_DeviceHamiltonian, _Predictive, _Model):
     """Incidence-rate regression: counts y_i with mean exposure_i exp(eta_i).
     The likelihood, its gradient and the Hessian-vector products run on the
     device through one bbx_poisson handle (csrc/poisson.hip); the coefficients
@@ -308,6 +560,7 @@ class PoissonModel(_DeviceHamiltonian, _Model):
     column."""
 
     _handle_attr = '_poisson'
+    _pred_family = _lib.PRED_POISSON
 
     def __init__(self, y, exposure, design, strata=None):
         """Counts must line up with the rows of the design and be
@@ -316,22 +569,7 @@ class PoissonModel(_DeviceHamiltonian, _Model):
         strata the rows must be stratum-major, the strata in the sorted order
         of their labels, and every stratum must hold a positive count."""
         n_row = design.shape[0]
-        y = np.asarray(y, dtype=np.float64)
-        if exposure is None:
-            exposure = np.ones(y.shape)
-        else:
-            exposure = np.asarray(exposure, dtype=np.float64)
-        if not (y.shape == exposure.shape == (n_row,)):
-            raise ValueError(
-                "Outcome vectors and design matrix have incompatible sizes: "
-                "%s counts, %s exposures, %d rows."
-                % (y.shape, exposure.shape, n_row))
-        if not np.all(np.isfinite(y)) or (y < 0).any() \
-                or (y != np.floor(y)).any():
-            raise ValueError("Every count must be a non-negative integer.")
-        if not np.all(np.isfinite(exposure)) or (exposure <= 0).any():
-            raise ValueError(
-                "Every exposure must be strictly positive and finite.")
+        y, exposure = _count_outcome(y, exposure, n_row)
         self.y = y
         self.exposure = exposure
         self.log_exposure = np.log(exposure)
@@ -404,6 +642,43 @@ class PoissonModel(_DeviceHamiltonian, _Model):
 
     def calc_intercept_mle(self):
         return np.log(self.y.sum() / self.exposure.sum())
+
+    def predict(self, coef, X_new=None, y_new=None, exposure_new=None,
+                return_draws=False, _draws_per_pass=0):
+        """Posterior prediction over the draws coef (P,) or (P, S) -- what
+        samples['coef'] is.  X_new=None: the training rows with the model's
+        own counts and exposure; otherwise n_new rows of the model's raw
+        columns (NumPy or SciPy), centred with the TRAINING design's column
+        means, with exposure_new (None: 1) and with y_new or without.  A
+        dict: 'mean' and 'sd' (n,), the posterior mean of the expected count
+        exposure * rate and its population standard deviation over the
+        draws; with an outcome 'lpd' (the log pointwise predictive density
+        of every row), 'loglik_mean' and 'loglik_var' (n,) and the floats
+        'lppd' = sum lpd, 'p_waic' = sum loglik_var and 'waic' =
+        -2 (lppd - p_waic), the log density being the Poisson's with its
+        -log y!; with return_draws 'draws' (n, S).  One device call for all
+        the draws.  The conditional Poisson model (strata) refuses: its
+        baseline rates are conditioned away."""
+        if self.strata is not None:
+            raise ValueError(
+                "The conditional Poisson model has nothing to predict: the "
+                "baseline rates of its strata are conditioned away.")
+        draws, X_new, n_row = self._predict_rows(coef, X_new)
+        _training_rows_only(X_new, y_new=y_new, exposure_new=exposure_new)
+        y = ll_const = None
+        if X_new is None:
+            y, offset = self.y, self.log_exposure
+        else:
+            y, exposure = _count_outcome(
+                np.zeros(n_row) if y_new is None else y_new, exposure_new,
+                n_row)
+            y = None if y_new is None else y
+            offset = None if exposure_new is None else np.log(exposure)
+        if y is not None:
+            ll_const = -_log_factorial(y)
+        return self._predictive_summary(
+            draws, X_new, n_row, y=y, offset=offset, ll_const=ll_const,
+            return_draws=return_draws, draws_per_pass=_draws_per_pass)
 
     @staticmethod
     def simulate_outcome(X, beta, exposure=None, seed=None):
@@ -1210,14 +1485,7 @@ class CoxModel(_DeviceHamiltonian, _Model):
     def _coef_draws(self, coef):
         """coef (P,) or (P, S) as (the draws (S, P) C-contiguous, whether a
         draw axis was given)."""
-        coef = np.asarray(coef, dtype=np.float64)
-        if coef.ndim not in (1, 2) or coef.shape[0] != self.n_pred \
-                or coef.size == 0:
-            raise ValueError(
-                "coef must have shape (%d,) or (%d, n_draw): %s."
-                % (self.n_pred, self.n_pred, coef.shape))
-        return (np.ascontiguousarray(coef.reshape(self.n_pred, -1).T),
-                coef.ndim == 2)
+        return _coef_draws(coef, self.n_pred)
 
     def _log_baseline_hazard(self, draws, grid_event):
         """bbx_<family>_baseline_hazard: (n_draw, grid_event.size)."""
@@ -1276,30 +1544,7 @@ class CoxModel(_DeviceHamiltonian, _Model):
     def _new_design(self, X_new):
         """X_new (raw columns) as a design centred with the TRAINING design's
         column offsets, by the constructors that keep constant columns."""
-        train = self.design
-        offset = train.column_offset if train.centered else None
-        if sparse.issparse(X_new):
-            X_new = X_new.tocsr().copy()
-            X_new.sort_indices()
-            return HipSparseDesignMatrix.from_csr_arrays(
-                X_new.shape, X_new.indptr, X_new.indices, X_new.data,
-                column_offset=offset, add_intercept=False,
-                device=train.device)
-        import torch
-        dev = 'cuda:%d' % train.device
-        X_dev = torch.from_numpy(
-            np.ascontiguousarray(X_new, dtype=np.float64)).to(dev)
-        off_dev = None
-        if offset is not None:
-            off_dev = torch.from_numpy(
-                np.ascontiguousarray(offset, dtype=np.float64)).to(dev)
-        torch.cuda.synchronize(train.device)
-        # (the arrays are copied: the tensors may go once it returns)
-        return HipDenseDesignMatrix.from_device_array(
-            X_new.shape[0], X_new.shape[1], X_dev.data_ptr(),
-            off_dev.data_ptr() if off_dev is not None else None,
-            add_intercept=False, device=train.device, in_dtype='float64',
-            storage_dtype=getattr(train, 'storage_dtype', 'float64'))
+        return _new_design(self.design, X_new, add_intercept=False)
 
     def predict_survival(self, coef, X_new=None, times=None, strata_new=None,
                          linear_predictor=None, return_draws=False):

@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-/* 113: + prediction from the Cox handles: the cumulative baseline hazard and
+/* 113: + bbx_design_predictive_summary: posterior prediction, log pointwise
+ *      predictive density and the WAIC terms of the linear, logit and Poisson
+ *      models.  One new symbol and nothing else, so the number stays 113.
+ *      + prediction from the Cox handles: the cumulative baseline hazard and
  *      the martingale residuals of every handle type (BBX_COX_PREDICT_DECL)
  *      and bbx_cox_survival_summary.  New symbols and nothing else, so the
  *      number stays 113.
@@ -1178,6 +1181,62 @@ int bbx_cox_survival_summary(int device, int64_t n_row, int64_t n_time,
                              const double* eta, const double* log_hazard,
                              const int32_t* group, double* mean, double* sd,
                              double* draws);
+
+/* ------------------------------------------- posterior prediction and scores
+ * Posterior prediction and pointwise predictive scores of the linear, logit
+ * and Poisson models on the rows of a design, from n_draw draws of the
+ * coefficients (csrc/predict.hip).  The design holds the rows to predict (n x
+ * P): the training design itself, or new rows centred with the training
+ * design's column offsets.  Every pointer is a host pointer.
+ *
+ * coef[n_draw][P] (draw-major).  Per draw s, eta = X~ coef_s through the
+ * launches of bbx_design_dot (the same bits), plus offset[n] where given
+ * (Poisson: the log exposure).  With m = n_trial (logit; NULL: 1) and c =
+ * ll_const (NULL: nothing is added):
+ *
+ *   BBX_PRED_LINEAR   mu = eta              ll = 0.5 log(tau_s) - 0.5 tau_s (y - eta)^2 + c
+ *   BBX_PRED_LOGIT    mu = 1/(1 + exp(-eta))  ll = y eta - m softplus(eta) + c
+ *   BBX_PRED_POISSON  mu = exp(eta)         ll = y eta - mu + c
+ *
+ * tau = obs_prec[n_draw], required for the linear model (finite and positive)
+ * and refused for the others.  softplus(x) = max(x, 0) + log1p(exp(-|x|)); the
+ * logit mu is exp(eta)/(1 + exp(eta)) for eta < 0; an overflowing Poisson mu
+ * is +inf and its ll -inf.
+ *
+ * mean[n], sd[n]: the mean of mu over the draws and its population standard
+ * deviation sqrt(M2 / n_draw), by Welford's update in draw order.  With y[n]
+ * (NULL: no scoring, and lpd, ll_mean, ll_var are not touched): ll_mean[n] and
+ * ll_var[n] = M2 / (n_draw - 1) by the same update on ll (n_draw == 1 gives
+ * 0/0), and lpd[n] = log((1/n_draw) sum_s exp(ll_s)) by an online
+ * log-sum-exp in draw order; a draw with ll = -inf adds exactly 0, every draw
+ * -inf gives -inf, a NaN stays a NaN.  mu_draws[n_draw][n] (draw-major): every
+ * mu, or NULL.
+ *
+ * The draws go through the device in passes of draws_per_pass (0: 16, fewer
+ * where 16 x n doubles, twice that with mu_draws, pass 256 MiB; never fewer
+ * than 1): that many products, then ONE summary kernel that walks the pass's
+ * draws in draw order, one update per draw, so no result depends on
+ * draws_per_pass.  All passes are enqueued back to back on the design's
+ * stream; ONE host synchronisation per call (the explicit one: the arrays are
+ * pageable host memory as far as the library knows).  No atomics: the same
+ * inputs give the same bits.  The call uses buffers of its own: no likelihood
+ * handle's location and no chain's state is touched.
+ *
+ * BBX_ERR_INVALID, with a bbx_last_error() that names the offender, for a NULL
+ * or destroyed design, a family out of range, n_draw < 1, a NULL coef, mean or
+ * sd, y with a NULL lpd, ll_mean or ll_var, the linear model without obs_prec,
+ * obs_prec with another family, an obs_prec[s] that is not finite and
+ * positive, draws_per_pass < 0.  These are checked before anything touches
+ * the device; the design stays usable. */
+#define BBX_PRED_LINEAR 0
+#define BBX_PRED_LOGIT 1
+#define BBX_PRED_POISSON 2
+int bbx_design_predictive_summary(
+    bbx_design* design, int family, int64_t n_draw, const double* coef,
+    const double* obs_prec, const double* offset, const double* y,
+    const double* n_trial, const double* ll_const, int draws_per_pass,
+    double* mean, double* sd, double* lpd, double* ll_mean, double* ll_var,
+    double* mu_draws);
 
 /* ----------------------------------------------------------- logit model
  * The binomial-logit likelihood of model/logistic_model.py:49-74 on a design
