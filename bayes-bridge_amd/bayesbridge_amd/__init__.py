@@ -8,13 +8,13 @@ from .cg_sampler import HipCGSampler
 from .device_chain import HipChainBatch, HipGibbsChain
 from .design_matrix import (HipDenseDesignMatrix, HipDesignMatrix,
                             HipSparseDesignMatrix)
-from .model import (CoxModel, LinearModel, LogisticModel, PoissonModel,
-                    RegressionModel, cpoisson_preprocess)
+from .model import (CoxModel, LinearModel, LogisticModel, NegBinModel,
+                    PoissonModel, RegressionModel, cpoisson_preprocess)
 from .prior import RegressionCoefPrior
 
 __all__ = [
     "BayesBridge", "RegressionModel", "RegressionCoefPrior", "SamplerOptions",
     "HipDesignMatrix", "HipSparseDesignMatrix", "HipDenseDesignMatrix",
-    "HipCGSampler", "HipGibbsChain", "HipChainBatch", "LinearModel", "LogisticModel", "CoxModel", "PoissonModel", "cpoisson_preprocess", "BbxError",
+    "HipCGSampler", "HipGibbsChain", "HipChainBatch", "LinearModel", "LogisticModel", "CoxModel", "PoissonModel", "NegBinModel", "cpoisson_preprocess", "BbxError",
     "device_count",
 ]

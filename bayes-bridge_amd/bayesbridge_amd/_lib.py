@@ -225,10 +225,19 @@ def _declare(lib):
             [hp, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
              c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
              c_void_p, c_void_p, c_void_p], c_int),
+        "bbx_design_predictive_summary_negbin": (
+            [hp, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_void_p], c_int),
         "bbx_logit_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_poisson_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_cpoisson_create": (
             [hp, c_void_p, c_void_p, c_int64, c_void_p, POINTER(hp)], c_int),
+        "bbx_negbin_create": (
+            [hp, c_void_p, c_void_p, c_double, POINTER(hp)], c_int),
+        "bbx_negbin_set_dispersion": ([hp, c_double], c_int),
+        "bbx_negbin_dispersion_loglik": (
+            [hp, c_void_p, c_int, c_void_p, c_void_p], c_int),
     }
     # the ten entry points every Hamiltonian likelihood handle has
     # (csrc/hamiltonian.hpp): the same argument lists in every family
@@ -253,7 +262,7 @@ def _declare(lib):
         "nuts_sample": [hp, c_void_p, POINTER(c_double), c_void_p],
     }
     for family in ("cox", "coxcp", "coxef", "coxw", "coxfg", "logit",
-                   "poisson", "cpoisson"):
+                   "poisson", "cpoisson", "negbin"):
         for entry, argtypes in shared.items():
             sigs["bbx_%s_%s" % (family, entry)] = (list(argtypes), c_int)
     for name, (argtypes, restype) in sigs.items():

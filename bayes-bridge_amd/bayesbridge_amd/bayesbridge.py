@@ -27,6 +27,7 @@ from warnings import warn
 import numpy as np
 
 from . import _lib
+from .dispersion import update_dispersion
 from .device_chain import HipGibbsChain
 from .hostrng import ReferenceRandom
 from .model import LogisticModel
@@ -43,7 +44,10 @@ HMC_INFO_KEYS = ('stepsize', 'n_hessian_matvec', 'n_grad_evals',
 NUTS_INFO_KEYS = HMC_INFO_KEYS[:6] + ('tree_height', 'ave_accept_prob')
 # models without an observation precision (or Polya-Gamma) parameter: their
 # chains carry no 'obs_prec' and draw the coefficients by 'hmc' / 'nuts' only
-NO_OBS_PREC = ('cox', 'poisson')
+NO_OBS_PREC = ('cox', 'poisson', 'negbin')
+# models whose only coefficient samplers are 'hmc' and 'nuts', and what the
+# refusals call them
+HAMILTONIAN_ONLY = {'poisson': 'Poisson', 'negbin': 'negative-binomial'}
 
 
 def _ptr(a):
@@ -112,15 +116,16 @@ class SamplerOptions():
                 coef_sampler_type = None
             options['coef_sampler_type'] = coef_sampler_type or 'hmc'
             return SamplerOptions(**options)
-        if model_name == 'poisson':
-            # no Polya-Gamma form: there is no Gaussian conditional for 'cg',
+        if model_name in HAMILTONIAN_ONLY:
+            # no Polya-Gamma form (the negative-binomial model has one, but
+            # not in this backend): there is no Gaussian conditional for 'cg',
             # 'cholesky' or 'woodbury' to draw from, and a chain that was
             # asked for one of them is not run with another sampler
             if coef_sampler_type not in (None, 'hmc', 'nuts'):
                 raise ValueError(
-                    "The Poisson model draws its coefficients with 'hmc' or "
+                    "The %s model draws its coefficients with 'hmc' or "
                     "'nuts' only; '%s' needs a Gaussian conditional."
-                    % coef_sampler_type)
+                    % (HAMILTONIAN_ONLY[model_name], coef_sampler_type))
             options['coef_sampler_type'] = coef_sampler_type or 'hmc'
             return SamplerOptions(**options)
         if model_name == 'logit' and coef_sampler_type in ('hmc', 'nuts'):
@@ -252,12 +257,14 @@ class BayesBridge():
             if not _is_hip_dense(self.model.design):
                 raise ValueError(
                     "Only 'cg' sampler supported with HIP matrices.")
-        if self.model.name == 'poisson' \
+        if self.model.name in HAMILTONIAN_ONLY \
                 and options.coef_sampler_type not in ('hmc', 'nuts'):
-            raise ValueError("The Poisson model draws its coefficients with "
-                             "'hmc' or 'nuts' only.")
+            raise ValueError("The %s model draws its coefficients with "
+                             "'hmc' or 'nuts' only."
+                             % HAMILTONIAN_ONLY[self.model.name])
         if options.coef_sampler_type in ('hmc', 'nuts') \
-                and self.model.name not in ('cox', 'logit', 'poisson'):
+                and self.model.name not in ('cox', 'logit', 'poisson',
+                                            'negbin'):
             # the reference's sample_by_hmc never passes obs_prec to the
             # linear model's likelihood
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
@@ -265,6 +272,8 @@ class BayesBridge():
             params_to_save = ('coef', 'local_scale', 'global_scale', 'logp')
             if self.model.name not in NO_OBS_PREC:    # bayesbridge.py:187-191
                 params_to_save += ('obs_prec',)
+            if self.model.name == 'negbin':
+                params_to_save += ('dispersion',)
         start_time = time.time()
         if options.rng == 'reference':
             if _device_out:
@@ -305,6 +314,10 @@ class BayesBridge():
                      else np.array(obs_prec, copy=True),
                      'local_scale': np.array(lscale, copy=True),
                      'global_scale': float(gscale)}
+        extra = dict(extra)
+        dispersion = extra.pop('_dispersion', None)
+        if dispersion is not None:          # the negative-binomial model
+            raw_state['dispersion'] = dispersion
         if self.prior._gscale_paramet == 'coef_magnitude':  # bayesbridge.py:244-251
             gscale, lscale = self.prior.adjust_scale(
                 gscale, lscale, to='coef_magnitude')
@@ -330,6 +343,8 @@ class BayesBridge():
                                                     gscale),
             '_markov_chain_state_raw': raw_state,
         }
+        if dispersion is not None:
+            mcmc_info['_markov_chain_state']['dispersion'] = dispersion
         mcmc_info.update(extra)
         return samples, mcmc_info
 
@@ -504,6 +519,8 @@ class BayesBridge():
                 samples['obs_prec'] = np.zeros((self.n_obs, n_sample))
         if 'logp' in params_to_save:
             samples['logp'] = np.zeros(n_sample)
+        if 'dispersion' in params_to_save and self.model.name == 'negbin':
+            samples['dispersion'] = np.zeros(n_sample)
         info_keys = {'hmc': HMC_INFO_KEYS, 'nuts': NUTS_INFO_KEYS,
                      'cg': ('n_cg_iter',)}.get(coef_sampler_type, ())
         return samples, {key: np.zeros(n_sample)      # gibbs_util.py:141-160
@@ -525,6 +542,26 @@ class BayesBridge():
         return LogisticModel.compute_polya_gamma_mean(
             self.model.n_trial, self.model.design.dot(coef))
 
+    def _initial_dispersion(self, init):
+        """The negative-binomial chain's first dispersion: the resumed
+        chain's, else init['dispersion'], else 1; a model with a fixed
+        dispersion keeps its own."""
+        model = self.model
+        if isinstance(init, dict) and '_raw' in init:
+            r = init['_raw']['dispersion']
+        else:
+            r = init.get('dispersion')
+        if model.dispersion_fixed:
+            if r is not None and float(r) != model.dispersion:
+                raise ValueError(
+                    "The model's dispersion is held fixed at %r: the initial "
+                    "state gives %r." % (model.dispersion, r))
+            return model.dispersion
+        r = 1. if r is None else float(r)
+        if not (math.isfinite(r) and r > 0.):
+            raise ValueError('An invalid initial state.')
+        return r
+
     def _initialize_chain(self, init, bridge_exp, update_local_scale,
                           update_obs_precision, update_global_scale,
                           sampler):
@@ -544,9 +581,11 @@ class BayesBridge():
             return (coef, obs_prec, lscale, gscale,
                     {'coef': coef, 'obs_prec': obs_prec,
                      'local_scale': lscale, 'global_scale': gscale}, None)
+        valid = ('coef', 'local_scale', 'global_scale', 'obs_prec', 'logp')
+        if self.model.name == 'negbin':
+            valid += ('dispersion',)
         for key in init:
-            if key not in ('coef', 'local_scale', 'global_scale', 'obs_prec',
-                           'logp'):
+            if key not in valid:
                 warn("'{:s}' is not a valid parameter name and "
                      "will be ignored.".format(key))
         coef_only_specified = 'coef' in init and ('global_scale' not in init)
@@ -684,6 +723,9 @@ class BayesBridge():
             return lscale
 
         def compute_posterior_logprob(coef, gscale, obs_prec):
+            # (negative binomial: the likelihood's beta-part at the current
+            # dispersion plus the priors below; neither G(y, r) - log y! nor
+            # the dispersion's prior is in logp)
             if model.name == 'linear':                   # bayesbridge.py:480-511
                 loglik, _ = model.compute_loglik_and_gradient(
                     coef, obs_prec, loglik_only=True)
@@ -702,10 +744,18 @@ class BayesBridge():
                 - hyper['rate'] * gscale
             return loglik + prior_logp
 
+        dispersion = None
+        if model.name == 'negbin':
+            # the model carries the chain's dispersion: the mode search, the
+            # coefficient draw and logp all evaluate the likelihood at it
+            dispersion = self._initial_dispersion(init)
+            model.dispersion = dispersion
         coef, obs_prec, lscale, gscale, init_used, optim_info = \
             self._initialize_chain(init, bridge_exp, update_local_scale,
                                    update_obs_precision, update_global_scale,
                                    sampler)
+        if dispersion is not None:
+            init_used['dispersion'] = dispersion
         samples, sampling_info = self._pre_allocate(
             n_iter - n_burnin, thin, params_to_save,
             options.coef_sampler_type)
@@ -728,6 +778,13 @@ class BayesBridge():
                     y_gaussian, design, obs_prec, gscale, lscale,
                     options.coef_sampler_type)
             obs_prec = update_obs_precision(coef)
+            if dispersion is not None and not model.dispersion_fixed:
+                # r | beta: one slice update on log r, its uniforms from the
+                # chain's host stream (dispersion.py states their order)
+                dispersion = update_dispersion(
+                    model, coef, dispersion, model.dispersion_prior,
+                    rg.np_random.uniform)
+                model.dispersion = dispersion
             gscale = update_global_scale(
                 gscale, coef[nu:], bridge_exp, method=options.gscale_update)
             lscale = update_local_scale(gscale, coef[nu:], bridge_exp)
@@ -747,6 +804,8 @@ class BayesBridge():
                         samples['obs_prec'][:, idx] = obs_prec
                 if 'logp' in samples:
                     samples['logp'][idx] = logp
+                if 'dispersion' in samples:
+                    samples['dispersion'][idx] = dispersion
                 for key in info_keys:
                     if key in info:
                         sampling_info[key][idx] = info[key]
@@ -759,6 +818,8 @@ class BayesBridge():
                 stamp = now
         extra = {'_random_gen_state': rg.get_state(),
                  '_reg_coef_sampler_state': sampler.get_internal_state()}
+        if dispersion is not None:
+            extra['_dispersion'] = dispersion
         return (samples, sampling_info, (coef, obs_prec, lscale, gscale),
                 init_used, optim_info, extra)
 

@@ -14,7 +14,10 @@ the posterior survival of new rows (csrc/cox_family.hpp,
 csrc/cox_predict.hip).  The linear, logit and Poisson models predict from
 their draws -- posterior mean and spread, log pointwise predictive density,
 WAIC -- with the draws' linear predictors kept on the device
-(csrc/predict.hip)."""
+(csrc/predict.hip).  The negative-binomial model (csrc/negbin.hip) is the
+Poisson model's overdispersed sibling: the same device path, one more
+parameter -- the dispersion, updated by dispersion.py inside the Gibbs loop --
+and the same prediction (csrc/negbin_predict.hip)."""
 import math
 from ctypes import byref, c_double, c_int, c_void_p
 from warnings import catch_warnings, simplefilter, warn
@@ -688,6 +691,222 @@ class PoissonModel(_DeviceHamiltonian, _Predictive, _Model):
         if seed is not None:
             np.random.seed(seed)
         return np.random.poisson(rate)
+
+
+class NegBinModel(_DeviceHamiltonian, _Predictive, _Model):
+    """Negative-binomial regression: counts y_i with mean mu_i = exposure_i
+    exp(eta_i) and variance mu_i + mu_i^2 / r.  The dispersion r > 0 is a
+    "size": r -> inf is the Poisson model.  The likelihood, its gradient and
+    the Hessian-vector products run on the device through one bbx_negbin
+    handle (csrc/negbin.hip); the coefficients are drawn by 'hmc' or 'nuts',
+    as the Poisson model's are, and the dispersion by a slice update on log r
+    (dispersion.py) right after them, unless it is given and held fixed.
+
+    With t = eta + log(exposure) - log r the log density of a row is
+    G(y, r) - log y! + y t - (y + r) softplus(t), G(y, r) = lgamma(y + r) -
+    lgamma(r).  compute_loglik_and_gradient and the samplers see the part
+    that depends on the coefficients, y t - (y + r) softplus(t): G - log y! is
+    constant in them and is left out, as the Poisson model leaves out its
+    constant.  dispersion_loglik adds G; predict scores with the full
+    density."""
+
+    _handle_attr = '_negbin'
+
+    def __init__(self, y, exposure, design, dispersion=None,
+                 dispersion_prior=None):
+        """The outcome checks of the Poisson model.  dispersion: None -- the
+        dispersion is a parameter of the chain, with the prior
+        dispersion_prior = {'shape': a0, 'rate': b0} (None: Gamma(2, 0.1),
+        whose shape keeps mass off r = 0), and starts at 1 -- or a finite,
+        positive number that is held fixed."""
+        from .dispersion import check_prior
+        n_row = design.shape[0]
+        y, exposure = _count_outcome(y, exposure, n_row)
+        self.y = y
+        self.exposure = exposure
+        self.log_exposure = np.log(exposure)
+        self.design = design
+        self.name = 'negbin'
+        self.dispersion_fixed = dispersion is not None
+        if dispersion is None:
+            dispersion = 1.
+        elif dispersion_prior is not None:
+            raise ValueError("dispersion_prior is the prior of a sampled "
+                             "dispersion: dispersion is given and held fixed.")
+        self._dispersion = self._checked_dispersion(dispersion)
+        self.dispersion_prior = check_prior(dispersion_prior)
+        # one bbx_negbin handle, made by the first call that needs it
+        self._ham_prefix = 'bbx_negbin_'
+        self._negbin = c_void_p()
+        self._location_serial = 0
+
+    @staticmethod
+    def _checked_dispersion(r):
+        try:
+            r = float(r)
+        except (TypeError, ValueError):
+            raise ValueError("The dispersion must be a number.") from None
+        if not (math.isfinite(r) and r > 0.):
+            raise ValueError("The dispersion must be finite and positive.")
+        return r
+
+    @property
+    def handle(self):
+        if not self._negbin:
+            if not getattr(self.design, 'use_hip', False):
+                raise TypeError("the device likelihood needs a HipDesignMatrix")
+            y = np.ascontiguousarray(self.y, dtype=np.float64)
+            o = np.ascontiguousarray(self.log_exposure, dtype=np.float64)
+            _lib.check(_lib.load().bbx_negbin_create(
+                self.design.handle, _ptr(y), _ptr(o), self._dispersion,
+                byref(self._negbin)))
+        return self._negbin
+
+    @property
+    def dispersion(self):
+        return self._dispersion
+
+    @dispersion.setter
+    def dispersion(self, r):
+        """bbx_negbin_set_dispersion: a Hessian operator made before it stops
+        working, as after a move of its location."""
+        r = self._checked_dispersion(r)
+        if self._negbin:
+            _lib.check(_lib.load().bbx_negbin_set_dispersion(self._negbin, r))
+            self._location_serial += 1
+        self._dispersion = r
+
+    def compute_loglik_and_gradient(self, beta, loglik_only=False):
+        """sum y t - (y + r) softplus(t) and X~^T (y - (y + r) sigma(t)), t =
+        eta + log(exposure) - log r, at the model's dispersion.  The terms
+        constant in beta (sum G(y, r) - log y!) are dropped.  Finite for
+        every finite beta: there is no exp(eta) to overflow; (-inf, None)
+        where an infinite eta makes the likelihood -inf."""
+        return self._device_loglik_and_gradient(beta, loglik_only)
+
+    # the trajectory's f(q0) (hmc.py:95-97) is the model's own likelihood
+    hamiltonian_loglik_and_gradient = compute_loglik_and_gradient
+
+    def get_hessian_matvec_operator(self, beta):
+        """v -> -X~^T (omega .* (X~ v)) at beta and the model's dispersion,
+        omega = (y + r) sigma(t) (1 - sigma(t)).  The handle holds one
+        location: an operator stops working once a later call has moved it or
+        the dispersion has changed."""
+        return self._hessian_operator(beta)
+
+    def calc_intercept_mle(self):
+        return np.log(self.y.sum() / self.exposure.sum())
+
+    def dispersion_loglik(self, coef, r):
+        """L(r) = sum_i G(y_i, r) + y_i t_i - (y_i + r) softplus(t_i) at the
+        coefficients coef, for r a scalar or up to 8 values, in one pass over
+        the rows (bbx_negbin_dispersion_loglik); a float or an array like r.
+        coef=None reuses the linear predictor of the previous call.  The
+        value for a given r depends neither on how many values are asked for
+        nor on its place among them.  The model's own dispersion is not
+        touched."""
+        scalar = np.ndim(r) == 0
+        r = np.ascontiguousarray(np.atleast_1d(r), dtype=np.float64)
+        if r.ndim != 1 or not 1 <= r.size <= 8:
+            raise ValueError("r must be a scalar or hold 1 to 8 values.")
+        if coef is not None:
+            coef = np.ascontiguousarray(coef, dtype=np.float64)
+            if coef.shape != (self.n_pred,):
+                raise ValueError("coef must have length %d" % self.n_pred)
+        out = np.empty(r.size)
+        _lib.check(_lib.load().bbx_negbin_dispersion_loglik(
+            self.handle, _ptr(coef), r.size, _ptr(r), _ptr(out)))
+        return float(out[0]) if scalar else out
+
+    def _predictive_summary(self, draws, X_new, n_row, y=None, obs_prec=None,
+                            offset=None, n_trial=None, ll_const=None,
+                            return_draws=False, draws_per_pass=0):
+        """_Predictive's, through bbx_design_predictive_summary_negbin;
+        obs_prec carries the draws' dispersion."""
+        n_draw = len(draws)
+        if y is not None and n_draw < 2:
+            raise ValueError(
+                "Scoring an outcome needs at least 2 draws (loglik_var is a "
+                "variance over the draws): coef holds %d." % n_draw)
+        if X_new is None:
+            design = self.design
+        else:
+            design = _new_design(self.design, X_new,
+                                 bool(self.intercept_added))
+        if not getattr(design, 'use_hip', False):
+            raise TypeError("prediction needs a HipDesignMatrix")
+        arrays = [None if a is None
+                  else np.ascontiguousarray(a, dtype=np.float64)
+                  for a in (obs_prec, offset, y, ll_const)]
+        mean, sd = np.empty(n_row), np.empty(n_row)
+        score = [np.empty(n_row) if y is not None else None for _ in range(3)]
+        out = np.empty((n_draw, n_row)) if return_draws else None
+        _lib.check(_lib.load().bbx_design_predictive_summary_negbin(
+            design.handle, n_draw, _ptr(draws), *[_ptr(a) for a in arrays],
+            int(draws_per_pass), _ptr(mean), _ptr(sd),
+            *[_ptr(a) for a in score], _ptr(out)))
+        res = {'mean': mean, 'sd': sd}
+        if y is not None:
+            lpd, ll_mean, ll_var = score
+            lppd, p_waic = float(np.sum(lpd)), float(np.sum(ll_var))
+            res.update({'lpd': lpd, 'loglik_mean': ll_mean,
+                        'loglik_var': ll_var, 'lppd': lppd, 'p_waic': p_waic,
+                        'waic': -2. * (lppd - p_waic)})
+        if return_draws:
+            res['draws'] = out.T
+        return res
+
+    def predict(self, coef, dispersion, X_new=None, y_new=None,
+                exposure_new=None, return_draws=False, _draws_per_pass=0):
+        """Posterior prediction over the draws coef (P,) or (P, S) -- what
+        samples['coef'] is -- with dispersion a scalar or one value per draw
+        -- samples['dispersion'].  The arguments and the dict are those of
+        PoissonModel.predict: 'mean' and 'sd' of the expected count exposure *
+        rate over the draws and, with an outcome, 'lpd', 'loglik_mean',
+        'loglik_var', 'lppd', 'p_waic' and 'waic' under the negative-binomial
+        log density with all its terms, G(y, r) - log y! included, so that a
+        WAIC compares with the Poisson model's.  One device call for all the
+        draws."""
+        draws, X_new, n_row = self._predict_rows(coef, X_new)
+        _training_rows_only(X_new, y_new=y_new, exposure_new=exposure_new)
+        r = np.asarray(dispersion, dtype=np.float64)
+        if r.ndim == 0:
+            r = np.full(len(draws), float(r))
+        if r.shape != (len(draws),):
+            raise ValueError(
+                "dispersion must be a scalar or hold one value per draw: "
+                "%s, %d draws." % (r.shape, len(draws)))
+        if not np.all(np.isfinite(r)) or (r <= 0).any():
+            raise ValueError(
+                "Every dispersion must be strictly positive and finite.")
+        y = ll_const = None
+        if X_new is None:
+            y, offset = self.y, self.log_exposure
+        else:
+            y, exposure = _count_outcome(
+                np.zeros(n_row) if y_new is None else y_new, exposure_new,
+                n_row)
+            y = None if y_new is None else y
+            offset = None if exposure_new is None else np.log(exposure)
+        if y is not None:
+            ll_const = -_log_factorial(y)
+        return self._predictive_summary(
+            draws, X_new, n_row, y=y, obs_prec=r, offset=offset,
+            ll_const=ll_const, return_draws=return_draws,
+            draws_per_pass=_draws_per_pass)
+
+    @staticmethod
+    def simulate_outcome(X, beta, dispersion, exposure=None, seed=None):
+        """Counts with mean mu = exposure exp(X beta) and variance mu + mu^2 /
+        dispersion: a Poisson count whose rate is mu times a Gamma(dispersion,
+        1 / dispersion) factor."""
+        mu = np.exp(np.asarray(X.dot(beta), dtype=np.float64).ravel())
+        if exposure is not None:
+            mu = mu * np.asarray(exposure, dtype=np.float64)
+        if seed is not None:
+            np.random.seed(seed)
+        r = float(dispersion)
+        return np.random.poisson(mu * np.random.gamma(r, 1. / r, mu.shape))
 
 
 def cox_sort_permutation(event_time, censoring_time):
@@ -1652,7 +1871,8 @@ class CoxModel(_DeviceHamiltonian, _Model):
 def RegressionModel(outcome, X, family='linear', add_intercept=None,
                     center_predictor=True, device=0, storage='auto',
                     dense_storage_dtype='float64', entry_time=None,
-                    ties='breslow', weights=None, competing_time=None):
+                    ties='breslow', weights=None, dispersion=None,
+                    dispersion_prior=None, competing_time=None):
     """model/factory.py:10-68 with the design placed on an MI355X.  `X` may be
     a SciPy sparse matrix, a NumPy array, or an already built HipDesignMatrix.
     For family='cox', outcome = (event_time, censoring_time) or, for the
@@ -1677,7 +1897,13 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     (y, exposure, strata) (exposure may be None):
     the rows are sorted stratum-major and uninformative strata dropped
     (cpoisson_preprocess) before the design goes to the GPU; a prebuilt
-    HipDesignMatrix must already be in that order."""
+    HipDesignMatrix must already be in that order.  For family='negbin',
+    outcome = y or (y, exposure); `dispersion` (None: sampled, with the prior
+    `dispersion_prior` = {'shape': .., 'rate': ..}, None: Gamma(2, 0.1); a
+    number: held fixed) is the negative-binomial size.  Strata are refused:
+    the conditional model has no negative-binomial form here.  (The two
+    keywords stand before `competing_time`, which stays the last one: pass
+    them by name.)"""
     if entry_time is not None and family != 'cox':
         raise ValueError("entry_time is an argument of family='cox' only.")
     if ties != 'breslow' and family != 'cox':
@@ -1686,6 +1912,17 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         raise ValueError("weights is an argument of family='cox' only.")
     if competing_time is not None and family != 'cox':
         raise ValueError("competing_time is an argument of family='cox' only.")
+    if dispersion is not None and family != 'negbin':
+        raise ValueError("dispersion is an argument of family='negbin' only.")
+    if dispersion_prior is not None and family != 'negbin':
+        raise ValueError(
+            "dispersion_prior is an argument of family='negbin' only.")
+    if family == 'negbin' and isinstance(outcome, tuple) \
+            and len(outcome) != 2:
+        raise ValueError(
+            "The negative-binomial model takes outcome = y or (y, exposure): "
+            "strata are not supported, the conditional model has no "
+            "negative-binomial form here.")
     stratified_poisson = (family == 'poisson' and isinstance(outcome, tuple)
                           and len(outcome) == 3)
     if add_intercept is None:
@@ -1839,4 +2076,10 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         else:
             y, exposure = outcome, None
         return PoissonModel(y, exposure, design)
+    if family == 'negbin':
+        if isinstance(outcome, tuple):
+            y, exposure = outcome
+        else:
+            y, exposure = outcome, None
+        return NegBinModel(y, exposure, design, dispersion, dispersion_prior)
     raise NotImplementedError()

@@ -90,12 +90,19 @@ def demo_beta(n_pred):
 
 
 def simulate_outcome(X, beta, model, intercept=0., n_trial=None, seed=None,
-                     censoring_frac=.9):
+                     censoring_frac=.9, dispersion=1., exposure=None):
     """simulate_data.py:8-27 for the linear and logit families; for 'cox',
-    (event_time, censoring_time) of cox_model.py:275-298."""
+    (event_time, censoring_time) of cox_model.py:275-298; for 'negbin',
+    counts with mean exposure exp(intercept + X beta) and size `dispersion`
+    (NegBinModel.simulate_outcome)."""
     if model == 'cox':
         from .model import CoxModel
         return CoxModel.simulate_outcome(X, beta, censoring_frac, seed)
+    if model == 'negbin':
+        from .model import NegBinModel
+        scale = np.exp(intercept) * (1. if exposure is None
+                                     else np.asarray(exposure, np.float64))
+        return NegBinModel.simulate_outcome(X, beta, dispersion, scale, seed)
     if seed is not None:
         np.random.seed(seed)
     if model == 'linear':

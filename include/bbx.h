@@ -40,6 +40,11 @@ extern "C" {
  *      the martingale residuals of every handle type (BBX_COX_PREDICT_DECL)
  *      and bbx_cox_survival_summary.  New symbols and nothing else, so the
  *      number stays 113.
+ *      + the negative-binomial likelihood with a dispersion parameter
+ *      (bbx_negbin_*: create, destroy, the shared entry points of every
+ *      likelihood handle, set_dispersion, dispersion_loglik) and its
+ *      prediction (bbx_design_predictive_summary_negbin).  New symbols and
+ *      nothing else, so the number stays 113.
  *      + the Fine-Gray competing-risks model (bbx_coxfg_*: create, destroy and
  *      the shared entry points of every likelihood handle).  New symbols and
  *      nothing else, so the number stays 113.
@@ -1238,6 +1243,26 @@ int bbx_design_predictive_summary(
     double* mean, double* sd, double* lpd, double* ll_mean, double* ll_var,
     double* mu_draws);
 
+/* The same summary for the negative-binomial model (csrc/negbin_predict.hip:
+ * one more instantiation of the summary kernel), from draws of the
+ * coefficients and of the dispersion: dispersion[n_draw], finite and positive.
+ * With r = dispersion[s], eta = X~ coef_s + offset and t = eta - log r:
+ *
+ *   mu = exp(eta)    ll = G(y, r) + y t - (y + r) softplus(t) + c
+ *
+ * G(y, r) = sum_{j < y} log(r + j) (see the negative-binomial model below);
+ * with c = -log y! this is the model's full log density.  The passes, the
+ * single synchronisation, the independence of draws_per_pass, the outputs and
+ * the refusals are those of bbx_design_predictive_summary; a NULL dispersion
+ * or a dispersion[s] that is not finite and positive is BBX_ERR_INVALID.
+ * bbx_design_predictive_summary itself keeps refusing every family code but
+ * the three above. */
+int bbx_design_predictive_summary_negbin(
+    bbx_design* design, int64_t n_draw, const double* coef,
+    const double* dispersion, const double* offset, const double* y,
+    const double* ll_const, int draws_per_pass, double* mean, double* sd,
+    double* lpd, double* ll_mean, double* ll_var, double* mu_draws);
+
 /* ----------------------------------------------------------- logit model
  * The binomial-logit likelihood of model/logistic_model.py:49-74 on a design
  * (intercept column and centred predictors included), with the trajectory and
@@ -1416,6 +1441,94 @@ int bbx_cpoisson_nuts_doubling(bbx_cpoisson* cpoisson, double dt,
                                double* averages);
 int bbx_cpoisson_nuts_sample(bbx_cpoisson* cpoisson, double* q, double* logp,
                              double* grad);
+
+/* ------------------------------------------------ negative-binomial model
+ * Overdispersed counts on a design (intercept column and centred predictors
+ * included): y_i >= 0 with mean mu_i = exp(eta_i + o_i), eta = X~ beta,
+ * o = log(exposure), and variance mu_i + mu_i^2 / r; the dispersion r > 0 is a
+ * "size", and r -> inf is the Poisson model (csrc/negbin.hip; the leapfrog and
+ * tree kernels are the Cox handle's, csrc/hamiltonian.hpp).  With
+ * t_i = (eta_i + o_i) - log r,
+ *   softplus(x) = max(x, 0) + log1p(exp(-|x|)),
+ *   sigma(x) = 1 / (1 + exp(-x)), exp(x) / (1 + exp(x)) for x < 0,
+ *   G(y, r) = sum_{j < y} log(r + j) = lgamma(y + r) - lgamma(r).
+ * The ten shared entry points have the argument lists, the status codes and
+ * the synchronisation of their bbx_logit_* counterparts above.  The handle
+ * borrows the design (it must outlive the handle) and runs on its stream.
+ * Every sum has a fixed order: the same inputs give the same bits on every
+ * call.
+ *
+ * create: y[n], log_exposure[n] (host; log_exposure may be NULL: all 0), the
+ * dispersion the handle starts with.  BBX_ERR_INVALID for a NULL y or output
+ * pointer, a destroyed or foreign design, a count that is negative or not
+ * finite, an offset that is not finite, a dispersion that is not finite and
+ * positive. */
+typedef struct bbx_negbin bbx_negbin;
+int bbx_negbin_create(bbx_design* design, const double* y,
+                      const double* log_exposure, double dispersion,
+                      bbx_negbin** out);
+int bbx_negbin_destroy(bbx_negbin* negbin);
+/* Replaces the handle's r.  It invalidates the Hessian's location (omega holds
+ * r): a later hessian_matvec without set_location is BBX_ERR_STATE.
+ * BBX_ERR_INVALID for an r that is not finite and positive; BBX_ERR_STATE
+ * between bbx_negbin_nuts_begin and bbx_negbin_nuts_sample, while a
+ * No-U-Turn tree built with the previous r is open. */
+int bbx_negbin_set_dispersion(bbx_negbin* negbin, double r);
+/* loglik = sum_i y_i t_i - (y_i + r) softplus(t_i), the part of the log
+ * density that depends on beta (sum_i G(y_i, r) - log y_i! is dropped);
+ * grad[P] = X~^T w, w_i = y_i - (y_i + r) sigma(t_i).  There is no exp(eta):
+ * both are finite for every finite beta.  An infinite eta gives loglik = -inf
+ * (grad is then not meaningful) or NaN; a NaN in beta gives NaN.  grad may be
+ * NULL. */
+int bbx_negbin_loglik_grad(bbx_negbin* negbin, const double* beta,
+                           double* loglik, double* grad);
+int bbx_negbin_loglik_grad_dev(bbx_negbin* negbin, const double* d_beta,
+                               double* loglik, double* d_grad);
+/* Hessian-vector products at a fixed beta and the handle's r: set_location
+ * stores omega_i = (y_i + r) sigma(t_i) (1 - sigma(t_i)); hessian_matvec gives
+ * out = -X~^T (omega .* (X~ v)) (BBX_ERR_STATE before a set_location, and
+ * after a set_dispersion until the next one). */
+int bbx_negbin_set_location(bbx_negbin* negbin, const double* beta);
+int bbx_negbin_hessian_matvec(bbx_negbin* negbin, const double* v,
+                              double* out);
+int bbx_negbin_hessian_matvec_dev(bbx_negbin* negbin, const double* d_v,
+                                  double* d_out);
+/* bbx_cox_hmc_trajectory on the negative-binomial f.  A step at which the
+ * likelihood is -inf (an infinite eta) is the last one: logp = -inf,
+ * *instability = 1. */
+int bbx_negbin_hmc_trajectory(bbx_negbin* negbin, double dt, int n_step,
+                              const double* precond_scale,
+                              const double* prior_prec, const double* q0,
+                              const double* p0, double logp0,
+                              const double* grad0, double hamiltonian_tol,
+                              double* q, double* p, double* logp,
+                              double* grad, int* n_grad_evals,
+                              int* instability, double* hamiltonian);
+/* bbx_cox_nuts_begin / _doubling / _sample on the negative-binomial f. */
+int bbx_negbin_nuts_begin(bbx_negbin* negbin, const double* precond_scale,
+                          const double* prior_prec, const double* q0,
+                          const double* p0, double logp0, const double* grad0,
+                          double joint_logp0, double joint_logp_threshold,
+                          double hamiltonian_tol);
+int bbx_negbin_nuts_doubling(bbx_negbin* negbin, double dt, int direction,
+                             int height, const double* uniforms,
+                             int* n_uniform_used, int* n_steps, int* flags,
+                             int* tree, double* averages);
+int bbx_negbin_nuts_sample(bbx_negbin* negbin, double* q, double* logp,
+                           double* grad);
+/* out[k] = L(r[k]) = sum_i G(y_i, r[k]) + y_i t_i - (y_i + r[k]) softplus(t_i),
+ * t_i = (eta_i + o_i) - log r[k], for n_r values of r (1 <= n_r <= 8; host
+ * arrays) in ONE pass over the rows: what the dispersion's conditional
+ * density needs.  beta[P] (host): eta = X~ beta is formed and kept on the
+ * handle; NULL: the eta of the previous call on this handle (BBX_ERR_STATE if
+ * there was none).  One launch of the row kernel, plus the product for a
+ * non-NULL beta; one synchronisation.  out[k] depends on r[k] alone: neither
+ * on n_r nor on k, bit for bit.  The handle's r, its Hessian location and the
+ * scratch of a trajectory or an open tree are not touched.  BBX_ERR_INVALID
+ * for n_r outside [1, 8], a NULL r or out, an r[k] that is not finite and
+ * positive. */
+int bbx_negbin_dispersion_loglik(bbx_negbin* negbin, const double* beta,
+                                 int n_r, const double* r, double* out);
 
 /* ----------------------- host-side reference-stream samplers (libbbx_hostrng)
  * Exported by the separate, HIP-free libbbx_hostrng.so.  `bitgen` is the
