@@ -25,7 +25,7 @@
 // eta: this family has no overflow or empty-sum case and never raises
 // CoxTraj::zero.  A NaN in eta comes out of the sums as a NaN.
 //
-// Contract (cox_strat.hpp, poisson.hip): the partition is FIXED by n alone --
+// Contract (cox_strat.hpp, glm_rows.hpp): the partition is FIXED by n alone --
 // the row range [0, n) is cut into CP_G chunks of ceil(n / CP_G) rows, scanned
 // in tiles of CP_BLOCK x CP_E -- and neither the number nor the sizes of the
 // strata enter it or the number of launches.  Pass A (cp_agg_kernel) leaves one
@@ -33,7 +33,7 @@
 // before its own in order, scans its chunk again and writes L_s at the last
 // row of every stratum; the row kernel (cp_row_kernel) computes pi, w and the
 // NPART partials of sum ll and sum w over the (i / VEC_BLOCK) % NPART partition
-// of poisson.hip, which launch_tdot and the post kernels consume unchanged.
+// of glm_rows.hpp, which launch_tdot and the post kernels consume unchanged.
 // The Hessian's ubar_s is the same two passes under the plain sum.  No float
 // atomics, every combination in a fixed order: the same inputs give the same
 // bits on every run.  Nothing synchronises with the host.
@@ -315,7 +315,7 @@ enum CpMode {
 
 // `a`: eta (CM_GRAD, CM_LOC) or u = X~ v (CM_HESS); `ps`: L_s (CM_GRAD,
 // CM_LOC) or ubar_s (CM_HESS) per stratum; `pi`: the location's pi (CM_HESS);
-// `out`: w or pi.  poisson_row_kernel's partition and lap order.
+// `out`: w or pi.  glm_row_kernel's partition and lap order (glm_rows.hpp).
 template <int MODE>
 static __global__ __launch_bounds__(VEC_BLOCK) void cp_row_kernel(
     int64_t n, const double* __restrict__ a, const CpRow* __restrict__ row,

@@ -1,8 +1,8 @@
 // The preconditioned Hamiltonian trajectory shared by the likelihood families
-// (cox.hip, cox_interval.hip, logit.hip, poisson.hip, cpoisson.hip): the
-// leapfrog kernels, the No-U-Turn tree, their drivers and the front of the C
-// ABI (the ten entry points every handle has).  Velocity Verlet in
-// preconditioned coordinates
+// (the Cox handles on cox_family.hpp; logit.hip, poisson.hip and negbin.hip on
+// glm_rows.hpp; cpoisson.hip): the leapfrog kernels, the No-U-Turn tree, their
+// drivers and the front of the C ABI (the ten entry points every handle has).
+// Velocity Verlet in preconditioned coordinates
 // q = coef / scale, f(q) = loglik(scale q) - 1/2 sum prior_prec q^2
 // (hmc.py:137-174, dynamics.py, nuts.py).
 //
@@ -479,8 +479,9 @@ static __global__ __launch_bounds__(WAVE) void cox_nuts_merge_b_kernel(
 }
 // ---------------------------------------------------------------- host side
 // What the trajectory, the tree and the C ABI front need from a likelihood
-// handle; bbx_cox, bbx_logit, bbx_poisson and bbx_cpoisson derive from it (the
-// design is borrowed: it must outlive them).
+// handle; every handle derives from it -- the Cox ones through CoxCore, the
+// row-wise GLM ones through GlmRowsCore, bbx_cpoisson directly (the design is
+// borrowed: it must outlive them).
 struct HamCore {
   bbx_design* h = nullptr;
   int device = 0;

@@ -43,6 +43,16 @@ def _resource_table(src, tmp_path):
     return table
 
 
+def glm_row_occupancy(table):
+    """Occupancy [waves/SIMD] of the three modes (GRAD, LOC, HESS) of the one
+    glm_row_kernel that a row-wise family's file instantiates."""
+    # (anonymous namespace)::<Policy>, <mode>: ...<Policy>ELi<mode>EEEv...
+    modes = {int(re.search(r'ELi(\d)EEEv', k).group(1)): res
+             for k, res in table.items() if "glm_row_kernel" in k}
+    assert sorted(modes) == [0, 1, 2], sorted(table)
+    return tuple(modes[m]["Occupancy [waves/SIMD]"] for m in range(3))
+
+
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_cholesky_kernels_do_not_spill(tmp_path):
     table = _resource_table(

@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 
 RTOL, ATOL = 1e-6, 1e-9          # the seeded Hamiltonian chains' tolerance
 
-U = _constant('NEGBIN_U', 'negbin.hip')
+U = _constant('GLM_ROW_U', 'glm_rows.hpp')
 ROWS = (1, VEC_BLOCK - 1, VEC_BLOCK + 1, LAP + 1, U * LAP + 3)
 DISPERSIONS = (.05, 1., 30., 1e4)
 

@@ -34,7 +34,7 @@ def _constant(name, src):
 # NPART, a thread keeps U rows of consecutive laps in flight
 VEC_BLOCK = _constant('VEC_BLOCK', 'common.hpp')
 NPART = _constant('NPART', 'common.hpp')
-U = _constant('POISSON_U', 'poisson.hip')
+U = _constant('GLM_ROW_U', 'glm_rows.hpp')
 LAP = NPART * VEC_BLOCK
 ROWS = (1, VEC_BLOCK - 1, VEC_BLOCK + 1, LAP + 1, U * LAP + 3)
 KINDS = ('tiled_binary', 'csr_valued', 'dense64', 'dense32', 'mixed')

@@ -11,7 +11,8 @@ import scipy.sparse as sparse
 
 import logit_oracle as lo
 from conftest import ROOT
-from test_cholesky_kernel_resources import HIPCC, _resource_table
+from test_cholesky_kernel_resources import (HIPCC, _resource_table,
+                                            glm_row_occupancy)
 
 
 class _Design:
@@ -145,7 +146,11 @@ def test_logit_kernels_use_no_scratch(tmp_path):
     table = _resource_table(
         os.path.join(ROOT, "bayes-bridge_amd", "csrc", "logit.hip"), tmp_path)
     # the three modes of the row kernel and the shared trajectory kernels
-    assert sum("logit_row_kernel" in k for k in table) == 3
+    assert sum("glm_row_kernel" in k for k in table) == 3
+    # no fewer waves per SIMD than logit_row_kernel<GRAD / LOC / HESS> had
+    # before the fold onto glm_rows.hpp (116 / 72 / 50 VGPRs)
+    occupancy = glm_row_occupancy(table)
+    assert all(got >= was for got, was in zip(occupancy, (4, 7, 8))), occupancy
     for k in ("cox_step1_kernel", "cox_post_a_kernel", "cox_post_b_kernel",
               "cox_finish_kernel", "cox_nuts_leaf_kernel",
               "cox_nuts_merge_a_kernel", "cox_nuts_merge_b_kernel"):
