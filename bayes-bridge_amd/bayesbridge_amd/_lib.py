@@ -238,6 +238,14 @@ def _declare(lib):
         "bbx_negbin_set_dispersion": ([hp, c_double], c_int),
         "bbx_negbin_dispersion_loglik": (
             [hp, c_void_p, c_int, c_void_p, c_void_p], c_int),
+        "bbx_design_predictive_summary_ordinal": (
+            [hp, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+        "bbx_ordinal_create": (
+            [hp, c_void_p, c_void_p, c_int, c_void_p, POINTER(hp)], c_int),
+        "bbx_ordinal_set_cutpoints": ([hp, c_void_p], c_int),
+        "bbx_ordinal_cutpoint_loglik": (
+            [hp, c_void_p, c_int, c_void_p, c_void_p], c_int),
     }
     # the ten entry points every Hamiltonian likelihood handle has
     # (csrc/hamiltonian.hpp): the same argument lists in every family
@@ -262,7 +270,7 @@ def _declare(lib):
         "nuts_sample": [hp, c_void_p, POINTER(c_double), c_void_p],
     }
     for family in ("cox", "coxcp", "coxef", "coxw", "coxfg", "logit",
-                   "poisson", "cpoisson", "negbin"):
+                   "poisson", "cpoisson", "negbin", "ordinal"):
         for entry, argtypes in shared.items():
             sigs["bbx_%s_%s" % (family, entry)] = (list(argtypes), c_int)
     for name, (argtypes, restype) in sigs.items():

@@ -27,6 +27,8 @@ from warnings import warn
 import numpy as np
 
 from . import _lib
+from .cutpoints import (check_cutpoints, initial_cutpoints,
+                        update_cutpoints)
 from .dispersion import update_dispersion
 from .device_chain import HipGibbsChain
 from .hostrng import ReferenceRandom
@@ -44,10 +46,11 @@ HMC_INFO_KEYS = ('stepsize', 'n_hessian_matvec', 'n_grad_evals',
 NUTS_INFO_KEYS = HMC_INFO_KEYS[:6] + ('tree_height', 'ave_accept_prob')
 # models without an observation precision (or Polya-Gamma) parameter: their
 # chains carry no 'obs_prec' and draw the coefficients by 'hmc' / 'nuts' only
-NO_OBS_PREC = ('cox', 'poisson', 'negbin')
+NO_OBS_PREC = ('cox', 'poisson', 'negbin', 'ordinal')
 # models whose only coefficient samplers are 'hmc' and 'nuts', and what the
 # refusals call them
-HAMILTONIAN_ONLY = {'poisson': 'Poisson', 'negbin': 'negative-binomial'}
+HAMILTONIAN_ONLY = {'poisson': 'Poisson', 'negbin': 'negative-binomial',
+                    'ordinal': 'ordinal'}
 
 
 def _ptr(a):
@@ -264,7 +267,7 @@ class BayesBridge():
                              % HAMILTONIAN_ONLY[self.model.name])
         if options.coef_sampler_type in ('hmc', 'nuts') \
                 and self.model.name not in ('cox', 'logit', 'poisson',
-                                            'negbin'):
+                                            'negbin', 'ordinal'):
             # the reference's sample_by_hmc never passes obs_prec to the
             # linear model's likelihood
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
@@ -274,6 +277,8 @@ class BayesBridge():
                 params_to_save += ('obs_prec',)
             if self.model.name == 'negbin':
                 params_to_save += ('dispersion',)
+            if self.model.name == 'ordinal':
+                params_to_save += ('cutpoints',)
         start_time = time.time()
         if options.rng == 'reference':
             if _device_out:
@@ -318,6 +323,9 @@ class BayesBridge():
         dispersion = extra.pop('_dispersion', None)
         if dispersion is not None:          # the negative-binomial model
             raw_state['dispersion'] = dispersion
+        cutpoints = extra.pop('_cutpoints', None)
+        if cutpoints is not None:           # the ordinal model
+            raw_state['cutpoints'] = np.array(cutpoints, copy=True)
         if self.prior._gscale_paramet == 'coef_magnitude':  # bayesbridge.py:244-251
             gscale, lscale = self.prior.adjust_scale(
                 gscale, lscale, to='coef_magnitude')
@@ -345,6 +353,9 @@ class BayesBridge():
         }
         if dispersion is not None:
             mcmc_info['_markov_chain_state']['dispersion'] = dispersion
+        if cutpoints is not None:
+            mcmc_info['_markov_chain_state']['cutpoints'] = np.array(
+                cutpoints, copy=True)
         mcmc_info.update(extra)
         return samples, mcmc_info
 
@@ -521,6 +532,9 @@ class BayesBridge():
             samples['logp'] = np.zeros(n_sample)
         if 'dispersion' in params_to_save and self.model.name == 'negbin':
             samples['dispersion'] = np.zeros(n_sample)
+        if 'cutpoints' in params_to_save and self.model.name == 'ordinal':
+            samples['cutpoints'] = np.zeros((self.model.n_category - 1,
+                                             n_sample))
         info_keys = {'hmc': HMC_INFO_KEYS, 'nuts': NUTS_INFO_KEYS,
                      'cg': ('n_cg_iter',)}.get(coef_sampler_type, ())
         return samples, {key: np.zeros(n_sample)      # gibbs_util.py:141-160
@@ -562,6 +576,30 @@ class BayesBridge():
             raise ValueError('An invalid initial state.')
         return r
 
+    def _initial_cutpoints(self, init):
+        """The ordinal chain's first cutpoints: the resumed chain's, else
+        init['cutpoints'], else the empirical logits of the cumulative
+        category proportions; a model with fixed cutpoints keeps its own."""
+        model = self.model
+        if isinstance(init, dict) and '_raw' in init:
+            cuts = init['_raw']['cutpoints']
+        else:
+            cuts = init.get('cutpoints')
+        if cuts is not None:
+            try:
+                cuts = check_cutpoints(cuts, model.n_category)
+            except ValueError:
+                raise ValueError('An invalid initial state.') from None
+        if model.cutpoints_fixed:
+            if cuts is not None and not np.array_equal(cuts, model.cutpoints):
+                raise ValueError(
+                    "The model's cutpoints are held fixed at %r: the initial "
+                    "state gives %r." % (model.cutpoints, cuts))
+            return model.cutpoints
+        if cuts is None:
+            cuts = initial_cutpoints(model.y, model.n_category)
+        return cuts
+
     def _initialize_chain(self, init, bridge_exp, update_local_scale,
                           update_obs_precision, update_global_scale,
                           sampler):
@@ -584,6 +622,8 @@ class BayesBridge():
         valid = ('coef', 'local_scale', 'global_scale', 'obs_prec', 'logp')
         if self.model.name == 'negbin':
             valid += ('dispersion',)
+        if self.model.name == 'ordinal':
+            valid += ('cutpoints',)
         for key in init:
             if key not in valid:
                 warn("'{:s}' is not a valid parameter name and "
@@ -725,7 +765,8 @@ class BayesBridge():
         def compute_posterior_logprob(coef, gscale, obs_prec):
             # (negative binomial: the likelihood's beta-part at the current
             # dispersion plus the priors below; neither G(y, r) - log y! nor
-            # the dispersion's prior is in logp)
+            # the dispersion's prior is in logp; ordinal: the whole likelihood
+            # at the iteration's cutpoints, without the cutpoints' prior)
             if model.name == 'linear':                   # bayesbridge.py:480-511
                 loglik, _ = model.compute_loglik_and_gradient(
                     coef, obs_prec, loglik_only=True)
@@ -750,12 +791,19 @@ class BayesBridge():
             # coefficient draw and logp all evaluate the likelihood at it
             dispersion = self._initial_dispersion(init)
             model.dispersion = dispersion
+        cutpoints = None
+        if model.name == 'ordinal':
+            # likewise: the model carries the chain's cutpoints
+            cutpoints = self._initial_cutpoints(init)
+            model.cutpoints = cutpoints
         coef, obs_prec, lscale, gscale, init_used, optim_info = \
             self._initialize_chain(init, bridge_exp, update_local_scale,
                                    update_obs_precision, update_global_scale,
                                    sampler)
         if dispersion is not None:
             init_used['dispersion'] = dispersion
+        if cutpoints is not None:
+            init_used['cutpoints'] = np.array(cutpoints, copy=True)
         samples, sampling_info = self._pre_allocate(
             n_iter - n_burnin, thin, params_to_save,
             options.coef_sampler_type)
@@ -785,6 +833,14 @@ class BayesBridge():
                     model, coef, dispersion, model.dispersion_prior,
                     rg.np_random.uniform)
                 model.dispersion = dispersion
+            if cutpoints is not None and not model.cutpoints_fixed:
+                # c_k | beta, the others: one slice update per cutpoint, in
+                # increasing order, their uniforms from the chain's host
+                # stream (cutpoints.py)
+                cutpoints = update_cutpoints(
+                    model, coef, cutpoints, model.cutpoint_prior,
+                    rg.np_random.uniform)
+                model.cutpoints = cutpoints
             gscale = update_global_scale(
                 gscale, coef[nu:], bridge_exp, method=options.gscale_update)
             lscale = update_local_scale(gscale, coef[nu:], bridge_exp)
@@ -806,6 +862,8 @@ class BayesBridge():
                     samples['logp'][idx] = logp
                 if 'dispersion' in samples:
                     samples['dispersion'][idx] = dispersion
+                if 'cutpoints' in samples:
+                    samples['cutpoints'][:, idx] = cutpoints
                 for key in info_keys:
                     if key in info:
                         sampling_info[key][idx] = info[key]
@@ -820,6 +878,8 @@ class BayesBridge():
                  '_reg_coef_sampler_state': sampler.get_internal_state()}
         if dispersion is not None:
             extra['_dispersion'] = dispersion
+        if cutpoints is not None:
+            extra['_cutpoints'] = cutpoints
         return (samples, sampling_info, (coef, obs_prec, lscale, gscale),
                 init_used, optim_info, extra)
 

@@ -17,7 +17,11 @@ WAIC -- with the draws' linear predictors kept on the device
 (csrc/predict.hip).  The negative-binomial model (csrc/negbin.hip) is the
 Poisson model's overdispersed sibling: the same device path, one more
 parameter -- the dispersion, updated by dispersion.py inside the Gibbs loop --
-and the same prediction (csrc/negbin_predict.hip)."""
+and the same prediction (csrc/negbin_predict.hip).  The ordinal model
+(csrc/ordinal.hip) is the proportional-odds model of an ordered outcome on the
+same device path: its K - 1 cutpoints are updated by cutpoints.py inside the
+Gibbs loop, and it predicts the K category probabilities
+(csrc/ordinal_predict.hip)."""
 import math
 from ctypes import byref, c_double, c_int, c_void_p
 from warnings import catch_warnings, simplefilter, warn
@@ -907,6 +911,253 @@ class NegBinModel(_DeviceHamiltonian, _Predictive, _Model):
             np.random.seed(seed)
         r = float(dispersion)
         return np.random.poisson(mu * np.random.gamma(r, 1. / r, mu.shape))
+
+
+def _ordinal_outcome(y, offset, n_row, n_category=None):
+    """The outcome checks of the ordinal model on n_row rows: (y, offset,
+    K).  n_category=None: K = max y + 1 and every category must hold a row;
+    otherwise the categories of new rows, 0 ... n_category - 1."""
+    y = np.asarray(y, dtype=np.float64)
+    offset = np.zeros(y.shape) if offset is None \
+        else np.asarray(offset, dtype=np.float64)
+    if not (y.shape == offset.shape == (n_row,)):
+        raise ValueError(
+            "Outcome vectors and design matrix have incompatible sizes: "
+            "%s categories, %s offsets, %d rows."
+            % (y.shape, offset.shape, n_row))
+    if not np.all(np.isfinite(y)) or (y < 0).any() \
+            or (y != np.floor(y)).any():
+        raise ValueError("Every category must be a non-negative integer.")
+    if not np.all(np.isfinite(offset)):
+        raise ValueError("Every offset must be finite.")
+    top = int(y.max()) + 1 if y.size else 0
+    if n_category is None:
+        if not 2 <= top <= OrdinalModel.MAX_CATEGORY:
+            raise ValueError(
+                "The ordinal model takes 2 to %d categories, 0 ... K - 1: "
+                "the outcome's largest is %d."
+                % (OrdinalModel.MAX_CATEGORY, top - 1))
+        counts = np.bincount(y.astype(np.intp), minlength=top)
+        if (counts == 0).any():
+            raise ValueError(
+                "Category %d of 0 ... %d has no row: recode the outcome to "
+                "consecutive categories." % (int(np.argmin(counts > 0)),
+                                             top - 1))
+        n_category = top
+    elif top > n_category:
+        raise ValueError("The model has the categories 0 ... %d: the "
+                         "outcome holds %d." % (n_category - 1, top - 1))
+    return y, offset, n_category
+
+
+class OrdinalModel(_DeviceHamiltonian, _Model):
+    """Proportional-odds (cumulative logit) regression of an ordered outcome:
+    categories y_i in {0, ..., K - 1}, 2 <= K <= 16, with P(y_i <= k) =
+    sigma(c_{k+1} - (eta_i + o_i)) for cutpoints c_1 < ... < c_{K-1} and an
+    optional per-row offset o.  The design has no intercept column: the
+    cutpoints are the intercepts (centring the predictors only shifts them).
+    The likelihood, its gradient and the Hessian-vector products run on the
+    device through one bbx_ordinal handle (csrc/ordinal.hip); the
+    coefficients are drawn by 'hmc' or 'nuts' and the cutpoints by one slice
+    update each (cutpoints.py) right after them, unless they are given and
+    held fixed.
+
+    With a = c_{y+1} - (eta + o) and b = c_y - (eta + o) the log-probability
+    of a row is g_y - softplus(-a) - softplus(b), g_k = log(1 - exp(-(c_{k+1}
+    - c_k))) for the inner categories and 0 for the two end ones (where the
+    softplus term of the infinite cutpoint is absent): every term is kept, g
+    depends on the cutpoints."""
+
+    _handle_attr = '_ordinal'
+    MAX_CATEGORY = 16
+
+    def __init__(self, y, design, offset=None, cutpoints=None,
+                 cutpoint_prior=None):
+        """y: integers 0 ... K - 1, every category with at least one row;
+        offset (None: 0) finite.  cutpoints: None -- they are parameters of
+        the chain, with the prior cutpoint_prior = {'sd': s} (None: 10), c_k ~
+        N(0, s^2) on the ordered cone, and start at the empirical logits of
+        the cumulative proportions -- or K - 1 finite, strictly increasing
+        numbers that are held fixed."""
+        from .cutpoints import (check_cutpoints, check_prior,
+                                initial_cutpoints)
+        if design.intercept_added:
+            raise ValueError("The ordinal model takes a design without an "
+                             "intercept column: the cutpoints are the "
+                             "intercepts.")
+        y, offset, K = _ordinal_outcome(y, offset, design.shape[0])
+        self.y = y
+        self.offset = offset
+        self.n_category = K
+        self.design = design
+        self.name = 'ordinal'
+        self.cutpoints_fixed = cutpoints is not None
+        if cutpoints is None:
+            cutpoints = initial_cutpoints(y, K)
+        elif cutpoint_prior is not None:
+            raise ValueError("cutpoint_prior is the prior of sampled "
+                             "cutpoints: cutpoints are given and held fixed.")
+        self._cutpoints = check_cutpoints(cutpoints, K)
+        self.cutpoint_prior = check_prior(cutpoint_prior)
+        # one bbx_ordinal handle, made by the first call that needs it
+        self._ham_prefix = 'bbx_ordinal_'
+        self._ordinal = c_void_p()
+        self._location_serial = 0
+
+    @property
+    def handle(self):
+        if not self._ordinal:
+            if not getattr(self.design, 'use_hip', False):
+                raise TypeError("the device likelihood needs a HipDesignMatrix")
+            y = np.ascontiguousarray(self.y, dtype=np.float64)
+            o = np.ascontiguousarray(self.offset, dtype=np.float64) \
+                if self.offset.any() else None
+            _lib.check(_lib.load().bbx_ordinal_create(
+                self.design.handle, _ptr(y), _ptr(o), self.n_category,
+                _ptr(self._cutpoints), byref(self._ordinal)))
+        return self._ordinal
+
+    @property
+    def cutpoints(self):
+        return self._cutpoints.copy()
+
+    @cutpoints.setter
+    def cutpoints(self, cuts):
+        self.set_cutpoints(cuts)
+
+    def set_cutpoints(self, cuts):
+        """bbx_ordinal_set_cutpoints: a Hessian operator made before it stops
+        working, as after a move of its location."""
+        from .cutpoints import check_cutpoints
+        cuts = check_cutpoints(cuts, self.n_category)
+        if self._ordinal:
+            _lib.check(_lib.load().bbx_ordinal_set_cutpoints(
+                self._ordinal, _ptr(cuts)))
+            self._location_serial += 1
+        self._cutpoints = cuts
+
+    def compute_loglik_and_gradient(self, beta, loglik_only=False):
+        """sum g_y - softplus(-a) - softplus(b) and X~^T (sigma(b) -
+        sigma(-a)) at the model's cutpoints: the whole log-probability.
+        Finite for every finite beta; (-inf, None) where an infinite eta
+        gives a row's category the probability 0."""
+        return self._device_loglik_and_gradient(beta, loglik_only)
+
+    # the trajectory's f(q0) (hmc.py:95-97) is the model's own likelihood
+    hamiltonian_loglik_and_gradient = compute_loglik_and_gradient
+
+    def get_hessian_matvec_operator(self, beta):
+        """v -> -X~^T (d .* (X~ v)) at beta and the model's cutpoints, d =
+        sigma(a) sigma(-a) + sigma(b) sigma(-b).  The handle holds one
+        location: an operator stops working once a later call has moved it or
+        the cutpoints have changed."""
+        return self._hessian_operator(beta)
+
+    def cutpoint_loglik(self, coef, cuts):
+        """L(c) = sum_i ll_i at the coefficients coef, for one cutpoint
+        vector (K - 1,) or up to 8 of them (n_c, K - 1), in one pass over the
+        rows (bbx_ordinal_cutpoint_loglik); a float or an array (n_c,).
+        coef=None reuses the linear predictor of the previous call.  The
+        value of a given vector depends neither on how many are asked for nor
+        on its place among them.  The model's own cutpoints are not
+        touched."""
+        cuts = np.ascontiguousarray(cuts, dtype=np.float64)
+        single = cuts.ndim == 1
+        if single:
+            cuts = cuts[None, :]
+        if cuts.ndim != 2 or cuts.shape[1] != self.n_category - 1 \
+                or not 1 <= cuts.shape[0] <= 8:
+            raise ValueError("cuts must hold 1 to 8 vectors of %d cutpoints: "
+                             "shape %s." % (self.n_category - 1, cuts.shape))
+        if coef is not None:
+            coef = np.ascontiguousarray(coef, dtype=np.float64)
+            if coef.shape != (self.n_pred,):
+                raise ValueError("coef must have length %d" % self.n_pred)
+        out = np.empty(cuts.shape[0])
+        _lib.check(_lib.load().bbx_ordinal_cutpoint_loglik(
+            self.handle, _ptr(coef), cuts.shape[0], _ptr(cuts), _ptr(out)))
+        return float(out[0]) if single else out
+
+    def calc_intercept_mle(self):
+        raise ValueError("The ordinal model has no intercept: the cutpoints "
+                         "are the intercepts.")
+
+    def predict(self, coef, cutpoints, X_new=None, y_new=None,
+                offset_new=None, _draws_per_pass=0):
+        """Posterior prediction over the draws coef (P,) or (P, S) -- what
+        samples['coef'] is -- with cutpoints (K - 1,) for every draw or
+        (K - 1, S) -- samples['cutpoints'].  X_new=None: the training rows
+        with the model's own outcome and offset; otherwise n_new rows of the
+        model's raw columns (NumPy or SciPy), centred with the TRAINING
+        design's column means, with offset_new (None: 0) and with y_new or
+        without.  A dict: 'mean' and 'sd' (n, K), the posterior mean of every
+        category's probability and its population standard deviation over the
+        draws (the rows of 'mean' sum to 1); with an outcome 'lpd' (the log
+        pointwise predictive density of every row), 'loglik_mean' and
+        'loglik_var' (n,) and the floats 'lppd' = sum lpd, 'p_waic' = sum
+        loglik_var and 'waic' = -2 (lppd - p_waic).  One device call for all
+        the draws (bbx_design_predictive_summary_ordinal)."""
+        from .cutpoints import check_cutpoints
+        draws, X_new, n_row = _Predictive._predict_rows(self, coef, X_new)
+        _training_rows_only(X_new, y_new=y_new, offset_new=offset_new)
+        K, n_draw = self.n_category, len(draws)
+        cuts = np.asarray(cutpoints, dtype=np.float64)
+        if cuts.ndim == 1:
+            cuts = np.repeat(cuts[:, None], n_draw, axis=1)
+        if cuts.shape != (K - 1, n_draw):
+            raise ValueError(
+                "cutpoints must have shape (%d,) or (%d, n_draw): %s, %d "
+                "draws." % (K - 1, K - 1, cuts.shape, n_draw))
+        cuts = np.ascontiguousarray(cuts.T)
+        for c in cuts:
+            check_cutpoints(c, K)
+        if X_new is None:
+            y, offset = self.y, self.offset
+        else:
+            y, offset, _ = _ordinal_outcome(
+                np.zeros(n_row) if y_new is None else y_new, offset_new,
+                n_row, K)
+            y = None if y_new is None else y
+            offset = None if offset_new is None else offset
+        if y is not None and n_draw < 2:
+            raise ValueError(
+                "Scoring an outcome needs at least 2 draws (loglik_var is a "
+                "variance over the draws): coef holds %d." % n_draw)
+        design = self.design if X_new is None \
+            else _new_design(self.design, X_new, False)
+        if not getattr(design, 'use_hip', False):
+            raise TypeError("prediction needs a HipDesignMatrix")
+        y, offset = (None if a is None
+                     else np.ascontiguousarray(a, dtype=np.float64)
+                     for a in (y, offset))
+        mean, sd = np.empty((K, n_row)), np.empty((K, n_row))
+        score = [np.empty(n_row) if y is not None else None for _ in range(3)]
+        _lib.check(_lib.load().bbx_design_predictive_summary_ordinal(
+            design.handle, n_draw, K, _ptr(draws), _ptr(cuts), _ptr(offset),
+            _ptr(y), int(_draws_per_pass), _ptr(mean), _ptr(sd),
+            *[_ptr(a) for a in score]))
+        res = {'mean': mean.T, 'sd': sd.T}
+        if y is not None:
+            lpd, ll_mean, ll_var = score
+            lppd, p_waic = float(np.sum(lpd)), float(np.sum(ll_var))
+            res.update({'lpd': lpd, 'loglik_mean': ll_mean,
+                        'loglik_var': ll_var, 'lppd': lppd, 'p_waic': p_waic,
+                        'waic': -2. * (lppd - p_waic)})
+        return res
+
+    @staticmethod
+    def simulate_outcome(X, beta, cutpoints, offset=None, seed=None):
+        """Categories 0 ... K - 1 with P(y <= k) = sigma(c_{k+1} - (X beta +
+        offset)): the number of cutpoints below a logistic variate centred
+        at X beta + offset."""
+        eta = np.asarray(X.dot(beta), dtype=np.float64).ravel()
+        if offset is not None:
+            eta = eta + np.asarray(offset, dtype=np.float64)
+        cuts = np.asarray(cutpoints, dtype=np.float64)
+        if seed is not None:
+            np.random.seed(seed)
+        latent = eta + np.random.logistic(size=eta.shape)
+        return np.searchsorted(cuts, latent, side='left')
 
 
 def cox_sort_permutation(event_time, censoring_time):
@@ -1872,7 +2123,8 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
                     center_predictor=True, device=0, storage='auto',
                     dense_storage_dtype='float64', entry_time=None,
                     ties='breslow', weights=None, dispersion=None,
-                    dispersion_prior=None, competing_time=None):
+                    dispersion_prior=None, cutpoints=None,
+                    cutpoint_prior=None, competing_time=None):
     """model/factory.py:10-68 with the design placed on an MI355X.  `X` may be
     a SciPy sparse matrix, a NumPy array, or an already built HipDesignMatrix.
     For family='cox', outcome = (event_time, censoring_time) or, for the
@@ -1901,9 +2153,14 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     outcome = y or (y, exposure); `dispersion` (None: sampled, with the prior
     `dispersion_prior` = {'shape': .., 'rate': ..}, None: Gamma(2, 0.1); a
     number: held fixed) is the negative-binomial size.  Strata are refused:
-    the conditional model has no negative-binomial form here.  (The two
-    keywords stand before `competing_time`, which stays the last one: pass
-    them by name.)"""
+    the conditional model has no negative-binomial form here.  For
+    family='ordinal', outcome = y or (y, offset) with y in 0 ... K - 1, every
+    category present; `cutpoints` (None: sampled, with the prior
+    `cutpoint_prior` = {'sd': ..}, None: 10; K - 1 increasing numbers: held
+    fixed) are the model's intercepts, so no intercept column is added
+    (asking for one warns and drops it, as for Cox).  (The four keywords
+    stand before `competing_time`, which stays the last one: pass them by
+    name.)"""
     if entry_time is not None and family != 'cox':
         raise ValueError("entry_time is an argument of family='cox' only.")
     if ties != 'breslow' and family != 'cox':
@@ -1917,6 +2174,16 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     if dispersion_prior is not None and family != 'negbin':
         raise ValueError(
             "dispersion_prior is an argument of family='negbin' only.")
+    if cutpoints is not None and family != 'ordinal':
+        raise ValueError("cutpoints is an argument of family='ordinal' only.")
+    if cutpoint_prior is not None and family != 'ordinal':
+        raise ValueError(
+            "cutpoint_prior is an argument of family='ordinal' only.")
+    if family == 'ordinal' and isinstance(outcome, tuple) \
+            and len(outcome) != 2:
+        raise ValueError(
+            "The ordinal model takes outcome = y or (y, offset): strata are "
+            "not supported.")
     if family == 'negbin' and isinstance(outcome, tuple) \
             and len(outcome) != 2:
         raise ValueError(
@@ -1926,7 +2193,16 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     stratified_poisson = (family == 'poisson' and isinstance(outcome, tuple)
                           and len(outcome) == 3)
     if add_intercept is None:
-        add_intercept = (family != 'cox') and not stratified_poisson
+        add_intercept = family not in ('cox', 'ordinal') \
+            and not stratified_poisson
+    if family == 'ordinal':
+        if add_intercept:
+            add_intercept = False
+            warn("Intercept is not identifiable in the ordinal model (the "
+                 "cutpoints are its intercepts) and won't be added.")
+        if isinstance(X, HipDesignMatrix) and X.intercept_added:
+            raise ValueError("The ordinal model takes a design without an "
+                             "intercept column.")
     if stratified_poisson:
         if add_intercept:
             add_intercept = False
@@ -2082,4 +2358,10 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         else:
             y, exposure = outcome, None
         return NegBinModel(y, exposure, design, dispersion, dispersion_prior)
+    if family == 'ordinal':
+        if isinstance(outcome, tuple):
+            y, offset = outcome
+        else:
+            y, offset = outcome, None
+        return OrdinalModel(y, design, offset, cutpoints, cutpoint_prior)
     raise NotImplementedError()

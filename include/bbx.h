@@ -45,6 +45,11 @@ extern "C" {
  *      likelihood handle, set_dispersion, dispersion_loglik) and its
  *      prediction (bbx_design_predictive_summary_negbin).  New symbols and
  *      nothing else, so the number stays 113.
+ *      + the proportional-odds model of an ordered outcome with K - 1
+ *      cutpoints (bbx_ordinal_*: create, destroy, the shared entry points of
+ *      every likelihood handle, set_cutpoints, cutpoint_loglik) and its
+ *      prediction (bbx_design_predictive_summary_ordinal).  New symbols and
+ *      nothing else, so the number stays 113.
  *      + the Fine-Gray competing-risks model (bbx_coxfg_*: create, destroy and
  *      the shared entry points of every likelihood handle).  New symbols and
  *      nothing else, so the number stays 113.
@@ -1263,6 +1268,36 @@ int bbx_design_predictive_summary_negbin(
     const double* ll_const, int draws_per_pass, double* mean, double* sd,
     double* lpd, double* ll_mean, double* ll_var, double* mu_draws);
 
+/* The summary of the proportional-odds model (csrc/ordinal_predict.hip: a
+ * kernel of its own), from draws of the coefficients, coef[n_draw][P], and of
+ * the cutpoints, cutpoints[n_draw][K - 1] with K = n_category in [2, 16], every
+ * draw's finite and strictly increasing.  With c = cutpoints[s], c_0 = -inf,
+ * c_K = +inf and xo = X~ coef_s + offset (offset[n] or NULL), per row and draw
+ *
+ *   p_k = sigma(c_{k+1} - xo) - sigma(c_k - xo),  k = 0 .. K - 1
+ *   ll  = (g_y - softplus(xo - c_{y+1})) - softplus(c_y - xo)
+ *
+ * (the stable form of log p_y: see the ordinal model below; the probabilities
+ * themselves are differences of sigma, whose absolute error is what a mean
+ * needs).  mean[K][n], sd[K][n] (category-major): the mean of p_k over the
+ * draws and its population standard deviation.  With y[n] (categories 0 ..
+ * K - 1): lpd[n], ll_mean[n], ll_var[n] as in bbx_design_predictive_summary;
+ * without y the three may be NULL.  Per pass of draws_per_pass draws (0: the
+ * library's choice) the products X~ coef_s, then ONE streaming kernel that
+ * keeps, per row, Welford's mean and M2 of each p_k and the four scoring
+ * states; all passes are enqueued back to back, ONE host synchronisation, no
+ * atomics, and no result depends on draws_per_pass.  BBX_ERR_INVALID for a
+ * NULL or destroyed design, n_draw < 1, n_category outside [2, 16], a NULL
+ * coef, cutpoints, mean or sd, a draw whose cutpoints are not finite and
+ * strictly increasing, an offset that is not finite, a y that is not a
+ * category, y with a NULL lpd, ll_mean or ll_var, draws_per_pass < 0: checked
+ * before anything touches the device. */
+int bbx_design_predictive_summary_ordinal(
+    bbx_design* design, int64_t n_draw, int n_category, const double* coef,
+    const double* cutpoints, const double* offset, const double* y,
+    int draws_per_pass, double* mean, double* sd, double* lpd, double* ll_mean,
+    double* ll_var);
+
 /* ----------------------------------------------------------- logit model
  * The binomial-logit likelihood of model/logistic_model.py:49-74 on a design
  * (intercept column and centred predictors included), with the trajectory and
@@ -1529,6 +1564,106 @@ int bbx_negbin_nuts_sample(bbx_negbin* negbin, double* q, double* logp,
  * positive. */
 int bbx_negbin_dispersion_loglik(bbx_negbin* negbin, const double* beta,
                                  int n_r, const double* r, double* out);
+
+/* ---------------------------------------------------------- ordinal model
+ * Proportional odds (cumulative logit) for an ordered outcome on a design
+ * WITHOUT an intercept column -- the cutpoints are the intercepts: categories
+ * y_i in {0, .., K - 1}, 2 <= K <= 16, cutpoints c_1 < .. < c_{K-1}, c_0 =
+ * -inf, c_K = +inf, and P(y_i <= k) = sigma(c_{k+1} - (eta_i + o_i)), eta =
+ * X~ beta, o an optional per-row offset (csrc/ordinal.hip; the leapfrog and
+ * tree kernels are the Cox handle's, csrc/hamiltonian.hpp).  With
+ * a = c_{y+1} - (eta + o), b = c_y - (eta + o), delta_k = c_{k+1} - c_k,
+ *   softplus(x) = max(x, 0) + log1p(exp(-|x|)),
+ *   sigma(x) = 1 / (1 + e), e / (1 + e) for x < 0, e = exp(-|x|),
+ *   g_k = log(1 - exp(-delta_k)) for 0 < k < K - 1, else 0
+ *         (log(-expm1(-delta)) for delta <= log 2, else log1p(-exp(-delta))),
+ *   ll_i = (g_y - softplus(-a)) - softplus(b)     (= log P(y_i), every term:
+ *          the softplus(-a) term is absent for y = K - 1, softplus(b) for
+ *          y = 0)
+ *   w_i  = sigma(b) - sigma(-a)
+ *   d_i  = sigma(a) sigma(-a) + sigma(b) sigma(-b),
+ *          sigma(x) sigma(-x) = e / ((1 + e) (1 + e)).
+ * Nothing cancels and no exp overflows: every value is finite for a finite
+ * eta.  The ten shared entry points have the argument lists, the status codes
+ * and the synchronisation of their bbx_logit_* counterparts above.  The handle
+ * borrows the design (it must outlive the handle) and runs on its stream.
+ * Every sum has a fixed order: the same inputs give the same bits on every
+ * call.
+ *
+ * create: y[n], offset[n] (host; offset may be NULL: all 0), n_category = K
+ * and the K - 1 cutpoints the handle starts with.  BBX_ERR_INVALID for a NULL
+ * y, cutpoints or output pointer, a destroyed or foreign design, K outside
+ * [2, 16], a y that is not an integer in [0, K - 1], an offset that is not
+ * finite, cutpoints that are not finite and strictly increasing. */
+typedef struct bbx_ordinal bbx_ordinal;
+int bbx_ordinal_create(bbx_design* design, const double* y,
+                       const double* offset, int n_category,
+                       const double* cutpoints, bbx_ordinal** out);
+int bbx_ordinal_destroy(bbx_ordinal* ordinal);
+/* Replaces the handle's K - 1 cutpoints (host array): the table of (c_k,
+ * c_{k+1}, g_k) per category is rebuilt on the host and uploaded in stream
+ * order.  It invalidates the Hessian's location (d holds the cutpoints): a
+ * later hessian_matvec without set_location is BBX_ERR_STATE.
+ * BBX_ERR_INVALID for NULL or for cutpoints that are not finite and strictly
+ * increasing; BBX_ERR_STATE between bbx_ordinal_nuts_begin and
+ * bbx_ordinal_nuts_sample, while a No-U-Turn tree built with the previous
+ * cutpoints is open. */
+int bbx_ordinal_set_cutpoints(bbx_ordinal* ordinal, const double* cutpoints);
+/* loglik = sum_i ll_i, the whole log-probability (g_y included: it depends on
+ * the cutpoints); grad[P] = X~^T w.  An infinite eta gives loglik = -inf where
+ * the row's category has probability 0 (grad is then not meaningful); in the
+ * end category on that side (y = K - 1 at eta = +inf, y = 0 at eta = -inf)
+ * the row gives ll_i = 0, w_i = 0, d_i = 0.  A NaN in beta gives NaN.  grad
+ * may be NULL. */
+int bbx_ordinal_loglik_grad(bbx_ordinal* ordinal, const double* beta,
+                            double* loglik, double* grad);
+int bbx_ordinal_loglik_grad_dev(bbx_ordinal* ordinal, const double* d_beta,
+                                double* loglik, double* d_grad);
+/* Hessian-vector products at a fixed beta and the handle's cutpoints:
+ * set_location stores d_i; hessian_matvec gives out = -X~^T (d .* (X~ v))
+ * (BBX_ERR_STATE before a set_location, and after a set_cutpoints until the
+ * next one). */
+int bbx_ordinal_set_location(bbx_ordinal* ordinal, const double* beta);
+int bbx_ordinal_hessian_matvec(bbx_ordinal* ordinal, const double* v,
+                               double* out);
+int bbx_ordinal_hessian_matvec_dev(bbx_ordinal* ordinal, const double* d_v,
+                                   double* d_out);
+/* bbx_cox_hmc_trajectory on the proportional-odds f.  A step at which the
+ * likelihood is -inf (an infinite eta) is the last one: logp = -inf,
+ * *instability = 1. */
+int bbx_ordinal_hmc_trajectory(bbx_ordinal* ordinal, double dt, int n_step,
+                               const double* precond_scale,
+                               const double* prior_prec, const double* q0,
+                               const double* p0, double logp0,
+                               const double* grad0, double hamiltonian_tol,
+                               double* q, double* p, double* logp,
+                               double* grad, int* n_grad_evals,
+                               int* instability, double* hamiltonian);
+/* bbx_cox_nuts_begin / _doubling / _sample on the proportional-odds f. */
+int bbx_ordinal_nuts_begin(bbx_ordinal* ordinal, const double* precond_scale,
+                           const double* prior_prec, const double* q0,
+                           const double* p0, double logp0, const double* grad0,
+                           double joint_logp0, double joint_logp_threshold,
+                           double hamiltonian_tol);
+int bbx_ordinal_nuts_doubling(bbx_ordinal* ordinal, double dt, int direction,
+                              int height, const double* uniforms,
+                              int* n_uniform_used, int* n_steps, int* flags,
+                              int* tree, double* averages);
+int bbx_ordinal_nuts_sample(bbx_ordinal* ordinal, double* q, double* logp,
+                            double* grad);
+/* out[k] = L(cuts[k]) = sum_i ll_i at the cutpoint vector cuts[k][K - 1], for
+ * n_c whole vectors (1 <= n_c <= 8; host arrays, candidate-major) in ONE pass
+ * over the rows: what a cutpoint's conditional density needs.  beta[P]
+ * (host): eta = X~ beta is formed and kept on the handle; NULL: the eta of the
+ * previous call on this handle (BBX_ERR_STATE if there was none).  One launch
+ * of the cutpoint kernel, plus the product for a non-NULL beta; one
+ * synchronisation.  out[k] depends on cuts[k] alone: neither on n_c nor on k,
+ * bit for bit.  The handle's cutpoints, its Hessian location and the scratch
+ * of a trajectory or an open tree are not touched.  BBX_ERR_INVALID for n_c
+ * outside [1, 8], a NULL cuts or out, a cuts[k] that is not finite and
+ * strictly increasing. */
+int bbx_ordinal_cutpoint_loglik(bbx_ordinal* ordinal, const double* beta,
+                                int n_c, const double* cuts, double* out);
 
 /* ----------------------- host-side reference-stream samplers (libbbx_hostrng)
  * Exported by the separate, HIP-free libbbx_hostrng.so.  `bitgen` is the
