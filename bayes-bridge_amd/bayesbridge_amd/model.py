@@ -161,11 +161,13 @@ def _log_factorial(x):
 
 class _Predictive():
     """Posterior prediction and pointwise predictive scores of the linear,
-    logit and Poisson models (bbx_design_predictive_summary,
-    csrc/predict.hip): the draws' linear predictors stay on the device, one
-    kernel reduces them per row, n-vectors come back.  A model names its
-    family in `_pred_family` and checks its own outcome arguments in its
-    `predict`, which ends in `_predictive_summary`."""
+    logit, Poisson, negative-binomial and ordinal models
+    (bbx_design_predictive_summary and its two siblings, csrc/predict.hip):
+    the draws' linear predictors stay on the device, one kernel reduces them
+    per row, n-vectors come back.  A model checks its own outcome arguments
+    in its `predict`, which ends in `_predictive_summary`; `_pred_call` names
+    its entry point (the linear, logit and Poisson models: the shared one,
+    under their `_pred_family`)."""
 
     def _predict_rows(self, coef, X_new):
         """The shared checks of every predict: (draws (S, P), X_new as an
@@ -189,10 +191,21 @@ class _Predictive():
                 "cannot be centred with them.")
         return draws, X_new, X_new.shape[0]
 
+    def _pred_call(self, n_draw, draws, obs_prec, offset, y, n_trial,
+                   ll_const):
+        """(The entry point, its integers after the design, its input
+        arrays): what stands before draws_per_pass in the C call."""
+        return 'bbx_design_predictive_summary', (self._pred_family, n_draw), \
+            (draws, obs_prec, offset, y, n_trial, ll_const)
+
     def _predictive_summary(self, draws, X_new, n_row, y=None, obs_prec=None,
                             offset=None, n_trial=None, ll_const=None,
-                            return_draws=False, draws_per_pass=0):
-        """Every check is done: the device from here on."""
+                            return_draws=False, draws_per_pass=0,
+                            n_plane=None):
+        """Every check is done: the device from here on.  obs_prec is the
+        family's per-draw input (the negative binomial's dispersion, the
+        ordinal model's cutpoints (S, K - 1)).  n_plane=K: 'mean' and 'sd'
+        are (n, K), and the entry point has no argument for the draws."""
         n_draw = len(draws)
         if y is not None and n_draw < 2:
             raise ValueError(
@@ -205,17 +218,22 @@ class _Predictive():
                                  bool(self.intercept_added))
         if not getattr(design, 'use_hip', False):
             raise TypeError("prediction needs a HipDesignMatrix")
-        arrays = [None if a is None
-                  else np.ascontiguousarray(a, dtype=np.float64)
-                  for a in (obs_prec, offset, y, n_trial, ll_const)]
-        mean, sd = np.empty(n_row), np.empty(n_row)
+        obs_prec, offset, y, n_trial, ll_const = (
+            None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+            for a in (obs_prec, offset, y, n_trial, ll_const))
+        entry, integers, arrays = self._pred_call(
+            n_draw, draws, obs_prec, offset, y, n_trial, ll_const)
+        shape = (n_row,) if n_plane is None else (n_plane, n_row)
+        mean, sd = np.empty(shape), np.empty(shape)
         score = [np.empty(n_row) if y is not None else None for _ in range(3)]
         out = np.empty((n_draw, n_row)) if return_draws else None
-        _lib.check(_lib.load().bbx_design_predictive_summary(
-            design.handle, self._pred_family, n_draw, _ptr(draws),
-            *[_ptr(a) for a in arrays], int(draws_per_pass), _ptr(mean),
-            _ptr(sd), *[_ptr(a) for a in score], _ptr(out)))
-        res = {'mean': mean, 'sd': sd}
+        _lib.check(getattr(_lib.load(), entry)(
+            design.handle, *integers, *[_ptr(a) for a in arrays],
+            int(draws_per_pass), _ptr(mean), _ptr(sd),
+            *[_ptr(a) for a in score], *([_ptr(out)] if n_plane is None
+                                         else [])))
+        res = {'mean': mean, 'sd': sd} if n_plane is None \
+            else {'mean': mean.T, 'sd': sd.T}
         if y is not None:
             lpd, ll_mean, ll_var = score
             lppd, p_waic = float(np.sum(lpd)), float(np.sum(ll_var))
@@ -822,43 +840,10 @@ class NegBinModel(_DeviceHamiltonian, _Predictive, _Model):
             self.handle, _ptr(coef), r.size, _ptr(r), _ptr(out)))
         return float(out[0]) if scalar else out
 
-    def _predictive_summary(self, draws, X_new, n_row, y=None, obs_prec=None,
-                            offset=None, n_trial=None, ll_const=None,
-                            return_draws=False, draws_per_pass=0):
-        """_Predictive's, through bbx_design_predictive_summary_negbin;
-        obs_prec carries the draws' dispersion."""
-        n_draw = len(draws)
-        if y is not None and n_draw < 2:
-            raise ValueError(
-                "Scoring an outcome needs at least 2 draws (loglik_var is a "
-                "variance over the draws): coef holds %d." % n_draw)
-        if X_new is None:
-            design = self.design
-        else:
-            design = _new_design(self.design, X_new,
-                                 bool(self.intercept_added))
-        if not getattr(design, 'use_hip', False):
-            raise TypeError("prediction needs a HipDesignMatrix")
-        arrays = [None if a is None
-                  else np.ascontiguousarray(a, dtype=np.float64)
-                  for a in (obs_prec, offset, y, ll_const)]
-        mean, sd = np.empty(n_row), np.empty(n_row)
-        score = [np.empty(n_row) if y is not None else None for _ in range(3)]
-        out = np.empty((n_draw, n_row)) if return_draws else None
-        _lib.check(_lib.load().bbx_design_predictive_summary_negbin(
-            design.handle, n_draw, _ptr(draws), *[_ptr(a) for a in arrays],
-            int(draws_per_pass), _ptr(mean), _ptr(sd),
-            *[_ptr(a) for a in score], _ptr(out)))
-        res = {'mean': mean, 'sd': sd}
-        if y is not None:
-            lpd, ll_mean, ll_var = score
-            lppd, p_waic = float(np.sum(lpd)), float(np.sum(ll_var))
-            res.update({'lpd': lpd, 'loglik_mean': ll_mean,
-                        'loglik_var': ll_var, 'lppd': lppd, 'p_waic': p_waic,
-                        'waic': -2. * (lppd - p_waic)})
-        if return_draws:
-            res['draws'] = out.T
-        return res
+    def _pred_call(self, n_draw, draws, dispersion, offset, y, n_trial,
+                   ll_const):
+        return 'bbx_design_predictive_summary_negbin', (n_draw,), \
+            (draws, dispersion, offset, y, ll_const)
 
     def predict(self, coef, dispersion, X_new=None, y_new=None,
                 exposure_new=None, return_draws=False, _draws_per_pass=0):
@@ -950,7 +935,7 @@ def _ordinal_outcome(y, offset, n_row, n_category=None):
     return y, offset, n_category
 
 
-class OrdinalModel(_DeviceHamiltonian, _Model):
+class OrdinalModel(_DeviceHamiltonian, _Predictive, _Model):
     """Proportional-odds (cumulative logit) regression of an ordered outcome:
     categories y_i in {0, ..., K - 1}, 2 <= K <= 16, with P(y_i <= k) =
     sigma(c_{k+1} - (eta_i + o_i)) for cutpoints c_1 < ... < c_{K-1} and an
@@ -1098,7 +1083,7 @@ class OrdinalModel(_DeviceHamiltonian, _Model):
         loglik_var and 'waic' = -2 (lppd - p_waic).  One device call for all
         the draws (bbx_design_predictive_summary_ordinal)."""
         from .cutpoints import check_cutpoints
-        draws, X_new, n_row = _Predictive._predict_rows(self, coef, X_new)
+        draws, X_new, n_row = self._predict_rows(coef, X_new)
         _training_rows_only(X_new, y_new=y_new, offset_new=offset_new)
         K, n_draw = self.n_category, len(draws)
         cuts = np.asarray(cutpoints, dtype=np.float64)
@@ -1119,31 +1104,15 @@ class OrdinalModel(_DeviceHamiltonian, _Model):
                 n_row, K)
             y = None if y_new is None else y
             offset = None if offset_new is None else offset
-        if y is not None and n_draw < 2:
-            raise ValueError(
-                "Scoring an outcome needs at least 2 draws (loglik_var is a "
-                "variance over the draws): coef holds %d." % n_draw)
-        design = self.design if X_new is None \
-            else _new_design(self.design, X_new, False)
-        if not getattr(design, 'use_hip', False):
-            raise TypeError("prediction needs a HipDesignMatrix")
-        y, offset = (None if a is None
-                     else np.ascontiguousarray(a, dtype=np.float64)
-                     for a in (y, offset))
-        mean, sd = np.empty((K, n_row)), np.empty((K, n_row))
-        score = [np.empty(n_row) if y is not None else None for _ in range(3)]
-        _lib.check(_lib.load().bbx_design_predictive_summary_ordinal(
-            design.handle, n_draw, K, _ptr(draws), _ptr(cuts), _ptr(offset),
-            _ptr(y), int(_draws_per_pass), _ptr(mean), _ptr(sd),
-            *[_ptr(a) for a in score]))
-        res = {'mean': mean.T, 'sd': sd.T}
-        if y is not None:
-            lpd, ll_mean, ll_var = score
-            lppd, p_waic = float(np.sum(lpd)), float(np.sum(ll_var))
-            res.update({'lpd': lpd, 'loglik_mean': ll_mean,
-                        'loglik_var': ll_var, 'lppd': lppd, 'p_waic': p_waic,
-                        'waic': -2. * (lppd - p_waic)})
-        return res
+        # (the constructor refuses a design with an intercept column: the
+        # shared tail's bool(self.intercept_added) is False here)
+        return self._predictive_summary(
+            draws, X_new, n_row, y=y, obs_prec=cuts, offset=offset,
+            draws_per_pass=_draws_per_pass, n_plane=K)
+
+    def _pred_call(self, n_draw, draws, cuts, offset, y, n_trial, ll_const):
+        return 'bbx_design_predictive_summary_ordinal', \
+            (n_draw, self.n_category), (draws, cuts, offset, y)
 
     @staticmethod
     def simulate_outcome(X, beta, cutpoints, offset=None, seed=None):

@@ -10,8 +10,7 @@ using namespace bbx::pred;
 // bbx_design_predictive_summary with mu = exp(eta +
 // offset), the full log-likelihood term G(y, r_s) + y t - (y + r_s)
 // softplus(t) + c, t = eta + offset - log r_s, and r_s the dispersion of draw
-// s.  The same passes, the same single synchronisation, the same independence
-// of draws_per_pass.
+// s, through the same driver (predictive_summary_impl).
 extern "C" int bbx_design_predictive_summary_negbin(
     bbx_design* design, int64_t n_draw, const double* coef,
     const double* dispersion, const double* offset, const double* y,
@@ -47,9 +46,6 @@ extern "C" int bbx_design_predictive_summary_negbin(
                      offset, y,           nullptr, ll_const, draws_per_pass,
                      mean,   sd,          lpd,     ll_mean,  ll_var,
                      mu_draws};
-    return predictive_summary_impl(
-        q, [](hipStream_t s, bool score, const PredArgs& a) {
-          launch_summary<PRED_NEGBIN>(s, score, a);
-        });
+    return predictive_summary_impl(q, launch_summary<PRED_NEGBIN>);
   });
 }

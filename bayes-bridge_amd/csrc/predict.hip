@@ -4,30 +4,28 @@
 // model from draws of the coefficients and of the dispersion
 // (bbx_design_predictive_summary_negbin, negbin_predict.hip: one more
 // instantiation of the same kernel, predict_summary.hpp, under a family code
-// that is no BBX_PRED_* of the header).
+// that is no BBX_PRED_* of the header).  The ordinal model's kernel
+// (ordinal_predict.hip) follows the same method with K means per row.
 //
 // Per draw s the linear predictor eta_s = X~ beta_s is formed on the device by
 // the launches of bbx_design_dot (launch_prep_v + launch_dot, as ham::eta_of),
-// so a draw's eta has that call's bits.  The draws go through in blocks of K:
-// K products into a K x n buffer, then ONE summary kernel that walks the K
-// etas of every row in draw order and updates the row's running statistics:
+// so a draw's eta has that call's bits.  The draws go through in passes of K
+// (PredPasses): K products into a K x n buffer, then ONE summary kernel that
+// walks the K etas of every row in draw order and pushes
 //
 //   mu_s  = eta | 1 / (1 + exp(-eta)) | exp(eta)     (eta = X~ beta_s + offset)
 //           (negative binomial: exp(eta), as the Poisson model)
 //   ll_s  = the row's log-likelihood term of draw s (see pred_terms)
-//   Welford on mu and on ll, k the 1-based draw index:
-//     delta = x - mean;  mean += delta / k;  M2 += delta * (x - mean)
-//     (an infinite mean stays: welford_mean)
-//   lpd online: ll > M ? (sum = sum * exp(M - ll) + 1, M = ll)
-//                      : (sum += exp(ll - M));  a draw of -inf adds exactly 0
 //
-// One update per draw whatever K is, so the results do not depend on K.  The
-// state (six doubles per row, SoA) lives in HBM between blocks and in
-// registers within one; the first block starts it in registers and the last
-// one writes the five results instead.  Rows along the lanes, one row per
-// thread: eta, the state and the optional mu draws (draw-major) are read and
-// written 64 consecutive doubles per wave.  No atomics, no reduction across
-// rows: the same inputs give the same bits.
+// into the row's Moments and Scores, whose recurrences and rules for
+// non-finite draws predict_summary.hpp states: one push per draw whatever K
+// is, so the results do not depend on K.  The state (six doubles per row,
+// SoA) lives in HBM between passes and in registers within one; the first
+// pass starts it in registers and the last one writes the five results
+// instead.  Rows along the lanes, one row per thread: eta, the state and the
+// optional mu draws (draw-major) are read and written 64 consecutive doubles
+// per wave.  No atomics, no reduction across rows: the same inputs give the
+// same bits.
 //
 // Per-draw traffic: 8 B per row for eta plus (48 B read + 48 B written) / K
 // for the state; K = 16 makes the state's share 6 B.  K x n x 8 B (twice that
@@ -90,14 +88,8 @@ extern "C" int bbx_design_predictive_summary(
                      mean,   sd,      lpd,     ll_mean, ll_var,
                      mu_draws};
     return predictive_summary_impl(
-        q, [&](hipStream_t s, bool score, const PredArgs& a) {
-          if (family == BBX_PRED_LINEAR) {
-            launch_summary<BBX_PRED_LINEAR>(s, score, a);
-          } else if (family == BBX_PRED_LOGIT) {
-            launch_summary<BBX_PRED_LOGIT>(s, score, a);
-          } else {
-            launch_summary<BBX_PRED_POISSON>(s, score, a);
-          }
-        });
+        q, family == BBX_PRED_LINEAR  ? launch_summary<BBX_PRED_LINEAR>
+           : family == BBX_PRED_LOGIT ? launch_summary<BBX_PRED_LOGIT>
+                                      : launch_summary<BBX_PRED_POISSON>);
   });
 }

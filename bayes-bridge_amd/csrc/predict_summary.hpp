@@ -1,12 +1,32 @@
-// The streaming summary kernel of posterior prediction and its host driver,
-// shared by predict.hip (linear, logit, Poisson: bbx_design_predictive_summary)
-// and negbin_predict.hip (negative binomial:
-// bbx_design_predictive_summary_negbin).  The kernel and the driver are static
-// templates: a translation unit holds the instantiations it launches and no
-// others.  predict.hip describes the method.
+// What the streaming summaries of posterior prediction share: the per-row
+// accumulators (Moments, Scores) and the host driver of the passes
+// (PredPasses), which ordinal_predict.hip's own kernel uses too, and the
+// summary kernel of the one-mean families with its host side (predict.hip:
+// linear, logit, Poisson; negbin_predict.hip: negative binomial).  Kernels and
+// drivers are static: a translation unit holds the instantiations it launches
+// and no others.  predict.hip describes the method.
+//
+// THE ACCUMULATORS' CONTRACT.  A thread owns a row and pushes its draws in
+// draw order, k = 1, 2, ... the 1-based index over ALL draws; between two
+// passes the state lives in a state-major array ([state][n]: coalesced), and
+// a store followed by a load is the identity.  So a result is a function of
+// the row's draws alone: it does not depend on the pass size.
+//   Moments (mean, M2), Welford:
+//     delta = x - mean;  mean += delta / k;  M2 += delta * (x - mean)
+//     Once a draw has overflowed (a Poisson mu of +inf, its ll of -inf) the
+//     mean is that infinity and stays it, as the plain sum would: inf - inf in
+//     the update would turn it into a NaN.  A NaN draw or the opposite infinity
+//     still gives a NaN.  (M2 is a NaN from there on: the spread of infinite
+//     values has no value.)  Results: mean, sd = sqrt(M2 / S)
+//   Scores: the Moments of ll and the online log-sum-exp (max, sum):
+//     ll > max ? (sum = sum * exp(max - ll) + 1, max = ll)
+//              : (sum += exp(ll - max)), but a draw of -inf adds exactly 0
+//     (all draws -inf: lpd = -inf, not a NaN);  a NaN draw makes the sum a NaN
+//     results: lpd = max + log(sum) - log(S), mean of ll, M2 / (S - 1)
 #pragma once
 #include <math.h>
 
+#include <algorithm>
 #include <cmath>
 
 #include <string>
@@ -23,7 +43,7 @@ namespace pred {
 constexpr int PRED_BLOCK = 256;
 constexpr int PRED_DRAWS = 16;                    // default draws per pass
 constexpr size_t PRED_BUDGET = size_t(256) << 20; // eta (+ mu draws) of a pass
-constexpr int PRED_STATE = 6;  // mean, M2 of mu; mean, M2 of ll; max, sum
+constexpr int PRED_STATE = 6;  // Moments of mu, then Scores
 // The negative-binomial model's code.  Not a BBX_PRED_* of include/bbx.h:
 // bbx_design_predictive_summary refuses it, the family has its own entry point
 // and its instantiation lives in negbin_predict.hip.
@@ -47,6 +67,13 @@ struct PredArgs {
   double* mu_draws;       // [kn][n] or null
 };
 
+// sigma(x) = 1 / (1 + exp(-x)) from e = exp(-|x|) <= 1: nothing overflows,
+// absolute error ~1e-16
+__device__ __forceinline__ double pred_sigma(double x) {
+  const double e = exp(-fabs(x));
+  return x >= 0. ? 1. / (1. + e) : e / (1. + e);
+}
+
 // mu and (SCORE) ll of one draw of one row; eta holds the row's offset
 template <int FAMILY, bool SCORE>
 __device__ __forceinline__ void pred_terms(double eta, double y, double m,
@@ -60,10 +87,9 @@ __device__ __forceinline__ void pred_terms(double eta, double y, double m,
       *ll = hlt - 0.5 * tau * r * r;
     }
   } else if (FAMILY == BBX_PRED_LOGIT) {
-    const double e = exp(-fabs(eta));
-    *mu = eta >= 0. ? 1. / (1. + e) : e / (1. + e);
+    *mu = pred_sigma(eta);
     if (SCORE) {
-      const double sp = fmax(eta, 0.) + log1p(e);
+      const double sp = fmax(eta, 0.) + log1p(exp(-fabs(eta)));
       *ll = y * eta - m * sp;
     }
   } else if (FAMILY == BBX_PRED_POISSON) {
@@ -83,16 +109,73 @@ __device__ __forceinline__ void pred_terms(double eta, double y, double m,
   if (SCORE && has_c) *ll += c;
 }
 
-// Welford's mean.  Once a draw has overflowed (a Poisson mu of +inf, its ll of
-// -inf) the mean is that infinity and stays it, as the plain sum would:
-// inf - inf in the update would turn it into a NaN.  A NaN draw or the
-// opposite infinity still gives a NaN.  (M2 is a NaN from there on: the
-// spread of infinite values has no value.)
+// Welford's mean with the contract's rule for an infinite one
 __device__ __forceinline__ double welford_mean(double mean, double x,
                                                double delta, double k) {
   if (isinf(mean)) return (x != x || x == -mean) ? NAN : mean;
   return mean + delta / k;
 }
+
+// The two accumulators of the head comment, by value in a thread's
+// registers.  `st` is the accumulator's first state plane, `n` the length of
+// a plane, `i` the row.
+struct Moments {
+  double mean = 0., m2 = 0.;   // fresh
+  __device__ __forceinline__ void load(const double* st, int64_t n,
+                                       int64_t i) {
+    mean = st[i];
+    m2 = st[n + i];
+  }
+  __device__ __forceinline__ void push(double x, double k) {
+    const double delta = x - mean;
+    mean = welford_mean(mean, x, delta, k);
+    m2 += delta * (x - mean);
+  }
+  __device__ __forceinline__ void store(double* st, int64_t n,
+                                        int64_t i) const {
+    st[i] = mean;
+    st[n + i] = m2;
+  }
+  // the mean and the population sd over the S draws, each into its own plane
+  __device__ __forceinline__ void finish(double S, double* mean_out,
+                                         double* sd_out, int64_t i) const {
+    mean_out[i] = mean;
+    sd_out[i] = sqrt(m2 / S);
+  }
+};
+
+struct Scores {
+  Moments ll;
+  double lmax = -INFINITY, lsum = 0.;
+  __device__ __forceinline__ void load(const double* st, int64_t n,
+                                       int64_t i) {
+    ll.load(st, n, i);
+    lmax = st[2 * n + i];
+    lsum = st[3 * n + i];
+  }
+  __device__ __forceinline__ void push(double x, double k) {
+    ll.push(x, k);
+    if (x > lmax) {
+      lsum = lsum * exp(lmax - x) + 1.;
+      lmax = x;
+    } else if (x != -INFINITY) {   // (-inf adds exactly 0; a NaN gets here)
+      lsum += exp(x - lmax);
+    }
+  }
+  __device__ __forceinline__ void store(double* st, int64_t n,
+                                        int64_t i) const {
+    ll.store(st, n, i);
+    st[2 * n + i] = lmax;
+    st[3 * n + i] = lsum;
+  }
+  // lpd, ll_mean, ll_var into three planes from `out`
+  __device__ __forceinline__ void finish(double S, double* out, int64_t n,
+                                         int64_t i) const {
+    out[i] = lmax + log(lsum) - log(S);
+    out[n + i] = ll.mean;
+    out[2 * n + i] = ll.m2 / (S - 1.);
+  }
+};
 
 template <int FAMILY, bool SCORE>
 static __global__ __launch_bounds__(PRED_BLOCK) void predict_summary_kernel(
@@ -100,16 +183,11 @@ static __global__ __launch_bounds__(PRED_BLOCK) void predict_summary_kernel(
   const int64_t i = (int64_t)blockIdx.x * PRED_BLOCK + threadIdx.x;
   const int64_t n = a.n;
   if (i >= n) return;
-  double mean = 0., m2 = 0., lmean = 0., lm2 = 0., lmax = -INFINITY, lsum = 0.;
+  Moments mom;
+  Scores sc;   // (used with an outcome only)
   if (a.k0 > 0) {
-    mean = a.state[i];
-    m2 = a.state[n + i];
-    if (SCORE) {
-      lmean = a.state[2 * n + i];
-      lm2 = a.state[3 * n + i];
-      lmax = a.state[4 * n + i];
-      lsum = a.state[5 * n + i];
-    }
+    mom.load(a.state, n, i);
+    if (SCORE) sc.load(a.state + 2 * n, n, i);
   }
   const bool has_off = a.offset != nullptr;
   const double off = has_off ? a.offset[i] : 0.;
@@ -136,40 +214,17 @@ static __global__ __launch_bounds__(PRED_BLOCK) void predict_summary_kernel(
             : nullptr;
     pred_terms<FAMILY, SCORE>(eta, y, m, c, has_c, tau, hlt, gtab, &mu, &ll);
     if (a.mu_draws) a.mu_draws[(int64_t)d * n + i] = mu;
-    const double delta = mu - mean;
-    mean = welford_mean(mean, mu, delta, k);
-    m2 += delta * (mu - mean);
-    if (SCORE) {
-      const double ld = ll - lmean;
-      lmean = welford_mean(lmean, ll, ld, k);
-      lm2 += ld * (ll - lmean);
-      if (ll > lmax) {
-        lsum = lsum * exp(lmax - ll) + 1.;
-        lmax = ll;
-      } else if (ll != -INFINITY) {   // (-inf adds exactly 0; a NaN gets here)
-        lsum += exp(ll - lmax);
-      }
-    }
+    mom.push(mu, k);
+    if (SCORE) sc.push(ll, k);
   }
   if (a.k0 + a.kn < a.n_draw) {
-    a.state[i] = mean;
-    a.state[n + i] = m2;
-    if (SCORE) {
-      a.state[2 * n + i] = lmean;
-      a.state[3 * n + i] = lm2;
-      a.state[4 * n + i] = lmax;
-      a.state[5 * n + i] = lsum;
-    }
+    mom.store(a.state, n, i);
+    if (SCORE) sc.store(a.state + 2 * n, n, i);
     return;
   }
   const double S = (double)a.n_draw;
-  a.out[i] = mean;
-  a.out[n + i] = sqrt(m2 / S);
-  if (SCORE) {
-    a.out[2 * n + i] = lmax + log(lsum) - log(S);
-    a.out[3 * n + i] = lmean;
-    a.out[4 * n + i] = lm2 / (S - 1.);
-  }
+  mom.finish(S, a.out, a.out + n, i);
+  if (SCORE) sc.finish(S, a.out + 2 * n, n, i);
 }
 
 template <int FAMILY>
@@ -180,6 +235,96 @@ static void launch_summary(hipStream_t s, bool score, const PredArgs& a) {
                       : predict_summary_kernel<FAMILY, false>;
   BBX_LAUNCH(kernel, grid, dim3(PRED_BLOCK), 0, s, a);
 }
+
+// The host side every family shares: the draws go through in passes of `per`
+// draws -- `per` products into the eta buffer, then the family's summary
+// kernel(s) over them and, where asked for, the pass's mu draws back -- all on
+// the design's stream, in the order uploads, products and summaries pass by
+// pass, the results back, ONE synchronisation (finish): the host arrays
+// handed to begin, upload and row outlive their copies.  (Internal linkage, as
+// the static functions around it: the library exports none of it.)
+namespace {
+struct PredPasses {
+  bbx_design* h = nullptr;
+  int64_t n_draw = 0, per = 0, pitch = 0;
+  size_t nb = 0;             // bytes of an n-vector
+  DevMem d_beta, d_eta, d_mu, d_up[5];
+  int n_up = 0;
+  double* mu_host = nullptr;   // [S][n] or null: every draw's mu, pass by pass
+  // Sizes the pass (draws_per_pass, or 0: PRED_DRAWS, fewer where the eta and,
+  // with mu_draws, the mu of a pass would exceed PRED_BUDGET, never below 1),
+  // allocates them and uploads the draws coef[S][P].
+  int begin(bbx_design* design, int64_t S, const double* coef,
+            int draws_per_pass, double* mu_draws = nullptr) {
+    const size_t d8 = sizeof(double);
+    h = design;
+    n_draw = S;
+    mu_host = mu_draws;
+    nb = d8 * (size_t)h->n;
+    const int64_t P = h->P;
+    const int64_t fit = (int64_t)(PRED_BUDGET / (nb * (mu_host ? 2 : 1)));
+    per = draws_per_pass;
+    if (per == 0)
+      per = std::max<int64_t>(1, std::min<int64_t>(PRED_DRAWS, fit));
+    per = std::min(per, S);
+    // every draw starts 256 bytes apart, as the staging vector of
+    // bbx_design_dot does: the product kernels take the same path
+    pitch = (P + 31) / 32 * 32;
+    BBX_TRY(d_beta.alloc(d8 * (size_t)pitch * (size_t)S));
+    BBX_TRY(d_eta.alloc(nb * (size_t)per));
+    if (mu_host) BBX_TRY(d_mu.alloc(nb * (size_t)per));
+    BBX_HIP(hipMemcpy2DAsync(d_beta.ptr, d8 * (size_t)pitch, coef,
+                             d8 * (size_t)P, d8 * (size_t)P, (size_t)S,
+                             hipMemcpyHostToDevice, h->stream));
+    return BBX_OK;
+  }
+  // a host array on the device for the length of the call (at most 5)
+  int upload(const double* host, size_t bytes, const double** dev) {
+    DevMem& d = d_up[n_up++];
+    BBX_TRY(d.alloc(bytes));
+    BBX_HIP(hipMemcpyAsync(d.ptr, host, bytes, hipMemcpyHostToDevice,
+                           h->stream));
+    *dev = d.as<const double>();
+    return BBX_OK;
+  }
+  // an optional n-vector: *dev stays null for a null host
+  int row(const double* host, const double** dev) {
+    return host ? upload(host, nb, dev) : BBX_OK;
+  }
+  // `pass(k0, kn)` launches the family's summary of the kn draws from k0,
+  // whose linear predictors are in eta[kn][n]
+  template <class Pass>
+  int run(Pass&& pass) {
+    for (int64_t k0 = 0; k0 < n_draw; k0 += per) {
+      const int kn = (int)(k0 + per < n_draw ? per : n_draw - k0);
+      for (int d = 0; d < kn; ++d) {
+        const double* b = d_beta.as<const double>() + (k0 + d) * pitch;
+        BBX_TRY(launch_prep_v(h, b, nullptr, nullptr, part_slot(h, PS_C)));
+        BBX_TRY(launch_dot(h, b, nullptr,
+                           d_eta.as<double>() + (int64_t)d * h->n, nullptr));
+      }
+      pass(k0, kn);
+      BBX_HIP(hipGetLastError());
+      if (mu_host)
+        BBX_HIP(hipMemcpyAsync(mu_host + k0 * h->n, d_mu.ptr, nb * (size_t)kn,
+                               hipMemcpyDeviceToHost, h->stream));
+    }
+    return BBX_OK;
+  }
+  // The results out[mean_k ..., sd_k ..., lpd, ll_mean, ll_var][n], k < K, to
+  // the host arrays res[5] (the last three with `score` only), then the
+  // call's one synchronisation.
+  int finish(const double* out, int64_t K, bool score, double* const res[5]) {
+    for (int r = 0; r < (score ? 5 : 2); ++r) {
+      const int64_t plane = r < 2 ? r * K : 2 * K + r - 2;
+      BBX_HIP(hipMemcpyAsync(res[r], out + plane * h->n, nb * (r < 2 ? K : 1),
+                             hipMemcpyDeviceToHost, h->stream));
+    }
+    BBX_HIP(hipStreamSynchronize(h->stream));
+    return BBX_OK;
+  }
+};
+}  // namespace
 
 struct PredCall {
   bbx_design* h;
@@ -194,37 +339,17 @@ struct PredCall {
 // translation unit chooses which instantiations it holds.
 template <class Launch>
 static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
-  bbx_design* h = q.h;
-  hipStream_t s = h->stream;
-  const int64_t n = h->n, P = h->P, S = q.n_draw;
+  const int64_t n = q.h->n, S = q.n_draw;
   const size_t d8 = sizeof(double);
-  const size_t nb = d8 * (size_t)n;
   const bool score = q.y != nullptr;
   const bool linear = q.family == BBX_PRED_LINEAR;
   const bool negbin = q.family == PRED_NEGBIN;
 
-  int64_t K = q.draws_per_pass;
-  if (K == 0) {
-    K = PRED_DRAWS;
-    const int64_t fit =
-        (int64_t)(PRED_BUDGET / (nb * (q.mu_draws ? 2 : 1)));
-    if (K > fit) K = fit;
-    if (K < 1) K = 1;
-  }
-  if (K > S) K = S;
-
-  // every draw starts 256 bytes apart, as the staging vector of
-  // bbx_design_dot does: the product kernels take the same path
-  const int64_t pitch = (P + 31) / 32 * 32;
-  DevMem d_beta, d_tau, d_eta, d_state, d_out, d_mu, d_row[4];
-  BBX_TRY(d_beta.alloc(d8 * (size_t)pitch * (size_t)S));
-  BBX_TRY(d_eta.alloc(nb * (size_t)K));
-  BBX_TRY(d_state.alloc(nb * PRED_STATE));
-  BBX_TRY(d_out.alloc(nb * 5));
-  if (q.mu_draws) BBX_TRY(d_mu.alloc(nb * (size_t)K));
-  BBX_HIP(hipMemcpy2DAsync(d_beta.ptr, d8 * (size_t)pitch, q.coef,
-                           d8 * (size_t)P, d8 * (size_t)P, (size_t)S,
-                           hipMemcpyHostToDevice, s));
+  PredPasses p;
+  DevMem d_state, d_out;
+  BBX_TRY(p.begin(q.h, S, q.coef, q.draws_per_pass, q.mu_draws));
+  BBX_TRY(d_state.alloc(p.nb * PRED_STATE));
+  BBX_TRY(d_out.alloc(p.nb * 5));
   std::vector<double> tau_host;
   if (negbin && score) {
     // (obs_prec holds the draws' dispersion)
@@ -239,63 +364,36 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
       tau_host[S + d] = 0.5 * log(q.obs_prec[d]);
     }
   }
-  if (!tau_host.empty()) {
-    BBX_TRY(d_tau.alloc(d8 * tau_host.size()));
-    BBX_HIP(hipMemcpyAsync(d_tau.ptr, tau_host.data(), d8 * tau_host.size(),
-                           hipMemcpyHostToDevice, s));
-  }
-  const double* rows[4] = {q.offset, score ? q.y : nullptr,
-                           score && q.family == BBX_PRED_LOGIT ? q.n_trial
-                                                               : nullptr,
-                           score ? q.ll_const : nullptr};
-  for (int r = 0; r < 4; ++r) {
-    if (!rows[r]) continue;
-    BBX_TRY(d_row[r].alloc(nb));
-    BBX_HIP(hipMemcpyAsync(d_row[r].ptr, rows[r], nb, hipMemcpyHostToDevice,
-                           s));
-  }
+  const double* tab = nullptr;
+  if (!tau_host.empty())
+    BBX_TRY(p.upload(tau_host.data(), d8 * tau_host.size(), &tab));
 
   PredArgs a{};
   a.n = n;
   a.n_draw = S;
-  a.eta = d_eta.as<const double>();
+  a.eta = p.d_eta.as<const double>();
   if (linear) {
-    a.tau = d_tau.as<const double>();
-    a.hlt = d_tau.ptr ? d_tau.as<const double>() + S : nullptr;
+    a.tau = tab;
+    a.hlt = tab ? tab + S : nullptr;
   } else {
-    a.gtab = d_tau.as<const double>();
+    a.gtab = tab;
   }
-  a.offset = d_row[0].as<const double>();
-  a.y = d_row[1].as<const double>();
-  a.m = d_row[2].as<const double>();
-  a.c = d_row[3].as<const double>();
+  BBX_TRY(p.row(q.offset, &a.offset));
+  BBX_TRY(p.row(score ? q.y : nullptr, &a.y));
+  BBX_TRY(p.row(score && q.family == BBX_PRED_LOGIT ? q.n_trial : nullptr,
+                &a.m));
+  BBX_TRY(p.row(score ? q.ll_const : nullptr, &a.c));
   a.state = d_state.as<double>();
   a.out = d_out.as<double>();
-  a.mu_draws = d_mu.as<double>();
-  for (int64_t k0 = 0; k0 < S; k0 += K) {
-    const int kn = (int)(k0 + K < S ? K : S - k0);
-    for (int d = 0; d < kn; ++d) {
-      const double* b = d_beta.as<const double>() + (k0 + d) * pitch;
-      BBX_TRY(launch_prep_v(h, b, nullptr, nullptr, part_slot(h, PS_C)));
-      BBX_TRY(launch_dot(h, b, nullptr, d_eta.as<double>() + (int64_t)d * n,
-                         nullptr));
-    }
+  a.mu_draws = p.d_mu.as<double>();
+  BBX_TRY(p.run([&](int64_t k0, int kn) {
     a.k0 = k0;
     a.kn = kn;
-    launch(s, score, a);
-    BBX_HIP(hipGetLastError());
-    if (q.mu_draws)
-      BBX_HIP(hipMemcpyAsync(q.mu_draws + k0 * n, d_mu.ptr, nb * (size_t)kn,
-                             hipMemcpyDeviceToHost, s));
-  }
-  double* outs[5] = {q.mean, q.sd, q.lpd, q.ll_mean, q.ll_var};
-  for (int r = 0; r < (score ? 5 : 2); ++r)
-    BBX_HIP(hipMemcpyAsync(outs[r], d_out.as<double>() + (int64_t)r * n, nb,
-                           hipMemcpyDeviceToHost, s));
-  BBX_HIP(hipStreamSynchronize(s));
-  return BBX_OK;
+    launch(q.h->stream, score, a);
+  }));
+  double* const res[5] = {q.mean, q.sd, q.lpd, q.ll_mean, q.ll_var};
+  return p.finish(a.out, 1, score, res);
 }
-
 
 }  // namespace pred
 }  // namespace bbx
