@@ -233,7 +233,16 @@ def test_matrix_core_gemv_variant_gives_the_same_product(shape):
                                    (20001, 4001, 'float64'),
                                    (16500, 5000, 'float64'),
                                    (33001, 8001, 'float64'),
-                                   (65537, 801, 'float64')])
+                                   (65537, 801, 'float64'),
+                                   # edges (tests/dense_ld_oracle.py,
+                                   # RING_CASES): 17 rows per workgroup with
+                                   # empty workgroups, a single-row workgroup
+                                   # (n_blk = 1 < D), a column group with few
+                                   # live threads, full rows of 4096 and 8192
+                                   (4097, 8, 'float32'),
+                                   (4098, 4100, 'float32'),
+                                   (4097, 4095, 'float64'),
+                                   (4098, 8190, 'float64')])
 def test_lds_ring_variant_of_the_single_pass_operator_is_bit_identical(shape):
     """dense_fused_ring_kernel (LDS-DMA ring, the default from 64 rows per
     workgroup on) against dense_fused_kernel (register prefetch,
