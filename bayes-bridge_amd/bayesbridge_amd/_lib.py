@@ -246,6 +246,15 @@ def _declare(lib):
         "bbx_ordinal_set_cutpoints": ([hp, c_void_p], c_int),
         "bbx_ordinal_cutpoint_loglik": (
             [hp, c_void_p, c_int, c_void_p, c_void_p], c_int),
+        "bbx_design_predictive_summary_weibull": (
+            [hp, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_void_p], c_int),
+        "bbx_weibull_create": (
+            [hp, c_void_p, c_void_p, c_double, POINTER(hp)], c_int),
+        "bbx_weibull_set_shape": ([hp, c_double], c_int),
+        "bbx_weibull_shape_loglik": (
+            [hp, c_void_p, c_int, c_void_p, c_void_p], c_int),
     }
     # the ten entry points every Hamiltonian likelihood handle has
     # (csrc/hamiltonian.hpp): the same argument lists in every family
@@ -270,7 +279,7 @@ def _declare(lib):
         "nuts_sample": [hp, c_void_p, POINTER(c_double), c_void_p],
     }
     for family in ("cox", "coxcp", "coxef", "coxw", "coxfg", "logit",
-                   "poisson", "cpoisson", "negbin", "ordinal"):
+                   "poisson", "cpoisson", "negbin", "ordinal", "weibull"):
         for entry, argtypes in shared.items():
             sigs["bbx_%s_%s" % (family, entry)] = (list(argtypes), c_int)
     for name, (argtypes, restype) in sigs.items():

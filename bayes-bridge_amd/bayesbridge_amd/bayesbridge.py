@@ -37,6 +37,7 @@ from .prior import RegressionCoefPrior, unit_magnitude
 from .hmc import HipHMCCoefficientSampler
 from .reg_coef_sampler import (HipRegressionCoefficientSampler,
                                RegressionCoeffficientPosteriorSummarizer)
+from .weibull_shape import update_shape
 
 # the HMC draw's sampling info (gibbs_util.py:141-160)
 HMC_INFO_KEYS = ('stepsize', 'n_hessian_matvec', 'n_grad_evals',
@@ -46,11 +47,11 @@ HMC_INFO_KEYS = ('stepsize', 'n_hessian_matvec', 'n_grad_evals',
 NUTS_INFO_KEYS = HMC_INFO_KEYS[:6] + ('tree_height', 'ave_accept_prob')
 # models without an observation precision (or Polya-Gamma) parameter: their
 # chains carry no 'obs_prec' and draw the coefficients by 'hmc' / 'nuts' only
-NO_OBS_PREC = ('cox', 'poisson', 'negbin', 'ordinal')
+NO_OBS_PREC = ('cox', 'poisson', 'negbin', 'ordinal', 'weibull')
 # models whose only coefficient samplers are 'hmc' and 'nuts', and what the
 # refusals call them
 HAMILTONIAN_ONLY = {'poisson': 'Poisson', 'negbin': 'negative-binomial',
-                    'ordinal': 'ordinal'}
+                    'ordinal': 'ordinal', 'weibull': 'Weibull'}
 
 
 def _ptr(a):
@@ -267,7 +268,7 @@ class BayesBridge():
                              % HAMILTONIAN_ONLY[self.model.name])
         if options.coef_sampler_type in ('hmc', 'nuts') \
                 and self.model.name not in ('cox', 'logit', 'poisson',
-                                            'negbin', 'ordinal'):
+                                            'negbin', 'ordinal', 'weibull'):
             # the reference's sample_by_hmc never passes obs_prec to the
             # linear model's likelihood
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
@@ -279,6 +280,8 @@ class BayesBridge():
                 params_to_save += ('dispersion',)
             if self.model.name == 'ordinal':
                 params_to_save += ('cutpoints',)
+            if self.model.name == 'weibull':
+                params_to_save += ('weibull_shape',)
         start_time = time.time()
         if options.rng == 'reference':
             if _device_out:
@@ -326,6 +329,9 @@ class BayesBridge():
         cutpoints = extra.pop('_cutpoints', None)
         if cutpoints is not None:           # the ordinal model
             raw_state['cutpoints'] = np.array(cutpoints, copy=True)
+        weibull_shape = extra.pop('_weibull_shape', None)
+        if weibull_shape is not None:       # the Weibull model
+            raw_state['weibull_shape'] = weibull_shape
         if self.prior._gscale_paramet == 'coef_magnitude':  # bayesbridge.py:244-251
             gscale, lscale = self.prior.adjust_scale(
                 gscale, lscale, to='coef_magnitude')
@@ -356,6 +362,8 @@ class BayesBridge():
         if cutpoints is not None:
             mcmc_info['_markov_chain_state']['cutpoints'] = np.array(
                 cutpoints, copy=True)
+        if weibull_shape is not None:
+            mcmc_info['_markov_chain_state']['weibull_shape'] = weibull_shape
         mcmc_info.update(extra)
         return samples, mcmc_info
 
@@ -535,6 +543,9 @@ class BayesBridge():
         if 'cutpoints' in params_to_save and self.model.name == 'ordinal':
             samples['cutpoints'] = np.zeros((self.model.n_category - 1,
                                              n_sample))
+        if 'weibull_shape' in params_to_save \
+                and self.model.name == 'weibull':
+            samples['weibull_shape'] = np.zeros(n_sample)
         info_keys = {'hmc': HMC_INFO_KEYS, 'nuts': NUTS_INFO_KEYS,
                      'cg': ('n_cg_iter',)}.get(coef_sampler_type, ())
         return samples, {key: np.zeros(n_sample)      # gibbs_util.py:141-160
@@ -575,6 +586,26 @@ class BayesBridge():
         if not (math.isfinite(r) and r > 0.):
             raise ValueError('An invalid initial state.')
         return r
+
+    def _initial_weibull_shape(self, init):
+        """The Weibull chain's first shape: the resumed chain's, else
+        init['weibull_shape'], else 1 (the exponential model); a model with a
+        fixed shape keeps its own."""
+        model = self.model
+        if isinstance(init, dict) and '_raw' in init:
+            k = init['_raw']['weibull_shape']
+        else:
+            k = init.get('weibull_shape')
+        if model.shape_fixed:
+            if k is not None and float(k) != model.shape:
+                raise ValueError(
+                    "The model's shape is held fixed at %r: the initial "
+                    "state gives %r." % (model.shape, k))
+            return model.shape
+        k = 1. if k is None else float(k)
+        if not (math.isfinite(k) and k > 0.):
+            raise ValueError('An invalid initial state.')
+        return k
 
     def _initial_cutpoints(self, init):
         """The ordinal chain's first cutpoints: the resumed chain's, else
@@ -624,6 +655,8 @@ class BayesBridge():
             valid += ('dispersion',)
         if self.model.name == 'ordinal':
             valid += ('cutpoints',)
+        if self.model.name == 'weibull':
+            valid += ('weibull_shape',)
         for key in init:
             if key not in valid:
                 warn("'{:s}' is not a valid parameter name and "
@@ -766,7 +799,9 @@ class BayesBridge():
             # (negative binomial: the likelihood's beta-part at the current
             # dispersion plus the priors below; neither G(y, r) - log y! nor
             # the dispersion's prior is in logp; ordinal: the whole likelihood
-            # at the iteration's cutpoints, without the cutpoints' prior)
+            # at the iteration's cutpoints, without the cutpoints' prior;
+            # Weibull: the beta-part at the iteration's shape, without
+            # d (log k + (k - 1) log t) and without the shape's prior)
             if model.name == 'linear':                   # bayesbridge.py:480-511
                 loglik, _ = model.compute_loglik_and_gradient(
                     coef, obs_prec, loglik_only=True)
@@ -796,10 +831,17 @@ class BayesBridge():
             # likewise: the model carries the chain's cutpoints
             cutpoints = self._initial_cutpoints(init)
             model.cutpoints = cutpoints
+        weibull_shape = None
+        if model.name == 'weibull':
+            # likewise: the model carries the chain's shape
+            weibull_shape = self._initial_weibull_shape(init)
+            model.shape = weibull_shape
         coef, obs_prec, lscale, gscale, init_used, optim_info = \
             self._initialize_chain(init, bridge_exp, update_local_scale,
                                    update_obs_precision, update_global_scale,
                                    sampler)
+        if weibull_shape is not None:
+            init_used['weibull_shape'] = weibull_shape
         if dispersion is not None:
             init_used['dispersion'] = dispersion
         if cutpoints is not None:
@@ -841,6 +883,13 @@ class BayesBridge():
                     model, coef, cutpoints, model.cutpoint_prior,
                     rg.np_random.uniform)
                 model.cutpoints = cutpoints
+            if weibull_shape is not None and not model.shape_fixed:
+                # k | beta: one slice update on log k, its uniforms from the
+                # chain's host stream (dispersion.py states their order)
+                weibull_shape = update_shape(
+                    model, coef, weibull_shape, model.shape_prior,
+                    rg.np_random.uniform)
+                model.shape = weibull_shape
             gscale = update_global_scale(
                 gscale, coef[nu:], bridge_exp, method=options.gscale_update)
             lscale = update_local_scale(gscale, coef[nu:], bridge_exp)
@@ -864,6 +913,8 @@ class BayesBridge():
                     samples['dispersion'][idx] = dispersion
                 if 'cutpoints' in samples:
                     samples['cutpoints'][:, idx] = cutpoints
+                if 'weibull_shape' in samples:
+                    samples['weibull_shape'][idx] = weibull_shape
                 for key in info_keys:
                     if key in info:
                         sampling_info[key][idx] = info[key]
@@ -880,6 +931,8 @@ class BayesBridge():
             extra['_dispersion'] = dispersion
         if cutpoints is not None:
             extra['_cutpoints'] = cutpoints
+        if weibull_shape is not None:
+            extra['_weibull_shape'] = weibull_shape
         return (samples, sampling_info, (coef, obs_prec, lscale, gscale),
                 init_used, optim_info, extra)
 

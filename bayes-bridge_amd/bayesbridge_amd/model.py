@@ -17,7 +17,11 @@ WAIC -- with the draws' linear predictors kept on the device
 (csrc/predict.hip).  The negative-binomial model (csrc/negbin.hip) is the
 Poisson model's overdispersed sibling: the same device path, one more
 parameter -- the dispersion, updated by dispersion.py inside the Gibbs loop --
-and the same prediction (csrc/negbin_predict.hip).  The ordinal model
+and the same prediction (csrc/negbin_predict.hip).  The Weibull model
+(csrc/weibull.hip) is the parametric proportional-hazards model of
+right-censored times on the same device path: its shape is updated by
+weibull_shape.py inside the Gibbs loop, and it predicts median survival times
+(csrc/weibull_predict.hip) and survival curves.  The ordinal model
 (csrc/ordinal.hip) is the proportional-odds model of an ordered outcome on the
 same device path: its K - 1 cutpoints are updated by cutpoints.py inside the
 Gibbs loop, and it predicts the K category probabilities
@@ -896,6 +900,298 @@ class NegBinModel(_DeviceHamiltonian, _Predictive, _Model):
             np.random.seed(seed)
         r = float(dispersion)
         return np.random.poisson(mu * np.random.gamma(r, 1. / r, mu.shape))
+
+
+def _survival_outcome(event_time, censoring_time, n_row):
+    """The outcome checks of the Weibull model on n_row rows: (event
+    indicator d, time t = min of the two), the Cox model's convention --
+    exactly one of a row's two times is finite."""
+    et = np.asarray(event_time, dtype=np.float64)
+    ct = np.asarray(censoring_time, dtype=np.float64)
+    if not (et.shape == ct.shape == (n_row,)):
+        raise ValueError(
+            "Outcome vectors and design matrix have incompatible sizes: "
+            "%s event times, %s censoring times, %d rows."
+            % (et.shape, ct.shape, n_row))
+    if np.any(np.isnan(et)) or np.any(np.isnan(ct)) \
+            or np.any(np.isfinite(et) == np.isfinite(ct)):
+        raise ValueError(
+            "Exactly one of event_time and censoring_time must be finite in "
+            "every row (inf marks the one that was not observed).")
+    t = np.minimum(et, ct)
+    if (t <= 0).any():
+        raise ValueError("Every time must be strictly positive.")
+    return np.isfinite(et).astype(np.float64), t
+
+
+class WeibullModel(_DeviceHamiltonian, _Predictive, _Model):
+    """Weibull proportional-hazards regression of right-censored times: the
+    hazard of row i is h(t | x_i) = k t^(k - 1) exp(eta_i), eta = X~ beta with
+    an intercept (the log rate is identifiable), so the coefficients are log
+    hazard ratios and compare directly with a Cox fit of the same data; the
+    shape k > 0 is a parameter of the chain, and k = 1 is the exponential
+    model.  The likelihood, its gradient and the Hessian-vector products run
+    on the device through one bbx_weibull handle (csrc/weibull.hip); the
+    coefficients are drawn by 'hmc' or 'nuts' and the shape by a slice update
+    on log k (weibull_shape.py) right after them, unless it is given and held
+    fixed.
+
+    With t = min(event_time, censoring_time), d = 1 for an event and lt =
+    log t the log density of a row is d (log k + (k - 1) lt + eta) -
+    exp(eta + k lt).  compute_loglik_and_gradient and the samplers see the
+    part that depends on the coefficients, d eta - exp(eta + k lt);
+    shape_loglik and predict use the whole density.
+
+    R's survreg fits the same model in the accelerated-failure-time
+    parametrisation: beta_aft = -beta_ph / k and scale = 1 / k.  Agreement
+    with survreg is not tested."""
+
+    _handle_attr = '_weibull'
+
+    def __init__(self, event_time, censoring_time, design, shape=None,
+                 shape_prior=None):
+        """The times of the Cox model: exactly one of a row's event_time and
+        censoring_time is finite, and it is strictly positive.  shape: None --
+        the shape is a parameter of the chain, with the prior shape_prior =
+        {'shape': a0, 'rate': b0} on k (None: Gamma(2, 1)), and starts at 1
+        -- or a finite, positive number that is held fixed."""
+        from .weibull_shape import check_prior
+        n_row = design.shape[0]
+        event, time = _survival_outcome(event_time, censoring_time, n_row)
+        self.event = event
+        self.time = time
+        self.log_time = np.log(time)
+        self.event_time = np.asarray(event_time, dtype=np.float64)
+        self.censoring_time = np.asarray(censoring_time, dtype=np.float64)
+        self.design = design
+        self.name = 'weibull'
+        self.shape_fixed = shape is not None
+        if shape is None:
+            shape = 1.
+        elif shape_prior is not None:
+            raise ValueError("shape_prior is the prior of a sampled shape: "
+                             "shape is given and held fixed.")
+        self._shape = self._checked_shape(shape)
+        self.shape_prior = check_prior(shape_prior)
+        # one bbx_weibull handle, made by the first call that needs it
+        self._ham_prefix = 'bbx_weibull_'
+        self._weibull = c_void_p()
+        self._location_serial = 0
+
+    @staticmethod
+    def _checked_shape(k):
+        try:
+            k = float(k)
+        except (TypeError, ValueError):
+            raise ValueError("The shape must be a number.") from None
+        if not (math.isfinite(k) and k > 0.):
+            raise ValueError("The shape must be finite and positive.")
+        return k
+
+    @property
+    def handle(self):
+        if not self._weibull:
+            if not getattr(self.design, 'use_hip', False):
+                raise TypeError("the device likelihood needs a HipDesignMatrix")
+            d = np.ascontiguousarray(self.event, dtype=np.float64)
+            lt = np.ascontiguousarray(self.log_time, dtype=np.float64)
+            _lib.check(_lib.load().bbx_weibull_create(
+                self.design.handle, _ptr(d), _ptr(lt), self._shape,
+                byref(self._weibull)))
+        return self._weibull
+
+    @property
+    def shape(self):
+        return self._shape
+
+    @shape.setter
+    def shape(self, k):
+        """bbx_weibull_set_shape: a Hessian operator made before it stops
+        working, as after a move of its location."""
+        k = self._checked_shape(k)
+        if self._weibull:
+            _lib.check(_lib.load().bbx_weibull_set_shape(self._weibull, k))
+            self._location_serial += 1
+        self._shape = k
+
+    def compute_loglik_and_gradient(self, beta, loglik_only=False):
+        """sum d eta - m and X~^T (d - m), m = exp(eta + k log t), at the
+        model's shape.  The terms constant in beta (sum d (log k + (k - 1)
+        log t)) are dropped; (-inf, None) where an m overflows."""
+        return self._device_loglik_and_gradient(beta, loglik_only)
+
+    # the trajectory's f(q0) (hmc.py:95-97) is the model's own likelihood
+    hamiltonian_loglik_and_gradient = compute_loglik_and_gradient
+
+    def get_hessian_matvec_operator(self, beta):
+        """v -> -X~^T (m .* (X~ v)) at beta and the model's shape.  The handle
+        holds one location: an operator stops working once a later call has
+        moved it or the shape has changed."""
+        return self._hessian_operator(beta)
+
+    def calc_intercept_mle(self):
+        """log(sum d / sum t^k) at the model's current shape."""
+        return math.log(self.event.sum() / np.sum(self.time ** self._shape))
+
+    def shape_loglik(self, coef, k):
+        """L(k) = sum_i d_i (log k + (k - 1) log t_i + eta_i) - exp(eta_i + k
+        log t_i) at the coefficients coef, for k a scalar or up to 8 values,
+        in one pass over the rows (bbx_weibull_shape_loglik); a float or an
+        array like k.  coef=None reuses the linear predictor of the previous
+        call.  The value for a given k depends neither on how many values are
+        asked for nor on its place among them.  The model's own shape is not
+        touched."""
+        scalar = np.ndim(k) == 0
+        k = np.ascontiguousarray(np.atleast_1d(k), dtype=np.float64)
+        if k.ndim != 1 or not 1 <= k.size <= 8:
+            raise ValueError("k must be a scalar or hold 1 to 8 values.")
+        if coef is not None:
+            coef = np.ascontiguousarray(coef, dtype=np.float64)
+            if coef.shape != (self.n_pred,):
+                raise ValueError("coef must have length %d" % self.n_pred)
+        out = np.empty(k.size)
+        _lib.check(_lib.load().bbx_weibull_shape_loglik(
+            self.handle, _ptr(coef), k.size, _ptr(k), _ptr(out)))
+        return float(out[0]) if scalar else out
+
+    def _shape_draws(self, shape, n_draw):
+        k = np.asarray(shape, dtype=np.float64)
+        if k.ndim == 0:
+            k = np.full(n_draw, float(k))
+        if k.shape != (n_draw,):
+            raise ValueError(
+                "shape must be a scalar or hold one value per draw: "
+                "%s, %d draws." % (k.shape, n_draw))
+        if not np.all(np.isfinite(k)) or (k <= 0).any():
+            raise ValueError(
+                "Every shape must be strictly positive and finite.")
+        return np.ascontiguousarray(k)
+
+    def _pred_call(self, n_draw, draws, shape, offset, y, n_trial, ll_const):
+        # (y is the event indicator and n_trial's place holds log t)
+        return 'bbx_design_predictive_summary_weibull', (n_draw,), \
+            (draws, shape, y, n_trial, ll_const)
+
+    def predict(self, coef, shape, X_new=None, event_time_new=None,
+                censoring_time_new=None, return_draws=False,
+                _draws_per_pass=0):
+        """Posterior prediction over the draws coef (P,) or (P, S) -- what
+        samples['coef'] is -- with shape a scalar or one value per draw --
+        samples['weibull_shape'].  X_new=None: the training rows with the
+        model's own times; otherwise n_new rows of the model's raw columns
+        (NumPy or SciPy), centred with the TRAINING design's column means,
+        with event_time_new and censoring_time_new (both, under the model's
+        convention) or without.  A dict: 'mean' and 'sd' (n,), the posterior
+        mean of the median survival time exp((log(log 2) - eta) / k) and its
+        population standard deviation over the draws; with an outcome 'lpd',
+        'loglik_mean' and 'loglik_var' (n,) and the floats 'lppd', 'p_waic'
+        and 'waic' = -2 (lppd - p_waic) under the whole log density d (log k
+        + (k - 1) log t + eta) - exp(eta + k log t); with return_draws 'draws'
+        (n, S).  One device call for all the draws."""
+        draws, X_new, n_row = self._predict_rows(coef, X_new)
+        _training_rows_only(X_new, event_time_new=event_time_new,
+                            censoring_time_new=censoring_time_new)
+        k = self._shape_draws(shape, len(draws))
+        event = log_time = None
+        if X_new is None:
+            event, log_time = self.event, self.log_time
+        elif event_time_new is not None or censoring_time_new is not None:
+            if event_time_new is None or censoring_time_new is None:
+                raise ValueError(
+                    "event_time_new and censoring_time_new are given "
+                    "together or not at all.")
+            event, time = _survival_outcome(event_time_new,
+                                            censoring_time_new, n_row)
+            log_time = np.log(time)
+        return self._predictive_summary(
+            draws, X_new, n_row, y=event, obs_prec=k, n_trial=log_time,
+            return_draws=return_draws, draws_per_pass=_draws_per_pass)
+
+    def predict_survival(self, coef, shape, X_new=None, times=None,
+                         return_draws=False):
+        """Posterior survival S(t | x) = exp(-exp(k log t + x~ . beta)) over
+        the draws coef (P,) or (P, S) with shape a scalar or one value per
+        draw: a dict with 'time' (T,), 'mean' and 'sd' (n, T) -- the mean and
+        the population standard deviation over the draws -- and, with
+        return_draws, 'draws' (n, T, S).  X_new=None: the training rows;
+        otherwise rows of the model's raw columns, centred with the training
+        design's column means.  times: strictly positive and increasing
+        (None: the distinct event times of the training rows).  The summary
+        is bbx_cox_survival_summary with one group, whose log cumulative
+        baseline hazard of draw s at time t is k_s log t: a parametric
+        baseline, so any t may be asked for."""
+        draws, X_new, n_row = self._predict_rows(coef, X_new)
+        n_draw = len(draws)
+        k = self._shape_draws(shape, n_draw)
+        if times is None:
+            times = np.unique(self.time[self.event == 1.])
+        times = np.ascontiguousarray(np.atleast_1d(times), dtype=np.float64)
+        if times.ndim != 1 or times.size == 0 \
+                or not np.all(np.isfinite(times)) or (times <= 0).any() \
+                or np.any(np.diff(times) <= 0):
+            raise ValueError("times must be finite, strictly positive and "
+                             "strictly increasing.")
+        # every check is done: the device from here on
+        design = self.design if X_new is None else _new_design(
+            self.design, X_new, bool(self.intercept_added))
+        if not getattr(design, 'use_hip', False):
+            raise TypeError("prediction needs a HipDesignMatrix")
+        eta = np.ascontiguousarray(np.stack([design.dot(b) for b in draws]))
+        log_hazard = np.ascontiguousarray(k[:, None] * np.log(times)[None, :])
+        n_time = len(times)
+        mean, sd = np.empty((n_row, n_time)), np.empty((n_row, n_time))
+        out = np.empty((n_row, n_time, n_draw)) if return_draws else None
+        _lib.check(_lib.load().bbx_cox_survival_summary(
+            design.device, n_row, n_time, n_draw, 1, _ptr(eta),
+            _ptr(log_hazard), None, _ptr(mean), _ptr(sd), _ptr(out)))
+        res = {'time': times, 'mean': mean, 'sd': sd}
+        if return_draws:
+            res['draws'] = out
+        return res
+
+    @staticmethod
+    def _simulate_from_eta(eta, shape, censoring_frac, seed):
+        """Event times with the cumulative hazard t^k exp(eta) -- t = (E /
+        exp(eta))^(1 / k), E standard exponential, so that the median of row
+        i is (log 2 / exp(eta_i))^(1 / k) -- and independent Weibull
+        censoring times of the same shape whose common rate is chosen so that
+        the expected censored fraction is censoring_frac."""
+        if not 0. <= censoring_frac < 1.:
+            raise ValueError("censoring_frac must lie in [0, 1).")
+        if seed is not None:
+            np.random.seed(seed)
+        k = WeibullModel._checked_shape(shape)
+        rate = np.exp(np.asarray(eta, dtype=np.float64))
+        event_time = (np.random.exponential(size=rate.shape) / rate) \
+            ** (1. / k)
+        censoring_time = np.full(rate.shape, np.inf)
+        if censoring_frac > 0.:
+            # with t^k ~ Exp(rate_i) and c^k ~ Exp(nu): P(censored) =
+            # mean of nu / (nu + rate_i), increasing in nu: bisection on log nu
+            lo, hi = -80., 80.
+            for _ in range(200):
+                mid = .5 * (lo + hi)
+                nu = math.exp(mid)
+                if np.mean(nu / (nu + rate)) < censoring_frac:
+                    lo = mid
+                else:
+                    hi = mid
+            nu = math.exp(.5 * (lo + hi))
+            censoring_time = (np.random.exponential(size=rate.shape) / nu) \
+                ** (1. / k)
+        censored = censoring_time < event_time
+        event_time = np.where(censored, np.inf, event_time)
+        censoring_time = np.where(censored, censoring_time, np.inf)
+        return event_time, censoring_time
+
+    @staticmethod
+    def simulate_outcome(X, beta, shape, censoring_frac=.5, seed=None):
+        """(event_time, censoring_time) under the hazard shape t^(shape - 1)
+        exp(X beta), about censoring_frac of the rows censored; exactly one
+        of a row's two times is finite."""
+        eta = np.asarray(X.dot(beta), dtype=np.float64).ravel()
+        return WeibullModel._simulate_from_eta(eta, shape, censoring_frac,
+                                               seed)
 
 
 def _ordinal_outcome(y, offset, n_row, n_category=None):
@@ -2093,7 +2389,8 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
                     dense_storage_dtype='float64', entry_time=None,
                     ties='breslow', weights=None, dispersion=None,
                     dispersion_prior=None, cutpoints=None,
-                    cutpoint_prior=None, competing_time=None):
+                    cutpoint_prior=None, weibull_shape=None,
+                    weibull_shape_prior=None, competing_time=None):
     """model/factory.py:10-68 with the design placed on an MI355X.  `X` may be
     a SciPy sparse matrix, a NumPy array, or an already built HipDesignMatrix.
     For family='cox', outcome = (event_time, censoring_time) or, for the
@@ -2127,9 +2424,14 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     category present; `cutpoints` (None: sampled, with the prior
     `cutpoint_prior` = {'sd': ..}, None: 10; K - 1 increasing numbers: held
     fixed) are the model's intercepts, so no intercept column is added
-    (asking for one warns and drops it, as for Cox).  (The four keywords
-    stand before `competing_time`, which stays the last one: pass them by
-    name.)"""
+    (asking for one warns and drops it, as for Cox).  For family='weibull',
+    outcome = (event_time, censoring_time) as for Cox -- exactly one of a
+    row's two times finite -- but the rows stay in their order and an
+    intercept is added; `weibull_shape` (None: sampled, with the prior
+    `weibull_shape_prior` = {'shape': .., 'rate': ..}, None: Gamma(2, 1); a
+    number: held fixed) is the Weibull shape k.  Strata are refused.  (The
+    six keywords stand before `competing_time`, which stays the last one:
+    pass them by name.)"""
     if entry_time is not None and family != 'cox':
         raise ValueError("entry_time is an argument of family='cox' only.")
     if ties != 'breslow' and family != 'cox':
@@ -2148,6 +2450,17 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     if cutpoint_prior is not None and family != 'ordinal':
         raise ValueError(
             "cutpoint_prior is an argument of family='ordinal' only.")
+    if weibull_shape is not None and family != 'weibull':
+        raise ValueError(
+            "weibull_shape is an argument of family='weibull' only.")
+    if weibull_shape_prior is not None and family != 'weibull':
+        raise ValueError(
+            "weibull_shape_prior is an argument of family='weibull' only.")
+    if family == 'weibull' and not (isinstance(outcome, tuple)
+                                    and len(outcome) == 2):
+        raise ValueError(
+            "The Weibull model takes outcome = (event_time, censoring_time): "
+            "strata are not supported.")
     if family == 'ordinal' and isinstance(outcome, tuple) \
             and len(outcome) != 2:
         raise ValueError(
@@ -2327,6 +2640,10 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         else:
             y, exposure = outcome, None
         return NegBinModel(y, exposure, design, dispersion, dispersion_prior)
+    if family == 'weibull':
+        event_time, censoring_time = outcome
+        return WeibullModel(event_time, censoring_time, design, weibull_shape,
+                            weibull_shape_prior)
     if family == 'ordinal':
         if isinstance(outcome, tuple):
             y, offset = outcome

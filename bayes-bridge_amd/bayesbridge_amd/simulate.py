@@ -90,11 +90,15 @@ def demo_beta(n_pred):
 
 
 def simulate_outcome(X, beta, model, intercept=0., n_trial=None, seed=None,
-                     censoring_frac=.9, dispersion=1., exposure=None):
+                     censoring_frac=.9, dispersion=1., exposure=None,
+                     weibull_shape=1.):
     """simulate_data.py:8-27 for the linear and logit families; for 'cox',
     (event_time, censoring_time) of cox_model.py:275-298; for 'negbin',
     counts with mean exposure exp(intercept + X beta) and size `dispersion`
-    (NegBinModel.simulate_outcome)."""
+    (NegBinModel.simulate_outcome); for 'weibull', (event_time,
+    censoring_time) with the hazard weibull_shape t^(weibull_shape - 1)
+    exp(intercept + X beta) and the censoring fraction asked for
+    (WeibullModel.simulate_outcome)."""
     if model == 'cox':
         from .model import CoxModel
         return CoxModel.simulate_outcome(X, beta, censoring_frac, seed)
@@ -103,6 +107,11 @@ def simulate_outcome(X, beta, model, intercept=0., n_trial=None, seed=None,
         scale = np.exp(intercept) * (1. if exposure is None
                                      else np.asarray(exposure, np.float64))
         return NegBinModel.simulate_outcome(X, beta, dispersion, scale, seed)
+    if model == 'weibull':
+        from .model import WeibullModel
+        eta = intercept + np.asarray(X.dot(beta), dtype=np.float64).ravel()
+        return WeibullModel._simulate_from_eta(eta, weibull_shape,
+                                               censoring_frac, seed)
     if seed is not None:
         np.random.seed(seed)
     if model == 'linear':

@@ -2,7 +2,8 @@
 // accumulators (Moments, Scores) and the host driver of the passes
 // (PredPasses), which ordinal_predict.hip's own kernel uses too, and the
 // summary kernel of the one-mean families with its host side (predict.hip:
-// linear, logit, Poisson; negbin_predict.hip: negative binomial).  Kernels and
+// linear, logit, Poisson; negbin_predict.hip: negative binomial;
+// weibull_predict.hip: Weibull).  Kernels and
 // drivers are static: a translation unit holds the instantiations it launches
 // and no others.  predict.hip describes the method.
 //
@@ -34,6 +35,7 @@
 
 #include "common.hpp"
 #include "negbin_terms.hpp"
+#include "weibull_terms.hpp"
 
 #pragma clang fp contract(off)  // a + b * c rounded as NumPy rounds it
 
@@ -48,6 +50,9 @@ constexpr int PRED_STATE = 6;  // Moments of mu, then Scores
 // bbx_design_predictive_summary refuses it, the family has its own entry point
 // and its instantiation lives in negbin_predict.hip.
 constexpr int PRED_NEGBIN = 3;
+// The Weibull model's, likewise: its entry point and its instantiation live in
+// weibull_predict.hip.  Its "mean" is the median survival time.
+constexpr int PRED_WEIBULL = 4;
 
 struct PredArgs {
   int64_t n;
@@ -55,12 +60,12 @@ struct PredArgs {
   int kn;           // draws of this pass
   int64_t n_draw;   // all draws: the last pass writes the results
   const double* eta;      // [kn][n]
-  const double* tau;      // [n_draw] linear: obs_prec
-  const double* hlt;      // [n_draw] linear: 0.5 log(obs_prec)
+  const double* tau;      // [n_draw] linear: obs_prec; Weibull: the shape k
+  const double* hlt;      // [n_draw] linear: 0.5 log(obs_prec); Weibull: log k
   const double* gtab;     // [n_draw][NEGBIN_GTAB] negbin: negbin_gtab(r)
   const double* offset;   // [n] or null
   const double* y;        // [n]   (SCORE)
-  const double* m;        // [n] or null (logit, SCORE)
+  const double* m;        // [n] or null (logit, SCORE); Weibull: log t (SCORE)
   const double* c;        // [n] or null (SCORE)
   double* state;          // [PRED_STATE][n]
   double* out;            // [5][n]: mean, sd, lpd, ll_mean, ll_var
@@ -95,6 +100,11 @@ __device__ __forceinline__ void pred_terms(double eta, double y, double m,
   } else if (FAMILY == BBX_PRED_POISSON) {
     *mu = exp(eta);
     if (SCORE) *ll = y * eta - *mu;
+  } else if (FAMILY == PRED_WEIBULL) {
+    // Weibull: y is the event indicator, m is log t, tau and hlt are the
+    // draw's k and log k; the predicted quantity is the median survival time
+    *mu = weibull_median(eta, tau);
+    if (SCORE) *ll = weibull_full(eta, y, m, tau, hlt);
   } else {
     // negative binomial: r and log r of the draw are in its table
     *mu = exp(eta);
@@ -192,7 +202,8 @@ static __global__ __launch_bounds__(PRED_BLOCK) void predict_summary_kernel(
   const bool has_off = a.offset != nullptr;
   const double off = has_off ? a.offset[i] : 0.;
   const double y = SCORE ? a.y[i] : 0.;
-  const double m = SCORE && FAMILY == BBX_PRED_LOGIT && a.m ? a.m[i] : 1.;
+  const bool has_m = FAMILY == BBX_PRED_LOGIT || FAMILY == PRED_WEIBULL;
+  const double m = SCORE && has_m && a.m ? a.m[i] : 1.;
   const bool has_c = SCORE && a.c != nullptr;
   const double c = has_c ? a.c[i] : 0.;
   // (the negative-binomial body unrolled holds more wave-uniform values than
@@ -203,7 +214,7 @@ static __global__ __launch_bounds__(PRED_BLOCK) void predict_summary_kernel(
     if (has_off) eta += off;
     const double k = (double)(a.k0 + d + 1);
     double tau = 0., hlt = 0.;
-    if (FAMILY == BBX_PRED_LINEAR && SCORE) {
+    if ((FAMILY == BBX_PRED_LINEAR && SCORE) || FAMILY == PRED_WEIBULL) {
       tau = a.tau[a.k0 + d];
       hlt = a.hlt[a.k0 + d];
     }
@@ -344,6 +355,7 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
   const bool score = q.y != nullptr;
   const bool linear = q.family == BBX_PRED_LINEAR;
   const bool negbin = q.family == PRED_NEGBIN;
+  const bool weibull = q.family == PRED_WEIBULL;
 
   PredPasses p;
   DevMem d_state, d_out;
@@ -364,6 +376,15 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
       tau_host[S + d] = 0.5 * log(q.obs_prec[d]);
     }
   }
+  if (weibull) {
+    // (obs_prec holds the draws' shape: the median needs it without an
+    // outcome too)
+    tau_host.resize(2 * (size_t)S);
+    for (int64_t d = 0; d < S; ++d) {
+      tau_host[d] = q.obs_prec[d];
+      tau_host[S + d] = log(q.obs_prec[d]);
+    }
+  }
   const double* tab = nullptr;
   if (!tau_host.empty())
     BBX_TRY(p.upload(tau_host.data(), d8 * tau_host.size(), &tab));
@@ -372,7 +393,7 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
   a.n = n;
   a.n_draw = S;
   a.eta = p.d_eta.as<const double>();
-  if (linear) {
+  if (linear || weibull) {
     a.tau = tab;
     a.hlt = tab ? tab + S : nullptr;
   } else {
@@ -380,7 +401,8 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
   }
   BBX_TRY(p.row(q.offset, &a.offset));
   BBX_TRY(p.row(score ? q.y : nullptr, &a.y));
-  BBX_TRY(p.row(score && q.family == BBX_PRED_LOGIT ? q.n_trial : nullptr,
+  BBX_TRY(p.row(score && (q.family == BBX_PRED_LOGIT || weibull) ? q.n_trial
+                                                                   : nullptr,
                 &a.m));
   BBX_TRY(p.row(score ? q.ll_const : nullptr, &a.c));
   a.state = d_state.as<double>();

@@ -50,6 +50,11 @@ extern "C" {
  *      every likelihood handle, set_cutpoints, cutpoint_loglik) and its
  *      prediction (bbx_design_predictive_summary_ordinal).  New symbols and
  *      nothing else, so the number stays 113.
+ *      + the Weibull proportional-hazards model of right-censored times with
+ *      a shape parameter (bbx_weibull_*: create, destroy, the shared entry
+ *      points of every likelihood handle, set_shape, shape_loglik) and its
+ *      prediction (bbx_design_predictive_summary_weibull).  New symbols and
+ *      nothing else, so the number stays 113.
  *      + the Fine-Gray competing-risks model (bbx_coxfg_*: create, destroy and
  *      the shared entry points of every likelihood handle).  New symbols and
  *      nothing else, so the number stays 113.
@@ -1268,6 +1273,32 @@ int bbx_design_predictive_summary_negbin(
     const double* ll_const, int draws_per_pass, double* mean, double* sd,
     double* lpd, double* ll_mean, double* ll_var, double* mu_draws);
 
+/* The same summary for the Weibull model (csrc/weibull_predict.hip: one more
+ * instantiation of the summary kernel), from draws of the coefficients and of
+ * the shape: shape[n_draw], finite and positive.  With k = shape[s] and
+ * eta = X~ coef_s (no offset), per row and draw
+ *
+ *   mu = exp((log(log 2) - eta) / k)                  the median survival time
+ *   ll = d ((log k + (k - 1) lt) + eta) - exp(eta + k lt) + c
+ *
+ * d = event[i] in {0, 1}, lt = log_time[i]: the model's whole log density
+ * (see the Weibull model below), c = ll_const[i] or 0.  event and log_time
+ * are given together (scoring) or both NULL; without them lpd, ll_mean and
+ * ll_var may be NULL.  The passes, the single synchronisation, the
+ * independence of draws_per_pass, the outputs and the overflow rules are those
+ * of bbx_design_predictive_summary.  BBX_ERR_INVALID for a NULL or destroyed
+ * design, n_draw < 1 (< 2 with an outcome), a NULL coef, shape, mean or sd, a
+ * shape[s] that is not finite and positive, one of event and log_time without
+ * the other, an event that is not 0 or 1, a log_time that is not finite, an
+ * outcome with a NULL lpd, ll_mean or ll_var, draws_per_pass < 0: checked
+ * before anything touches the device.  bbx_design_predictive_summary itself
+ * keeps refusing every family code but its three. */
+int bbx_design_predictive_summary_weibull(
+    bbx_design* design, int64_t n_draw, const double* coef,
+    const double* shape, const double* event, const double* log_time,
+    const double* ll_const, int draws_per_pass, double* mean, double* sd,
+    double* lpd, double* ll_mean, double* ll_var, double* mu_draws);
+
 /* The summary of the proportional-odds model (csrc/ordinal_predict.hip: a
  * kernel of its own), from draws of the coefficients, coef[n_draw][P], and of
  * the cutpoints, cutpoints[n_draw][K - 1] with K = n_category in [2, 16], every
@@ -1664,6 +1695,93 @@ int bbx_ordinal_nuts_sample(bbx_ordinal* ordinal, double* q, double* logp,
  * strictly increasing. */
 int bbx_ordinal_cutpoint_loglik(bbx_ordinal* ordinal, const double* beta,
                                 int n_c, const double* cuts, double* out);
+
+/* ---------------------------------------------------------- Weibull model
+ * Proportional hazards with a Weibull baseline for right-censored times on a
+ * design (intercept column and centred predictors included): rows (d_i, lt_i),
+ * d = 1 for an event at t and 0 for a row censored at t, lt = log t; hazard
+ * h(t | x) = k t^(k - 1) exp(eta), eta = X~ beta, shape k > 0 (k = 1: the
+ * exponential model) (csrc/weibull.hip; the leapfrog and tree kernels are the
+ * Cox handle's, csrc/hamiltonian.hpp).  Every product is rounded before the
+ * sum it enters:
+ *   m_i  = exp(eta_i + (k * lt_i))
+ *   ll_i = (d_i * eta_i) - m_i        the part that depends on beta
+ *   w_i  = d_i - m_i
+ *   full_i = d_i * ((log k + ((k - 1) * lt_i)) + eta_i) - m_i
+ * At k = 1 every value is the bbx_poisson handle's on y = d, log_exposure =
+ * lt, bit for bit.  The ten shared entry points have the argument lists, the
+ * status codes and the synchronisation of their bbx_logit_* counterparts
+ * above.  The handle borrows the design (it must outlive the handle) and runs
+ * on its stream.  Every sum has a fixed order: the same inputs give the same
+ * bits on every call.
+ *
+ * create: event[n], log_time[n] (host) and the shape the handle starts with.
+ * BBX_ERR_INVALID for a NULL array or output pointer, a destroyed or foreign
+ * design, an event[i] that is not 0 or 1, a log_time[i] that is not finite
+ * (the message names the row), a shape that is not finite and positive. */
+typedef struct bbx_weibull bbx_weibull;
+int bbx_weibull_create(bbx_design* design, const double* event,
+                       const double* log_time, double shape,
+                       bbx_weibull** out);
+int bbx_weibull_destroy(bbx_weibull* weibull);
+/* Replaces the handle's k.  It invalidates the Hessian's location (m holds
+ * k): a later hessian_matvec without set_location is BBX_ERR_STATE.
+ * BBX_ERR_INVALID for a k that is not finite and positive; BBX_ERR_STATE
+ * between bbx_weibull_nuts_begin and bbx_weibull_nuts_sample, while a
+ * No-U-Turn tree built with the previous k is open. */
+int bbx_weibull_set_shape(bbx_weibull* weibull, double k);
+/* loglik = sum_i ll_i, the part of the log density that depends on beta
+ * (sum_i d_i (log k + (k - 1) lt_i) is dropped); grad[P] = X~^T w.  Where
+ * eta + k lt is past exp's range m = inf: loglik = -inf and grad is not
+ * meaningful (NaN where eta itself is +inf and d = 1); a NaN in beta gives
+ * NaN.  grad may be NULL. */
+int bbx_weibull_loglik_grad(bbx_weibull* weibull, const double* beta,
+                            double* loglik, double* grad);
+int bbx_weibull_loglik_grad_dev(bbx_weibull* weibull, const double* d_beta,
+                                double* loglik, double* d_grad);
+/* Hessian-vector products at a fixed beta and the handle's k: set_location
+ * stores m_i; hessian_matvec gives out = -X~^T (m .* (X~ v)) (BBX_ERR_STATE
+ * before a set_location, and after a set_shape until the next one). */
+int bbx_weibull_set_location(bbx_weibull* weibull, const double* beta);
+int bbx_weibull_hessian_matvec(bbx_weibull* weibull, const double* v,
+                               double* out);
+int bbx_weibull_hessian_matvec_dev(bbx_weibull* weibull, const double* d_v,
+                                   double* d_out);
+/* bbx_cox_hmc_trajectory on the Weibull f.  A step at which an m overflows is
+ * the last one: logp = -inf, *instability = 1. */
+int bbx_weibull_hmc_trajectory(bbx_weibull* weibull, double dt, int n_step,
+                               const double* precond_scale,
+                               const double* prior_prec, const double* q0,
+                               const double* p0, double logp0,
+                               const double* grad0, double hamiltonian_tol,
+                               double* q, double* p, double* logp,
+                               double* grad, int* n_grad_evals,
+                               int* instability, double* hamiltonian);
+/* bbx_cox_nuts_begin / _doubling / _sample on the Weibull f. */
+int bbx_weibull_nuts_begin(bbx_weibull* weibull, const double* precond_scale,
+                           const double* prior_prec, const double* q0,
+                           const double* p0, double logp0, const double* grad0,
+                           double joint_logp0, double joint_logp_threshold,
+                           double hamiltonian_tol);
+int bbx_weibull_nuts_doubling(bbx_weibull* weibull, double dt, int direction,
+                              int height, const double* uniforms,
+                              int* n_uniform_used, int* n_steps, int* flags,
+                              int* tree, double* averages);
+int bbx_weibull_nuts_sample(bbx_weibull* weibull, double* q, double* logp,
+                            double* grad);
+/* out[j] = L(k[j]) = sum_i full_i at the shape k[j], for n_k values (1 <= n_k
+ * <= 8; host arrays) in ONE pass over the rows: what the shape's conditional
+ * density needs.  beta[P] (host): eta = X~ beta is formed and kept on the
+ * handle; NULL: the eta of the previous call on this handle (BBX_ERR_STATE if
+ * there was none).  One launch of the shape kernel, plus the product for a
+ * non-NULL beta; one synchronisation.  out[j] depends on k[j] alone: neither
+ * on n_k nor on j, bit for bit.  A k[j] at which a row's exp overflows gives
+ * exactly -inf for a finite eta.  The handle's k, its Hessian location and
+ * the scratch of a trajectory or an open tree are not touched.
+ * BBX_ERR_INVALID for n_k outside [1, 8], a NULL k or out, a k[j] that is not
+ * finite and positive. */
+int bbx_weibull_shape_loglik(bbx_weibull* weibull, const double* beta, int n_k,
+                             const double* k, double* out);
 
 /* ----------------------- host-side reference-stream samplers (libbbx_hostrng)
  * Exported by the separate, HIP-free libbbx_hostrng.so.  `bitgen` is the
