@@ -16,6 +16,7 @@ ABI_VERSION = 113         # BBX_VERSION of include/bbx.h
 FORMAT_AUTO, FORMAT_CSR, FORMAT_TILED = 0, 1, 2
 F64, F32 = 0, 1
 MODEL_LINEAR, MODEL_LOGIT = 0, 1
+MODEL_PROBIT = 2
 PRED_LINEAR, PRED_LOGIT, PRED_POISSON = 0, 1, 2   # BBX_PRED_*
 GSCALE_SAMPLE, GSCALE_OPTIMIZE, GSCALE_FIXED = 0, 1, 2
 BATCH_ALLOW_SLOW = 1
@@ -171,6 +172,8 @@ def _declare(lib):
         "bbx_chain_eta": ([hp, c_int64, c_void_p, c_void_p], c_int),
         "bbx_chain_get_logp": (
             [hp, POINTER(c_double), POINTER(c_double)], c_int),
+        "bbx_chain_get_latent": ([hp, c_void_p], c_int),
+        "bbx_chain_get_zbase": ([hp, c_void_p], c_int),
         "bbx_chain_run": (
             [hp, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p,
              c_void_p, c_void_p, c_void_p, c_void_p], c_int),
@@ -200,6 +203,8 @@ def _declare(lib):
             [c_int, c_uint64, c_int64, c_double, c_void_p, c_void_p], c_int),
         "bbx_device_gamma": (
             [c_int, c_uint64, c_int64, c_double, c_void_p], c_int),
+        "bbx_device_truncated_normal": (
+            [c_int, c_uint64, c_int64, c_void_p, c_void_p, c_void_p], c_int),
         "bbx_device_normal": (
             [c_int, c_uint64, c_uint64, c_int64, c_void_p], c_int),
         "bbx_cox_create": (
@@ -229,6 +234,10 @@ def _declare(lib):
             [hp, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
              c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
              c_void_p], c_int),
+        "bbx_design_predictive_summary_probit": (
+            [hp, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+            c_int),
         "bbx_logit_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_poisson_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_cpoisson_create": (

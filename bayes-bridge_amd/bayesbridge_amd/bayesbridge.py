@@ -47,7 +47,9 @@ HMC_INFO_KEYS = ('stepsize', 'n_hessian_matvec', 'n_grad_evals',
 NUTS_INFO_KEYS = HMC_INFO_KEYS[:6] + ('tree_height', 'ave_accept_prob')
 # models without an observation precision (or Polya-Gamma) parameter: their
 # chains carry no 'obs_prec' and draw the coefficients by 'hmc' / 'nuts' only
-NO_OBS_PREC = ('cox', 'poisson', 'negbin', 'ordinal', 'weibull')
+# -- but for the probit model, whose observation precision is fixed at 1 and
+# whose coefficients the Gaussian samplers draw ('cg', 'cholesky', 'woodbury')
+NO_OBS_PREC = ('cox', 'poisson', 'negbin', 'ordinal', 'weibull', 'probit')
 # models whose only coefficient samplers are 'hmc' and 'nuts', and what the
 # refusals call them
 HAMILTONIAN_ONLY = {'poisson': 'Poisson', 'negbin': 'negative-binomial',
@@ -132,6 +134,8 @@ class SamplerOptions():
                     % (HAMILTONIAN_ONLY[model_name], coef_sampler_type))
             options['coef_sampler_type'] = coef_sampler_type or 'hmc'
             return SamplerOptions(**options)
+        if model_name == 'probit':
+            _check_probit_options(coef_sampler_type, options.get('rng'))
         if model_name == 'logit' and coef_sampler_type in ('hmc', 'nuts'):
             # gibbs_util.py:52-75 lets 'hmc' through for the logit model.  Its
             # draw exists on the reference's host streams only, and a logit
@@ -148,8 +152,9 @@ class SamplerOptions():
                 coef_sampler_type in ('cholesky', 'woodbury')
                 and _is_hip_dense(design)):
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
-        if model_name not in ('linear', 'logit'):
-            raise ValueError("Only linear and logit models use the CG sampler.")
+        if model_name not in ('linear', 'logit', 'probit'):
+            raise ValueError("Only linear, logit and probit models use the CG "
+                             "sampler.")
         n_obs, n_pred = design.shape
         if n_pred > n_obs:
             # (the reference's TODO here, gibbs_util.py:66-68, is the
@@ -162,6 +167,21 @@ class SamplerOptions():
         # (gibbs_util.py:53-65); here 'cg' stays the default for every design
         options['coef_sampler_type'] = coef_sampler_type or 'cg'
         return SamplerOptions(**options)
+
+
+def _check_probit_options(coef_sampler_type, rng):
+    """The probit chain exists on the device only: its latents are drawn by
+    csrc/probit.hip and its coefficients by the Gaussian samplers."""
+    if coef_sampler_type in ('hmc', 'nuts'):
+        raise ValueError(
+            "The probit model draws its coefficients with 'cg', 'cholesky' "
+            "or 'woodbury': the '%s' sampler is not supported (there is no "
+            "Hamiltonian handle for probit)." % coef_sampler_type)
+    if rng == 'reference':
+        raise ValueError(
+            "The probit model runs with rng='device' only: rng='reference' "
+            "is not supported (the reference has no probit model whose "
+            "streams could be followed).")
 
 
 def _is_hip_dense(design):
@@ -257,6 +277,12 @@ class BayesBridge():
         if not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
                 coef_sampler_type, options, self.model.name, self.model.design)
+        if self.model.name == 'probit':
+            _check_probit_options(options.coef_sampler_type, options.rng)
+            if isinstance(init, dict) and 'obs_prec' in init:
+                raise ValueError(
+                    "The probit model has no observation precision: "
+                    "init['obs_prec'] is not supported.")
         if options.coef_sampler_type in ('cholesky', 'woodbury'):
             if not _is_hip_dense(self.model.design):
                 raise ValueError(
@@ -387,6 +413,8 @@ class BayesBridge():
         other).  Batches keep 'coef', 'global_scale', 'logp' and use
         the device RNG."""
         design = self.model.design
+        if self.model.name == 'probit':
+            return 0
         if options is not None and not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
                 None, options, self.model.name, design)
@@ -447,6 +475,9 @@ class BayesBridge():
         below single chains raises unless `allow_slow`."""
         import copy
         from .device_chain import HipChainBatch
+        if self.model.name == 'probit':
+            raise ValueError("gibbs_batch is not supported for the probit "
+                             "model: its chains run one at a time (gibbs).")
         if not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
                 None, options, self.model.name, self.model.design)
@@ -504,6 +535,10 @@ class BayesBridge():
         samples[name] shaped (n_chain, ..., n_sample) on rank 0.  `batch`:
         False (default; chain k's samples do not depend on the number of
         ranks), 'auto' or a width -- see chains.run_chains."""
+        if self.model.name == 'probit':
+            raise ValueError("gibbs_multichain is not supported for the "
+                             "probit model: its chains run one at a time "
+                             "(gibbs).")
         if self.model.name in NO_OBS_PREC:
             raise ValueError("gibbs_multichain draws the coefficients with "
                              "'cg' only; the Cox model needs 'hmc'")
@@ -1058,6 +1093,8 @@ class BayesBridge():
         # through the chain: set the state, then let one kernel refresh it.
         def update_obs_precision(coef):
             # bayesbridge.py:397-410 with the device samplers
+            if model.name in NO_OBS_PREC:      # probit: Omega = I, no state
+                return None
             eta = model.design.dot(coef)
             if model.name == 'linear':
                 scale = np.sum((model.y - eta) ** 2) / 2

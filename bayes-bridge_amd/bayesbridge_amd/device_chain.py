@@ -15,6 +15,10 @@ _GSCALE_MODES = {'sample': _lib.GSCALE_SAMPLE, 'optimize': _lib.GSCALE_OPTIMIZE,
                  None: _lib.GSCALE_FIXED}
 
 
+_MODEL_CODES = {'linear': _lib.MODEL_LINEAR, 'logit': _lib.MODEL_LOGIT,
+                'probit': _lib.MODEL_PROBIT}
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(c_void_p)
 
@@ -29,12 +33,13 @@ class HipGibbsChain():
                  sd_unshrunk=(float('inf'),), bridge_exponent=.5,
                  slab_size=float('inf'), gscale_shape=0., gscale_rate=0.,
                  seed=0):
-        """family: 'linear' (outcome = y) or 'logit' (outcome = n_success);
+        """family: 'linear' (outcome = y), 'logit' (outcome = n_success) or
+        'probit' (outcome = y in {0, 1}; n_trial None or all ones);
         sd_unshrunk: prior sd of the unshrunk coefficients, intercept first
         (bayesbridge.py:26-32); gscale_shape/rate: Gamma prior on
         tau^-bridge_exponent (prior.py:77-81), raw parametrisation."""
-        if family not in ('linear', 'logit'):
-            raise ValueError("family must be 'linear' or 'logit'")
+        if family not in _MODEL_CODES:
+            raise ValueError("family must be 'linear', 'logit' or 'probit'")
         self._lib = _lib.load()
         self._c = c_void_p()
         self.design = design            # keeps the operator alive
@@ -49,7 +54,7 @@ class HipGibbsChain():
             n_trial = _f64(n_trial)
         _lib.check(self._lib.bbx_chain_create(
             design.handle,
-            _lib.MODEL_LINEAR if family == 'linear' else _lib.MODEL_LOGIT,
+            _MODEL_CODES[family],
             _ptr(outcome), _ptr(n_trial), self.n_unshrunk, _ptr(sd),
             float(bridge_exponent), float(slab_size), float(gscale_shape),
             float(gscale_rate), int(seed) & 0xFFFFFFFFFFFFFFFF,
@@ -76,7 +81,8 @@ class HipGibbsChain():
 
     @property
     def _obs_len(self):
-        return self.n if self.family == 'logit' else 1
+        # (a probit chain has no observation precision: 0)
+        return {'logit': self.n, 'probit': 0}.get(self.family, 1)
 
     # ---- Markov-chain state (raw parametrisation, prior.py:129-141)
     def set_state(self, coef=None, obs_prec=None, local_scale=None,
@@ -86,6 +92,8 @@ class HipGibbsChain():
         ls = None if local_scale is None else _f64(local_scale)
         if coef is not None and coef.shape != (self.P,):
             raise ValueError("coef must have length %d" % self.P)
+        if obs is not None and self.family == 'probit':
+            raise ValueError("a probit chain has no obs_prec")
         if obs is not None and obs.shape != (self._obs_len,):
             raise ValueError("obs_prec must have length %d" % self._obs_len)
         if ls is not None and ls.shape != (self.n_shrunk,):
@@ -97,15 +105,29 @@ class HipGibbsChain():
 
     def get_state(self):
         """(coef, obs_prec, local_scale, global_scale); obs_prec is a float
-        for the linear model."""
+        for the linear model and None for the probit model."""
         coef = np.empty(self.P)
         ls = np.empty(self.n_shrunk)
-        obs = np.empty(self._obs_len)
+        obs = None if self.family == 'probit' else np.empty(self._obs_len)
         g = c_double()
         _lib.check(self._lib.bbx_chain_get_state(
             self._c, _ptr(coef), _ptr(obs), _ptr(ls), byref(g)))
-        return (coef, obs if self.family == 'logit' else float(obs[0]), ls,
-                float(g.value))
+        if self.family == 'linear':
+            obs = float(obs[0])
+        return coef, obs, ls, float(g.value)
+
+    def get_latent(self):
+        """The n latents z of a probit chain's current state."""
+        out = np.empty(self.n)
+        _lib.check(self._lib.bbx_chain_get_latent(self._c, _ptr(out)))
+        return out
+
+    def get_zbase(self):
+        """X~^T kappa (logit), X~^T y (linear) or X~^T z (probit): what the
+        next draw's right-hand side is scaled from."""
+        out = np.empty(self.P)
+        _lib.check(self._lib.bbx_chain_get_zbase(self._c, _ptr(out)))
+        return out
 
     def init_obs_prec(self):
         _lib.check(self._lib.bbx_chain_init_obs_prec(self._c))
@@ -210,7 +232,7 @@ class HipGibbsChain():
             'local_scale': np.zeros((rows, max(self.n_shrunk, 1)))
             if 'local_scale' in save else None,
             'obs_prec': np.zeros((rows, self._obs_len))
-            if 'obs_prec' in save else None,
+            if 'obs_prec' in save and self.family != 'probit' else None,
         }
         gs, lp, ncg = np.zeros(rows), np.zeros(rows), np.zeros(rows)
         n_unconv = _lib.check(self._lib.bbx_chain_run_host(

@@ -577,6 +577,94 @@ class LogisticModel(_DeviceHamiltonian, _Predictive, _Model):
         return np.random.binomial(n_trial, prob)
 
 
+def _binary_outcome(y, n_row):
+    """The outcome check of the probit model on n_row rows: y in {0, 1}."""
+    if isinstance(y, tuple):
+        raise ValueError(
+            "The probit model takes a binary outcome y, not (n_success, "
+            "n_trial): a binomial outcome is the logit model's "
+            "(family='logit').")
+    y = np.asarray(y, dtype=np.float64)
+    if y.shape != (n_row,):
+        raise ValueError(
+            "Incompatible sizes of the outcome and design matrix: %s "
+            "outcomes, %d rows." % (y.shape, n_row))
+    bad = np.flatnonzero(~((y == 0.) | (y == 1.)))
+    if bad.size:
+        raise ValueError(
+            "The probit model takes a binary outcome: y[%d] = %r is not 0 "
+            "or 1." % (bad[0], float(y[bad[0]])))
+    return y
+
+
+class ProbitModel(_Predictive, _Model):
+    """Binary regression with the probit link, P(y_i = 1) = Phi(eta_i), no
+    counterpart in the reference.  Under Albert & Chib's augmentation, z_i |
+    beta ~ N(eta_i, 1) truncated to z > 0 (y_i = 1) or z <= 0 (y_i = 0), the
+    coefficients' conditional is the linear model's with outcome z and the
+    observation precision fixed at 1: the chain draws them with 'cg',
+    'cholesky' or 'woodbury' on the device (csrc/probit.hip draws z).  The
+    augmentation mixes slowly on very imbalanced outcomes, as Polya-Gamma
+    does."""
+
+    def __init__(self, y, design):
+        self.y = _binary_outcome(y, design.shape[0])
+        self.n_success = self.y          # what the device chain is handed
+        self.design = design
+        self.name = 'probit'
+
+    def compute_loglik_and_gradient(self, beta, loglik_only=False):
+        """sum_i log Phi(s_i eta_i), s_i = 2 y_i - 1, and its gradient
+        X~^T (s phi(eta) / Phi(s eta))."""
+        from scipy.special import log_ndtr
+        eta = self.design.dot(beta)
+        s = 2. * self.y - 1.
+        ll = log_ndtr(s * eta)
+        grad = None
+        if not loglik_only:
+            hazard = np.exp(-.5 * eta * eta - .5 * math.log(2. * math.pi) - ll)
+            grad = self.design.Tdot(s * hazard)
+        return float(np.sum(ll)), grad
+
+    def calc_intercept_mle(self):
+        from scipy.special import ndtri
+        return float(ndtri(self.y.mean()))
+
+    def _pred_call(self, n_draw, draws, obs_prec, offset, y, n_trial,
+                   ll_const):
+        return 'bbx_design_predictive_summary_probit', (n_draw,), \
+            (draws, offset, y, ll_const)
+
+    def predict(self, coef, X_new=None, y_new=None, return_draws=False,
+                _draws_per_pass=0):
+        """Posterior prediction over the draws coef (P,) or (P, S) -- what
+        samples['coef'] is.  X_new=None: the training rows with the model's
+        own outcome; otherwise n_new rows of the model's raw columns (NumPy or
+        SciPy), centred with the TRAINING design's column means, with a
+        binary y_new or without.  A dict: 'mean' and 'sd' (n,), the posterior
+        mean of Phi(eta) and its population standard deviation over the
+        draws; with an outcome 'lpd', 'loglik_mean' and 'loglik_var' (n,) and
+        the floats 'lppd' = sum lpd, 'p_waic' = sum loglik_var and 'waic' =
+        -2 (lppd - p_waic), the log density being log Phi(eta) for y = 1 and
+        log Phi(-eta) for y = 0; with return_draws 'draws' (n, S).  One
+        device call for all the draws."""
+        draws, X_new, n_row = self._predict_rows(coef, X_new)
+        _training_rows_only(X_new, y_new=y_new)
+        y = self.y if X_new is None else y_new
+        if y is not None:
+            y = _binary_outcome(y, n_row)
+        return self._predictive_summary(
+            draws, X_new, n_row, y=y, return_draws=return_draws,
+            draws_per_pass=_draws_per_pass)
+
+    @staticmethod
+    def simulate_outcome(X, beta, seed=None):
+        """y_i = 1 when eta_i + a standard normal is positive."""
+        rng = np.random.default_rng(seed)
+        return (X.dot(beta) + rng.standard_normal(X.shape[0]) > 0.) \
+            .astype(np.float64)
+
+
 class PoissonModel(_DeviceHamiltonian, _Predictive, _Model):
     """Incidence-rate regression: counts y_i with mean exposure_i exp(eta_i).
     The likelihood, its gradient and the Hessian-vector products run on the
@@ -2429,7 +2517,9 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     row's two times finite -- but the rows stay in their order and an
     intercept is added; `weibull_shape` (None: sampled, with the prior
     `weibull_shape_prior` = {'shape': .., 'rate': ..}, None: Gamma(2, 1); a
-    number: held fixed) is the Weibull shape k.  Strata are refused.  (The
+    number: held fixed) is the Weibull shape k.  Strata are refused.  For
+    family='probit', outcome = y in {0, 1}; a tuple with n_trial is refused
+    (the binomial outcome is the logit model's).  (The
     six keywords stand before `competing_time`, which stays the last one:
     pass them by name.)"""
     if entry_time is not None and family != 'cox':
@@ -2472,6 +2562,9 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
             "The negative-binomial model takes outcome = y or (y, exposure): "
             "strata are not supported, the conditional model has no "
             "negative-binomial form here.")
+    if family == 'probit':
+        # (before the design goes to the GPU)
+        outcome = _binary_outcome(outcome, X.shape[0])
     stratified_poisson = (family == 'poisson' and isinstance(outcome, tuple)
                           and len(outcome) == 3)
     if add_intercept is None:
@@ -2619,6 +2712,8 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         else:
             n_success, n_trial = outcome, None
         return LogisticModel(n_success, n_trial, design)
+    if family == 'probit':
+        return ProbitModel(outcome, design)
     if family == 'cox':
         if competing_time is not None:
             return CoxModel._finegray(event_time, censoring_time,

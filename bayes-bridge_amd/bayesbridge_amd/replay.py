@@ -16,6 +16,7 @@ from . import hostrng
 # csrc/philox.hpp PhiloxStream
 STREAM_ETA1, STREAM_ETA2, STREAM_PG, STREAM_GSCALE, STREAM_LSCALE, \
     STREAM_OBSVAR = 1, 2, 3, 4, 5, 6
+STREAM_LATENT = 7
 
 _SIGS = {
     "bbx_replay_philox_block": [c_void_p, c_void_p, c_void_p],
@@ -28,6 +29,9 @@ _SIGS = {
                                c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "bbx_replay_tilted_stable": [c_uint64, c_uint64, c_int64, c_double,
                                  c_void_p, c_int, c_void_p, c_void_p],
+    "bbx_replay_truncated_normal": [c_uint64, c_uint64, c_int64, c_void_p,
+                                    c_void_p, c_int, c_void_p, c_void_p],
+    "bbx_host_log_norm_cdf": [c_int64, c_void_p, c_void_p],
     "bbx_replay_gamma": [c_uint64, c_uint64, c_uint64, c_int64, c_double,
                          c_void_p],
 }
@@ -123,6 +127,33 @@ def tilted_stable(seed, stream, char_exp, tilt, variant=0, trace=False):
         seed, stream, tilt.size, float(char_exp), _p(tilt), int(variant),
         _p(out), _p(win)), 'tilted-stable')
     return (out, win) if trace else out
+
+
+def truncated_normal(seed, stream, psi, positive, variant=0, trace=False):
+    """N(psi_i, 1) on z > 0 where positive[i], else on z <= 0, as
+    chain_probit_kernel draws it (csrc/probit.hip); with trace, (draws,
+    trials): the trials each element took (0: psi was not finite, the draw is
+    a NaN).  `stream`: `iter_stream(STREAM_LATENT, it)` for the chain's
+    iteration `it` (`it = -1`: the state of a chain that has not run), the
+    bare STREAM_LATENT for bbx_device_truncated_normal."""
+    psi = np.ascontiguousarray(psi, dtype=np.float64)
+    positive = np.ascontiguousarray(np.asarray(positive) != 0, dtype=np.uint8)
+    assert psi.ndim == 1 and positive.shape == psi.shape
+    out = np.empty(psi.size)
+    trials = np.zeros(psi.size, dtype=np.int32)
+    _check(_lib().bbx_replay_truncated_normal(
+        seed, stream, psi.size, _p(psi), _p(positive), int(variant), _p(out),
+        _p(trials)), 'truncated-normal')
+    return (out, trials) if trace else out
+
+
+def log_norm_cdf(x):
+    """log Phi(x) in the host form of csrc/samplers.hpp."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.empty(x.shape)
+    _check(_lib().bbx_host_log_norm_cdf(x.size, _p(x), _p(out)),
+           'log_norm_cdf')
+    return out
 
 
 def gamma(seed, stream, shape, n=1, index=0):

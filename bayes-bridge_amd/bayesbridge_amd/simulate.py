@@ -98,7 +98,8 @@ def simulate_outcome(X, beta, model, intercept=0., n_trial=None, seed=None,
     (NegBinModel.simulate_outcome); for 'weibull', (event_time,
     censoring_time) with the hazard weibull_shape t^(weibull_shape - 1)
     exp(intercept + X beta) and the censoring fraction asked for
-    (WeibullModel.simulate_outcome)."""
+    (WeibullModel.simulate_outcome); for 'probit', y in {0, 1} with
+    P(y = 1) = Phi(intercept + X beta)."""
     if model == 'cox':
         from .model import CoxModel
         return CoxModel.simulate_outcome(X, beta, censoring_frac, seed)
@@ -122,6 +123,10 @@ def simulate_outcome(X, beta, model, intercept=0., n_trial=None, seed=None,
         prob = 1 / (1 + np.exp(- intercept - X.dot(beta)))
         n_success = np.random.binomial(n_trial.astype(np.int32), prob)
         return n_success, n_trial
+    if model == 'probit':
+        # y = 1 when the latent intercept + X beta + N(0, 1) is positive
+        latent = intercept + X.dot(beta) + np.random.randn(X.shape[0])
+        return (np.asarray(latent).ravel() > 0.).astype(np.float64)
     raise NotImplementedError(model)
 
 

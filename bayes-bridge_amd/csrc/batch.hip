@@ -696,6 +696,10 @@ int bbx_batch_create_opts(bbx_design* design, int n_chain,
     if (chains[c]->coef_sampler != BBX_SAMPLER_CG)
       return fail(BBX_ERR_INVALID,
                   "batched chains draw the coefficients with BBX_SAMPLER_CG only");
+    if (chains[c]->model == BBX_MODEL_PROBIT)
+      return fail(BBX_ERR_INVALID,
+                  "batched chains are linear or logit: a probit chain runs on "
+                  "its own");
     if (chains[c]->n_unshrunk != chains[0]->n_unshrunk)
       return fail(BBX_ERR_INVALID,
                   "the chains of a batch must agree on n_unshrunk");

@@ -4,6 +4,7 @@
 // by Philox counters.
 #include <cmath>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "chain.hpp"
@@ -193,7 +194,7 @@ __device__ inline double sum_row_parts(const double* part, int count) {
 }
 
 // Finishes the observation-level reductions (single block).
-//   logit : loglik = sum of partials
+//   logit, probit: loglik = sum of partials
 //   linear: obs_prec ~ Gamma(n/2, 1) / (rss/2); loglik = n log(w)/2 - w rss/2
 //           (bayesbridge.py:400-404; linear_model.py:13-17); `init` => 1/mean
 __global__ __launch_bounds__(256) void chain_obs_finish_kernel(
@@ -201,7 +202,7 @@ __global__ __launch_bounds__(256) void chain_obs_finish_kernel(
     const double* __restrict__ part, int count, ChainScalars* __restrict__ sc) {
   const double tot = sum_row_parts(part, count);
   if (threadIdx.x != 0) return;
-  if (model == BBX_MODEL_LOGIT) {
+  if (model == BBX_MODEL_LOGIT || model == BBX_MODEL_PROBIT) {
     sc->loglik = tot;
   } else {
     double w;
@@ -557,6 +558,34 @@ static int chain_linear_predictor(bbx_chain* c) {
                     nullptr);
 }
 
+// z | beta of a probit chain from the psi in place, with the latent stream of
+// iteration `it` (-1: the reserved index of a chain that has not run), then
+// zbase = X~^T z: the one product a probit iteration adds.  The log-likelihood
+// partials are left in row_part[0 .. *row_blocks) for chain_obs_finish_kernel.
+static int chain_probit_update(bbx_chain* c, int64_t it, int* row_blocks) {
+  bbx_design* h = c->h;
+  BBX_TRY(launch_chain_probit(c, iter_stream(STREAM_LATENT, it), row_blocks));
+  TdotEpilogue ep;
+  return launch_tdot(h, c->latent.as<double>(), part_slot(h, PS_SUMW), ep,
+                     c->zbase.as<double>());
+}
+
+// psi, z, zbase and the log-likelihood of a probit chain recomputed from its
+// coefficients: z is a function of (seed, iteration, element, psi), so the
+// state a finished iteration left is reproduced bit for bit.
+static int chain_probit_refresh(bbx_chain* c) {
+  bbx_design* h = c->h;
+  BBX_TRY(chain_linear_predictor(c));
+  int rg = 0;
+  BBX_TRY(chain_probit_update(c, c->iter - 1, &rg));
+  BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, h->stream,
+             c->model, 0, h->n, c->seed, 0, c->row_part.as<double>(), rg,
+             c->scalars.as<ChainScalars>());
+  BBX_HIP(hipGetLastError());
+  BBX_HIP(hipStreamSynchronize(h->stream));
+  return BBX_OK;
+}
+
 // The pass for X~ beta enqueued by the CG loop itself, right behind a look at
 // the stop flag (bbx_design::tail_hook): when the host wakes up from that look
 // the pass is already running, and the kernels of both branches are launched
@@ -752,6 +781,8 @@ int chain_post_draw(bbx_chain* c, bool have_psi, int phases,
     else if (elems >= 4) BBX_PG_LAUNCH(chain_pg_kernel<4>, 1024);
     else BBX_PG_LAUNCH(chain_pg_kernel<1>, 256);
 #undef BBX_PG_LAUNCH
+  } else if (c->model == BBX_MODEL_PROBIT) {
+    BBX_TRY(chain_probit_update(c, c->iter, &rg));
   } else {
     BBX_LAUNCH(chain_rss_kernel, dim3(rg), dim3(256), 0, s, n,
                        c->outcome.as<double>(), c->psi.as<double>(), rp);
@@ -792,9 +823,12 @@ static int chain_step(bbx_chain* c, int maxiter, double atol, int* n_cg_iter) {
       BBX_TRY(launch_fill_normal(h, h->P, cg_draw_seed(c, it), STREAM_ETA2,
                                  c->eta2_next.as<double>()));
     }
+    // (probit: the linear model's branch at the fixed precision 1 -- the
+    // cached Gram, no weighted one)
     const bool linear = c->model == BBX_MODEL_LINEAR;
+    const bool probit = c->model == BBX_MODEL_PROBIT;
     const int st = chol_sample_device(
-        h, linear ? nullptr : c->obs_prec.as<double>(), 1.,
+        h, linear || probit ? nullptr : c->obs_prec.as<double>(), 1.,
         linear ? &c->scalars.as<ChainScalars>()->obs_prec : nullptr,
         c->phi.as<double>(), c->z.as<double>(), c->eta2_next.as<double>(),
         c->coef.as<double>());
@@ -821,13 +855,17 @@ static int chain_step(bbx_chain* c, int maxiter, double atol, int* n_cg_iter) {
                                  c->eta2_next.as<double>()));
     }
     const bool linear = c->model == BBX_MODEL_LINEAR;
-    // logit: kappa = Omega y (the pseudo-outcome is kappa / Omega)
+    const bool probit = c->model == BBX_MODEL_PROBIT;
+    // logit: kappa = Omega y (the pseudo-outcome is kappa / Omega); probit: the
+    // linear branch with the latents as outcome at the fixed precision 1
     const int st = woodbury_sample_device(
-        h, linear ? nullptr : c->obs_prec.as<double>(), 1.,
+        h, linear || probit ? nullptr : c->obs_prec.as<double>(), 1.,
         linear ? &c->scalars.as<ChainScalars>()->obs_prec : nullptr,
         c->phi.as<double>(),
-        linear ? c->outcome.as<double>() : c->kappa.as<double>(),
-        linear ? 0 : 1, c->eta1_next.as<double>(), c->eta2_next.as<double>(),
+        linear   ? c->outcome.as<double>()
+        : probit ? c->latent.as<double>()
+                 : c->kappa.as<double>(),
+        linear || probit ? 0 : 1, c->eta1_next.as<double>(), c->eta2_next.as<double>(),
         c->coef.as<double>());
     c->eta_iter = -1;
     if (st < 0) return st;
@@ -889,7 +927,7 @@ int chain_save_sample(bbx_chain* c, int idx, double* d_coef, double* d_lscale,
     BBX_HIP(hipMemcpyAsync(d_lscale + (size_t)idx * n_shrunk, c->lscale.ptr,
                            sizeof(double) * (size_t)n_shrunk,
                            hipMemcpyDeviceToDevice, h->stream));
-  if (d_obs_prec) {
+  if (d_obs_prec && c->model != BBX_MODEL_PROBIT) {
     if (c->model == BBX_MODEL_LOGIT)
       BBX_HIP(hipMemcpyAsync(d_obs_prec + (size_t)idx * n, c->obs_prec.ptr,
                              sizeof(double) * (size_t)n,
@@ -941,8 +979,20 @@ int bbx_chain_create(bbx_design* design, int model, const double* outcome,
   if (!out) return fail(BBX_ERR_INVALID, "out is NULL");
   *out = nullptr;
   if (!design || !outcome) return fail(BBX_ERR_INVALID, "NULL argument");
-  if (model != BBX_MODEL_LINEAR && model != BBX_MODEL_LOGIT)
+  if (model != BBX_MODEL_LINEAR && model != BBX_MODEL_LOGIT &&
+      model != BBX_MODEL_PROBIT)
     return fail(BBX_ERR_INVALID, "unknown model");
+  if (model == BBX_MODEL_PROBIT) {
+    for (int64_t i = 0; i < design->n; ++i) {
+      if (!(outcome[i] == 0. || outcome[i] == 1.))
+        return fail(BBX_ERR_INVALID, "probit: outcome[" + std::to_string(i) +
+                                         "] is not 0 or 1");
+      if (n_trial && n_trial[i] != 1.)
+        return fail(BBX_ERR_INVALID,
+                    "probit: n_trial[" + std::to_string(i) +
+                        "] is not 1 (a binomial outcome is the logit model's)");
+    }
+  }
   if (n_unshrunk < 0 || n_unshrunk > design->P)
     return fail(BBX_ERR_INVALID, "n_unshrunk out of range");
   if (n_unshrunk > 0 && !sd_unshrunk)
@@ -969,6 +1019,7 @@ int bbx_chain_create(bbx_design* design, int model, const double* outcome,
     BBX_TRY(c->kappa.alloc(nb));
     BBX_TRY(c->obs_prec.alloc(nb));
     BBX_TRY(c->psi.alloc(nb));
+    if (model == BBX_MODEL_PROBIT) BBX_TRY(c->latent.alloc(nb));
     for (DevMem* m : {&c->zbase, &c->coef, &c->phi, &c->x0, &c->sd, &c->z,
                       &c->mean, &c->square})
       BBX_TRY(m->alloc(Pb));
@@ -1001,10 +1052,13 @@ int bbx_chain_create(bbx_design* design, int model, const double* outcome,
                          c->n_trial.as<double>(), c->kappa.as<double>());
       src = c->kappa.as<double>();
     }
-    BBX_TRY(launch_sum_n(h, src, n, part_slot(h, PS_SUMW)));
-    TdotEpilogue ep;
-    BBX_TRY(launch_tdot(h, src, part_slot(h, PS_SUMW), ep,
-                        c->zbase.as<double>()));
+    // (probit: zbase = X~^T z, from the latents drawn below)
+    if (model != BBX_MODEL_PROBIT) {
+      BBX_TRY(launch_sum_n(h, src, n, part_slot(h, PS_SUMW)));
+      TdotEpilogue ep;
+      BBX_TRY(launch_tdot(h, src, part_slot(h, PS_SUMW), ep,
+                          c->zbase.as<double>()));
+    }
     // summariser initial state (reg_coef_posterior_summarizer.py:88-91)
     BBX_HIP(hipMemsetAsync(c->mean.ptr, 0, Pb, h->stream));
     std::vector<double> ones((size_t)P, 1.);
@@ -1033,6 +1087,14 @@ int bbx_chain_create(bbx_design* design, int model, const double* outcome,
                          c->psi.as<double>(), c->obs_prec.as<double>());
     else
       BBX_HIP(hipMemsetAsync(c->obs_prec.ptr, 0, nb, h->stream));
+    if (model == BBX_MODEL_PROBIT) {
+      // Omega = I, filled once (the scalar obs_prec stays 1), and the latents
+      // of coef = 0 on the reserved stream index
+      BBX_LAUNCH(chain_fill_obs_prec_kernel, dim3(grid_for(n, ROW_GRID)),
+                 dim3(256), 0, h->stream, n, c->scalars.as<ChainScalars>(),
+                 c->obs_prec.as<double>());
+      BBX_TRY(chain_probit_refresh(c));
+    }
     BBX_HIP(hipGetLastError());
     BBX_HIP(hipStreamSynchronize(h->stream));
     return BBX_OK;
@@ -1073,6 +1135,8 @@ static int bbx_chain_set_state_impl(bbx_chain* c, const double* coef,
   if (coef)
     BBX_HIP(hipMemcpy(c->coef.ptr, coef, sizeof(double) * (size_t)h->P,
                       hipMemcpyHostToDevice));
+  if (obs_prec && c->model == BBX_MODEL_PROBIT)
+    return fail(BBX_ERR_INVALID, "a probit chain has no obs_prec");
   ChainScalars sc;
   BBX_HIP(hipMemcpy(&sc, c->scalars.ptr, sizeof(sc), hipMemcpyDeviceToHost));
   if (obs_prec) {
@@ -1088,6 +1152,7 @@ static int bbx_chain_set_state_impl(bbx_chain* c, const double* coef,
                       hipMemcpyHostToDevice));
   if (gscale) sc.gscale = *gscale;
   BBX_HIP(hipMemcpy(c->scalars.ptr, &sc, sizeof(sc), hipMemcpyHostToDevice));
+  if (c->model == BBX_MODEL_PROBIT) BBX_TRY(chain_probit_refresh(c));
   return BBX_OK;
 }
 
@@ -1104,6 +1169,8 @@ static int bbx_chain_get_state_impl(bbx_chain* c, double* coef, double* obs_prec
                         double* lscale, double* gscale) {
   BBX_TRY(chain_check(c));
   bbx_design* h = c->h;
+  if (obs_prec && c->model == BBX_MODEL_PROBIT)
+    return fail(BBX_ERR_INVALID, "a probit chain has no obs_prec");
   BBX_HIP(hipSetDevice(h->device));
   BBX_HIP(hipStreamSynchronize(h->stream));
   if (coef)
@@ -1245,10 +1312,38 @@ int bbx_chain_get_logp(bbx_chain* c, double* loglik, double* logp) {
   return BBX_OK;
 }
 
+int bbx_chain_get_latent(bbx_chain* c, double* out) {
+  return no_throw([&]() -> int {
+    BBX_TRY(chain_check(c));
+    if (c->model != BBX_MODEL_PROBIT)
+      return fail(BBX_ERR_INVALID,
+                  "bbx_chain_get_latent: not a probit chain");
+    if (!out) return fail(BBX_ERR_INVALID, "bbx_chain_get_latent: out is NULL");
+    BBX_HIP(hipSetDevice(c->h->device));
+    BBX_HIP(hipStreamSynchronize(c->h->stream));
+    BBX_HIP(hipMemcpy(out, c->latent.ptr, sizeof(double) * (size_t)c->h->n,
+                      hipMemcpyDeviceToHost));
+    return BBX_OK;
+  });
+}
+
+int bbx_chain_get_zbase(bbx_chain* c, double* out) {
+  return no_throw([&]() -> int {
+    BBX_TRY(chain_check(c));
+    if (!out) return fail(BBX_ERR_INVALID, "bbx_chain_get_zbase: out is NULL");
+    BBX_HIP(hipSetDevice(c->h->device));
+    BBX_HIP(hipStreamSynchronize(c->h->stream));
+    BBX_HIP(hipMemcpy(out, c->zbase.ptr, sizeof(double) * (size_t)c->h->P,
+                      hipMemcpyDeviceToHost));
+    return BBX_OK;
+  });
+}
+
 int bbx_chain_init_obs_prec(bbx_chain* c) {
   BBX_TRY(chain_check(c));
   bbx_design* h = c->h;
   BBX_HIP(hipSetDevice(h->device));
+  if (c->model == BBX_MODEL_PROBIT) return chain_probit_refresh(c);
   BBX_TRY(chain_linear_predictor(c));
   const int rg = grid_for(h->n, ROW_GRID);
   if (c->model == BBX_MODEL_LOGIT) {
@@ -1275,6 +1370,8 @@ static int bbx_chain_run_impl(bbx_chain* c, int n_iter, int n_burnin, int thin,
   BBX_TRY(chain_check(c));
   if (n_iter < 0 || n_burnin < 0 || thin < 1 || n_burnin > n_iter)
     return fail(BBX_ERR_INVALID, "bad n_iter / n_burnin / thin");
+  if (d_obs_prec && c->model == BBX_MODEL_PROBIT)
+    return fail(BBX_ERR_INVALID, "a probit chain has no obs_prec");
   bbx_design* h = c->h;
   BBX_HIP(hipSetDevice(h->device));
   const int64_t P = h->P;
@@ -1334,6 +1431,8 @@ static int bbx_chain_run_host_impl(bbx_chain* c, int n_iter, int n_burnin, int t
   BBX_TRY(chain_check(c));
   if (n_iter < 0 || n_burnin < 0 || thin < 1 || n_burnin > n_iter)
     return fail(BBX_ERR_INVALID, "bad n_iter / n_burnin / thin");
+  if (obs_prec && c->model == BBX_MODEL_PROBIT)
+    return fail(BBX_ERR_INVALID, "a probit chain has no obs_prec");
   bbx_design* h = c->h;
   BBX_HIP(hipSetDevice(h->device));
   const int64_t P = h->P, n = h->n;
@@ -1527,9 +1626,10 @@ int bbx_chain_set_coef_sampler(bbx_chain* c, int sampler) {
       return fail(BBX_ERR_INVALID,
                   "the woodbury sampler needs a dense design (this one is sparse)");
     if (sampler == BBX_SAMPLER_WOODBURY && c->model != BBX_MODEL_LINEAR &&
-        c->model != BBX_MODEL_LOGIT)
+        c->model != BBX_MODEL_LOGIT && c->model != BBX_MODEL_PROBIT)
       return fail(BBX_ERR_INVALID,
-                  "the woodbury sampler draws linear and logit models only");
+                  "the woodbury sampler draws linear, logit and probit "
+                  "models only");
     if (sampler == BBX_SAMPLER_CHOLESKY && c->h->sparse)
       return fail(BBX_ERR_INVALID,
                   "the cholesky sampler needs a dense design (this one is sparse)");

@@ -50,7 +50,8 @@ struct bbx_chain {
   bbx::DevMem coef, phi, x0, sd, z, mean, square, sd_unshrunk;  // P-length
   bbx::DevMem lscale;                   // P - n_unshrunk
   bbx::DevMem obs_prec, psi;            // n
-  bbx::DevMem scalars;                  // ChainScalars
+  bbx::DevMem latent;                   // n: the probit model's z (else empty)
+  bbx::DevMem scalars;                 // ChainScalars
   bbx::DevMem row_part;                 // ROW_GRID partials x 2
   bbx::DevMem misc_part;                // NPART x 3: sums over the coefficients (tau branch)
   // The normals of the NEXT draw (cg_sampler.py:61-62), filled on the design's
@@ -102,5 +103,12 @@ int chain_begin_run(bbx_chain* c, int n_sample);
 int chain_save_sample(bbx_chain* c, int idx, double* d_coef, double* d_lscale,
                       double* d_obs_prec);
 int chain_end_run(bbx_chain* c, int n_sample, double* gscale, double* logp);
+
+// z | beta of a probit chain (probit.hip), on the design's stream: latent_i ~
+// N(psi_i, 1) on the half-line outcome_i selects, element i from Philox(seed,
+// stream, i, trial); the partials of sum_i log Phi(+-psi_i) into row_part[0 ..
+// *row_blocks) and the NPART partials of sum_i latent_i into the design's
+// PS_SUMW slot, what launch_tdot(latent) reads.
+int launch_chain_probit(bbx_chain* c, uint64_t stream, int* row_blocks);
 
 }  // namespace bbx

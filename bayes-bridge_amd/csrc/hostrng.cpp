@@ -88,4 +88,10 @@ int bbx_host_pg_series_accept(int64_t n, const double* x, const double* u,
   return BBX_OK;
 }
 
+int bbx_host_log_norm_cdf(int64_t n, const double* x, double* out) {
+  if (!x || !out || n < 0) return BBX_ERR_INVALID;
+  for (int64_t i = 0; i < n; ++i) out[i] = bbx::log_norm_cdf(x[i]);
+  return BBX_OK;
+}
+
 }  // extern "C"

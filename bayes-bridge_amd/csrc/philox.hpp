@@ -85,7 +85,8 @@ enum PhiloxStream : uint64_t {
   STREAM_PG = 3,     // bayesbridge.py:406
   STREAM_GSCALE = 4, // bayesbridge.py:438
   STREAM_LSCALE = 5, // bayesbridge.py:463
-  STREAM_OBSVAR = 6  // bayesbridge.py:403
+  STREAM_OBSVAR = 6, // bayesbridge.py:403
+  STREAM_LATENT = 7  // the probit model's truncated-normal latents (probit.hip)
 };
 
 }  // namespace bbx

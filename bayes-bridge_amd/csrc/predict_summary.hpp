@@ -3,7 +3,7 @@
 // (PredPasses), which ordinal_predict.hip's own kernel uses too, and the
 // summary kernel of the one-mean families with its host side (predict.hip:
 // linear, logit, Poisson; negbin_predict.hip: negative binomial;
-// weibull_predict.hip: Weibull).  Kernels and
+// weibull_predict.hip: Weibull; probit_predict.hip: probit).  Kernels and
 // drivers are static: a translation unit holds the instantiations it launches
 // and no others.  predict.hip describes the method.
 //
@@ -35,6 +35,7 @@
 
 #include "common.hpp"
 #include "negbin_terms.hpp"
+#include "samplers.hpp"   // log_norm_cdf
 #include "weibull_terms.hpp"
 
 #pragma clang fp contract(off)  // a + b * c rounded as NumPy rounds it
@@ -53,6 +54,9 @@ constexpr int PRED_NEGBIN = 3;
 // The Weibull model's, likewise: its entry point and its instantiation live in
 // weibull_predict.hip.  Its "mean" is the median survival time.
 constexpr int PRED_WEIBULL = 4;
+// The probit model's, likewise (probit_predict.hip): mu = Phi(eta),
+// ll = log Phi(+-eta).
+constexpr int PRED_PROBIT = 5;
 
 struct PredArgs {
   int64_t n;
@@ -105,6 +109,11 @@ __device__ __forceinline__ void pred_terms(double eta, double y, double m,
     // draw's k and log k; the predicted quantity is the median survival time
     *mu = weibull_median(eta, tau);
     if (SCORE) *ll = weibull_full(eta, y, m, tau, hlt);
+  } else if (FAMILY == PRED_PROBIT) {
+    // Phi(eta) = erfc(-eta / sqrt 2) / 2: absolute error ~1e-16, what a mean
+    // needs; the score is the log of the outcome's own tail
+    *mu = 0.5 * erfc(-0.70710678118654752440 * eta);
+    if (SCORE) *ll = log_norm_cdf(y != 0. ? eta : -eta);
   } else {
     // negative binomial: r and log r of the draw are in its table
     *mu = exp(eta);

@@ -12,6 +12,9 @@ void polya_gamma(uint64_t seed, uint64_t stream, int64_t n, int shape_is_double,
                  int32_t* attempts, int32_t* restarts);
 void tilted_stable(uint64_t seed, uint64_t stream, int64_t n, double a,
                    const double* tilt, double* out, int32_t* winner);
+void truncated_normal(uint64_t seed, uint64_t stream, int64_t n,
+                      const double* psi, const unsigned char* positive,
+                      double* out, int32_t* trials);
 }  // namespace replay_device_forms_api
 
 namespace ref = replay_reference_forms;
@@ -79,6 +82,20 @@ int bbx_replay_tilted_stable(uint64_t seed, uint64_t stream, int64_t n,
                                            winner);
   else
     ref::tilted_stable(seed, stream, n, char_exp, tilt, out, winner);
+  return BBX_OK;
+}
+
+int bbx_replay_truncated_normal(uint64_t seed, uint64_t stream, int64_t n,
+                                const double* psi,
+                                const unsigned char* positive, int variant,
+                                double* out, int32_t* trials) {
+  if (!psi || !positive || !out || n < 0 || (variant != 0 && variant != 1))
+    return BBX_ERR_INVALID;
+  if (variant == 1)
+    replay_device_forms_api::truncated_normal(seed, stream, n, psi, positive,
+                                              out, trials);
+  else
+    ref::truncated_normal(seed, stream, n, psi, positive, out, trials);
   return BBX_OK;
 }
 

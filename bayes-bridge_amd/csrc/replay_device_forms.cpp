@@ -25,4 +25,11 @@ void tilted_stable(uint64_t seed, uint64_t stream, int64_t n, double a,
   replay_device_forms::tilted_stable(seed, stream, n, a, tilt, out, winner);
 }
 
+void truncated_normal(uint64_t seed, uint64_t stream, int64_t n,
+                      const double* psi, const unsigned char* positive,
+                      double* out, int32_t* trials) {
+  replay_device_forms::truncated_normal(seed, stream, n, psi, positive, out,
+                                        trials);
+}
+
 }  // namespace replay_device_forms_api

@@ -222,6 +222,37 @@ inline void tilted_stable(uint64_t seed, uint64_t stream, int64_t n, double a,
   }
 }
 
+// chain_probit_kernel / dev_truncated_normal_kernel (probit.hip): trials 0, 1,
+// 2, ... of element i in order, trial t on sub-stream t; the first accepted
+// proposal is the draw.  trials[i]: trials made (0: psi was not finite).
+inline void truncated_normal(uint64_t seed, uint64_t stream, int64_t n,
+                             const double* psi, const unsigned char* positive,
+                             double* out, int32_t* trials) {
+  using bbx::TruncatedNormal;
+  for (int64_t i = 0; i < n; ++i) {
+    const double p = psi[i];
+    const bool pos = positive[i] != 0;
+    if (trials) trials[i] = 0;
+    if (!(fabs(p) <= 1.7e308)) {
+      out[i] = p - p;
+      continue;
+    }
+    int t = 0;
+    double z = TruncatedNormal::at_cap(p, pos);
+    for (; t < TruncatedNormal::kMaxTrials; ++t) {
+      HostPhilox g(seed, stream, (uint64_t)i, (uint32_t)t);
+      double prop;
+      if (TruncatedNormal::trial(g, p, pos, prop)) {
+        z = prop;
+        ++t;
+        break;
+      }
+    }
+    out[i] = z;
+    if (trials) trials[i] = t;
+  }
+}
+
 inline double gamma(uint64_t seed, uint64_t stream, uint64_t index,
                     double shape) {
   HostPhilox g(seed, stream, index);

@@ -562,6 +562,95 @@ struct TiltedStable {
   }
 };
 
+// ------------------------------------------------------- truncated normal
+
+// z ~ N(psi, 1) restricted to a half-line: the latent variable of the probit
+// model under Albert & Chib's (1993) augmentation.  CONVENTION (host and
+// device alike): `positive` (y = 1) is the OPEN half-line z > 0, otherwise
+// (y = 0) the CLOSED one z <= 0 -- the boundary value 0 belongs to y = 0.
+//
+// With s = +1 / -1 and a = -s psi, the lower bound of the standardised
+// half-line, one trial is
+//   a <= 0  z' = psi + normal, accepted when it lies in the half-line:
+//           probability Phi(-a) >= 1/2;
+//   a > 0   Robert's (1995) translated exponential: lambda = (a + hypot(a, 2))
+//           / 2, e = -log(u1) / lambda, accepted when u2 <= exp(-(a + e -
+//           lambda)^2 / 2): probability >= 0.76 (at a -> 0+; 0.876 at 1, 0.983
+//           at 5, -> 1).  The draw is s e: psi + s (a + e) is the same number
+//           with |psi| ulps of cancellation.
+// Every trial consumes exactly two uniforms, one Philox block.  A non-finite
+// psi is the caller's business (the kernel and the replay return psi - psi).
+struct TruncatedNormal {
+  static constexpr int kMaxTrials = 128;  // reached with probability 2^-128
+
+  // rate of the exponential proposal, a > 0
+  BBX_HD static inline double rate(double a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (the kernel's form: no scaled hypot where a * a cannot overflow; from
+    // 1e150 on hypot(a, 2) == a in double)
+    return a < 1e150 ? 0.5 * (a + sqrt(a * a + 4.)) : a;
+#else
+    return 0.5 * a + 0.5 * hypot(a, 2.);
+#endif
+  }
+
+  // ONE trial; z is the proposal, true = accepted
+  template <class G>
+  BBX_HD static inline bool trial(G& g, double psi, bool positive, double& z) {
+    const double s = positive ? 1. : -1.;
+    const double a = -s * psi;
+    if (a <= 0.) {
+      z = psi + g.normal();
+      return positive ? z > 0. : z <= 0.;
+    }
+    const double lambda = rate(a);
+    const double u1 = g.uniform();
+    const double u2 = g.uniform();
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double e = -log(u1) * (1. / lambda);
+#else
+    const double e = -log(u1) / lambda;
+#endif
+    const double d = a + e - lambda;
+    z = s * e;
+    return u2 <= exp(-0.5 * (d * d));
+  }
+
+  // What a draw returns when all kMaxTrials trials were rejected: the mean of
+  // the proposal (psi, resp. s / lambda).
+  BBX_HD static inline double at_cap(double psi, bool positive) {
+    const double s = positive ? 1. : -1.;
+    const double a = -s * psi;
+    return a <= 0. ? psi : s / rate(a);
+  }
+
+  // Trials 0, 1, 2, ... on the generators make(0), make(1), ...; the first
+  // accepted proposal is the draw.  n_trials (may be null): trials made.
+  template <class Make>
+  BBX_HD static inline double draw_trials(Make&& make, double psi,
+                                          bool positive, int* n_trials) {
+    for (int t = 0; t < kMaxTrials; ++t) {
+      auto&& g = make((uint32_t)t);
+      double z;
+      if (trial(g, psi, positive, z)) {
+        if (n_trials) *n_trials = t + 1;
+        return z;
+      }
+    }
+    if (n_trials) *n_trials = kMaxTrials;
+    return at_cap(psi, positive);
+  }
+
+  // The trials one after the other on ONE generator (trial t reads its block
+  // t).  The chain's kernel gives every trial a sub-stream of its own instead:
+  // draw_trials with Philox(seed, stream, element, trial).
+  template <class G>
+  BBX_HD static inline double draw(G& g, double psi, bool positive) {
+    return draw_trials([&g](uint32_t) -> G& { return g; }, psi, positive,
+                       nullptr);
+  }
+};
+
 // ------------------------------------------------------------------ Gamma
 
 // Gamma(shape, 1), Marsaglia & Tsang (2000).  Device-only use (the reference

@@ -65,6 +65,11 @@ extern "C" {
  *      shared entry points of every likelihood handle).  New symbols and
  *      nothing else, so the number stays 113: a binding written against 113
  *      before them runs unchanged, one that needs them looks them up.
+ *      + the probit model on the device chain (BBX_MODEL_PROBIT,
+ *      bbx_chain_get_latent, bbx_chain_get_zbase, bbx_device_truncated_normal,
+ *      bbx_design_predictive_summary_probit; in libbbx_hostrng
+ *      bbx_replay_truncated_normal and bbx_host_log_norm_cdf).  A new model code
+ *      and new symbols and nothing else, so the number stays 113.
  * 112: + the Cox model in counting-process form (bbx_coxcp_*): delayed entry
  *      and (start, stop] rows, with the trajectory and the No-U-Turn sampler
  *      of the Cox handle.
@@ -116,6 +121,8 @@ extern "C" {
 /* likelihood families of a chain (model/factory.py:53-66) */
 #define BBX_MODEL_LINEAR 0
 #define BBX_MODEL_LOGIT 1
+#define BBX_MODEL_PROBIT 2 /* Albert-Chib latents: no counterpart in the
+                              reference; see bbx_chain_create                   */
 
 /* global-scale update of a chain: SamplerOptions.gscale_update
  * (gibbs_util.py:9-31; bayesbridge.py:412-448) */
@@ -571,6 +578,20 @@ int bbx_hbm_probe(int device, int64_t bytes, int reps, double* read_gbps,
  *   bridge_exp, slab_size    prior.py:9-15
  *   gscale_shape0, gscale_rate0  Gamma prior on tau^-bridge_exp (prior.py:77-81)
  * The chain borrows `design` (which must outlive it) and its stream.
+ *
+ * BBX_MODEL_PROBIT (no counterpart in the reference): P(y_i = 1) = Phi(psi_i)
+ * under Albert & Chib's augmentation.  outcome[n] must be 0 or 1 and n_trial
+ * NULL or all ones (BBX_ERR_INVALID names the first offending row).  Each
+ * iteration draws the latents z_i | beta ~ N(psi_i, 1) on z > 0 (y_i = 1) or
+ * z <= 0 (y_i = 0), element i from Philox(seed, 7 | iteration << 8, i, trial);
+ * beta | z is the linear model's conditional with outcome z and the
+ * observation precision fixed at 1, drawn by any of the three samplers.  The
+ * chain has no obs_prec: set_state, get_state and the runs refuse a non-NULL
+ * one.  bbx_chain_set_state and bbx_chain_init_obs_prec recompute psi, the
+ * latents, X~^T z and the log-likelihood from the coefficients with the stream
+ * of iteration `iteration - 1`, so a chain resumed from (coef, lscale, gscale,
+ * iteration, summaries) continues bit for bit.  bbx_batch_create refuses
+ * probit chains.
  */
 int bbx_chain_create(bbx_design* design, int model, const double* outcome,
                      const double* n_trial, int n_unshrunk,
@@ -633,6 +654,13 @@ int bbx_chain_eta(bbx_chain* c, int64_t iteration, double* eta1, double* eta2);
 /* Log-likelihood and log-posterior of the state left by the last iteration
  * (bayesbridge.py:480-511), host pointers, either may be NULL. */
 int bbx_chain_get_logp(bbx_chain* c, double* loglik, double* logp);
+/* The n latents of a BBX_MODEL_PROBIT chain's current state (host pointer);
+ * BBX_ERR_INVALID for a chain of another model or a NULL out. */
+int bbx_chain_get_latent(bbx_chain* c, double* out);
+/* The P-vector the next draw's right-hand side is scaled from: X~^T kappa
+ * (logit), X~^T y (linear), X~^T z of the current latents (probit); host
+ * pointer.  For the tests that pin it to the latents. */
+int bbx_chain_get_zbase(bbx_chain* c, double* out);
 
 /*
  * Runs n_iter Gibbs iterations; a sample is kept every `thin` iterations
@@ -742,6 +770,13 @@ int bbx_device_tilted_stable(int device, uint64_t seed, int64_t n_draw,
                              double char_exp, const double* tilt, double* out);
 int bbx_device_gamma(int device, uint64_t seed, int64_t n_draw, double shape,
                      double* out);
+/* N(psi_i, 1) restricted to z > 0 (positive[i] != 0) or z <= 0, on Philox
+ * stream 7 (the probit chain's latent stream at iteration 0); a psi that is not
+ * finite gives a NaN.  BBX_ERR_INVALID for n_draw < 0 or a NULL psi, positive
+ * or out. */
+int bbx_device_truncated_normal(int device, uint64_t seed, int64_t n_draw,
+                                const double* psi,
+                                const unsigned char* positive, double* out);
 /* n_draw standard normals of Philox stream `stream` (element i = counter i):
  * the generator behind eta1 / eta2 (cg_sampler.py:61-62 uses
  * np.random.randn). */
@@ -1299,6 +1334,26 @@ int bbx_design_predictive_summary_weibull(
     const double* ll_const, int draws_per_pass, double* mean, double* sd,
     double* lpd, double* ll_mean, double* ll_var, double* mu_draws);
 
+/* The same summary for the probit model (csrc/probit_predict.hip: one more
+ * instantiation of the summary kernel), from draws of the coefficients.  With
+ * eta = X~ coef_s + offset, per row and draw
+ *
+ *   mu = Phi(eta)    ll = log Phi(eta) (y = 1), log Phi(-eta) (y = 0), + c
+ *
+ * log Phi in the form that keeps its relative accuracy in the far tail
+ * (erfc, and an asymptotic series below -20).  y[n] in {0, 1} or NULL; without
+ * it lpd, ll_mean and ll_var may be NULL.  The passes, the single
+ * synchronisation, the independence of draws_per_pass and the outputs are
+ * those of bbx_design_predictive_summary.  BBX_ERR_INVALID for a NULL or
+ * destroyed design, n_draw < 1 (< 2 with an outcome), a NULL coef, mean or sd,
+ * a y that is not 0 or 1, an outcome with a NULL lpd, ll_mean or ll_var,
+ * draws_per_pass < 0: checked before anything touches the device. */
+int bbx_design_predictive_summary_probit(
+    bbx_design* design, int64_t n_draw, const double* coef,
+    const double* offset, const double* y, const double* ll_const,
+    int draws_per_pass, double* mean, double* sd, double* lpd, double* ll_mean,
+    double* ll_var, double* mu_draws);
+
 /* The summary of the proportional-odds model (csrc/ordinal_predict.hip: a
  * kernel of its own), from draws of the coefficients, coef[n_draw][P], and of
  * the cutpoints, cutpoints[n_draw][K - 1] with K = n_category in [2, 16], every
@@ -1804,6 +1859,9 @@ int bbx_host_pg_right_mass(int64_t n, const double* z, double* log_form,
                            double* direct);
 int bbx_host_pg_series_accept(int64_t n, const double* x, const double* u,
                               int32_t* sequential, int32_t* direct);
+/* out[i] = log Phi(x[i]) as csrc/samplers.hpp forms it on the host (the probit
+ * model's log-likelihood term is the same function on the device). */
+int bbx_host_log_norm_cdf(int64_t n, const double* x, double* out);
 
 /* ---------------------- sequential replay of the device draws (libbbx_hostrng)
  * Every draw of the device chain is a function of (seed, stream, element,
@@ -1837,6 +1895,17 @@ int bbx_replay_polya_gamma(uint64_t seed, uint64_t stream, int64_t n,
 int bbx_replay_tilted_stable(uint64_t seed, uint64_t stream, int64_t n,
                              double char_exp, const double* tilt, int variant,
                              double* out, int32_t* winner);
+/* chain_probit_kernel (csrc/probit.hip) restated: the trials 0, 1, 2, ... of
+ * element i in order, trial t on Philox(seed, stream, i, t), the first accepted
+ * proposal is the draw (TruncatedNormal of csrc/samplers.hpp; variant 1: the
+ * kernel's forms of the proposal rate and of the exponential variate).
+ * positive[i] != 0: the half-line z > 0 (y = 1), else z <= 0.  trials[i]
+ * (optional) = the trials made, 0 for a psi that is not finite (the draw is
+ * then a NaN). */
+int bbx_replay_truncated_normal(uint64_t seed, uint64_t stream, int64_t n,
+                                const double* psi,
+                                const unsigned char* positive, int variant,
+                                double* out, int32_t* trials);
 /* out[k] = gamma_draw on Philox(seed, stream, index + k). */
 int bbx_replay_gamma(uint64_t seed, uint64_t stream, uint64_t index, int64_t n,
                      double shape, double* out);
