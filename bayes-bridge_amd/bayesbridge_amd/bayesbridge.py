@@ -21,15 +21,17 @@ store).  Two execution modes, chosen by `options={'rng': ...}`:
 import copy
 import math
 import time
+from collections import namedtuple
 from ctypes import c_void_p
 from warnings import warn
 
 import numpy as np
 
 from . import _lib
-from .cutpoints import (check_cutpoints, initial_cutpoints,
+# (the update_* functions are AUX_PARAM's, looked up by name at every call)
+from .cutpoints import (check_cutpoints, initial_cutpoints,  # noqa: F401
                         update_cutpoints)
-from .dispersion import update_dispersion
+from .dispersion import update_dispersion  # noqa: F401
 from .device_chain import HipGibbsChain
 from .hostrng import ReferenceRandom
 from .model import LogisticModel
@@ -37,7 +39,7 @@ from .prior import RegressionCoefPrior, unit_magnitude
 from .hmc import HipHMCCoefficientSampler
 from .reg_coef_sampler import (HipRegressionCoefficientSampler,
                                RegressionCoeffficientPosteriorSummarizer)
-from .weibull_shape import update_shape
+from .weibull_shape import update_shape  # noqa: F401
 
 # the HMC draw's sampling info (gibbs_util.py:141-160)
 HMC_INFO_KEYS = ('stepsize', 'n_hessian_matvec', 'n_grad_evals',
@@ -54,6 +56,61 @@ NO_OBS_PREC = ('cox', 'poisson', 'negbin', 'ordinal', 'weibull', 'probit')
 # refusals call them
 HAMILTONIAN_ONLY = {'poisson': 'Poisson', 'negbin': 'negative-binomial',
                     'ordinal': 'ordinal', 'weibull': 'Weibull'}
+
+
+def _invalid_initial_state(*_):
+    raise ValueError('An invalid initial state.')
+
+
+def _initial_cutpoints(model, cuts):
+    try:
+        return check_cutpoints(cuts, model.n_category)
+    except ValueError:
+        _invalid_initial_state()
+
+
+def _initial_positive(model, value):
+    """(after the comparison with a fixed parameter: that one answers first)"""
+    return value if math.isfinite(value) and value > 0. \
+        else _invalid_initial_state()
+
+
+# A model's auxiliary parameter: one more block of the chain, drawn right
+# after the coefficients from the chain's host stream unless the model holds it
+# fixed.  The model carries the chain's value: the mode search, the
+# coefficient draw and logp all evaluate the likelihood at it.
+#   key                  in samples, info['init'] and the chain's state
+#   attr, fixed, prior   the model's attribute, its flag and its prior
+#   noun                 in the refusal of an initial value other than a fixed
+#                        parameter's
+#   convert, valid       an initial value given: before and after that refusal
+#   default              the initial value where none is given
+#   update               the Gibbs step, a name of this module looked up at
+#                        every call: (model, coef, value, prior, uniform) ->
+#                        value; its uniforms come in the order its own module
+#                        documents
+AuxParam = namedtuple('AuxParam', 'key attr fixed prior noun convert valid '
+                                  'default update')
+AUX_PARAM = {
+    'negbin': AuxParam(
+        'dispersion', 'dispersion', 'dispersion_fixed', 'dispersion_prior',
+        'dispersion is', lambda model, r: float(r), _initial_positive,
+        lambda model: 1., 'update_dispersion'),
+    'ordinal': AuxParam(
+        'cutpoints', 'cutpoints', 'cutpoints_fixed', 'cutpoint_prior',
+        'cutpoints are', _initial_cutpoints, lambda model, cuts: cuts,
+        lambda model: initial_cutpoints(model.y, model.n_category),
+        'update_cutpoints'),
+    'weibull': AuxParam(
+        'weibull_shape', 'shape', 'shape_fixed', 'shape_prior', 'shape is',
+        lambda model, k: float(k), _initial_positive, lambda model: 1.,
+        'update_shape'),
+}
+
+
+def _copied(value):
+    """A state's own copy of an auxiliary parameter (floats are values)"""
+    return np.array(value, copy=True) if np.ndim(value) else value
 
 
 def _ptr(a):
@@ -302,12 +359,8 @@ class BayesBridge():
             params_to_save = ('coef', 'local_scale', 'global_scale', 'logp')
             if self.model.name not in NO_OBS_PREC:    # bayesbridge.py:187-191
                 params_to_save += ('obs_prec',)
-            if self.model.name == 'negbin':
-                params_to_save += ('dispersion',)
-            if self.model.name == 'ordinal':
-                params_to_save += ('cutpoints',)
-            if self.model.name == 'weibull':
-                params_to_save += ('weibull_shape',)
+            if self.model.name in AUX_PARAM:
+                params_to_save += (AUX_PARAM[self.model.name].key,)
         start_time = time.time()
         if options.rng == 'reference':
             if _device_out:
@@ -349,15 +402,10 @@ class BayesBridge():
                      'local_scale': np.array(lscale, copy=True),
                      'global_scale': float(gscale)}
         extra = dict(extra)
-        dispersion = extra.pop('_dispersion', None)
-        if dispersion is not None:          # the negative-binomial model
-            raw_state['dispersion'] = dispersion
-        cutpoints = extra.pop('_cutpoints', None)
-        if cutpoints is not None:           # the ordinal model
-            raw_state['cutpoints'] = np.array(cutpoints, copy=True)
-        weibull_shape = extra.pop('_weibull_shape', None)
-        if weibull_shape is not None:       # the Weibull model
-            raw_state['weibull_shape'] = weibull_shape
+        aux = AUX_PARAM.get(self.model.name)
+        aux_value = extra.pop('_' + aux.key, None) if aux else None
+        if aux_value is not None:
+            raw_state[aux.key] = _copied(aux_value)
         if self.prior._gscale_paramet == 'coef_magnitude':  # bayesbridge.py:244-251
             gscale, lscale = self.prior.adjust_scale(
                 gscale, lscale, to='coef_magnitude')
@@ -383,13 +431,8 @@ class BayesBridge():
                                                     gscale),
             '_markov_chain_state_raw': raw_state,
         }
-        if dispersion is not None:
-            mcmc_info['_markov_chain_state']['dispersion'] = dispersion
-        if cutpoints is not None:
-            mcmc_info['_markov_chain_state']['cutpoints'] = np.array(
-                cutpoints, copy=True)
-        if weibull_shape is not None:
-            mcmc_info['_markov_chain_state']['weibull_shape'] = weibull_shape
+        if aux_value is not None:
+            mcmc_info['_markov_chain_state'][aux.key] = _copied(aux_value)
         mcmc_info.update(extra)
         return samples, mcmc_info
 
@@ -573,14 +616,11 @@ class BayesBridge():
                 samples['obs_prec'] = np.zeros((self.n_obs, n_sample))
         if 'logp' in params_to_save:
             samples['logp'] = np.zeros(n_sample)
-        if 'dispersion' in params_to_save and self.model.name == 'negbin':
-            samples['dispersion'] = np.zeros(n_sample)
-        if 'cutpoints' in params_to_save and self.model.name == 'ordinal':
-            samples['cutpoints'] = np.zeros((self.model.n_category - 1,
-                                             n_sample))
-        if 'weibull_shape' in params_to_save \
-                and self.model.name == 'weibull':
-            samples['weibull_shape'] = np.zeros(n_sample)
+        aux = AUX_PARAM.get(self.model.name)
+        if aux and aux.key in params_to_save:
+            # (a draw is a scalar or a vector: one column per sample)
+            samples[aux.key] = np.zeros(
+                np.shape(getattr(self.model, aux.attr)) + (n_sample,))
         info_keys = {'hmc': HMC_INFO_KEYS, 'nuts': NUTS_INFO_KEYS,
                      'cg': ('n_cg_iter',)}.get(coef_sampler_type, ())
         return samples, {key: np.zeros(n_sample)      # gibbs_util.py:141-160
@@ -602,69 +642,27 @@ class BayesBridge():
         return LogisticModel.compute_polya_gamma_mean(
             self.model.n_trial, self.model.design.dot(coef))
 
-    def _initial_dispersion(self, init):
-        """The negative-binomial chain's first dispersion: the resumed
-        chain's, else init['dispersion'], else 1; a model with a fixed
-        dispersion keeps its own."""
+    def _initial_aux(self, aux, init):
+        """The chain's first value of the model's auxiliary parameter: the
+        resumed chain's, else init[aux.key], else the parameter's default; a
+        model that holds it fixed keeps its own."""
         model = self.model
         if isinstance(init, dict) and '_raw' in init:
-            r = init['_raw']['dispersion']
+            given = init['_raw'][aux.key]
         else:
-            r = init.get('dispersion')
-        if model.dispersion_fixed:
-            if r is not None and float(r) != model.dispersion:
+            given = init.get(aux.key)
+        value = None if given is None else aux.convert(model, given)
+        if getattr(model, aux.fixed):
+            own = getattr(model, aux.attr)
+            if value is not None and not np.array_equal(value, own):
                 raise ValueError(
-                    "The model's dispersion is held fixed at %r: the initial "
-                    "state gives %r." % (model.dispersion, r))
-            return model.dispersion
-        r = 1. if r is None else float(r)
-        if not (math.isfinite(r) and r > 0.):
-            raise ValueError('An invalid initial state.')
-        return r
-
-    def _initial_weibull_shape(self, init):
-        """The Weibull chain's first shape: the resumed chain's, else
-        init['weibull_shape'], else 1 (the exponential model); a model with a
-        fixed shape keeps its own."""
-        model = self.model
-        if isinstance(init, dict) and '_raw' in init:
-            k = init['_raw']['weibull_shape']
-        else:
-            k = init.get('weibull_shape')
-        if model.shape_fixed:
-            if k is not None and float(k) != model.shape:
-                raise ValueError(
-                    "The model's shape is held fixed at %r: the initial "
-                    "state gives %r." % (model.shape, k))
-            return model.shape
-        k = 1. if k is None else float(k)
-        if not (math.isfinite(k) and k > 0.):
-            raise ValueError('An invalid initial state.')
-        return k
-
-    def _initial_cutpoints(self, init):
-        """The ordinal chain's first cutpoints: the resumed chain's, else
-        init['cutpoints'], else the empirical logits of the cumulative
-        category proportions; a model with fixed cutpoints keeps its own."""
-        model = self.model
-        if isinstance(init, dict) and '_raw' in init:
-            cuts = init['_raw']['cutpoints']
-        else:
-            cuts = init.get('cutpoints')
-        if cuts is not None:
-            try:
-                cuts = check_cutpoints(cuts, model.n_category)
-            except ValueError:
-                raise ValueError('An invalid initial state.') from None
-        if model.cutpoints_fixed:
-            if cuts is not None and not np.array_equal(cuts, model.cutpoints):
-                raise ValueError(
-                    "The model's cutpoints are held fixed at %r: the initial "
-                    "state gives %r." % (model.cutpoints, cuts))
-            return model.cutpoints
-        if cuts is None:
-            cuts = initial_cutpoints(model.y, model.n_category)
-        return cuts
+                    "The model's %s held fixed at %r: the initial "
+                    "state gives %r."
+                    % (aux.noun, own, value if np.ndim(value) else given))
+            return own
+        if value is None:
+            return aux.default(model)
+        return aux.valid(model, value)
 
     def _initialize_chain(self, init, bridge_exp, update_local_scale,
                           update_obs_precision, update_global_scale,
@@ -686,12 +684,8 @@ class BayesBridge():
                     {'coef': coef, 'obs_prec': obs_prec,
                      'local_scale': lscale, 'global_scale': gscale}, None)
         valid = ('coef', 'local_scale', 'global_scale', 'obs_prec', 'logp')
-        if self.model.name == 'negbin':
-            valid += ('dispersion',)
-        if self.model.name == 'ordinal':
-            valid += ('cutpoints',)
-        if self.model.name == 'weibull':
-            valid += ('weibull_shape',)
+        if self.model.name in AUX_PARAM:
+            valid += (AUX_PARAM[self.model.name].key,)
         for key in init:
             if key not in valid:
                 warn("'{:s}' is not a valid parameter name and "
@@ -855,32 +849,16 @@ class BayesBridge():
                 - hyper['rate'] * gscale
             return loglik + prior_logp
 
-        dispersion = None
-        if model.name == 'negbin':
-            # the model carries the chain's dispersion: the mode search, the
-            # coefficient draw and logp all evaluate the likelihood at it
-            dispersion = self._initial_dispersion(init)
-            model.dispersion = dispersion
-        cutpoints = None
-        if model.name == 'ordinal':
-            # likewise: the model carries the chain's cutpoints
-            cutpoints = self._initial_cutpoints(init)
-            model.cutpoints = cutpoints
-        weibull_shape = None
-        if model.name == 'weibull':
-            # likewise: the model carries the chain's shape
-            weibull_shape = self._initial_weibull_shape(init)
-            model.shape = weibull_shape
+        aux, aux_value = AUX_PARAM.get(model.name), None
+        if aux:
+            aux_value = self._initial_aux(aux, init)
+            setattr(model, aux.attr, aux_value)
         coef, obs_prec, lscale, gscale, init_used, optim_info = \
             self._initialize_chain(init, bridge_exp, update_local_scale,
                                    update_obs_precision, update_global_scale,
                                    sampler)
-        if weibull_shape is not None:
-            init_used['weibull_shape'] = weibull_shape
-        if dispersion is not None:
-            init_used['dispersion'] = dispersion
-        if cutpoints is not None:
-            init_used['cutpoints'] = np.array(cutpoints, copy=True)
+        if aux:
+            init_used[aux.key] = _copied(aux_value)
         samples, sampling_info = self._pre_allocate(
             n_iter - n_burnin, thin, params_to_save,
             options.coef_sampler_type)
@@ -903,28 +881,14 @@ class BayesBridge():
                     y_gaussian, design, obs_prec, gscale, lscale,
                     options.coef_sampler_type)
             obs_prec = update_obs_precision(coef)
-            if dispersion is not None and not model.dispersion_fixed:
-                # r | beta: one slice update on log r, its uniforms from the
-                # chain's host stream (dispersion.py states their order)
-                dispersion = update_dispersion(
-                    model, coef, dispersion, model.dispersion_prior,
+            if aux and not getattr(model, aux.fixed):
+                # the auxiliary parameter | beta: slice updates (one on log r
+                # or log k, one per cutpoint in increasing order), their
+                # uniforms from the chain's host stream
+                aux_value = globals()[aux.update](
+                    model, coef, aux_value, getattr(model, aux.prior),
                     rg.np_random.uniform)
-                model.dispersion = dispersion
-            if cutpoints is not None and not model.cutpoints_fixed:
-                # c_k | beta, the others: one slice update per cutpoint, in
-                # increasing order, their uniforms from the chain's host
-                # stream (cutpoints.py)
-                cutpoints = update_cutpoints(
-                    model, coef, cutpoints, model.cutpoint_prior,
-                    rg.np_random.uniform)
-                model.cutpoints = cutpoints
-            if weibull_shape is not None and not model.shape_fixed:
-                # k | beta: one slice update on log k, its uniforms from the
-                # chain's host stream (dispersion.py states their order)
-                weibull_shape = update_shape(
-                    model, coef, weibull_shape, model.shape_prior,
-                    rg.np_random.uniform)
-                model.shape = weibull_shape
+                setattr(model, aux.attr, aux_value)
             gscale = update_global_scale(
                 gscale, coef[nu:], bridge_exp, method=options.gscale_update)
             lscale = update_local_scale(gscale, coef[nu:], bridge_exp)
@@ -944,12 +908,8 @@ class BayesBridge():
                         samples['obs_prec'][:, idx] = obs_prec
                 if 'logp' in samples:
                     samples['logp'][idx] = logp
-                if 'dispersion' in samples:
-                    samples['dispersion'][idx] = dispersion
-                if 'cutpoints' in samples:
-                    samples['cutpoints'][:, idx] = cutpoints
-                if 'weibull_shape' in samples:
-                    samples['weibull_shape'][idx] = weibull_shape
+                if aux and aux.key in samples:
+                    samples[aux.key][..., idx] = aux_value
                 for key in info_keys:
                     if key in info:
                         sampling_info[key][idx] = info[key]
@@ -962,12 +922,8 @@ class BayesBridge():
                 stamp = now
         extra = {'_random_gen_state': rg.get_state(),
                  '_reg_coef_sampler_state': sampler.get_internal_state()}
-        if dispersion is not None:
-            extra['_dispersion'] = dispersion
-        if cutpoints is not None:
-            extra['_cutpoints'] = cutpoints
-        if weibull_shape is not None:
-            extra['_weibull_shape'] = weibull_shape
+        if aux:
+            extra['_' + aux.key] = aux_value
         return (samples, sampling_info, (coef, obs_prec, lscale, gscale),
                 init_used, optim_info, extra)
 

@@ -82,32 +82,32 @@ def slice_update(theta, logdensity, uniform, width=WIDTH,
                        "an accepted point." % MAX_SHRINKAGES)
 
 
-def check_prior(prior):
-    """dispersion_prior: None (the default Gamma(2, 0.1)) or a dict with
-    'shape' and 'rate', both finite and positive."""
+def check_gamma_prior(prior, option, default):
+    """A Gamma prior given as the option `option`: None (a copy of `default`)
+    or a dict with 'shape' and 'rate', both finite and positive."""
     if prior is None:
-        return dict(DEFAULT_PRIOR)
+        return dict(default)
     try:
         shape, rate = float(prior['shape']), float(prior['rate'])
         extra = set(prior) - {'shape', 'rate'}
     except (TypeError, KeyError, ValueError):
-        raise ValueError("dispersion_prior must be a dict with 'shape' and "
-                         "'rate'.") from None
+        raise ValueError("%s must be a dict with 'shape' and 'rate'."
+                         % option) from None
     if extra or not (math.isfinite(shape) and math.isfinite(rate)
                      and shape > 0. and rate > 0.):
-        raise ValueError("dispersion_prior takes a finite, positive 'shape' "
-                         "and 'rate' and nothing else.")
+        raise ValueError("%s takes a finite, positive 'shape' and 'rate' and "
+                         "nothing else." % option)
     return {'shape': shape, 'rate': rate}
 
 
-def log_conditional(model, coef, prior, jacobian=True):
-    """f(theta) = L(r) + shape theta - rate r, r = exp(theta): the log of the
-    dispersion's conditional density on the log scale, the Jacobian included
-    (Gamma(shape, rate) on r has density r^(shape - 1) exp(-rate r), and
-    dr = r dtheta).  L comes from model.dispersion_loglik: the first call
-    forms the linear predictor at `coef`, the later ones reuse it.
-    jacobian=False drops the Jacobian's theta: the wrong target, for the
-    tests' negative control."""
+def log_scale_conditional(model, loglik, coef, prior, jacobian=True):
+    """f(theta) = L(x) + shape theta - rate x, x = exp(theta): the log of the
+    conditional density of a positive parameter x on the log scale, the
+    Jacobian included (Gamma(shape, rate) on x has density x^(shape - 1)
+    exp(-rate x), and dx = x dtheta).  L comes from the model's method named
+    `loglik`: the first call forms the linear predictor at `coef`, the later
+    ones reuse it.  jacobian=False drops the Jacobian's theta: the wrong
+    target, for the tests' negative control."""
     shape = prior['shape'] - (0. if jacobian else 1.)
     rate = prior['rate']
     state = {'coef': coef}
@@ -115,17 +115,30 @@ def log_conditional(model, coef, prior, jacobian=True):
     def f(thetas):
         thetas = np.asarray(thetas, dtype=np.float64)
         with np.errstate(over='ignore', under='ignore'):
-            r = np.exp(thetas)
-        # an r that left the doubles' range has no density to speak of
-        ok = np.isfinite(r) & (r > 0.)
+            x = np.exp(thetas)
+        # an x that left the doubles' range has no density to speak of
+        ok = np.isfinite(x) & (x > 0.)
         out = np.full(thetas.shape, -np.inf)
         if ok.any():
-            loglik = np.asarray(model.dispersion_loglik(state['coef'], r[ok]))
+            L = np.asarray(getattr(model, loglik)(state['coef'], x[ok]))
             state['coef'] = None
-            out[ok] = loglik + shape * thetas[ok] - rate * r[ok]
+            out[ok] = L + shape * thetas[ok] - rate * x[ok]
         return out
 
     return f
+
+
+def check_prior(prior):
+    """dispersion_prior: None (the default Gamma(2, 0.1)) or a dict with
+    'shape' and 'rate', both finite and positive."""
+    return check_gamma_prior(prior, 'dispersion_prior', DEFAULT_PRIOR)
+
+
+def log_conditional(model, coef, prior, jacobian=True):
+    """log_scale_conditional of r = exp(theta) with L from
+    model.dispersion_loglik."""
+    return log_scale_conditional(model, 'dispersion_loglik', coef, prior,
+                                 jacobian)
 
 
 def update_dispersion(model, coef, r, prior, uniform):

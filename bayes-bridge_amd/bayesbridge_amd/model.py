@@ -807,6 +807,56 @@ class PoissonModel(_DeviceHamiltonian, _Predictive, _Model):
         return np.random.poisson(rate)
 
 
+def _positive_scalar(x, what):
+    """x as a float: a finite, positive number; `what`: 'dispersion'."""
+    try:
+        x = float(x)
+    except (TypeError, ValueError):
+        raise ValueError("The %s must be a number." % what) from None
+    if not (math.isfinite(x) and x > 0.):
+        raise ValueError("The %s must be finite and positive." % what)
+    return x
+
+
+def _positive_draws(x, n_draw, what):
+    """x, a scalar or one value per draw, as n_draw finite, positive numbers."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 0:
+        x = np.full(n_draw, float(x))
+    if x.shape != (n_draw,):
+        raise ValueError(
+            "%s must be a scalar or hold one value per draw: "
+            "%s, %d draws." % (what, x.shape, n_draw))
+    if not np.all(np.isfinite(x)) or (x <= 0).any():
+        raise ValueError(
+            "Every %s must be strictly positive and finite." % what)
+    return np.ascontiguousarray(x)
+
+
+def _candidate_loglik(model, entry, coef, cand, single):
+    """The C ABI's candidate sums (`entry`: bbx_negbin_dispersion_loglik and
+    its siblings) at the coefficients coef, or None for the linear predictor
+    of the previous call, for the 1 to 8 candidates that the caller has
+    checked: a float where `single`, else an array, one sum per candidate."""
+    if coef is not None:
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if coef.shape != (model.n_pred,):
+            raise ValueError("coef must have length %d" % model.n_pred)
+    out = np.empty(len(cand))
+    _lib.check(getattr(_lib.load(), entry)(
+        model.handle, _ptr(coef), len(cand), _ptr(cand), _ptr(out)))
+    return float(out[0]) if single else out
+
+
+def _scalar_candidates(x, name):
+    """(1 to 8 values as an array, whether x was a scalar)"""
+    single = np.ndim(x) == 0
+    x = np.ascontiguousarray(np.atleast_1d(x), dtype=np.float64)
+    if x.ndim != 1 or not 1 <= x.size <= 8:
+        raise ValueError("%s must be a scalar or hold 1 to 8 values." % name)
+    return x, single
+
+
 class NegBinModel(_DeviceHamiltonian, _Predictive, _Model):
     """Negative-binomial regression: counts y_i with mean mu_i = exposure_i
     exp(eta_i) and variance mu_i + mu_i^2 / r.  The dispersion r > 0 is a
@@ -847,22 +897,12 @@ class NegBinModel(_DeviceHamiltonian, _Predictive, _Model):
         elif dispersion_prior is not None:
             raise ValueError("dispersion_prior is the prior of a sampled "
                              "dispersion: dispersion is given and held fixed.")
-        self._dispersion = self._checked_dispersion(dispersion)
+        self._dispersion = _positive_scalar(dispersion, 'dispersion')
         self.dispersion_prior = check_prior(dispersion_prior)
         # one bbx_negbin handle, made by the first call that needs it
         self._ham_prefix = 'bbx_negbin_'
         self._negbin = c_void_p()
         self._location_serial = 0
-
-    @staticmethod
-    def _checked_dispersion(r):
-        try:
-            r = float(r)
-        except (TypeError, ValueError):
-            raise ValueError("The dispersion must be a number.") from None
-        if not (math.isfinite(r) and r > 0.):
-            raise ValueError("The dispersion must be finite and positive.")
-        return r
 
     @property
     def handle(self):
@@ -884,7 +924,7 @@ class NegBinModel(_DeviceHamiltonian, _Predictive, _Model):
     def dispersion(self, r):
         """bbx_negbin_set_dispersion: a Hessian operator made before it stops
         working, as after a move of its location."""
-        r = self._checked_dispersion(r)
+        r = _positive_scalar(r, 'dispersion')
         if self._negbin:
             _lib.check(_lib.load().bbx_negbin_set_dispersion(self._negbin, r))
             self._location_serial += 1
@@ -919,18 +959,8 @@ class NegBinModel(_DeviceHamiltonian, _Predictive, _Model):
         value for a given r depends neither on how many values are asked for
         nor on its place among them.  The model's own dispersion is not
         touched."""
-        scalar = np.ndim(r) == 0
-        r = np.ascontiguousarray(np.atleast_1d(r), dtype=np.float64)
-        if r.ndim != 1 or not 1 <= r.size <= 8:
-            raise ValueError("r must be a scalar or hold 1 to 8 values.")
-        if coef is not None:
-            coef = np.ascontiguousarray(coef, dtype=np.float64)
-            if coef.shape != (self.n_pred,):
-                raise ValueError("coef must have length %d" % self.n_pred)
-        out = np.empty(r.size)
-        _lib.check(_lib.load().bbx_negbin_dispersion_loglik(
-            self.handle, _ptr(coef), r.size, _ptr(r), _ptr(out)))
-        return float(out[0]) if scalar else out
+        return _candidate_loglik(self, 'bbx_negbin_dispersion_loglik', coef,
+                                 *_scalar_candidates(r, 'r'))
 
     def _pred_call(self, n_draw, draws, dispersion, offset, y, n_trial,
                    ll_const):
@@ -950,16 +980,7 @@ class NegBinModel(_DeviceHamiltonian, _Predictive, _Model):
         draws."""
         draws, X_new, n_row = self._predict_rows(coef, X_new)
         _training_rows_only(X_new, y_new=y_new, exposure_new=exposure_new)
-        r = np.asarray(dispersion, dtype=np.float64)
-        if r.ndim == 0:
-            r = np.full(len(draws), float(r))
-        if r.shape != (len(draws),):
-            raise ValueError(
-                "dispersion must be a scalar or hold one value per draw: "
-                "%s, %d draws." % (r.shape, len(draws)))
-        if not np.all(np.isfinite(r)) or (r <= 0).any():
-            raise ValueError(
-                "Every dispersion must be strictly positive and finite.")
+        r = _positive_draws(dispersion, len(draws), 'dispersion')
         y = ll_const = None
         if X_new is None:
             y, offset = self.y, self.log_exposure
@@ -1059,22 +1080,12 @@ class WeibullModel(_DeviceHamiltonian, _Predictive, _Model):
         elif shape_prior is not None:
             raise ValueError("shape_prior is the prior of a sampled shape: "
                              "shape is given and held fixed.")
-        self._shape = self._checked_shape(shape)
+        self._shape = _positive_scalar(shape, 'shape')
         self.shape_prior = check_prior(shape_prior)
         # one bbx_weibull handle, made by the first call that needs it
         self._ham_prefix = 'bbx_weibull_'
         self._weibull = c_void_p()
         self._location_serial = 0
-
-    @staticmethod
-    def _checked_shape(k):
-        try:
-            k = float(k)
-        except (TypeError, ValueError):
-            raise ValueError("The shape must be a number.") from None
-        if not (math.isfinite(k) and k > 0.):
-            raise ValueError("The shape must be finite and positive.")
-        return k
 
     @property
     def handle(self):
@@ -1096,7 +1107,7 @@ class WeibullModel(_DeviceHamiltonian, _Predictive, _Model):
     def shape(self, k):
         """bbx_weibull_set_shape: a Hessian operator made before it stops
         working, as after a move of its location."""
-        k = self._checked_shape(k)
+        k = _positive_scalar(k, 'shape')
         if self._weibull:
             _lib.check(_lib.load().bbx_weibull_set_shape(self._weibull, k))
             self._location_serial += 1
@@ -1129,31 +1140,8 @@ class WeibullModel(_DeviceHamiltonian, _Predictive, _Model):
         call.  The value for a given k depends neither on how many values are
         asked for nor on its place among them.  The model's own shape is not
         touched."""
-        scalar = np.ndim(k) == 0
-        k = np.ascontiguousarray(np.atleast_1d(k), dtype=np.float64)
-        if k.ndim != 1 or not 1 <= k.size <= 8:
-            raise ValueError("k must be a scalar or hold 1 to 8 values.")
-        if coef is not None:
-            coef = np.ascontiguousarray(coef, dtype=np.float64)
-            if coef.shape != (self.n_pred,):
-                raise ValueError("coef must have length %d" % self.n_pred)
-        out = np.empty(k.size)
-        _lib.check(_lib.load().bbx_weibull_shape_loglik(
-            self.handle, _ptr(coef), k.size, _ptr(k), _ptr(out)))
-        return float(out[0]) if scalar else out
-
-    def _shape_draws(self, shape, n_draw):
-        k = np.asarray(shape, dtype=np.float64)
-        if k.ndim == 0:
-            k = np.full(n_draw, float(k))
-        if k.shape != (n_draw,):
-            raise ValueError(
-                "shape must be a scalar or hold one value per draw: "
-                "%s, %d draws." % (k.shape, n_draw))
-        if not np.all(np.isfinite(k)) or (k <= 0).any():
-            raise ValueError(
-                "Every shape must be strictly positive and finite.")
-        return np.ascontiguousarray(k)
+        return _candidate_loglik(self, 'bbx_weibull_shape_loglik', coef,
+                                 *_scalar_candidates(k, 'k'))
 
     def _pred_call(self, n_draw, draws, shape, offset, y, n_trial, ll_const):
         # (y is the event indicator and n_trial's place holds log t)
@@ -1179,7 +1167,7 @@ class WeibullModel(_DeviceHamiltonian, _Predictive, _Model):
         draws, X_new, n_row = self._predict_rows(coef, X_new)
         _training_rows_only(X_new, event_time_new=event_time_new,
                             censoring_time_new=censoring_time_new)
-        k = self._shape_draws(shape, len(draws))
+        k = _positive_draws(shape, len(draws), 'shape')
         event = log_time = None
         if X_new is None:
             event, log_time = self.event, self.log_time
@@ -1210,7 +1198,7 @@ class WeibullModel(_DeviceHamiltonian, _Predictive, _Model):
         baseline, so any t may be asked for."""
         draws, X_new, n_row = self._predict_rows(coef, X_new)
         n_draw = len(draws)
-        k = self._shape_draws(shape, n_draw)
+        k = _positive_draws(shape, n_draw, 'shape')
         if times is None:
             times = np.unique(self.time[self.event == 1.])
         times = np.ascontiguousarray(np.atleast_1d(times), dtype=np.float64)
@@ -1248,7 +1236,7 @@ class WeibullModel(_DeviceHamiltonian, _Predictive, _Model):
             raise ValueError("censoring_frac must lie in [0, 1).")
         if seed is not None:
             np.random.seed(seed)
-        k = WeibullModel._checked_shape(shape)
+        k = _positive_scalar(shape, 'shape')
         rate = np.exp(np.asarray(eta, dtype=np.float64))
         event_time = (np.random.exponential(size=rate.shape) / rate) \
             ** (1. / k)
@@ -1438,14 +1426,8 @@ class OrdinalModel(_DeviceHamiltonian, _Predictive, _Model):
                 or not 1 <= cuts.shape[0] <= 8:
             raise ValueError("cuts must hold 1 to 8 vectors of %d cutpoints: "
                              "shape %s." % (self.n_category - 1, cuts.shape))
-        if coef is not None:
-            coef = np.ascontiguousarray(coef, dtype=np.float64)
-            if coef.shape != (self.n_pred,):
-                raise ValueError("coef must have length %d" % self.n_pred)
-        out = np.empty(cuts.shape[0])
-        _lib.check(_lib.load().bbx_ordinal_cutpoint_loglik(
-            self.handle, _ptr(coef), cuts.shape[0], _ptr(cuts), _ptr(out)))
-        return float(out[0]) if single else out
+        return _candidate_loglik(self, 'bbx_ordinal_cutpoint_loglik', coef,
+                                 cuts, single)
 
     def calc_intercept_mle(self):
         raise ValueError("The ordinal model has no intercept: the cutpoints "

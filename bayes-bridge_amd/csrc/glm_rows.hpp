@@ -1,7 +1,10 @@
 // What the row-wise GLM likelihood handles share (logit.hip, poisson.hip,
-// negbin.hip): the handle base, the one row kernel, its launch, the likelihood
-// block, the family that hamiltonian.hpp's entry points take and the body of
-// `create`.  A row holds a pair (s, t) -- (n_success, n_trial), or (y, log
+// negbin.hip, ordinal.hip, weibull.hip): the handle base, the one row kernel,
+// its launch, the likelihood block, the family that hamiltonian.hpp's entry
+// points take and the body of `create`; and, for the families with an
+// auxiliary parameter (negbin.hip's dispersion, weibull.hip's shape,
+// ordinal.hip's cutpoints), the one candidate kernel, its host driver and the
+// C ABI's front.  A row holds a pair (s, t) -- (n_success, n_trial), or (y, log
 // exposure) -- and every per-row value is a function of the row's linear
 // predictor and its pair alone.  A handle states a policy V, passed to the
 // kernel by value (empty, or the few numbers the expressions need):
@@ -45,6 +48,31 @@
 //    cox_scan_sum_kernel<SM_INVH>.  A NaN raises no flag: it comes out of the
 //    sums as a NaN.
 //
+// The candidate sums: L(candidate j), j < K <= MAXC, of an auxiliary parameter
+// in one pass over the rows, at the coefficients given or on the linear
+// predictor the previous call left in the handle.  A family states a policy C:
+//
+//   device side
+//     MAXC, TAB               candidates per call; doubles per candidate's
+//                             table
+//     struct Row              what a thread keeps of a row
+//     row(eta, pair)          ... from the row's linear predictor and pair
+//     term(row, tab)          the row's term for the candidate of table `tab`
+//   host side
+//     Handle, family          the C ABI's struct (a GlmCandCore) and "negbin"
+//     who, count, arg, must   the words of the front's messages
+//     stride(c)               doubles per candidate in the caller's array
+//     valid(c, v)             the front's test of one candidate
+//     fill(c, v, tab)         one candidate's table from the caller's array
+//     Sum                     the type the NPART partials are re-added in
+//
+// The candidate kernel stands under the row kernel's contract: its partition,
+// GLM_ROW_U rows in flight, a thread's rows added in lap order, one block sum
+// per candidate and K x NPART candidate-major partials, re-added on the host
+// in index order.  A row's term for candidate j is a function of the row and
+// table j alone, and every candidate has its own accumulator: the sum of a
+// candidate depends neither on K nor on its place among the K.
+//
 // The fp-contract pragma below is file-scope and meant to hold to the end of
 // the including translation unit: it binds where a template is written, not
 // where it is instantiated, so the kernel needs it here, and every file that
@@ -79,6 +107,14 @@ enum GlmRowMode {
 struct GlmRowsCore : HamCore {
   DevMem pair;   // 2 n: (s_i, t_i)
   DevMem loc;    // n: the Hessian's location
+};
+
+// ... and of every handle with candidate sums
+struct GlmCandCore : GlmRowsCore {
+  DevMem eta_cand;    // n: eta of the last candidate call with coefficients
+  DevMem cand_part;   // MAXC x NPART partials of the candidate sums
+  DevMem cand_tab;    // MAXC x TAB: the call's tables
+  bool have_eta_cand = false;
 };
 
 // `a`: eta (GLM_GRAD, GLM_LOC) or u = X~ v (GLM_HESS); `pair`: (s_i, t_i)
@@ -145,6 +181,48 @@ static __global__ __launch_bounds__(VEC_BLOCK) void glm_row_kernel(
   }
 }
 
+// K sums over the rows in one pass, on the row kernel's partition and in its
+// order of addition.  `tabs`: K tables, C::TAB doubles apart; `part`:
+// K x NPART partials, candidate-major.  The K running sums of a thread live in
+// LDS (one column per thread: no bank conflict, no barrier), so that the loop
+// over j is a loop and K a number: the K = 8 body unrolled holds more
+// wave-uniform values (the tables and the polynomial coefficients of exp,
+// log1p and log) than there are scalar registers, and more live values than
+// the register budget of the row kernels.
+template <class C>
+static __global__ __launch_bounds__(VEC_BLOCK) void glm_cand_kernel(
+    int64_t n, int K, const double* __restrict__ eta,
+    const double2* __restrict__ pair, const double* __restrict__ tabs,
+    double* __restrict__ part) {
+  __shared__ double s_acc[C::MAXC][VEC_BLOCK];
+  for (int j = 0; j < K; ++j) s_acc[j][threadIdx.x] = 0.;
+  const int64_t lap = (int64_t)gridDim.x * VEC_BLOCK;
+  for (int64_t i0 = (int64_t)blockIdx.x * VEC_BLOCK + threadIdx.x; i0 < n;
+       i0 += GLM_ROW_U * lap) {
+    typename C::Row row[GLM_ROW_U] = {};
+#pragma unroll
+    for (int u = 0; u < GLM_ROW_U; ++u) {
+      const int64_t i = i0 + u * lap;
+      if (i < n) row[u] = C::row(eta[i], pair[i]);
+    }
+#pragma unroll 1
+    for (int j = 0; j < K; ++j) {
+      const double* tab = tabs + j * C::TAB;
+      double acc = s_acc[j][threadIdx.x];
+#pragma unroll
+      for (int u = 0; u < GLM_ROW_U; ++u) {
+        if (i0 + u * lap >= n) break;
+        acc += C::term(row[u], tab);
+      }
+      s_acc[j][threadIdx.x] = acc;
+    }
+  }
+  for (int j = 0; j < K; ++j) {
+    const double sum = block_sum<VEC_BLOCK>(s_acc[j][threadIdx.x]);
+    if (threadIdx.x == 0) part[j * NPART + blockIdx.x] = sum;
+  }
+}
+
 namespace {  // host side: internal, as the handle types appear in the names
 
 using ham::cst;
@@ -206,6 +284,82 @@ struct GlmFamilyT {
                        ep, d_out);
   }
 };
+
+// The candidate buffers of a fresh handle (a `more` of glm_create_rows)
+template <class C>
+int alloc_cand(typename C::Handle* c) {
+  const size_t d8 = sizeof(double);
+  BBX_TRY(c->eta_cand.alloc(d8 * c->h->n));
+  BBX_TRY(c->cand_part.alloc(d8 * C::MAXC * NPART));
+  return c->cand_tab.alloc(d8 * C::MAXC * C::TAB);
+}
+
+// L(candidate j), j < K, at beta (null: the eta of the previous call): the
+// product into eta_cand, the candidates' tables up, one launch, the K x NPART
+// partials back in one copy and re-added on the host in index order in
+// C::Sum, rounded once.
+template <class C>
+int cand_loglik_impl(typename C::Handle* c, const double* beta, int K,
+                     const double* v, double* out) {
+  bbx_design* h = c->h;
+  if (beta) {
+    c->have_eta_cand = false;
+    double* d_in = h->stage_P.template as<double>();
+    BBX_HIP(hipMemcpyAsync(d_in, beta, sizeof(double) * c->P,
+                           hipMemcpyHostToDevice, h->stream));
+    BBX_TRY(launch_prep_v(h, d_in, nullptr, nullptr, part_slot(h, PS_C)));
+    BBX_TRY(launch_dot(h, d_in, nullptr, c->eta_cand.template as<double>(),
+                       nullptr));
+  }
+  double tab[C::MAXC * C::TAB] = {};
+  for (int j = 0; j < K; ++j)
+    C::fill(c, v + (size_t)j * C::stride(c), tab + j * C::TAB);
+  // (tab outlives the copy: this function synchronises before it returns)
+  BBX_HIP(hipMemcpyAsync(c->cand_tab.ptr, tab, sizeof(double) * K * C::TAB,
+                         hipMemcpyHostToDevice, h->stream));
+  BBX_LAUNCH(glm_cand_kernel<C>, dim3(NPART), dim3(VEC_BLOCK), 0, h->stream,
+             c->n, K, c->eta_cand.template as<const double>(),
+             c->pair.template as<const double2>(),
+             c->cand_tab.template as<const double>(),
+             c->cand_part.template as<double>());
+  BBX_HIP(hipGetLastError());
+  std::vector<double> part((size_t)K * NPART);
+  BBX_HIP(hipMemcpyAsync(part.data(), c->cand_part.ptr,
+                         sizeof(double) * part.size(), hipMemcpyDeviceToHost,
+                         h->stream));
+  BBX_HIP(hipStreamSynchronize(h->stream));   // the one synchronisation
+  if (beta) c->have_eta_cand = true;
+  for (int j = 0; j < K; ++j) {
+    typename C::Sum sum = 0.;
+    for (int b = 0; b < NPART; ++b) sum += part[(size_t)j * NPART + b];
+    out[j] = (double)sum;
+  }
+  return BBX_OK;
+}
+
+// The C ABI's front of the candidate sums
+template <class C>
+int cand_loglik(typename C::Handle* c, const double* beta, int K,
+                const double* v, double* out) {
+  const std::string who = C::who;
+  BBX_TRY(ham::check(c, C::family));
+  if (!v || !out) return fail(BBX_ERR_INVALID, who + "NULL argument");
+  if (K < 1 || K > C::MAXC)
+    return fail(BBX_ERR_INVALID, who + C::count + " outside [1, " +
+                                     std::to_string(C::MAXC) + "]");
+  for (int j = 0; j < K; ++j) {
+    if (!C::valid(c, v + (size_t)j * C::stride(c)))
+      return fail(BBX_ERR_INVALID, who + C::arg + "[" + std::to_string(j) +
+                                       "] is not finite and " + C::must);
+  }
+  if (!beta && !c->have_eta_cand)
+    return fail(BBX_ERR_STATE, who + "no linear predictor is cached: the "
+                                     "first call on a handle needs beta");
+  BBX_HIP(hipSetDevice(c->device));
+  return no_throw([&] { return cand_loglik_impl<C>(c, beta, K, v, out); });
+}
+
+inline bool finite_positive(double x) { return std::isfinite(x) && x > 0.; }
 
 // The shared head of a `create`; `counts`: every array the family needs is
 // given.

@@ -16,7 +16,7 @@
 //   w_i  = sigma(b) - sigma(-a),                   grad = X~^T w
 //   d_i  = sigma(a) sigma(-a) + sigma(b) sigma(-b)
 // Hessian-vector product at a fixed location: u = X~ v, out = X~^T (-(d u))
-// Cutpoints: L(c) = sum_i ll_i for up to ORDINAL_MAXC whole cutpoint vectors
+// Cutpoints: L(c) = sum_i ll_i for up to OrdinalCuts::MAXC whole cutpoint vectors
 // in one pass over the rows.
 //
 // ll_i is the whole log-probability of the row: g_y depends on the cutpoints
@@ -32,15 +32,13 @@
 // The row kernel, its contract and the host side are glm_rows.hpp's; this
 // file states the three expressions above on rows (y_i, o_i), with a pointer
 // to the handle's table of (lower cut, upper cut, g) per category in the
-// policy, and adds the cutpoint sums: a sibling kernel under the same
-// contract, in which each of the candidates has its own accumulator, block
-// sum and NPART partials, and a row's term for candidate k is computed from
-// (eta, y, o) and table k alone: the sum of a given cutpoint vector depends
-// neither on the number of candidates nor on its place among them.
+// policy, and the cutpoint sums as a candidate policy of glm_rows.hpp's
+// glm_cand_kernel: a row's term for candidate k is computed from (eta + o, y)
+// and ordinal_tab of candidate k alone, so the sum of a given cutpoint vector
+// depends neither on the number of candidates nor on its place among them.
 #include <math.h>
 
 #include <cmath>
-#include <vector>
 
 #include "common.hpp"
 #include "glm_rows.hpp"
@@ -49,71 +47,12 @@
 
 #pragma clang fp contract(off)  // a + b * c rounded as NumPy rounds it
 
-namespace bbx {
-
-constexpr int ORDINAL_MAXC = 8;   // cutpoint vectors per call
-
-// The cutpoint mode: n_c sums of ll_i in one pass over the rows, on the row
-// kernel's partition and in its order of addition.  `ctab`: n_c tables of
-// ordinal_tab, ORDINAL_TABLE doubles apart; `part`: n_c x NPART partials,
-// candidate-major.  The running sums of a thread live in LDS (one column per
-// thread: no bank conflict, no barrier) under a rolled loop over the
-// candidates, as in negbin_disp_kernel: the body unrolled eight times holds
-// more live values than the register budget of the row kernels.  y is a valid
-// category (checked at create): the table index is in range.
-static __global__ __launch_bounds__(VEC_BLOCK) void ordinal_cut_kernel(
-    int64_t n, int n_c, const double* __restrict__ eta,
-    const double2* __restrict__ yo, const double* __restrict__ ctab,
-    double* __restrict__ part) {
-  __shared__ double s_acc[ORDINAL_MAXC][VEC_BLOCK];
-  for (int k = 0; k < n_c; ++k) s_acc[k][threadIdx.x] = 0.;
-  const int64_t lap = (int64_t)gridDim.x * VEC_BLOCK;
-  for (int64_t i0 = (int64_t)blockIdx.x * VEC_BLOCK + threadIdx.x; i0 < n;
-       i0 += GLM_ROW_U * lap) {
-    double xo[GLM_ROW_U];
-    int cat[GLM_ROW_U];
-#pragma unroll
-    for (int u = 0; u < GLM_ROW_U; ++u) {
-      const int64_t i = i0 + u * lap;
-      xo[u] = 0.;
-      cat[u] = 0;
-      if (i < n) {
-        const double2 c = yo[i];
-        cat[u] = ORDINAL_TAB * (int)c.x;
-        xo[u] = eta[i] + c.y;
-      }
-    }
-#pragma unroll 1
-    for (int k = 0; k < n_c; ++k) {
-      const double* tab = ctab + k * ORDINAL_TABLE;
-      double acc = s_acc[k][threadIdx.x];
-#pragma unroll
-      for (int u = 0; u < GLM_ROW_U; ++u) {
-        if (i0 + u * lap >= n) break;
-        const double* t = tab + cat[u];
-        acc += ordinal_ll(xo[u], t[0], t[1], t[2]);
-      }
-      s_acc[k][threadIdx.x] = acc;
-    }
-  }
-  for (int k = 0; k < n_c; ++k) {
-    const double sum = block_sum<VEC_BLOCK>(s_acc[k][threadIdx.x]);
-    if (threadIdx.x == 0) part[k * NPART + blockIdx.x] = sum;
-  }
-}
-
-}  // namespace bbx
-
 using namespace bbx;
 
 // One proportional-odds likelihood on a design: rows (y_i, offset_i)
-struct bbx_ordinal : GlmRowsCore {
-  DevMem tab;        // ORDINAL_TABLE: ordinal_tab of the handle's cutpoints
-  DevMem eta_cut;    // n: eta of the last cutpoint call with coefficients
-  DevMem cut_part;   // ORDINAL_MAXC x NPART partials of the cutpoint sums
-  DevMem cut_tab;    // ORDINAL_MAXC x ORDINAL_TABLE: the call's tables
+struct bbx_ordinal : GlmCandCore {
+  DevMem tab;   // ORDINAL_TABLE: ordinal_tab of the handle's cutpoints
   int K = 0;
-  bool have_eta_cut = false;
 };
 
 namespace {
@@ -146,6 +85,39 @@ struct OrdinalRows {
     l = (t[2] - spa) - spb;
     // (l == -INFINITY without the literal: see ordinal_is_inf)
     return ordinal_is_inf(l) && l < 0.;
+  }
+};
+
+// The cutpoint sums: ll_i per whole cutpoint vector (K - 1 numbers) of the
+// caller's array.  y is a valid category (checked at create): the table index
+// is in range.
+struct OrdinalCuts {
+  using Handle = bbx_ordinal;
+  using Sum = double;
+  static constexpr int MAXC = 8;   // cutpoint vectors per call
+  static constexpr int TAB = ORDINAL_TABLE;
+  static constexpr const char* family = "ordinal";
+  static constexpr const char* who = "bbx_ordinal_cutpoint_loglik: ";
+  static constexpr const char* count = "n_c";
+  static constexpr const char* arg = "cuts";
+  static constexpr const char* must = "strictly increasing";
+  struct Row {
+    double xo;
+    int cat;   // the category's place in a table
+  };
+  __device__ static Row row(double eta, double2 yo) {
+    return Row{eta + yo.y, ORDINAL_TAB * (int)yo.x};
+  }
+  __device__ static double term(const Row& w, const double* tab) {
+    const double* t = tab + w.cat;
+    return ordinal_ll(w.xo, t[0], t[1], t[2]);
+  }
+  static size_t stride(const bbx_ordinal* c) { return c->K - 1; }
+  static bool valid(const bbx_ordinal* c, const double* cuts) {
+    return ordinal_cuts_ok(c->K, cuts);
+  }
+  static void fill(const bbx_ordinal* c, const double* cuts, double* tab) {
+    ordinal_tab(c->K, cuts, tab);
   }
 };
 
@@ -184,11 +156,8 @@ int ordinal_create_impl(bbx_design* h, const double* y, const double* offset,
       },
       [&](bbx_ordinal* c) {
         c->K = K;
-        const size_t d8 = sizeof(double);
-        BBX_TRY(c->tab.alloc(d8 * ORDINAL_TABLE));
-        BBX_TRY(c->eta_cut.alloc(d8 * h->n));
-        BBX_TRY(c->cut_part.alloc(d8 * ORDINAL_MAXC * NPART));
-        return c->cut_tab.alloc(d8 * ORDINAL_MAXC * ORDINAL_TABLE);
+        BBX_TRY(c->tab.alloc(sizeof(double) * ORDINAL_TABLE));
+        return alloc_cand<OrdinalCuts>(c);
       },
       out));
   const int st = upload_table(*out, cuts);
@@ -196,47 +165,6 @@ int ordinal_create_impl(bbx_design* h, const double* y, const double* offset,
     bbx_ordinal* c = *out;
     *out = nullptr;
     return ham::discard(c, st);
-  }
-  return BBX_OK;
-}
-
-// L(c_k), k < n_c, at beta (null: the eta of the previous call): the product
-// into eta_cut, the candidates' tables up, one launch of the cut kernel, the
-// n_c x NPART partials back in one copy and re-added on the host in index
-// order.
-int cutpoint_loglik_impl(bbx_ordinal* c, const double* beta, int n_c,
-                         const double* cuts, double* out) {
-  bbx_design* h = c->h;
-  if (beta) {
-    c->have_eta_cut = false;
-    double* d_in = h->stage_P.as<double>();
-    BBX_HIP(hipMemcpyAsync(d_in, beta, sizeof(double) * c->P,
-                           hipMemcpyHostToDevice, h->stream));
-    BBX_TRY(launch_prep_v(h, d_in, nullptr, nullptr, part_slot(h, PS_C)));
-    BBX_TRY(launch_dot(h, d_in, nullptr, c->eta_cut.as<double>(), nullptr));
-  }
-  double tab[ORDINAL_MAXC * ORDINAL_TABLE] = {};
-  for (int k = 0; k < n_c; ++k)
-    ordinal_tab(c->K, cuts + (size_t)k * (c->K - 1), tab + k * ORDINAL_TABLE);
-  // (tab outlives the copy: this function synchronises before it returns)
-  BBX_HIP(hipMemcpyAsync(c->cut_tab.ptr, tab,
-                         sizeof(double) * n_c * ORDINAL_TABLE,
-                         hipMemcpyHostToDevice, h->stream));
-  BBX_LAUNCH(ordinal_cut_kernel, dim3(NPART), dim3(VEC_BLOCK), 0, h->stream,
-             c->n, n_c, c->eta_cut.as<const double>(),
-             c->pair.as<const double2>(), c->cut_tab.as<const double>(),
-             c->cut_part.as<double>());
-  BBX_HIP(hipGetLastError());
-  std::vector<double> part((size_t)n_c * NPART);
-  BBX_HIP(hipMemcpyAsync(part.data(), c->cut_part.ptr,
-                         sizeof(double) * part.size(), hipMemcpyDeviceToHost,
-                         h->stream));
-  BBX_HIP(hipStreamSynchronize(h->stream));   // the one synchronisation
-  if (beta) c->have_eta_cut = true;
-  for (int k = 0; k < n_c; ++k) {
-    double sum = 0.;
-    for (int b = 0; b < NPART; ++b) sum += part[(size_t)k * NPART + b];
-    out[k] = sum;
   }
   return BBX_OK;
 }
@@ -273,26 +201,7 @@ extern "C" int bbx_ordinal_set_cutpoints(bbx_ordinal* c,
 extern "C" int bbx_ordinal_cutpoint_loglik(bbx_ordinal* c, const double* beta,
                                            int n_c, const double* cuts,
                                            double* out) {
-  const char* who = "bbx_ordinal_cutpoint_loglik: ";
-  BBX_TRY(ham::check(c, "ordinal"));
-  if (!cuts || !out)
-    return fail(BBX_ERR_INVALID, std::string(who) + "NULL argument");
-  if (n_c < 1 || n_c > ORDINAL_MAXC)
-    return fail(BBX_ERR_INVALID, std::string(who) + "n_c outside [1, " +
-                                     std::to_string(ORDINAL_MAXC) + "]");
-  for (int k = 0; k < n_c; ++k) {
-    if (!ordinal_cuts_ok(c->K, cuts + (size_t)k * (c->K - 1)))
-      return fail(BBX_ERR_INVALID, std::string(who) + "cuts[" +
-                                       std::to_string(k) +
-                                       "] is not finite and strictly "
-                                       "increasing");
-  }
-  if (!beta && !c->have_eta_cut)
-    return fail(BBX_ERR_STATE, std::string(who) +
-                                   "no linear predictor is cached: the first "
-                                   "call on a handle needs beta");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] { return cutpoint_loglik_impl(c, beta, n_c, cuts, out); });
+  return cand_loglik<OrdinalCuts>(c, beta, n_c, cuts, out);
 }
 
 BBX_HAM_ENTRY_POINTS(ordinal, GlmFamilyT<OrdinalRows>)

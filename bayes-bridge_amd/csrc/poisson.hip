@@ -26,13 +26,6 @@
 
 using namespace bbx;
 
-// GLM_ROW_U under the name it had in this file.  Nothing in this tree reads
-// it; the previous revision's tests/test_hip_poisson.py does, at import, and
-// a module that fails to import stops that revision's whole suite when it is
-// run over this build.  To be deleted with the next change to this file.
-constexpr int POISSON_U = 4;
-static_assert(POISSON_U == GLM_ROW_U, "the row kernel is glm_rows.hpp's");
-
 // One Poisson likelihood on a design: rows (y_i, log exposure_i)
 struct bbx_poisson : GlmRowsCore {};
 

@@ -15,8 +15,8 @@
 // Hessian-vector product at a fixed location: the location's value is m_i,
 // u = X~ v, out = X~^T (-(m u)).
 // Shape: L(k) = sum_i (d_i * ((log k + ((k - 1) * lt_i)) + eta_i)) - m_i, the
-// whole log density, for up to WEIBULL_MAXK values of k in one pass over the
-// rows (weibull_terms.hpp states the term).
+// whole log density, for up to WeibullShape::MAXC values of k in one pass over
+// the rows (weibull_terms.hpp states the term).
 //
 // At k = 1 the product k * lt is lt, so m, ll, w and the location are the
 // Poisson handle's on rows (y = d, o = lt), bit for bit.
@@ -29,15 +29,13 @@
 //
 // The row kernel, its contract and the host side are glm_rows.hpp's; this
 // file states the expressions above on rows (d_i, lt_i), with the handle's k
-// in the policy, and adds the shape sums: a sibling kernel under the same
-// contract, in which each of the K values has its own accumulator, block sum
-// and NPART partials, and a row's term for k_j is computed from (eta, d, lt,
-// k_j, log k_j) alone: the sum for a given k depends neither on K nor on its
-// place among the K values.
+// in the policy, and the shape sums as a candidate policy of glm_rows.hpp's
+// glm_cand_kernel: a row's term for k_j is computed from (eta, d, lt) and the
+// pair (k_j, log k_j) alone, so the sum for a given k depends neither on K nor
+// on its place among the K values.
 #include <math.h>
 
 #include <cmath>
-#include <vector>
 
 #include "common.hpp"
 #include "glm_rows.hpp"
@@ -46,67 +44,11 @@
 
 #pragma clang fp contract(off)  // a + b * c rounded as NumPy rounds it
 
-namespace bbx {
-
-constexpr int WEIBULL_MAXK = 8;   // values of k per shape call
-
-// K sums of the whole log density in one pass over the rows, on the row
-// kernel's partition and in its order of addition.  `tab`: (k_j, log k_j)
-// pairs; `part`: K x NPART partials, value-major.  The K running sums of a
-// thread live in LDS (one column per thread: no bank conflict, no barrier),
-// as negbin_disp_kernel's do, so that the loop over j is a loop and K a
-// number.  A row's term for k_j is a function of (eta, d, lt) and pair j
-// alone.
-static __global__ __launch_bounds__(VEC_BLOCK) void weibull_shape_kernel(
-    int64_t n, int K, const double* __restrict__ eta,
-    const double2* __restrict__ dlt, const double2* __restrict__ tab,
-    double* __restrict__ part) {
-  __shared__ double s_acc[WEIBULL_MAXK][VEC_BLOCK];
-  for (int j = 0; j < K; ++j) s_acc[j][threadIdx.x] = 0.;
-  const int64_t lap = (int64_t)gridDim.x * VEC_BLOCK;
-  for (int64_t i0 = (int64_t)blockIdx.x * VEC_BLOCK + threadIdx.x; i0 < n;
-       i0 += GLM_ROW_U * lap) {
-    double x[GLM_ROW_U], d[GLM_ROW_U], lt[GLM_ROW_U];
-#pragma unroll
-    for (int u = 0; u < GLM_ROW_U; ++u) {
-      const int64_t i = i0 + u * lap;
-      x[u] = d[u] = lt[u] = 0.;
-      if (i < n) {
-        const double2 c = dlt[i];
-        d[u] = c.x;
-        lt[u] = c.y;
-        x[u] = eta[i];
-      }
-    }
-#pragma unroll 1
-    for (int j = 0; j < K; ++j) {
-      const double2 kk = tab[j];
-      double acc = s_acc[j][threadIdx.x];
-#pragma unroll
-      for (int u = 0; u < GLM_ROW_U; ++u) {
-        if (i0 + u * lap >= n) break;
-        acc += weibull_full(x[u], d[u], lt[u], kk.x, kk.y);
-      }
-      s_acc[j][threadIdx.x] = acc;
-    }
-  }
-  for (int j = 0; j < K; ++j) {
-    const double sum = block_sum<VEC_BLOCK>(s_acc[j][threadIdx.x]);
-    if (threadIdx.x == 0) part[j * NPART + blockIdx.x] = sum;
-  }
-}
-
-}  // namespace bbx
-
 using namespace bbx;
 
 // One Weibull likelihood on a design: rows (d_i, log t_i)
-struct bbx_weibull : GlmRowsCore {
-  DevMem eta_shape;    // n: eta of the last shape call with coefficients
-  DevMem shape_part;   // WEIBULL_MAXK x NPART partials of the shape sums
-  DevMem shape_tab;    // WEIBULL_MAXK pairs (k, log k) of the call
+struct bbx_weibull : GlmCandCore {
   double k = 1., logk = 0.;
-  bool have_eta_shape = false;
 };
 
 namespace {
@@ -133,7 +75,39 @@ struct WeibullRows {
   }
 };
 
-bool finite_positive(double k) { return std::isfinite(k) && k > 0.; }
+// The shape sums: the whole log density (weibull_terms.hpp) per value k_j of
+// the caller's array.  The NPART partials are re-added in long double and
+// rounded once: partials of one size added in double one after the other lose
+// several ulps, which the slice sampler would not notice but the tests' bound
+// (4 float64 roundings) does.
+struct WeibullShape {
+  using Handle = bbx_weibull;
+  using Sum = long double;
+  static constexpr int MAXC = 8;   // values of k per shape call
+  static constexpr int TAB = 2;    // (k, log k)
+  static constexpr const char* family = "weibull";
+  static constexpr const char* who = "bbx_weibull_shape_loglik: ";
+  static constexpr const char* count = "n_k";
+  static constexpr const char* arg = "k";
+  static constexpr const char* must = "positive";
+  struct Row {
+    double eta, d, lt;
+  };
+  __device__ static Row row(double eta, double2 dlt) {
+    return Row{eta, dlt.x, dlt.y};
+  }
+  __device__ static double term(const Row& w, const double* tab) {
+    return weibull_full(w.eta, w.d, w.lt, tab[0], tab[1]);
+  }
+  static size_t stride(const bbx_weibull*) { return 1; }
+  static bool valid(const bbx_weibull*, const double* k) {
+    return finite_positive(*k);
+  }
+  static void fill(const bbx_weibull*, const double* k, double* tab) {
+    tab[0] = *k;
+    tab[1] = log(*k);
+  }
+};
 
 int weibull_row(int64_t i, double di, double lti) {
   if (!(di == 0. || di == 1.))
@@ -158,56 +132,9 @@ int weibull_create_impl(bbx_design* h, const double* event,
       [&](bbx_weibull* c) {
         c->k = shape;
         c->logk = log(shape);
-        const size_t d8 = sizeof(double);
-        BBX_TRY(c->eta_shape.alloc(d8 * h->n));
-        BBX_TRY(c->shape_part.alloc(d8 * WEIBULL_MAXK * NPART));
-        return c->shape_tab.alloc(d8 * WEIBULL_MAXK * 2);
+        return alloc_cand<WeibullShape>(c);
       },
       out);
-}
-
-// L(k_j), j < n_k, at beta (null: the eta of the previous call): the product
-// into eta_shape, the pairs (k, log k) up, one launch of the shape kernel,
-// the K x NPART partials back in one copy and re-added on the host in index
-// order, in long double and rounded once: NPART partials of one size added in
-// double one after the other lose several ulps, which the slice sampler would
-// not notice but the tests' bound (4 float64 roundings) does.
-int shape_loglik_impl(bbx_weibull* c, const double* beta, int n_k,
-                      const double* k, double* out) {
-  bbx_design* h = c->h;
-  if (beta) {
-    c->have_eta_shape = false;
-    double* d_in = h->stage_P.as<double>();
-    BBX_HIP(hipMemcpyAsync(d_in, beta, sizeof(double) * c->P,
-                           hipMemcpyHostToDevice, h->stream));
-    BBX_TRY(launch_prep_v(h, d_in, nullptr, nullptr, part_slot(h, PS_C)));
-    BBX_TRY(launch_dot(h, d_in, nullptr, c->eta_shape.as<double>(), nullptr));
-  }
-  double tab[WEIBULL_MAXK * 2];
-  for (int j = 0; j < n_k; ++j) {
-    tab[2 * j] = k[j];
-    tab[2 * j + 1] = log(k[j]);
-  }
-  // (tab outlives the copy: this function synchronises before it returns)
-  BBX_HIP(hipMemcpyAsync(c->shape_tab.ptr, tab, sizeof(double) * 2 * n_k,
-                         hipMemcpyHostToDevice, h->stream));
-  BBX_LAUNCH(weibull_shape_kernel, dim3(NPART), dim3(VEC_BLOCK), 0, h->stream,
-             c->n, n_k, c->eta_shape.as<const double>(),
-             c->pair.as<const double2>(), c->shape_tab.as<const double2>(),
-             c->shape_part.as<double>());
-  BBX_HIP(hipGetLastError());
-  std::vector<double> part((size_t)n_k * NPART);
-  BBX_HIP(hipMemcpyAsync(part.data(), c->shape_part.ptr,
-                         sizeof(double) * part.size(), hipMemcpyDeviceToHost,
-                         h->stream));
-  BBX_HIP(hipStreamSynchronize(h->stream));   // the one synchronisation
-  if (beta) c->have_eta_shape = true;
-  for (int j = 0; j < n_k; ++j) {
-    long double sum = 0.;
-    for (int b = 0; b < NPART; ++b) sum += part[(size_t)j * NPART + b];
-    out[j] = (double)sum;
-  }
-  return BBX_OK;
 }
 
 }  // namespace
@@ -239,24 +166,7 @@ extern "C" int bbx_weibull_set_shape(bbx_weibull* c, double k) {
 extern "C" int bbx_weibull_shape_loglik(bbx_weibull* c, const double* beta,
                                         int n_k, const double* k,
                                         double* out) {
-  const char* who = "bbx_weibull_shape_loglik: ";
-  BBX_TRY(ham::check(c, "weibull"));
-  if (!k || !out) return fail(BBX_ERR_INVALID, std::string(who) + "NULL argument");
-  if (n_k < 1 || n_k > WEIBULL_MAXK)
-    return fail(BBX_ERR_INVALID, std::string(who) + "n_k outside [1, " +
-                                     std::to_string(WEIBULL_MAXK) + "]");
-  for (int j = 0; j < n_k; ++j) {
-    if (!finite_positive(k[j]))
-      return fail(BBX_ERR_INVALID, std::string(who) + "k[" +
-                                       std::to_string(j) +
-                                       "] is not finite and positive");
-  }
-  if (!beta && !c->have_eta_shape)
-    return fail(BBX_ERR_STATE, std::string(who) +
-                                   "no linear predictor is cached: the first "
-                                   "call on a handle needs beta");
-  BBX_HIP(hipSetDevice(c->device));
-  return no_throw([&] { return shape_loglik_impl(c, beta, n_k, k, out); });
+  return cand_loglik<WeibullShape>(c, beta, n_k, k, out);
 }
 
 BBX_HAM_ENTRY_POINTS(weibull, GlmFamilyT<WeibullRows>)

@@ -551,13 +551,13 @@ def test_negbin_kernels_use_no_scratch(tmp_path):
     # the three modes of the row kernel, the dispersion kernel and the
     # shared trajectory kernels
     assert sum("glm_row_kernel" in k for k in table) == 3
-    assert sum("negbin_disp_kernel" in k for k in table) == 1
+    assert sum("glm_cand_kernel" in k for k in table) == 1
     # no fewer waves per SIMD than negbin_row_kernel<GRAD / LOC / HESS> (114 /
     # 78 / 50 VGPRs) and negbin_disp_kernel (104 VGPRs, 16 416 B of LDS) had
-    # before the fold onto glm_rows.hpp
+    # before the folds onto glm_rows.hpp
     occupancy = glm_row_occupancy(table) + tuple(
         res["Occupancy [waves/SIMD]"] for k, res in table.items()
-        if "negbin_disp_kernel" in k)
+        if "glm_cand_kernel" in k)
     assert all(got >= was
                for got, was in zip(occupancy, (4, 6, 8, 4))), occupancy
     for k in ("cox_step1_kernel", "cox_post_a_kernel", "cox_post_b_kernel",

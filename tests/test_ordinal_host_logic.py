@@ -602,13 +602,13 @@ def test_ordinal_kernels_use_no_scratch(tmp_path):
     table = _resource_table(os.path.join(src, "ordinal.hip"), tmp_path)
     # the three modes of the row kernel and the cutpoint kernel
     assert sum("glm_row_kernel" in k for k in table) == 3
-    assert sum("ordinal_cut_kernel" in k for k in table) == 1
+    assert sum("glm_cand_kernel" in k for k in table) == 1
     # the gradient mode holds two exp and two log1p per row, the logit row
     # kernel's count: no fewer waves per SIMD than the negative-binomial row
     # kernels, whose budget it shares
     occupancy = glm_row_occupancy(table) + tuple(
         res["Occupancy [waves/SIMD]"] for k, res in table.items()
-        if "ordinal_cut_kernel" in k)
+        if "glm_cand_kernel" in k)
     assert all(got >= was
                for got, was in zip(occupancy, (4, 6, 8, 4))), occupancy
     predict = _resource_table(os.path.join(src, "ordinal_predict.hip"),
