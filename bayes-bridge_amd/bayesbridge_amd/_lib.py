@@ -17,6 +17,7 @@ FORMAT_AUTO, FORMAT_CSR, FORMAT_TILED = 0, 1, 2
 F64, F32 = 0, 1
 MODEL_LINEAR, MODEL_LOGIT = 0, 1
 MODEL_PROBIT = 2
+MODEL_STUDENT_T = 3
 PRED_LINEAR, PRED_LOGIT, PRED_POISSON = 0, 1, 2   # BBX_PRED_*
 GSCALE_SAMPLE, GSCALE_OPTIMIZE, GSCALE_FIXED = 0, 1, 2
 BATCH_ALLOW_SLOW = 1
@@ -174,6 +175,8 @@ def _declare(lib):
             [hp, POINTER(c_double), POINTER(c_double)], c_int),
         "bbx_chain_get_latent": ([hp, c_void_p], c_int),
         "bbx_chain_get_zbase": ([hp, c_void_p], c_int),
+        "bbx_chain_set_df": ([hp, c_double], c_int),
+        "bbx_chain_get_df": ([hp, POINTER(c_double)], c_int),
         "bbx_chain_run": (
             [hp, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p,
              c_void_p, c_void_p, c_void_p, c_void_p], c_int),
@@ -238,6 +241,10 @@ def _declare(lib):
             [hp, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
             c_int),
+        "bbx_design_predictive_summary_student_t": (
+            [hp, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_void_p], c_int),
         "bbx_logit_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_poisson_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_cpoisson_create": (

@@ -193,6 +193,8 @@ class SamplerOptions():
             return SamplerOptions(**options)
         if model_name == 'probit':
             _check_probit_options(coef_sampler_type, options.get('rng'))
+        if model_name == 'student_t':
+            _check_student_t_options(coef_sampler_type, options.get('rng'))
         if model_name == 'logit' and coef_sampler_type in ('hmc', 'nuts'):
             # gibbs_util.py:52-75 lets 'hmc' through for the logit model.  Its
             # draw exists on the reference's host streams only, and a logit
@@ -209,9 +211,9 @@ class SamplerOptions():
                 coef_sampler_type in ('cholesky', 'woodbury')
                 and _is_hip_dense(design)):
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
-        if model_name not in ('linear', 'logit', 'probit'):
-            raise ValueError("Only linear, logit and probit models use the CG "
-                             "sampler.")
+        if model_name not in ('linear', 'logit', 'probit', 'student_t'):
+            raise ValueError("Only linear, logit, probit and student_t models "
+                             "use the CG sampler.")
         n_obs, n_pred = design.shape
         if n_pred > n_obs:
             # (the reference's TODO here, gibbs_util.py:66-68, is the
@@ -239,6 +241,23 @@ def _check_probit_options(coef_sampler_type, rng):
             "The probit model runs with rng='device' only: rng='reference' "
             "is not supported (the reference has no probit model whose "
             "streams could be followed).")
+
+
+def _check_student_t_options(coef_sampler_type, rng):
+    """The Student-t chain exists on the device only: its precision and mixing
+    weights are drawn by csrc/student_t.hip and its coefficients by the
+    Gaussian samplers."""
+    if coef_sampler_type in ('hmc', 'nuts'):
+        raise ValueError(
+            "The student_t model draws its coefficients with 'cg', "
+            "'cholesky' or 'woodbury': the '%s' sampler is not supported "
+            "(there is no Hamiltonian handle for student_t)."
+            % coef_sampler_type)
+    if rng == 'reference':
+        raise ValueError(
+            "The student_t model runs with rng='device' only: "
+            "rng='reference' is not supported (the reference has no "
+            "student_t model whose streams could be followed).")
 
 
 def _is_hip_dense(design):
@@ -340,6 +359,8 @@ class BayesBridge():
                 raise ValueError(
                     "The probit model has no observation precision: "
                     "init['obs_prec'] is not supported.")
+        if self.model.name == 'student_t':
+            _check_student_t_options(options.coef_sampler_type, options.rng)
         if options.coef_sampler_type in ('cholesky', 'woodbury'):
             if not _is_hip_dense(self.model.design):
                 raise ValueError(
@@ -456,7 +477,7 @@ class BayesBridge():
         other).  Batches keep 'coef', 'global_scale', 'logp' and use
         the device RNG."""
         design = self.model.design
-        if self.model.name == 'probit':
+        if self.model.name in ('probit', 'student_t'):
             return 0
         if options is not None and not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
@@ -521,6 +542,9 @@ class BayesBridge():
         if self.model.name == 'probit':
             raise ValueError("gibbs_batch is not supported for the probit "
                              "model: its chains run one at a time (gibbs).")
+        if self.model.name == 'student_t':
+            raise ValueError("gibbs_batch is not supported for the student_t "
+                             "model: its chains run one at a time (gibbs).")
         if not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
                 None, options, self.model.name, self.model.design)
@@ -582,6 +606,10 @@ class BayesBridge():
             raise ValueError("gibbs_multichain is not supported for the "
                              "probit model: its chains run one at a time "
                              "(gibbs).")
+        if self.model.name == 'student_t':
+            raise ValueError("gibbs_multichain is not supported for the "
+                             "student_t model: its chains run one at a time "
+                             "(gibbs).")
         if self.model.name in NO_OBS_PREC:
             raise ValueError("gibbs_multichain draws the coefficients with "
                              "'cg' only; the Cox model needs 'hmc'")
@@ -610,10 +638,13 @@ class BayesBridge():
             samples['global_scale'] = np.zeros(n_sample)
         if 'obs_prec' in params_to_save \
                 and self.model.name not in NO_OBS_PREC:
-            if self.model.name == 'linear':
+            if self.model.name in ('linear', 'student_t'):
                 samples['obs_prec'] = np.zeros(n_sample)
             else:
                 samples['obs_prec'] = np.zeros((self.n_obs, n_sample))
+        if 'mixing_weight' in params_to_save \
+                and self.model.name == 'student_t':
+            samples['mixing_weight'] = np.zeros((self.n_obs, n_sample))
         if 'logp' in params_to_save:
             samples['logp'] = np.zeros(n_sample)
         aux = AUX_PARAM.get(self.model.name)
@@ -636,7 +667,7 @@ class BayesBridge():
             if obs_prec.size != expected:
                 raise ValueError('An invalid initial state.')
             return obs_prec if self.model.name == 'logit' else float(obs_prec)
-        if self.model.name == 'linear':
+        if self.model.name in ('linear', 'student_t'):
             return np.mean(
                 (self.model.y - self.model.design.dot(coef)) ** 2) ** -1
         return LogisticModel.compute_polya_gamma_mean(
@@ -933,8 +964,10 @@ class BayesBridge():
         hyper = prior.param['gscale_neg_power']
         return HipGibbsChain(
             model.design, model.name,
-            model.y if model.name == 'linear' else model.n_success,
+            model.y if model.name in ('linear', 'student_t')
+            else model.n_success,
             n_trial=model.n_trial if model.name == 'logit' else None,
+            df=model.df if model.name == 'student_t' else None,
             sd_unshrunk=self.prior_sd_for_unshrunk,
             bridge_exponent=prior.bridge_exp, slab_size=prior.slab_size,
             gscale_shape=hyper['shape'], gscale_rate=hyper['rate'], seed=seed)
@@ -1019,6 +1052,11 @@ class BayesBridge():
                                  'obs_prec': 'obs_prec'}[k]: t.data_ptr()
                    for k, t in device_out.items()})
             kept = {'global_scale': gs, 'logp': lp, 'n_cg_iter': ncg}
+        elif 'mixing_weight' in samples:
+            kept, n_unconv = self._run_keeping_weights(
+                chain, n_iter, n_burnin, thin,
+                [k for k in ('coef', 'local_scale', 'obs_prec')
+                 if k in samples])
         else:
             kept, n_unconv = chain.run(
                 n_iter, n_burnin, thin, maxiter=500, atol=0.,
@@ -1027,6 +1065,33 @@ class BayesBridge():
         return self._device_collect(chain, seed, kept, n_unconv, n_iter,
                                     n_burnin, thin, host_params, init_used,
                                     optim_info)
+
+    @staticmethod
+    def _run_keeping_weights(chain, n_iter, n_burnin, thin, save):
+        """chain.run with the Student-t model's n mixing weights of every
+        kept iteration: the library keeps no n-vector per sample for this
+        model, so the run is cut at the kept iterations and the weights are
+        read there.  The chain does not notice the cuts: its draws are
+        addressed by (seed, iteration)."""
+        n_sample = (n_iter - n_burnin) // thin
+        _, n_unconv = chain.run(n_burnin, n_burnin, 1, maxiter=500, atol=0.,
+                                save=())
+        parts, weights = [], []
+        for _ in range(n_sample):
+            out, bad = chain.run(thin, 0, thin, maxiter=500, atol=0.,
+                                 save=save)
+            n_unconv += bad
+            parts.append(out)
+            weights.append(chain.get_latent())
+        rest = n_iter - n_burnin - n_sample * thin
+        if rest:
+            n_unconv += chain.run(rest, rest, 1, maxiter=500, atol=0.,
+                                  save=())[1]
+        keys = ['global_scale', 'logp', 'n_cg_iter'] + list(save)
+        kept = {k: np.concatenate([part[k] for part in parts])
+                if parts else np.zeros((0,)) for k in keys}
+        kept['mixing_weight'] = np.array(weights).reshape(n_sample, chain.n)
+        return kept, n_unconv
 
     def _device_setup(self, chain, seed, init, options, resume_from=None):
         """Brings a device chain to its initial state (bayesbridge.py:279-333:
@@ -1052,7 +1117,7 @@ class BayesBridge():
             if model.name in NO_OBS_PREC:      # probit: Omega = I, no state
                 return None
             eta = model.design.dot(coef)
-            if model.name == 'linear':
+            if model.name in ('linear', 'student_t'):
                 scale = np.sum((model.y - eta) ** 2) / 2
                 return 1 / (scale / host_rng.gamma(self.n_obs / 2, 1))
             out = np.empty(self.n_obs)
@@ -1115,7 +1180,10 @@ class BayesBridge():
                 samples[key][:] = kept[key].T
         if 'obs_prec' in samples:
             samples['obs_prec'][:] = kept['obs_prec'][:, 0] \
-                if model.name == 'linear' else kept['obs_prec'].T
+                if model.name in ('linear', 'student_t') \
+                else kept['obs_prec'].T
+        if 'mixing_weight' in samples:
+            samples['mixing_weight'][:] = kept['mixing_weight'].T
         for key in ('global_scale', 'logp'):
             if key in samples:
                 samples[key][:] = kept[key]

@@ -16,7 +16,8 @@ _GSCALE_MODES = {'sample': _lib.GSCALE_SAMPLE, 'optimize': _lib.GSCALE_OPTIMIZE,
 
 
 _MODEL_CODES = {'linear': _lib.MODEL_LINEAR, 'logit': _lib.MODEL_LOGIT,
-                'probit': _lib.MODEL_PROBIT}
+                'probit': _lib.MODEL_PROBIT,
+                'student_t': _lib.MODEL_STUDENT_T}
 
 
 def _ptr(a):
@@ -32,14 +33,20 @@ class HipGibbsChain():
     def __init__(self, design, family, outcome, n_trial=None,
                  sd_unshrunk=(float('inf'),), bridge_exponent=.5,
                  slab_size=float('inf'), gscale_shape=0., gscale_rate=0.,
-                 seed=0):
-        """family: 'linear' (outcome = y), 'logit' (outcome = n_success) or
-        'probit' (outcome = y in {0, 1}; n_trial None or all ones);
+                 seed=0, df=None):
+        """family: 'linear' (outcome = y), 'logit' (outcome = n_success),
+        'probit' (outcome = y in {0, 1}; n_trial None or all ones) or
+        'student_t' (outcome = y, finite; n_trial None; df: the degrees of
+        freedom, None = the library's default 4);
         sd_unshrunk: prior sd of the unshrunk coefficients, intercept first
         (bayesbridge.py:26-32); gscale_shape/rate: Gamma prior on
         tau^-bridge_exponent (prior.py:77-81), raw parametrisation."""
         if family not in _MODEL_CODES:
-            raise ValueError("family must be 'linear', 'logit' or 'probit'")
+            raise ValueError("family must be 'linear', 'logit', 'probit' or "
+                             "'student_t'")
+        if df is not None and family != 'student_t':
+            raise ValueError("df is the 'student_t' family's: family = %r"
+                             % family)
         self._lib = _lib.load()
         self._c = c_void_p()
         self.design = design            # keeps the operator alive
@@ -59,6 +66,8 @@ class HipGibbsChain():
             float(bridge_exponent), float(slab_size), float(gscale_shape),
             float(gscale_rate), int(seed) & 0xFFFFFFFFFFFFFFFF,
             byref(self._c)))
+        if df is not None:
+            self.set_df(df)
 
     def close(self):
         c = getattr(self, '_c', None)
@@ -105,26 +114,42 @@ class HipGibbsChain():
 
     def get_state(self):
         """(coef, obs_prec, local_scale, global_scale); obs_prec is a float
-        for the linear model and None for the probit model."""
+        for the linear and Student-t models (tau) and None for the probit
+        model."""
         coef = np.empty(self.P)
         ls = np.empty(self.n_shrunk)
         obs = None if self.family == 'probit' else np.empty(self._obs_len)
         g = c_double()
         _lib.check(self._lib.bbx_chain_get_state(
             self._c, _ptr(coef), _ptr(obs), _ptr(ls), byref(g)))
-        if self.family == 'linear':
+        if self.family in ('linear', 'student_t'):
             obs = float(obs[0])
         return coef, obs, ls, float(g.value)
 
     def get_latent(self):
-        """The n latents z of a probit chain's current state."""
+        """The n latents z of a probit chain's current state, or the n mixing
+        weights omega of a Student-t chain's."""
         out = np.empty(self.n)
         _lib.check(self._lib.bbx_chain_get_latent(self._c, _ptr(out)))
         return out
 
+    def set_df(self, df):
+        """The degrees of freedom nu > 0 of a Student-t chain; the weights,
+        zbase and the log-likelihood are recomputed under it."""
+        df = float(df)
+        if not (df > 0. and np.isfinite(df)):
+            raise ValueError("df must be finite and positive: %r" % df)
+        _lib.check(self._lib.bbx_chain_set_df(self._c, df))
+
+    def get_df(self):
+        df = c_double()
+        _lib.check(self._lib.bbx_chain_get_df(self._c, byref(df)))
+        return float(df.value)
+
     def get_zbase(self):
-        """X~^T kappa (logit), X~^T y (linear) or X~^T z (probit): what the
-        next draw's right-hand side is scaled from."""
+        """X~^T kappa (logit), X~^T y (linear), X~^T z (probit) or X~^T (tau
+        omega y) (Student-t): what the next draw's right-hand side is scaled
+        from."""
         out = np.empty(self.P)
         _lib.check(self._lib.bbx_chain_get_zbase(self._c, _ptr(out)))
         return out

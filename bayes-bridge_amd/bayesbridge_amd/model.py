@@ -665,6 +665,123 @@ class ProbitModel(_Predictive, _Model):
             .astype(np.float64)
 
 
+def _finite_outcome(y, n_row):
+    """The outcome check of the Student-t model on n_row rows: y finite."""
+    if isinstance(y, tuple):
+        raise ValueError(
+            "The Student-t model takes a continuous outcome y, not a tuple.")
+    y = np.asarray(y, dtype=np.float64)
+    if y.shape != (n_row,):
+        raise ValueError(
+            "Incompatible sizes of the outcome and design matrix: %s "
+            "outcomes, %d rows." % (y.shape, n_row))
+    bad = np.flatnonzero(~np.isfinite(y))
+    if bad.size:
+        raise ValueError(
+            "The Student-t model takes a finite outcome: y[%d] = %r."
+            % (bad[0], float(y[bad[0]])))
+    return y
+
+
+def _checked_df(df):
+    try:
+        value = float(df)
+    except (TypeError, ValueError):
+        value = float('nan')
+    if not (value > 0. and math.isfinite(value)):
+        raise ValueError(
+            "The degrees of freedom df must be finite and positive: %r."
+            % (df,))
+    return value
+
+
+class StudentTModel(_Predictive, _Model):
+    """Linear regression with Student-t errors, y_i = eta_i + e_i with
+    e_i sqrt(tau) ~ t on `df` degrees of freedom (fixed; Gelman's default 4),
+    no counterpart in the reference.  As a scale mixture of normals, omega_i
+    ~ Gamma(df/2, rate df/2) and y_i | omega_i ~ N(eta_i, 1 / (tau omega_i)),
+    the coefficients' conditional is Gaussian with the per-row precision tau
+    omega_i: the chain draws them with 'cg', 'cholesky' or 'woodbury' on the
+    device (csrc/student_t.hip draws tau and omega).  An outlying row gets a
+    small omega_i and with it a small say in the fit."""
+
+    def __init__(self, y, design, df=4.):
+        self.y = _finite_outcome(y, design.shape[0])
+        self.df = _checked_df(df)
+        self.design = design
+        self.name = 'student_t'
+
+    def compute_loglik_and_gradient(self, beta, obs_prec=1.,
+                                    loglik_only=False):
+        """The chain's log-likelihood, sum_i [1/2 log tau - (df+1)/2
+        log1p(tau r_i^2 / df)] + n [lgamma((df+1)/2) - lgamma(df/2) -
+        1/2 log(df/2)] (the linear model's convention: -n/2 log 2 pi
+        dropped), and its gradient X~^T ((df+1) tau r / (df + tau r^2))."""
+        nu, tau = self.df, float(obs_prec)
+        r = self.y - self.design.dot(beta)
+        const = math.lgamma((nu + 1.) / 2.) - math.lgamma(nu / 2.) \
+            - .5 * math.log(nu / 2.)
+        loglik = float(np.sum(.5 * math.log(tau) - (nu + 1.) / 2.
+                              * np.log1p(tau * r * r / nu))
+                       + len(r) * const)
+        grad = None
+        if not loglik_only:
+            grad = self.design.Tdot((nu + 1.) * tau * r / (nu + tau * r * r))
+        return loglik, grad
+
+    def calc_intercept_mle(self):
+        """The median of y: what a heavy tail does not drag."""
+        return float(np.median(self.y))
+
+    def _pred_call(self, n_draw, draws, obs_prec, offset, y, n_trial,
+                   ll_const):
+        return 'bbx_design_predictive_summary_student_t', \
+            (n_draw, self.df), (draws, obs_prec, offset, y, ll_const)
+
+    def predict(self, coef, obs_prec=None, X_new=None, y_new=None,
+                return_draws=False, _draws_per_pass=0):
+        """Posterior prediction over the draws coef (P,) or (P, S) -- what
+        samples['coef'] is -- with obs_prec (S,) -- samples['obs_prec'], the
+        draws' tau.  X_new=None: the training rows with the model's own
+        outcome; otherwise n_new rows of the model's raw columns (NumPy or
+        SciPy), centred with the TRAINING design's column means, with y_new or
+        without.  A dict: 'mean' and 'sd' (n,), the posterior mean of eta
+        (E[y | x] for df > 1) and its population standard deviation over the
+        draws; with an outcome 'lpd', 'loglik_mean' and 'loglik_var' (n,) and
+        the floats 'lppd' = sum lpd, 'p_waic' = sum loglik_var and 'waic' =
+        -2 (lppd - p_waic), the log density being the full t-density on df
+        degrees of freedom with precision obs_prec; with return_draws 'draws'
+        (n, S).  One device call for all the draws."""
+        draws, X_new, n_row = self._predict_rows(coef, X_new)
+        _training_rows_only(X_new, y_new=y_new)
+        y = self.y if X_new is None else y_new
+        if y is not None:
+            y = _finite_outcome(y, n_row)
+        if obs_prec is None:
+            raise ValueError(
+                "obs_prec (one observation precision per draw, "
+                "samples['obs_prec']) is required.")
+        obs_prec = np.asarray(obs_prec, dtype=np.float64).reshape(-1)
+        if obs_prec.shape != (len(draws),):
+            raise ValueError(
+                "obs_prec must hold one value per draw: %d values, %d draws."
+                % (len(obs_prec), len(draws)))
+        if not np.all(np.isfinite(obs_prec)) or (obs_prec <= 0).any():
+            raise ValueError(
+                "Every obs_prec must be strictly positive and finite.")
+        return self._predictive_summary(
+            draws, X_new, n_row, y=y, obs_prec=obs_prec,
+            return_draws=return_draws, draws_per_pass=_draws_per_pass)
+
+    @staticmethod
+    def simulate_outcome(X, beta, df=4., noise_scale=1., seed=None):
+        """y_i = eta_i + noise_scale times a Student-t variate on df degrees
+        of freedom."""
+        rng = np.random.default_rng(seed)
+        return np.asarray(X.dot(beta)).ravel() \
+            + noise_scale * rng.standard_t(_checked_df(df), X.shape[0])
+
+
 class PoissonModel(_DeviceHamiltonian, _Predictive, _Model):
     """Incidence-rate regression: counts y_i with mean exposure_i exp(eta_i).
     The likelihood, its gradient and the Hessian-vector products run on the
@@ -2459,7 +2576,7 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
                     dense_storage_dtype='float64', entry_time=None,
                     ties='breslow', weights=None, dispersion=None,
                     dispersion_prior=None, cutpoints=None,
-                    cutpoint_prior=None, weibull_shape=None,
+                    cutpoint_prior=None, df=None, weibull_shape=None,
                     weibull_shape_prior=None, competing_time=None):
     """model/factory.py:10-68 with the design placed on an MI355X.  `X` may be
     a SciPy sparse matrix, a NumPy array, or an already built HipDesignMatrix.
@@ -2501,8 +2618,10 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     `weibull_shape_prior` = {'shape': .., 'rate': ..}, None: Gamma(2, 1); a
     number: held fixed) is the Weibull shape k.  Strata are refused.  For
     family='probit', outcome = y in {0, 1}; a tuple with n_trial is refused
-    (the binomial outcome is the logit model's).  (The
-    six keywords stand before `competing_time`, which stays the last one:
+    (the binomial outcome is the logit model's).  For family='student_t',
+    outcome = y, finite, and `df` > 0 (None: 4) is the fixed degrees of
+    freedom of the errors.  (The
+    seven keywords stand before `competing_time`, which stays the last one:
     pass them by name.)"""
     if entry_time is not None and family != 'cox':
         raise ValueError("entry_time is an argument of family='cox' only.")
@@ -2544,9 +2663,14 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
             "The negative-binomial model takes outcome = y or (y, exposure): "
             "strata are not supported, the conditional model has no "
             "negative-binomial form here.")
+    if df is not None and family != 'student_t':
+        raise ValueError("df is an argument of family='student_t' only.")
     if family == 'probit':
         # (before the design goes to the GPU)
         outcome = _binary_outcome(outcome, X.shape[0])
+    if family == 'student_t':
+        outcome = _finite_outcome(outcome, X.shape[0])
+        df = _checked_df(4. if df is None else df)
     stratified_poisson = (family == 'poisson' and isinstance(outcome, tuple)
                           and len(outcome) == 3)
     if add_intercept is None:
@@ -2696,6 +2820,8 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         return LogisticModel(n_success, n_trial, design)
     if family == 'probit':
         return ProbitModel(outcome, design)
+    if family == 'student_t':
+        return StudentTModel(outcome, design, df)
     if family == 'cox':
         if competing_time is not None:
             return CoxModel._finegray(event_time, censoring_time,

@@ -242,7 +242,7 @@ class HipRegressionCoefficientSampler():
         design = model.design
 
         def loglik_and_grad(beta, loglik_only):
-            if model.name == 'linear':
+            if model.name in ('linear', 'student_t'):
                 return model.compute_loglik_and_gradient(
                     beta, obs_prec, loglik_only=loglik_only)
             return model.compute_loglik_and_gradient(

@@ -17,6 +17,7 @@ from . import hostrng
 STREAM_ETA1, STREAM_ETA2, STREAM_PG, STREAM_GSCALE, STREAM_LSCALE, \
     STREAM_OBSVAR = 1, 2, 3, 4, 5, 6
 STREAM_LATENT = 7
+STREAM_MIX = 8
 
 _SIGS = {
     "bbx_replay_philox_block": [c_void_p, c_void_p, c_void_p],

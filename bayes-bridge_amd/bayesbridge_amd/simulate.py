@@ -99,7 +99,9 @@ def simulate_outcome(X, beta, model, intercept=0., n_trial=None, seed=None,
     censoring_time) with the hazard weibull_shape t^(weibull_shape - 1)
     exp(intercept + X beta) and the censoring fraction asked for
     (WeibullModel.simulate_outcome); for 'probit', y in {0, 1} with
-    P(y = 1) = Phi(intercept + X beta)."""
+    P(y = 1) = Phi(intercept + X beta); for 'student_t', y = intercept +
+    X beta + a standard Student-t variate on 4 degrees of freedom
+    (StudentTModel.simulate_outcome takes df and the noise scale)."""
     if model == 'cox':
         from .model import CoxModel
         return CoxModel.simulate_outcome(X, beta, censoring_frac, seed)
@@ -127,6 +129,9 @@ def simulate_outcome(X, beta, model, intercept=0., n_trial=None, seed=None,
         # y = 1 when the latent intercept + X beta + N(0, 1) is positive
         latent = intercept + X.dot(beta) + np.random.randn(X.shape[0])
         return (np.asarray(latent).ravel() > 0.).astype(np.float64)
+    if model == 'student_t':
+        eta = np.asarray(intercept + X.dot(beta)).ravel()
+        return eta + np.random.standard_t(4., size=X.shape[0])
     raise NotImplementedError(model)
 
 

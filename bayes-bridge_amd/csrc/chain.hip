@@ -226,6 +226,23 @@ __global__ __launch_bounds__(256) void chain_fill_obs_prec_kernel(
     omega[i] = w;
 }
 
+// The `count` (<= ROW_GRID) block sums of an n-vector folded onto the NPART
+// slots launch_tdot re-adds: slot t takes blocks t, t + NPART, ... in that
+// order (the probit model's sum z, the Student-t model's sum kappa).
+__global__ __launch_bounds__(NPART) void chain_sumw_fold_kernel(
+    const double* __restrict__ z_part, int count, double* __restrict__ part) {
+  double acc = 0.;
+  for (int k = threadIdx.x; k < count; k += NPART) acc += z_part[k];
+  part[threadIdx.x] = acc;
+}
+
+int launch_sumw_fold(bbx_design* h, const double* block_sums, int count) {
+  BBX_LAUNCH(chain_sumw_fold_kernel, dim3(1), dim3(NPART), 0, h->stream,
+             block_sums, count, part_slot(h, PS_SUMW));
+  BBX_HIP(hipGetLastError());
+  return BBX_OK;
+}
+
 // Partials of sum |beta_j|^alpha (shrunk), sum (beta_j/slab)^2 (all) and
 // sum (beta_j/sd_j)^2 (unshrunk).  Grid = NPART.
 __global__ __launch_bounds__(256) void chain_coef_sums_kernel(
@@ -586,6 +603,37 @@ static int chain_probit_refresh(bbx_chain* c) {
   return BBX_OK;
 }
 
+// omega | beta, tau of a Student-t chain from the psi in place, with the
+// mixing stream of iteration `it` (-1: a chain that has not run); `draw_tau`:
+// first tau | beta, omega with the weights in place (an iteration; a refresh
+// keeps its tau).  Then zbase = X~^T kappa: the one product a Student-t
+// iteration adds.  The log-likelihood partials are left in row_part[0 ..
+// *row_blocks) for launch_student_t_finish.
+static int chain_student_t_update(bbx_chain* c, int64_t it, bool draw_tau,
+                                  int* row_blocks) {
+  bbx_design* h = c->h;
+  if (draw_tau)
+    BBX_TRY(launch_student_t_tau(c, iter_stream(STREAM_OBSVAR, it)));
+  BBX_TRY(launch_student_t_mix(c, iter_stream(STREAM_MIX, it), row_blocks));
+  TdotEpilogue ep;
+  return launch_tdot(h, c->kappa.as<double>(), part_slot(h, PS_SUMW), ep,
+                     c->zbase.as<double>());
+}
+
+// psi, omega, Omega, kappa, zbase and the log-likelihood of a Student-t chain
+// recomputed from (coef, tau): omega is a function of (seed, iteration, row,
+// nu, psi, tau), so the state a finished iteration left is reproduced bit for
+// bit.  tau is not redrawn.
+static int chain_student_t_refresh(bbx_chain* c) {
+  bbx_design* h = c->h;
+  BBX_TRY(chain_linear_predictor(c));
+  int rg = 0;
+  BBX_TRY(chain_student_t_update(c, c->iter - 1, false, &rg));
+  BBX_TRY(launch_student_t_finish(c, rg));
+  BBX_HIP(hipStreamSynchronize(h->stream));
+  return BBX_OK;
+}
+
 // The pass for X~ beta enqueued by the CG loop itself, right behind a look at
 // the stop flag (bbx_design::tail_hook): when the host wakes up from that look
 // the pass is already running, and the kernels of both branches are launched
@@ -783,13 +831,18 @@ int chain_post_draw(bbx_chain* c, bool have_psi, int phases,
 #undef BBX_PG_LAUNCH
   } else if (c->model == BBX_MODEL_PROBIT) {
     BBX_TRY(chain_probit_update(c, c->iter, &rg));
+  } else if (c->model == BBX_MODEL_STUDENT_T) {
+    BBX_TRY(chain_student_t_update(c, c->iter, true, &rg));
   } else {
     BBX_LAUNCH(chain_rss_kernel, dim3(rg), dim3(256), 0, s, n,
                        c->outcome.as<double>(), c->psi.as<double>(), rp);
   }
-  BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, s,
-                     c->model, 0, n, c->seed,
-                     iter_stream(STREAM_OBSVAR, c->iter), rp, rg, sc);
+  if (c->model == BBX_MODEL_STUDENT_T)
+    BBX_TRY(launch_student_t_finish(c, rg));
+  else
+    BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, s,
+                       c->model, 0, n, c->seed,
+                       iter_stream(STREAM_OBSVAR, c->iter), rp, rg, sc);
 
   }  // POST_MAIN
 
@@ -824,7 +877,8 @@ static int chain_step(bbx_chain* c, int maxiter, double atol, int* n_cg_iter) {
                                  c->eta2_next.as<double>()));
     }
     // (probit: the linear model's branch at the fixed precision 1 -- the
-    // cached Gram, no weighted one)
+    // cached Gram, no weighted one; Student-t: the logit model's branch with
+    // Omega = tau omega, a weighted Gram every iteration)
     const bool linear = c->model == BBX_MODEL_LINEAR;
     const bool probit = c->model == BBX_MODEL_PROBIT;
     const int st = chol_sample_device(
@@ -980,8 +1034,17 @@ int bbx_chain_create(bbx_design* design, int model, const double* outcome,
   *out = nullptr;
   if (!design || !outcome) return fail(BBX_ERR_INVALID, "NULL argument");
   if (model != BBX_MODEL_LINEAR && model != BBX_MODEL_LOGIT &&
-      model != BBX_MODEL_PROBIT)
+      model != BBX_MODEL_PROBIT && model != BBX_MODEL_STUDENT_T)
     return fail(BBX_ERR_INVALID, "unknown model");
+  if (model == BBX_MODEL_STUDENT_T) {
+    if (n_trial)
+      return fail(BBX_ERR_INVALID,
+                  "student_t: n_trial must be NULL (the outcome is continuous)");
+    for (int64_t i = 0; i < design->n; ++i)
+      if (!std::isfinite(outcome[i]))
+        return fail(BBX_ERR_INVALID, "student_t: outcome[" +
+                                         std::to_string(i) + "] is not finite");
+  }
   if (model == BBX_MODEL_PROBIT) {
     for (int64_t i = 0; i < design->n; ++i) {
       if (!(outcome[i] == 0. || outcome[i] == 1.))
@@ -1019,7 +1082,8 @@ int bbx_chain_create(bbx_design* design, int model, const double* outcome,
     BBX_TRY(c->kappa.alloc(nb));
     BBX_TRY(c->obs_prec.alloc(nb));
     BBX_TRY(c->psi.alloc(nb));
-    if (model == BBX_MODEL_PROBIT) BBX_TRY(c->latent.alloc(nb));
+    if (model == BBX_MODEL_PROBIT || model == BBX_MODEL_STUDENT_T)
+      BBX_TRY(c->latent.alloc(nb));
     for (DevMem* m : {&c->zbase, &c->coef, &c->phi, &c->x0, &c->sd, &c->z,
                       &c->mean, &c->square})
       BBX_TRY(m->alloc(Pb));
@@ -1052,8 +1116,9 @@ int bbx_chain_create(bbx_design* design, int model, const double* outcome,
                          c->n_trial.as<double>(), c->kappa.as<double>());
       src = c->kappa.as<double>();
     }
-    // (probit: zbase = X~^T z, from the latents drawn below)
-    if (model != BBX_MODEL_PROBIT) {
+    // (probit: zbase = X~^T z, from the latents drawn below; Student-t:
+    // X~^T kappa, from the weights drawn below)
+    if (model != BBX_MODEL_PROBIT && model != BBX_MODEL_STUDENT_T) {
       BBX_TRY(launch_sum_n(h, src, n, part_slot(h, PS_SUMW)));
       TdotEpilogue ep;
       BBX_TRY(launch_tdot(h, src, part_slot(h, PS_SUMW), ep,
@@ -1094,6 +1159,11 @@ int bbx_chain_create(bbx_design* design, int model, const double* outcome,
                  dim3(256), 0, h->stream, n, c->scalars.as<ChainScalars>(),
                  c->obs_prec.as<double>());
       BBX_TRY(chain_probit_refresh(c));
+    }
+    if (model == BBX_MODEL_STUDENT_T) {
+      // nu = 4, tau = 1, and the weights of coef = 0 on the reserved stream index
+      c->df_const = student_t_row_const(c->df);
+      BBX_TRY(chain_student_t_refresh(c));
     }
     BBX_HIP(hipGetLastError());
     BBX_HIP(hipStreamSynchronize(h->stream));
@@ -1153,6 +1223,7 @@ static int bbx_chain_set_state_impl(bbx_chain* c, const double* coef,
   if (gscale) sc.gscale = *gscale;
   BBX_HIP(hipMemcpy(c->scalars.ptr, &sc, sizeof(sc), hipMemcpyHostToDevice));
   if (c->model == BBX_MODEL_PROBIT) BBX_TRY(chain_probit_refresh(c));
+  if (c->model == BBX_MODEL_STUDENT_T) BBX_TRY(chain_student_t_refresh(c));
   return BBX_OK;
 }
 
@@ -1315,14 +1386,40 @@ int bbx_chain_get_logp(bbx_chain* c, double* loglik, double* logp) {
 int bbx_chain_get_latent(bbx_chain* c, double* out) {
   return no_throw([&]() -> int {
     BBX_TRY(chain_check(c));
-    if (c->model != BBX_MODEL_PROBIT)
+    if (c->model != BBX_MODEL_PROBIT && c->model != BBX_MODEL_STUDENT_T)
       return fail(BBX_ERR_INVALID,
-                  "bbx_chain_get_latent: not a probit chain");
+                  "bbx_chain_get_latent: not a probit or student_t chain");
     if (!out) return fail(BBX_ERR_INVALID, "bbx_chain_get_latent: out is NULL");
     BBX_HIP(hipSetDevice(c->h->device));
     BBX_HIP(hipStreamSynchronize(c->h->stream));
     BBX_HIP(hipMemcpy(out, c->latent.ptr, sizeof(double) * (size_t)c->h->n,
                       hipMemcpyDeviceToHost));
+    return BBX_OK;
+  });
+}
+
+int bbx_chain_set_df(bbx_chain* c, double df) {
+  return no_throw([&]() -> int {
+    BBX_TRY(chain_check(c));
+    if (c->model != BBX_MODEL_STUDENT_T)
+      return fail(BBX_ERR_INVALID, "bbx_chain_set_df: not a student_t chain");
+    if (!(df > 0.) || !std::isfinite(df))
+      return fail(BBX_ERR_INVALID,
+                  "bbx_chain_set_df: df must be finite and positive");
+    BBX_HIP(hipSetDevice(c->h->device));
+    c->df = df;
+    c->df_const = student_t_row_const(df);
+    return chain_student_t_refresh(c);
+  });
+}
+
+int bbx_chain_get_df(bbx_chain* c, double* df) {
+  return no_throw([&]() -> int {
+    BBX_TRY(chain_check(c));
+    if (c->model != BBX_MODEL_STUDENT_T)
+      return fail(BBX_ERR_INVALID, "bbx_chain_get_df: not a student_t chain");
+    if (!df) return fail(BBX_ERR_INVALID, "bbx_chain_get_df: df is NULL");
+    *df = c->df;
     return BBX_OK;
   });
 }
@@ -1346,6 +1443,17 @@ int bbx_chain_init_obs_prec(bbx_chain* c) {
   if (c->model == BBX_MODEL_PROBIT) return chain_probit_refresh(c);
   BBX_TRY(chain_linear_predictor(c));
   const int rg = grid_for(h->n, ROW_GRID);
+  if (c->model == BBX_MODEL_STUDENT_T) {
+    // tau = 1 / mean(r^2), the linear model's rule, then the weights under it
+    double* rp = c->row_part.as<double>();
+    BBX_LAUNCH(chain_rss_kernel, dim3(rg), dim3(256), 0, h->stream, h->n,
+               c->outcome.as<double>(), c->psi.as<double>(), rp);
+    BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, h->stream,
+               BBX_MODEL_LINEAR, 1, h->n, c->seed, 0, rp, rg,
+               c->scalars.as<ChainScalars>());
+    BBX_HIP(hipGetLastError());
+    return chain_student_t_refresh(c);
+  }
   if (c->model == BBX_MODEL_LOGIT) {
     BBX_LAUNCH(chain_pg_mean_kernel, dim3(rg), dim3(256), 0, h->stream,
                        h->n, c->n_trial.as<double>(), c->psi.as<double>(),
@@ -1626,10 +1734,11 @@ int bbx_chain_set_coef_sampler(bbx_chain* c, int sampler) {
       return fail(BBX_ERR_INVALID,
                   "the woodbury sampler needs a dense design (this one is sparse)");
     if (sampler == BBX_SAMPLER_WOODBURY && c->model != BBX_MODEL_LINEAR &&
-        c->model != BBX_MODEL_LOGIT && c->model != BBX_MODEL_PROBIT)
+        c->model != BBX_MODEL_LOGIT && c->model != BBX_MODEL_PROBIT &&
+        c->model != BBX_MODEL_STUDENT_T)
       return fail(BBX_ERR_INVALID,
-                  "the woodbury sampler draws linear, logit and probit "
-                  "models only");
+                  "the woodbury sampler draws linear, logit, probit and "
+                  "student_t models only");
     if (sampler == BBX_SAMPLER_CHOLESKY && c->h->sparse)
       return fail(BBX_ERR_INVALID,
                   "the cholesky sampler needs a dense design (this one is sparse)");

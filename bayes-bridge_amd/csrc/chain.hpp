@@ -21,7 +21,7 @@ struct alignas(128) ChainScalars {
   long long n_gscale_clamped;
   long long n_lscale_fixed;
   // ---- written by the Omega branch
-  alignas(128) double obs_prec;  // linear model only
+  alignas(128) double obs_prec;  // linear model; Student-t: tau
   double loglik;                 // of the current coef
   // log posterior (bayesbridge.py:480-511)
   __host__ __device__ double logp() const { return loglik + logprior; }
@@ -40,6 +40,10 @@ struct bbx_chain {
   bool mean_zero = true;   // running mean still all zeros => CG warm start 0
   int gscale_update = BBX_GSCALE_SAMPLE;
   int coef_sampler = BBX_SAMPLER_CG;   // bbx_chain_set_coef_sampler
+  // BBX_MODEL_STUDENT_T: the degrees of freedom nu (bbx_chain_set_df) and the
+  // log-likelihood's per-row constant lgamma((nu+1)/2) - lgamma(nu/2) -
+  // 1/2 log(nu/2), computed on the host when nu is set
+  double df = 4., df_const = 0.;
   // bbx_chain_set_progress: called from the host loop of a run every
   // `progress_every` iterations (gibbs_util.py:214-238 prints from there)
   void (*progress)(int, void*) = nullptr;
@@ -50,7 +54,8 @@ struct bbx_chain {
   bbx::DevMem coef, phi, x0, sd, z, mean, square, sd_unshrunk;  // P-length
   bbx::DevMem lscale;                   // P - n_unshrunk
   bbx::DevMem obs_prec, psi;            // n
-  bbx::DevMem latent;                   // n: the probit model's z (else empty)
+  bbx::DevMem latent;                   // n: the probit model's z, the Student-t
+                                        // model's omega (else empty)
   bbx::DevMem scalars;                 // ChainScalars
   bbx::DevMem row_part;                 // ROW_GRID partials x 2
   bbx::DevMem misc_part;                // NPART x 3: sums over the coefficients (tau branch)
@@ -110,5 +115,23 @@ int chain_end_run(bbx_chain* c, int n_sample, double* gscale, double* logp);
 // *row_blocks) and the NPART partials of sum_i latent_i into the design's
 // PS_SUMW slot, what launch_tdot(latent) reads.
 int launch_chain_probit(bbx_chain* c, uint64_t stream, int* row_blocks);
+// The `count` (<= ROW_GRID) block sums of an n-vector w folded onto the NPART
+// slots of the design's PS_SUMW that launch_tdot(w) re-adds: slot t takes
+// blocks t, t + NPART, ... in that order (chain.hip).
+int launch_sumw_fold(bbx_design* h, const double* block_sums, int count);
+
+// The Student-t model's updates (student_t.hip), on the design's stream, from
+// the psi in place.  launch_student_t_tau: S = sum_i latent_i (y_i - psi_i)^2
+// with the weights in place, then scalars->obs_prec = gamma_draw(Philox(seed,
+// stream, 0), n/2) / (S/2).  launch_student_t_mix: with that obs_prec (tau),
+// latent_i = gamma_draw(Philox(seed, stream, i), (df+1)/2) / ((df + tau
+// r_i^2)/2), obs_prec_i = tau latent_i, kappa_i = obs_prec_i y_i; the
+// log-likelihood partials into row_part[0 .. *row_blocks), the partials of
+// sum_i kappa_i into PS_SUMW.  launch_student_t_finish sums the former into
+// scalars->loglik.  student_t_row_const: the log-likelihood's per-row constant.
+int launch_student_t_tau(bbx_chain* c, uint64_t stream);
+int launch_student_t_mix(bbx_chain* c, uint64_t stream, int* row_blocks);
+int launch_student_t_finish(bbx_chain* c, int row_blocks);
+double student_t_row_const(double nu);
 
 }  // namespace bbx

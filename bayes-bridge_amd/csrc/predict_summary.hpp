@@ -3,7 +3,8 @@
 // (PredPasses), which ordinal_predict.hip's own kernel uses too, and the
 // summary kernel of the one-mean families with its host side (predict.hip:
 // linear, logit, Poisson; negbin_predict.hip: negative binomial;
-// weibull_predict.hip: Weibull; probit_predict.hip: probit).  Kernels and
+// weibull_predict.hip: Weibull; probit_predict.hip: probit;
+// student_t_predict.hip: Student-t).  Kernels and
 // drivers are static: a translation unit holds the instantiations it launches
 // and no others.  predict.hip describes the method.
 //
@@ -57,6 +58,9 @@ constexpr int PRED_WEIBULL = 4;
 // The probit model's, likewise (probit_predict.hip): mu = Phi(eta),
 // ll = log Phi(+-eta).
 constexpr int PRED_PROBIT = 5;
+// The Student-t regression model's, likewise (student_t_predict.hip): mu = eta,
+// ll = the full t-density at the draw's tau and the model's df.
+constexpr int PRED_STUDENT_T = 6;
 
 struct PredArgs {
   int64_t n;
@@ -64,9 +68,12 @@ struct PredArgs {
   int kn;           // draws of this pass
   int64_t n_draw;   // all draws: the last pass writes the results
   const double* eta;      // [kn][n]
-  const double* tau;      // [n_draw] linear: obs_prec; Weibull: the shape k
-  const double* hlt;      // [n_draw] linear: 0.5 log(obs_prec); Weibull: log k
-  const double* gtab;     // [n_draw][NEGBIN_GTAB] negbin: negbin_gtab(r)
+  const double* tau;      // [n_draw] linear, Student-t: obs_prec; Weibull: the
+                          // shape k
+  const double* hlt;      // [n_draw] linear: 0.5 log(obs_prec); Weibull: log k;
+                          // Student-t: the draw's normalising constant
+  const double* gtab;     // [n_draw][NEGBIN_GTAB] negbin: negbin_gtab(r);
+                          // Student-t: [2] = (df + 1) / 2, df
   const double* offset;   // [n] or null
   const double* y;        // [n]   (SCORE)
   const double* m;        // [n] or null (logit, SCORE); Weibull: log t (SCORE)
@@ -109,6 +116,13 @@ __device__ __forceinline__ void pred_terms(double eta, double y, double m,
     // draw's k and log k; the predicted quantity is the median survival time
     *mu = weibull_median(eta, tau);
     if (SCORE) *ll = weibull_full(eta, y, m, tau, hlt);
+  } else if (FAMILY == PRED_STUDENT_T) {
+    // hlt = lgamma((df+1)/2) - lgamma(df/2) + 1/2 log(tau / (df pi))
+    *mu = eta;
+    if (SCORE) {
+      const double r = y - eta;
+      *ll = hlt - gtab[0] * log1p(tau * (r * r) / gtab[1]);
+    }
   } else if (FAMILY == PRED_PROBIT) {
     // Phi(eta) = erfc(-eta / sqrt 2) / 2: absolute error ~1e-16, what a mean
     // needs; the score is the log of the outcome's own tail
@@ -223,7 +237,8 @@ static __global__ __launch_bounds__(PRED_BLOCK) void predict_summary_kernel(
     if (has_off) eta += off;
     const double k = (double)(a.k0 + d + 1);
     double tau = 0., hlt = 0.;
-    if ((FAMILY == BBX_PRED_LINEAR && SCORE) || FAMILY == PRED_WEIBULL) {
+    if (((FAMILY == BBX_PRED_LINEAR || FAMILY == PRED_STUDENT_T) && SCORE) ||
+        FAMILY == PRED_WEIBULL) {
       tau = a.tau[a.k0 + d];
       hlt = a.hlt[a.k0 + d];
     }
@@ -231,7 +246,8 @@ static __global__ __launch_bounds__(PRED_BLOCK) void predict_summary_kernel(
     const double* gtab =
         FAMILY == PRED_NEGBIN && SCORE
             ? a.gtab + (a.k0 + d) * (int64_t)NEGBIN_GTAB
-            : nullptr;
+        : FAMILY == PRED_STUDENT_T && SCORE ? a.gtab
+                                            : nullptr;
     pred_terms<FAMILY, SCORE>(eta, y, m, c, has_c, tau, hlt, gtab, &mu, &ll);
     if (a.mu_draws) a.mu_draws[(int64_t)d * n + i] = mu;
     mom.push(mu, k);
@@ -353,6 +369,7 @@ struct PredCall {
   const double *coef, *obs_prec, *offset, *y, *n_trial, *ll_const;
   int draws_per_pass;
   double *mean, *sd, *lpd, *ll_mean, *ll_var, *mu_draws;
+  double df = 0.;   // Student-t: the degrees of freedom
 };
 
 // `launch(stream, score, args)` starts the summary kernel of q.family: the
@@ -365,6 +382,7 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
   const bool linear = q.family == BBX_PRED_LINEAR;
   const bool negbin = q.family == PRED_NEGBIN;
   const bool weibull = q.family == PRED_WEIBULL;
+  const bool student_t = q.family == PRED_STUDENT_T;
 
   PredPasses p;
   DevMem d_state, d_out;
@@ -394,6 +412,17 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
       tau_host[S + d] = log(q.obs_prec[d]);
     }
   }
+  if (student_t && score) {
+    // per draw tau and the density's constant, then (df + 1) / 2 and df
+    tau_host.resize(2 * (size_t)S + 2);
+    const double lg = std::lgamma((q.df + 1.) / 2.) - std::lgamma(q.df / 2.);
+    for (int64_t d = 0; d < S; ++d) {
+      tau_host[d] = q.obs_prec[d];
+      tau_host[S + d] = lg + 0.5 * log(q.obs_prec[d] / (q.df * M_PI));
+    }
+    tau_host[2 * S] = (q.df + 1.) / 2.;
+    tau_host[2 * S + 1] = q.df;
+  }
   const double* tab = nullptr;
   if (!tau_host.empty())
     BBX_TRY(p.upload(tau_host.data(), d8 * tau_host.size(), &tab));
@@ -402,9 +431,10 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
   a.n = n;
   a.n_draw = S;
   a.eta = p.d_eta.as<const double>();
-  if (linear || weibull) {
+  if (linear || weibull || student_t) {
     a.tau = tab;
     a.hlt = tab ? tab + S : nullptr;
+    if (student_t) a.gtab = tab ? tab + 2 * S : nullptr;
   } else {
     a.gtab = tab;
   }

@@ -70,15 +70,6 @@ __global__ __launch_bounds__(256) void chain_probit_kernel(
   }
 }
 
-// The `count` (<= ROW_GRID) block sums of z folded onto the NPART slots
-// launch_tdot re-adds: slot t takes blocks t, t + NPART, ... in that order.
-__global__ __launch_bounds__(NPART) void probit_sumw_fold_kernel(
-    const double* __restrict__ z_part, int count, double* __restrict__ part) {
-  double acc = 0.;
-  for (int k = threadIdx.x; k < count; k += NPART) acc += z_part[k];
-  part[threadIdx.x] = acc;
-}
-
 __global__ __launch_bounds__(256) void dev_truncated_normal_kernel(
     int64_t n, uint64_t seed, const double* __restrict__ psi,
     const unsigned char* __restrict__ positive, double* __restrict__ out) {
@@ -103,9 +94,8 @@ int launch_chain_probit(bbx_chain* c, uint64_t stream, int* row_blocks) {
   BBX_LAUNCH(chain_probit_kernel, dim3(rg), dim3(256), 0, h->stream, h->n,
              c->seed, stream, c->outcome.as<double>(), c->psi.as<double>(),
              c->latent.as<double>(), rp, rp + ROW_GRID);
-  BBX_LAUNCH(probit_sumw_fold_kernel, dim3(1), dim3(NPART), 0, h->stream,
-             rp + ROW_GRID, rg, part_slot(h, PS_SUMW));
   BBX_HIP(hipGetLastError());
+  BBX_TRY(launch_sumw_fold(h, rp + ROW_GRID, rg));
   if (row_blocks) *row_blocks = rg;
   return BBX_OK;
 }

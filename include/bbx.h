@@ -70,6 +70,10 @@ extern "C" {
  *      bbx_design_predictive_summary_probit; in libbbx_hostrng
  *      bbx_replay_truncated_normal and bbx_host_log_norm_cdf).  A new model code
  *      and new symbols and nothing else, so the number stays 113.
+ *      + the Student-t regression model on the device chain
+ *      (BBX_MODEL_STUDENT_T, bbx_chain_set_df, bbx_chain_get_df,
+ *      bbx_design_predictive_summary_student_t; bbx_chain_get_latent serves
+ *      it too).  Again a new model code and new symbols: the number stays 113.
  * 112: + the Cox model in counting-process form (bbx_coxcp_*): delayed entry
  *      and (start, stop] rows, with the trajectory and the No-U-Turn sampler
  *      of the Cox handle.
@@ -123,6 +127,9 @@ extern "C" {
 #define BBX_MODEL_LOGIT 1
 #define BBX_MODEL_PROBIT 2 /* Albert-Chib latents: no counterpart in the
                               reference; see bbx_chain_create                   */
+#define BBX_MODEL_STUDENT_T 3 /* linear regression with Student-t errors as a
+                                 scale mixture of normals: no counterpart in
+                                 the reference; see bbx_chain_create            */
 
 /* global-scale update of a chain: SamplerOptions.gscale_update
  * (gibbs_util.py:9-31; bayesbridge.py:412-448) */
@@ -592,6 +599,31 @@ int bbx_hbm_probe(int device, int64_t bytes, int reps, double* read_gbps,
  * of iteration `iteration - 1`, so a chain resumed from (coef, lscale, gscale,
  * iteration, summaries) continues bit for bit.  bbx_batch_create refuses
  * probit chains.
+ *
+ * BBX_MODEL_STUDENT_T (no counterpart in the reference): y_i = psi_i + e_i with
+ * e_i sqrt(tau) ~ Student-t on nu degrees of freedom, nu fixed (4 at creation:
+ * bbx_chain_set_df), written as y_i | omega_i ~ N(psi_i, 1 / (tau omega_i)),
+ * omega_i ~ Gamma(nu/2, rate nu/2).  outcome[n] must be finite (BBX_ERR_INVALID
+ * names the first offending row) and n_trial NULL.  After the coefficient draw
+ * of iteration `it`, with r = y - psi:
+ *   tau     = gamma_draw(Philox(seed, 6 | it << 8, 0), n/2) / (S/2),
+ *             S = sum_i omega_i r_i^2 with the omega of the iteration before;
+ *   omega_i = gamma_draw(Philox(seed, 8 | it << 8, i), (nu+1)/2)
+ *             / ((nu + tau r_i^2)/2) with the new tau;
+ *   beta    | tau, omega is the Gaussian conditional at the per-row precision
+ *             tau omega_i, drawn by any of the three samplers.
+ * obs_prec is the scalar tau (length 1, as for the linear model) in set_state,
+ * get_state and the runs; bbx_chain_get_latent returns omega.  The
+ * log-likelihood is the marginal t-density, sum_i [1/2 log tau - (nu+1)/2
+ * log1p(tau r_i^2 / nu)] + n [lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu/2)]
+ * (the linear model's convention: -n/2 log 2 pi dropped).  bbx_chain_set_state,
+ * bbx_chain_set_df and bbx_chain_init_obs_prec (which first sets tau =
+ * 1 / mean(r^2)) recompute psi, omega, X~^T (tau omega y) and the
+ * log-likelihood from (coef, tau) with the stream of iteration `iteration -
+ * 1`, without redrawing tau, so a chain resumed from (coef, obs_prec, lscale,
+ * gscale, iteration, summaries, seed, nu) continues bit for bit.  A psi_i that
+ * is not finite gives a NaN omega_i and log-likelihood.  bbx_batch_create
+ * refuses student_t chains.
  */
 int bbx_chain_create(bbx_design* design, int model, const double* outcome,
                      const double* n_trial, int n_unshrunk,
@@ -654,12 +686,20 @@ int bbx_chain_eta(bbx_chain* c, int64_t iteration, double* eta1, double* eta2);
 /* Log-likelihood and log-posterior of the state left by the last iteration
  * (bayesbridge.py:480-511), host pointers, either may be NULL. */
 int bbx_chain_get_logp(bbx_chain* c, double* loglik, double* logp);
-/* The n latents of a BBX_MODEL_PROBIT chain's current state (host pointer);
+/* The n latents of a BBX_MODEL_PROBIT chain's current state, or the n mixing
+ * weights omega of a BBX_MODEL_STUDENT_T chain's (host pointer);
  * BBX_ERR_INVALID for a chain of another model or a NULL out. */
 int bbx_chain_get_latent(bbx_chain* c, double* out);
+/* The degrees of freedom nu of a BBX_MODEL_STUDENT_T chain (4 at creation).
+ * Setting them recomputes the weights, X~^T kappa and the log-likelihood of
+ * the current (coef, tau) under the new nu, as bbx_chain_set_state does.
+ * BBX_ERR_INVALID for a chain of another model, a df that is not finite and
+ * positive, a NULL df pointer. */
+int bbx_chain_set_df(bbx_chain* c, double df);
+int bbx_chain_get_df(bbx_chain* c, double* df);
 /* The P-vector the next draw's right-hand side is scaled from: X~^T kappa
- * (logit), X~^T y (linear), X~^T z of the current latents (probit); host
- * pointer.  For the tests that pin it to the latents. */
+ * (logit), X~^T y (linear), X~^T z of the current latents (probit), X~^T (tau
+ * omega y) of the current weights (student_t); host pointer.  For the tests that pin it to the latents. */
 int bbx_chain_get_zbase(bbx_chain* c, double* out);
 
 /*
@@ -1353,6 +1393,28 @@ int bbx_design_predictive_summary_probit(
     const double* offset, const double* y, const double* ll_const,
     int draws_per_pass, double* mean, double* sd, double* lpd, double* ll_mean,
     double* ll_var, double* mu_draws);
+
+/* The same summary for the Student-t regression model
+ * (csrc/student_t_predict.hip), from draws of the coefficients and of the
+ * precision tau, obs_prec[n_draw], at the fixed degrees of freedom df.  With
+ * eta = X~ coef_s + offset and r = y - eta, per row and draw
+ *
+ *   mu = eta   (E[y | x] for df > 1)
+ *   ll = lgamma((df+1)/2) - lgamma(df/2) + 1/2 log(tau_s / (df pi))
+ *        - (df+1)/2 log1p(tau_s r^2 / df) + c
+ *
+ * the FULL t-density.  y[n] finite or NULL; without it lpd, ll_mean, ll_var and
+ * obs_prec may be NULL.  Passes, synchronisation and outputs are those of
+ * bbx_design_predictive_summary.  BBX_ERR_INVALID for a NULL or destroyed
+ * design, n_draw < 1 (< 2 with an outcome), a NULL coef, mean or sd, a df that
+ * is not finite and positive, an outcome with a NULL obs_prec, lpd, ll_mean or
+ * ll_var, an obs_prec[d] that is not finite and positive, a y[i] that is not
+ * finite, draws_per_pass < 0: checked before anything touches the device. */
+int bbx_design_predictive_summary_student_t(
+    bbx_design* design, int64_t n_draw, double df, const double* coef,
+    const double* obs_prec, const double* offset, const double* y,
+    const double* ll_const, int draws_per_pass, double* mean, double* sd,
+    double* lpd, double* ll_mean, double* ll_var, double* mu_draws);
 
 /* The summary of the proportional-odds model (csrc/ordinal_predict.hip: a
  * kernel of its own), from draws of the coefficients, coef[n_draw][P], and of
