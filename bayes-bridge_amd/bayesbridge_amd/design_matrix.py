@@ -201,7 +201,10 @@ class HipDesignMatrix():
         """None, or how a mixed design was split by value in the tiled format:
         {'ones_nnz', 'rest_nnz', 'dense_nnz', 'dense_cols'} (entries equal to
         1.0 in the value-free layout, a dense block for columns full of other
-        values, the rest in the valued layout)."""
+        values, the rest in the valued layout), and the form the last products
+        took: 'dot_form' in (None, 'epi', 'fused_wave<gw>', 'fused_wg<g>',
+        'separate', 'separate_slabs'), 'tdot_form' in (None, 'dw_reused',
+        'tdot_separate') -- see bbx_design_hybrid_forms in bbx.h."""
         from ctypes import c_int
         hy, kd = c_int(), c_int()
         a, b, c = c_int64(), c_int64(), c_int64()
@@ -209,8 +212,16 @@ class HipDesignMatrix():
             self._h, byref(hy), byref(a), byref(b), byref(c), byref(kd)))
         if not hy.value:
             return None
+        df, dw, tf = c_int(), c_int(), c_int()
+        _lib.check(self._lib.bbx_design_hybrid_forms(
+            self._h, byref(df), byref(dw), byref(tf)))
+        dot_form = (None, 'epi', 'fused_wave%d' % dw.value,
+                    'fused_wg%d' % dw.value, 'separate',
+                    'separate_slabs')[df.value]
+        tdot_form = (None, 'dw_reused', 'tdot_separate')[tf.value]
         return dict(ones_nnz=a.value, rest_nnz=b.value, dense_nnz=c.value,
-                    dense_cols=kd.value)
+                    dense_cols=kd.value, dot_form=dot_form,
+                    tdot_form=tdot_form)
 
     # -- the operator -------------------------------------------------------
     def dot(self, v):

@@ -1398,6 +1398,17 @@ int bbx_design_hybrid_info(const bbx_design* h, int* is_hybrid,
   return BBX_OK;
 }
 
+int bbx_design_hybrid_forms(const bbx_design* h, int* dot_form, int* dot_width,
+                            int* tdot_form) {
+  BBX_TRY(check_handle(h));
+  if (dot_form) *dot_form = BBX_HYB_DOT_NONE;
+  if (dot_width) *dot_width = 0;
+  if (tdot_form) *tdot_form = BBX_HYB_TDOT_NONE;
+  if (h->sparse && h->format == BBX_FORMAT_TILED)
+    tiled_hybrid_forms(h, dot_form, dot_width, tdot_form);
+  return BBX_OK;
+}
+
 static int matvec_bytes_impl(const bbx_design* h, bool timed_only,
                              int64_t* dot_bytes, int64_t* tdot_bytes) {
   BBX_TRY(check_handle(h));

@@ -553,6 +553,8 @@ int64_t tiled_storage_bytes(const bbx_design* h);
 // 1 when the design is stored split by value (HybridParts), else 0
 int tiled_hybrid_info(const bbx_design* h, int64_t* ones_nnz,
                       int64_t* rest_nnz, int64_t* dense_nnz, int* kd);
+void tiled_hybrid_forms(const bbx_design* h, int* dot_form, int* dot_width,
+                        int* tdot_form);
 int tiled_describe(const bbx_design* h, int which, int* W, int* n_block,
                    int* PR, int* G, int64_t* n_quad, int64_t* n_slice,
                    int* packed = nullptr);

@@ -122,7 +122,8 @@ struct TiledPair {
 
 constexpr int HYB_TDOT_CHUNKS = 256;  // row chunks of the dense block's D^T w
 constexpr int HYB_FUSED_WAVE_KD = 1024; // widest dense block of the wave-per-row kernel
-constexpr int HYB_FUSED_MAX_KD = 8192;  // ... of the workgroup-per-row-block kernel (= the split's cap)
+// (HYB_FUSED_MAX_KD = 8192, tiled_layout.hpp: ... of the workgroup-per-row-block
+// kernel = the split's cap)
 
 // Mixed designs: X = B + D + S.
 //
@@ -164,6 +165,9 @@ struct HybridParts {
   int dw_chunks = 0;
   DevMem slab;           // double[(G_B + G_S + 1)][p]
   int n_slab = 0;
+  // which form the last X~ v / X~^T w took (bbx_design_hybrid_forms; written
+  // at the launch sites, read by tests)
+  int dot_form = 0, dot_width = 0, tdot_form = 0;
   // batches (K = 2, 4 right-hand sides) of a design WITHOUT a valued rest keep
   // the split: B in its K-layout (bbx_design::tiled_k), D shared
   bool split_k[2] = {false, false};   // slot K == 2, K == 4
@@ -1318,39 +1322,6 @@ static int build_tiled_pair(bbx_design* h, int K, void** slot) {
   return check_lds(tp);
 }
 
-// Rows of one orientation split by value (see HybridParts): the entries equal
-// to 1.0, and the others outside the dense columns.  `col_is_dense` is indexed
-// by the ORIGINAL column id: the row id for the transposed orientation.
-static void split_rows(int64_t R, const CsrRef& c, bool transpose,
-                       const std::vector<uint8_t>& col_is_dense, HostCsr* ones,
-                       HostCsr* rest) {
-  ones->rowptr.assign((size_t)R + 1, 0);
-  rest->rowptr.assign((size_t)R + 1, 0);
-  ones->colidx.clear();
-  rest->colidx.clear();
-  ones->vals.clear();
-  rest->vals.clear();
-  for (int64_t r = 0; r < R; ++r) {
-    for (int64_t k = c.rowptr[(size_t)r]; k < c.rowptr[(size_t)r + 1]; ++k) {
-      const double v = c.vals[(size_t)k];
-      const int32_t j = c.colidx[(size_t)k];
-      if (v == 1.0) {
-        ones->colidx.push_back(j);
-      } else if (!col_is_dense[(size_t)(transpose ? r : j)]) {
-        rest->colidx.push_back(j);
-        rest->vals.push_back(v);
-      }
-    }
-    ones->rowptr[(size_t)r + 1] = (int64_t)ones->colidx.size();
-    rest->rowptr[(size_t)r + 1] = (int64_t)rest->colidx.size();
-  }
-  if (ones->colidx.empty()) ones->colidx.push_back(0);
-  if (rest->colidx.empty()) {
-    rest->colidx.push_back(0);
-    rest->vals.push_back(0.);
-  }
-}
-
 // Decides whether the design is worth splitting and builds the parts.
 // Returns BBX_OK with h->hybrid set, or 1 when the plain valued layout is the
 // right one (nothing built).
@@ -1360,46 +1331,15 @@ static int build_hybrid(bbx_design* h) {
   HostCsr store;
   CsrRef cx;
   BBX_TRY(fetch_host_csr(h, false, &store, &cx));
-  // per column: entries equal to 1.0 and other entries
-  std::vector<int64_t> c_one((size_t)p, 0), c_val((size_t)p, 0);
-  for (int64_t k = 0; k < nnz; ++k)
-    (cx.vals[(size_t)k] == 1.0 ? c_one : c_val)[(size_t)cx.colidx[(size_t)k]] += 1;
-  // a dense column: at least half of its rows hold a value other than 1.0 (a
-  // continuous covariate; it is stored as n doubles, so a sparser column costs
-  // more in the block than in the valued layout's 10 bytes per entry)
-  const int64_t dense_min = std::max<int64_t>(n / 2, 1);
-  std::vector<uint8_t> is_dense((size_t)p, 0);
-  std::vector<int32_t> dense_cols;
-  int64_t ones_nnz = 0, dense_nnz = 0;
-  for (int64_t j = 0; j < p; ++j) {
-    ones_nnz += c_one[(size_t)j];
-    if (c_val[(size_t)j] >= dense_min) {
-      is_dense[(size_t)j] = 1;
-      dense_cols.push_back((int32_t)j);
-      dense_nnz += c_val[(size_t)j];
-    }
-  }
-  // a dense block beyond 32 GB (it is held twice: by column for the separate
-  // products, by row for the operator's single pass) or wider than the
-  // single-pass kernels reach (8192 columns: four column pairs per thread)
-  // stays in the valued tiled part
-  if ((double)dense_cols.size() * (double)n * 8. > 32e9 ||
-      dense_cols.size() > (size_t)HYB_FUSED_MAX_KD) {
-    std::fill(is_dense.begin(), is_dense.end(), 0);
-    dense_cols.clear();
-    dense_nnz = 0;
-  }
-  const int64_t rest_nnz = nnz - ones_nnz - dense_nnz;
-  // worth it when the value-free part and the dense block carry most entries
-  // (a design without dense columns: when at least a quarter of the entries
-  // are ones; with a dense block the block itself is the cheap part -- 1 000
-  // Gaussian columns next to 9 000 binary ones, tests/helper.py:13 at scale,
-  // are 92 % dense entries and still belong here)
-  if (2 * (ones_nnz + dense_nnz) < nnz) return 1;
-  // ... and outside the dense block at least a quarter of the entries are ones
-  // (what the value-free layout is for; also keeps designs without a single
-  // 1.0 in the plain valued layout)
-  if (ones_nnz == 0 || 4 * ones_nnz < nnz - dense_nnz) return 1;
+  // the decision (dense columns, the two "worth it" inequalities) and the row
+  // split are host code shared with the CPU tests: tiled_layout.cpp
+  HybridPlan plan;
+  plan_hybrid(n, p, nnz, cx.colidx, cx.vals, &plan);
+  if (!plan.split) return 1;
+  const std::vector<uint8_t>& is_dense = plan.is_dense;
+  const std::vector<int32_t>& dense_cols = plan.dense_cols;
+  const int64_t ones_nnz = plan.ones_nnz, rest_nnz = plan.rest_nnz,
+                dense_nnz = plan.dense_nnz;
   HybridParts* hp = new (std::nothrow) HybridParts();
   if (!hp) return fail(BBX_ERR_INVALID, "out of host memory");
   h->hybrid = hp;  // owned by the handle (destroy_tiled)
@@ -1408,7 +1348,7 @@ static int build_hybrid(bbx_design* h) {
   hp->dense_nnz = dense_nnz;
   hp->kd = (int)dense_cols.size();
   HostCsr ones, rest;
-  split_rows(n, cx, false, is_dense, &ones, &rest);
+  split_rows(n, cx.rowptr, cx.colidx, cx.vals, false, is_dense, &ones, &rest);
   BBX_TRY(build_one(hp->ones.x, n, p, ones_nnz, ones.rowptr.data(),
                     ones.colidx.data(), nullptr, false, 1));
   if (rest_nnz > 0)
@@ -1416,16 +1356,8 @@ static int build_hybrid(bbx_design* h) {
                       rest.colidx.data(), rest.vals.data(), false, 1));
   if (hp->kd > 0) {
     // D column-major: D[slot][i] = the non-one entry of row i in that column
-    std::vector<int32_t> slot_of((size_t)p, -1);
-    for (int s_ = 0; s_ < hp->kd; ++s_) slot_of[(size_t)dense_cols[(size_t)s_]] = s_;
-    std::vector<double> D((size_t)hp->kd * (size_t)n, 0.);
-    for (int64_t r = 0; r < n; ++r)
-      for (int64_t k = cx.rowptr[(size_t)r]; k < cx.rowptr[(size_t)r + 1]; ++k) {
-        const int32_t s_ = slot_of[(size_t)cx.colidx[(size_t)k]];
-        // (duplicates of one (row, column) add up, like everywhere else)
-        if (s_ >= 0 && cx.vals[(size_t)k] != 1.0)
-          D[(size_t)s_ * (size_t)n + (size_t)r] += cx.vals[(size_t)k];
-      }
+    std::vector<double> D;
+    hybrid_dense_block(n, p, cx.rowptr, cx.colidx, cx.vals, dense_cols, &D);
     BBX_TRY(upload(hp->D, D.data(), D.size() * sizeof(double)));
     if (hp->kd > DENSE_EPI_MAX && hp->kd <= HYB_FUSED_MAX_KD) {
       // row-major copy for the single pass of an operator application
@@ -1444,7 +1376,7 @@ static int build_hybrid(bbx_design* h) {
   {  // transposed orientation of B and S
     CsrRef ct;
     BBX_TRY(fetch_host_csr(h, true, &store, &ct));
-    split_rows(p, ct, true, is_dense, &ones, &rest);
+    split_rows(p, ct.rowptr, ct.colidx, ct.vals, true, is_dense, &ones, &rest);
     BBX_TRY(build_one(hp->ones.xt, p, n, ones_nnz, ones.rowptr.data(),
                       ones.colidx.data(), nullptr, true, 1));
     if (rest_nnz > 0)
@@ -1519,7 +1451,7 @@ static int build_split_k(bbx_design* h, int K, void** slot) {
   HostCsr store, ones, rest;
   CsrRef c;
   BBX_TRY(fetch_host_csr(h, false, &store, &c));
-  split_rows(n, c, false, is_dense, &ones, &rest);
+  split_rows(n, c.rowptr, c.colidx, c.vals, false, is_dense, &ones, &rest);
   BBX_TRY(build_one(tp->x, n, p, hp->ones_nnz, ones.rowptr.data(),
                     ones.colidx.data(), nullptr, false, K));
   if (hp->rest_nnz > 0) {
@@ -1530,7 +1462,7 @@ static int build_split_k(bbx_design* h, int K, void** slot) {
                       rest.colidx.data(), rest.vals.data(), false, K));
   }
   BBX_TRY(fetch_host_csr(h, true, &store, &c));
-  split_rows(p, c, true, is_dense, &ones, &rest);
+  split_rows(p, c.rowptr, c.colidx, c.vals, true, is_dense, &ones, &rest);
   BBX_TRY(build_one(tp->xt, p, n, hp->ones_nnz, ones.rowptr.data(),
                     ones.colidx.data(), nullptr, true, K));
   int G_rest = 0;
@@ -2194,6 +2126,8 @@ static int launch_dot_hybrid(bbx_design* h, const double* d_v,
       hp->dw_for = d_t;
       hp->dw_serial = h->operator_serial;
       hp->dw_chunks = mb.n_panel * mb.G;
+      hp->dot_form = BBX_HYB_DOT_EPI;
+      hp->dot_width = 0;
       return BBX_OK;
     }
   }
@@ -2234,6 +2168,8 @@ static int launch_dot_hybrid(bbx_design* h, const double* d_v,
         else BBX_HYB_WG(4, 1);
 #undef BBX_HYB_WG
         BBX_HIP(hipGetLastError());
+        hp->dot_form = BBX_HYB_DOT_FUSED_WG;
+        hp->dot_width = ldp <= 1024 ? 1 : ldp <= 2048 ? 2 : 4;
         hp->dw_for = d_t;
         hp->dw_serial = h->operator_serial;
         hp->dw_chunks = NPART;
@@ -2266,6 +2202,8 @@ static int launch_dot_hybrid(bbx_design* h, const double* d_v,
       else BBX_HYB_FUSED(8, 1, 512);
 #undef BBX_HYB_FUSED
       BBX_HIP(hipGetLastError());
+      hp->dot_form = BBX_HYB_DOT_FUSED_WAVE;
+      hp->dot_width = gw;
       hp->dw_for = d_t;
       hp->dw_serial = h->operator_serial;
       hp->dw_chunks = NPART;
@@ -2298,6 +2236,8 @@ static int launch_dot_hybrid(bbx_design* h, const double* d_v,
                        part_slot(h, PS_C), x0, d_rowscale, d_t,
                        hp->addend.as<double>());
     BBX_HIP(hipGetLastError());
+    hp->dot_form = BBX_HYB_DOT_SEPARATE_SLABS;
+    hp->dot_width = 0;
     return timer_end(h, 0);
   }
   double* fused = nullptr;
@@ -2313,6 +2253,8 @@ static int launch_dot_hybrid(bbx_design* h, const double* d_v,
   BBX_TRY(launch_tiled(h, mb, x, part_slot(h, PS_C), x0, d_rowscale, d_t,
                        nullptr, fused, nullptr, nullptr, twt_off, nullptr,
                        hp->addend.as<double>()));
+  hp->dot_form = BBX_HYB_DOT_SEPARATE;
+  hp->dot_width = 0;
   return timer_end(h, 0);
 }
 
@@ -2348,6 +2290,7 @@ static int launch_tdot_hybrid(bbx_design* h, const double* d_w,
                        slab + (size_t)at * (size_t)h->p, h->skip_flag);
     BBX_HIP(hipGetLastError());
     at += 1;
+    hp->tdot_form = BBX_HYB_TDOT_DW_REUSED;
   } else if (hp->kd > 0) {
     const int64_t n_task = (int64_t)hp->kd * HYB_TDOT_CHUNKS;
     BBX_LAUNCH(hyb_dense_tdot_kernel,
@@ -2361,6 +2304,9 @@ static int launch_tdot_hybrid(bbx_design* h, const double* d_w,
                        slab + (size_t)at * (size_t)h->p, h->skip_flag);
     BBX_HIP(hipGetLastError());
     at += 1;
+    hp->tdot_form = BBX_HYB_TDOT_SEPARATE;
+  } else {
+    hp->tdot_form = BBX_HYB_TDOT_SEPARATE;   // (no dense block)
   }
   hp->dw_for = nullptr;
   BBX_TRY(timer_end(h, 1));
@@ -2739,6 +2685,14 @@ int tiled_hybrid_info(const bbx_design* h, int64_t* ones_nnz,
   if (dense_nnz) *dense_nnz = hp ? hp->dense_nnz : 0;
   if (kd) *kd = hp ? hp->kd : 0;
   return hp ? 1 : 0;
+}
+
+void tiled_hybrid_forms(const bbx_design* h, int* dot_form, int* dot_width,
+                        int* tdot_form) {
+  const HybridParts* hp = static_cast<const HybridParts*>(h->hybrid);
+  if (dot_form) *dot_form = hp ? hp->dot_form : 0;
+  if (dot_width) *dot_width = hp ? hp->dot_width : 0;
+  if (tdot_form) *tdot_form = hp ? hp->tdot_form : 0;
 }
 
 int64_t tiled_storage_bytes(const bbx_design* h) {

@@ -1095,8 +1095,16 @@ int build_tiled_host(int64_t R, int64_t C, int64_t nnz, const int64_t* rowptr,
   }
   if (tot_ids / LANES >= ((size_t)1 << 32))
     return fail("matrix too large for the tiled format");
-  std::vector<Ids4> ids(tot_ids);
-  std::vector<double> vv(m.has_vals ? tot_ids * 8 : 0);
+  // One more step of one lane (16 bytes of ids, 64 of values, zero) behind the
+  // stream.  The ring's loads that only keep the wait counts uniform -- steps
+  // past a slice end, marker and END batches -- read the first 16 (64) bytes of
+  // the WORKGROUP's stretch (spmv_tiled.hip BBX_ISSUE), and the stretch of a
+  // workgroup without a single step at the end of the stream -- trailing empty
+  // rows of the last panel, an empty last column group -- begins where the
+  // stream ends: without the pad those loads read past both buffers (the value
+  // stream is n_quad * 4 KiB: past the last page of its allocation).
+  std::vector<Ids4> ids(tot_ids + 1);
+  std::vector<double> vv(m.has_vals ? (tot_ids + 1) * 8 : 0);
   std::vector<BatchDesc> descs(tot_descs);
   std::vector<int32_t> wave_desc((size_t)m.n_panel * m.G * TILE_WAVES, 0);
   std::vector<uint32_t> wg_quad0((size_t)m.n_panel * m.G, 0u);
@@ -1514,6 +1522,225 @@ void transpose_csr_host(int64_t R, int64_t C, const int64_t* rowptr,
   }
 }
 
+// ------------------------------------------------- mixed designs: the split
+
+void plan_hybrid(int64_t n, int64_t p, int64_t nnz, const int32_t* colidx,
+                 const double* vals, HybridPlan* plan) {
+  *plan = HybridPlan();
+  plan->is_dense.assign((size_t)p, 0);
+  // per column: entries equal to 1.0 and other entries
+  std::vector<int64_t> c_one((size_t)p, 0), c_val((size_t)p, 0);
+  for (int64_t k = 0; k < nnz; ++k)
+    (vals[(size_t)k] == 1.0 ? c_one : c_val)[(size_t)colidx[(size_t)k]] += 1;
+  // a dense column: at least half of its rows hold a value other than 1.0 (a
+  // continuous covariate; it is stored as n doubles, so a sparser column costs
+  // more in the block than in the valued layout's 10 bytes per entry)
+  const int64_t dense_min = std::max<int64_t>(n / 2, 1);
+  int64_t ones_nnz = 0, dense_nnz = 0;
+  for (int64_t j = 0; j < p; ++j) {
+    ones_nnz += c_one[(size_t)j];
+    if (c_val[(size_t)j] >= dense_min) {
+      plan->is_dense[(size_t)j] = 1;
+      plan->dense_cols.push_back((int32_t)j);
+      dense_nnz += c_val[(size_t)j];
+    }
+  }
+  // a dense block beyond 32 GB (it is held twice: by column for the separate
+  // products, by row for the operator's single pass) or wider than the
+  // single-pass kernels reach (8192 columns: four column pairs per thread)
+  // stays in the valued tiled part
+  if ((double)plan->dense_cols.size() * (double)n * 8. > 32e9 ||
+      plan->dense_cols.size() > (size_t)HYB_FUSED_MAX_KD) {
+    std::fill(plan->is_dense.begin(), plan->is_dense.end(), 0);
+    plan->dense_cols.clear();
+    dense_nnz = 0;
+  }
+  plan->ones_nnz = ones_nnz;
+  plan->dense_nnz = dense_nnz;
+  plan->rest_nnz = nnz - ones_nnz - dense_nnz;
+  // worth it when the value-free part and the dense block carry most entries
+  // (a design without dense columns: when at least a quarter of the entries
+  // are ones; with a dense block the block itself is the cheap part -- 1 000
+  // Gaussian columns next to 9 000 binary ones, tests/helper.py:13 at scale,
+  // are 92 % dense entries and still belong here)
+  plan->split = nnz > 0 && 2 * (ones_nnz + dense_nnz) >= nnz &&
+                // ... and outside the dense block at least a quarter of the
+                // entries are ones (what the value-free layout is for; also
+                // keeps designs without a single 1.0 in the plain valued layout)
+                ones_nnz > 0 && 4 * ones_nnz >= nnz - dense_nnz;
+}
+
+void split_rows(int64_t R, const int64_t* rowptr, const int32_t* colidx,
+                const double* vals, bool transpose,
+                const std::vector<uint8_t>& col_is_dense, HostCsr* ones,
+                HostCsr* rest) {
+  ones->rowptr.assign((size_t)R + 1, 0);
+  rest->rowptr.assign((size_t)R + 1, 0);
+  ones->colidx.clear();
+  rest->colidx.clear();
+  ones->vals.clear();
+  rest->vals.clear();
+  for (int64_t r = 0; r < R; ++r) {
+    for (int64_t k = rowptr[(size_t)r]; k < rowptr[(size_t)r + 1]; ++k) {
+      const double v = vals[(size_t)k];
+      const int32_t j = colidx[(size_t)k];
+      if (v == 1.0) {
+        ones->colidx.push_back(j);
+      } else if (!col_is_dense[(size_t)(transpose ? r : j)]) {
+        rest->colidx.push_back(j);
+        rest->vals.push_back(v);
+      }
+    }
+    ones->rowptr[(size_t)r + 1] = (int64_t)ones->colidx.size();
+    rest->rowptr[(size_t)r + 1] = (int64_t)rest->colidx.size();
+  }
+  if (ones->colidx.empty()) ones->colidx.push_back(0);
+  if (rest->colidx.empty()) {
+    rest->colidx.push_back(0);
+    rest->vals.push_back(0.);
+  }
+}
+
+void hybrid_dense_block(int64_t n, int64_t p, const int64_t* rowptr,
+                        const int32_t* colidx, const double* vals,
+                        const std::vector<int32_t>& dense_cols,
+                        std::vector<double>* D) {
+  const size_t kd = dense_cols.size();
+  std::vector<int32_t> slot_of((size_t)p, -1);
+  for (size_t s_ = 0; s_ < kd; ++s_) slot_of[(size_t)dense_cols[s_]] = (int32_t)s_;
+  D->assign(kd * (size_t)n, 0.);
+  for (int64_t r = 0; r < n; ++r)
+    for (int64_t k = rowptr[(size_t)r]; k < rowptr[(size_t)r + 1]; ++k) {
+      const int32_t s_ = slot_of[(size_t)colidx[(size_t)k]];
+      if (s_ >= 0 && vals[(size_t)k] != 1.0)
+        (*D)[(size_t)s_ * (size_t)n + (size_t)r] += vals[(size_t)k];
+    }
+}
+
+#ifdef BBX_EMU_SHADOW_LOADS
+namespace {
+
+// A heap block of exactly the bytes build_one uploads (upload(): 8 for an
+// empty array), so that AddressSanitizer sees the first byte past it.
+struct ExactCopy {
+  unsigned char* p = nullptr;
+  ExactCopy(const void* src, size_t bytes) {
+    p = new unsigned char[bytes > 0 ? bytes : 8]();
+    if (bytes > 0) memcpy(p, src, bytes);
+  }
+  ~ExactCopy() { delete[] p; }
+  ExactCopy(const ExactCopy&) = delete;
+  ExactCopy& operator=(const ExactCopy&) = delete;
+};
+
+unsigned char g_sink[4096];
+inline void touch(const unsigned char* base, size_t byte_off, size_t bytes) {
+  // (memcpy is intercepted: a checked read of exactly these bytes)
+  for (size_t o = 0; o < bytes; o += sizeof(g_sink))
+    memcpy(g_sink, base + byte_off + o, std::min(bytes - o, sizeof(g_sink)));
+}
+
+}  // namespace
+
+int64_t emulate_tiled_loads(const TiledHost& m, const double* x, bool wide) {
+  const ExactCopy ids(m.ids.data(), m.ids.size() * sizeof(Ids4));
+  const ExactCopy vv(m.vals.data(), m.vals.size() * sizeof(double));
+  const ExactCopy descs(m.descs.data(), m.descs.size() * sizeof(BatchDesc));
+  const ExactCopy wave_desc(m.wave_desc.data(), m.wave_desc.size() * sizeof(int32_t));
+  const ExactCopy wgq(m.wg_quad0.data(), m.wg_quad0.size() * sizeof(uint32_t));
+  const ExactCopy rowids(m.rowids.data(), m.rowids.size() * sizeof(uint32_t));
+  const ExactCopy folds(m.folds.data(), m.folds.size() * sizeof(FoldDesc));
+  const ExactCopy pfold(m.panel_fold.data(), m.panel_fold.size() * sizeof(int32_t));
+  const ExactCopy xc(x, (size_t)m.C * sizeof(double));
+  // (spmv_tiled.hip: RING = 2 with stored values, BBX_RING_BIN = 3 without;
+  // BATCH = 1 in both; one right-hand side)
+  const int RING = m.has_vals ? 2 : 3;
+  const int bpg = (m.n_block + m.G - 1) / m.G;
+  int64_t n_load = 0;
+  for (int bid = 0; bid < m.n_panel * m.G; ++bid) {
+    const int panel = bid / m.G, group = bid - panel * m.G;
+    touch(wgq.p, (size_t)bid * 4, 4);
+    const size_t wg_q0 = (size_t)m.wg_quad0[(size_t)bid];
+    const size_t ids_base = wg_q0 * LANES * 16, vals_base = wg_q0 * LANES * 64;
+    for (int wave = 0; wave < TILE_WAVES; ++wave) {
+      int64_t blk;
+      if (m.desc_stride > 0) {
+        blk = (int64_t)(bid * TILE_WAVES + wave) * m.desc_stride;
+      } else {
+        touch(wave_desc.p, (size_t)(bid * TILE_WAVES + wave) * 4, 4);
+        blk = m.wave_desc[(size_t)bid * TILE_WAVES + wave];
+      }
+      // dcur, dnxt: one descriptor per lane, two blocks
+      touch(descs.p, (size_t)blk * 16, LANES * 16);
+      touch(descs.p, (size_t)(blk + LANES) * 16, LANES * 16);
+      n_load += 2;
+      int pos = 0;
+      int cb = group * bpg - 1;
+      bool done = false;
+      // ring slot k holds the info of the batch issued into it
+      uint32_t info[3] = {0, 0, 0};
+      auto issue = [&](int k) {
+        touch(descs.p, (size_t)(blk + pos) * 16, 16);  // (held in registers: in range by the loads above)
+        const BatchDesc& d = m.descs[(size_t)(blk + pos)];
+        const int cntk = (int)(d.info & 15u);
+        // (the 64 lanes of a real step read consecutive bytes; in a dummy
+        // step every lane reads slot 0 of the workgroup's stretch)
+        const size_t slot0 = cntk > 0 ? (size_t)d.quad0 * LANES : 0;
+        const size_t lanes = cntk > 0 ? LANES : 1;
+        touch(ids.p, ids_base + slot0 * 16, lanes * 16);
+        if (m.has_vals) touch(vv.p, vals_base + slot0 * 64, lanes * 64);
+        touch(rowids.p, (cntk > 0 ? (size_t)d.row_slot : 0) * 4, lanes * 4);
+        n_load += m.has_vals ? 6 : 2;
+        info[k] = d.info;
+        if (!(d.info & BD_END)) {
+          ++pos;
+          if (pos == LANES) {
+            pos = 0;
+            blk += LANES;
+            touch(descs.p, (size_t)(blk + LANES) * 16, LANES * 16);
+            ++n_load;
+          }
+        }
+      };
+      for (int k = 0; k < RING; ++k) issue(k);
+      while (!done) {
+        for (int k = 0; k < RING && !done; ++k) {
+          const uint32_t inf = info[k];
+          if (inf & BD_END) {
+            done = true;
+            break;
+          }
+          if ((inf & BD_TILE_FIRST) && wave == 0) {
+            // the slice fill (every thread of the workgroup takes part: walked
+            // once per workgroup and tile, with wave 0's schedule)
+            ++cb;
+            const int64_t col0 = (int64_t)cb * m.W;
+            const int64_t cols_here = std::min<int64_t>(m.C - col0, m.W);
+            // both forms read x[col0 .. col0 + cols_here) and nothing else:
+            // pairs while j + 1 < cols_here and one 8-byte load for an odd
+            // tail, or one 8-byte load per column
+            if (cols_here > 0) {
+              const int64_t paired = wide ? cols_here / 2 * 2 : 0;
+              if (paired > 0) touch(xc.p, (size_t)col0 * 8, (size_t)paired * 8);
+              for (int64_t j = paired; j < cols_here; ++j)
+                touch(xc.p, (size_t)(col0 + j) * 8, 8);
+            }
+            ++n_load;
+          }
+          issue(k);
+        }
+      }
+    }
+    // epilogue: the folds of this panel
+    touch(pfold.p, (size_t)panel * 4, 4);
+    touch(pfold.p, (size_t)(panel + 1) * 4, 4);
+    for (int f = m.panel_fold[(size_t)panel]; f < m.panel_fold[(size_t)panel + 1]; ++f)
+      touch(folds.p, (size_t)f * sizeof(FoldDesc), sizeof(FoldDesc));
+  }
+  return n_load;
+}
+#endif
+
 }  // namespace bbx
 
 #ifdef BBX_LAYOUT_CAPI
@@ -1592,6 +1819,58 @@ int bbx_layout_transpose64(int64_t R, int64_t C, const int64_t* rowptr,
   if (nnz > 0) memcpy(t_colidx, t.colidx.data(), sizeof(int32_t) * (size_t)nnz);
   if (vals && t_vals && nnz > 0)
     memcpy(t_vals, t.vals.data(), sizeof(double) * (size_t)nnz);
+  return 0;
+}
+
+// The split of a mixed design (plan_hybrid): info[0..3] = split (0 / 1),
+// ones_nnz, dense_nnz, rest_nnz; info[4] = number of dense columns;
+// info[5] = HYB_FUSED_MAX_KD.  dense_cols (may be NULL) receives up to
+// dense_cap ascending column ids.  `colidx` / `vals`: the nnz stored entries in
+// any order.
+int bbx_layout_hybrid_plan(int64_t n, int64_t p, int64_t nnz,
+                           const int32_t* colidx, const double* vals,
+                           int64_t* info, int32_t* dense_cols,
+                           int64_t dense_cap) {
+  if (n < 0 || p < 0 || nnz < 0 || !info) return -1;
+  bbx::HybridPlan plan;
+  bbx::plan_hybrid(n, p, nnz, colidx, vals, &plan);
+  info[0] = plan.split ? 1 : 0;
+  info[1] = plan.ones_nnz;
+  info[2] = plan.dense_nnz;
+  info[3] = plan.rest_nnz;
+  info[4] = (int64_t)plan.dense_cols.size();
+  info[5] = bbx::HYB_FUSED_MAX_KD;
+  if (dense_cols)
+    for (int64_t k = 0; k < (int64_t)plan.dense_cols.size() && k < dense_cap; ++k)
+      dense_cols[k] = plan.dense_cols[(size_t)k];
+  return 0;
+}
+
+// One orientation split by value (split_rows) with the dense columns given as
+// a list of ORIGINAL column ids (`transpose` != 0: the CSR is that of X^T, its
+// rows are the columns of X).  ones_rowptr / rest_rowptr [R + 1]; ones_colidx,
+// rest_colidx, rest_vals hold nnz entries at most.  Returns 0.
+int bbx_layout_split_rows(int64_t R, int64_t n_cols_x, const int64_t* rowptr,
+                          const int32_t* colidx, const double* vals,
+                          int transpose, const int32_t* dense_cols, int64_t kd,
+                          int64_t* ones_rowptr, int32_t* ones_colidx,
+                          int64_t* rest_rowptr, int32_t* rest_colidx,
+                          double* rest_vals) {
+  std::vector<uint8_t> is_dense((size_t)n_cols_x, 0);
+  for (int64_t k = 0; k < kd; ++k) {
+    if (dense_cols[k] < 0 || dense_cols[k] >= n_cols_x) return -1;
+    is_dense[(size_t)dense_cols[k]] = 1;
+  }
+  bbx::HostCsr ones, rest;
+  bbx::split_rows(R, rowptr, colidx, vals, transpose != 0, is_dense, &ones, &rest);
+  memcpy(ones_rowptr, ones.rowptr.data(), sizeof(int64_t) * (size_t)(R + 1));
+  memcpy(rest_rowptr, rest.rowptr.data(), sizeof(int64_t) * (size_t)(R + 1));
+  const int64_t n1 = ones.rowptr[(size_t)R], n2 = rest.rowptr[(size_t)R];
+  if (n1 > 0) memcpy(ones_colidx, ones.colidx.data(), sizeof(int32_t) * (size_t)n1);
+  if (n2 > 0) {
+    memcpy(rest_colidx, rest.colidx.data(), sizeof(int32_t) * (size_t)n2);
+    memcpy(rest_vals, rest.vals.data(), sizeof(double) * (size_t)n2);
+  }
   return 0;
 }
 

@@ -128,8 +128,9 @@ struct TiledHost {
   int desc_stride = 0;  // > 0: wave k's schedule starts at k * desc_stride
   int n_extra = 0;      // extra accumulators per panel (row splitting)
   int split_T = 0;      // smallest split threshold used by any panel (0 = none)
-  std::vector<Ids4> ids;            // [n_quad * 64]
-  std::vector<double> vals;         // [n_quad * 64 * 8] when has_vals
+  std::vector<Ids4> ids;            // [n_quad * 64 + 1]: one zero entry behind the
+                                    // stream for the kernel's dummy loads
+  std::vector<double> vals;         // [(n_quad * 64 + 1) * 8] when has_vals
   std::vector<BatchDesc> descs;     // per-wave schedules (+ 2 blocks of END)
   std::vector<int32_t> wave_desc;   // [n_panel * G * TILE_WAVES]
   std::vector<uint32_t> wg_quad0;   // [n_panel * G] first step of each workgroup
@@ -181,6 +182,67 @@ struct HostCsr {
   std::vector<int32_t> colidx;
   std::vector<double> vals;
 };
+
+// ---- mixed designs: the split by value X = B + D + S (spmv_tiled.hip,
+// HybridParts).  The decision and the row split are plain host code, so they
+// live here, where the CPU tests and the sanitizer self-test reach them.
+constexpr int HYB_FUSED_MAX_KD = 8192;  // widest dense block (the one-pass kernels' reach)
+
+struct HybridPlan {
+  bool split = false;             // false: the plain valued layout is the right one
+  int64_t ones_nnz = 0;           // entries equal to 1.0            -> B
+  int64_t dense_nnz = 0;          // other entries of dense columns  -> D
+  int64_t rest_nnz = 0;           // what is left                    -> S
+  std::vector<int32_t> dense_cols;  // ascending
+  std::vector<uint8_t> is_dense;    // [p]
+};
+
+// Decides whether an n x p design of nnz stored entries (column ids and values
+// in any order) is worth splitting, and which columns are dense: a column with
+// at least max(n / 2, 1) stored values other than 1.0.  A dense block beyond
+// 32 GB or wider than HYB_FUSED_MAX_KD columns is given up (its entries stay
+// in S).  split = 2 (ones + dense) >= nnz  and  ones > 0  and
+// 4 ones >= nnz - dense.  The counts are filled either way.
+void plan_hybrid(int64_t n, int64_t p, int64_t nnz, const int32_t* colidx,
+                 const double* vals, HybridPlan* plan);
+
+// Rows of one orientation split by value: the entries equal to 1.0 (`ones`,
+// no values) and the others outside the dense columns (`rest`).  `col_is_dense`
+// is indexed by the ORIGINAL column id: the row id for the transposed
+// orientation.  Stored order is kept, duplicates stay separate entries.  An
+// empty part still holds one (unused) column id, so that .data() is valid.
+void split_rows(int64_t R, const int64_t* rowptr, const int32_t* colidx,
+                const double* vals, bool transpose,
+                const std::vector<uint8_t>& col_is_dense, HostCsr* ones,
+                HostCsr* rest);
+
+// D column-major, double[kd][n]: D[slot][i] = the entries other than 1.0 of
+// row i in dense column dense_cols[slot] (duplicates of one (row, column) add
+// up in stored order, like everywhere else).  CSR of X (rows = observations).
+void hybrid_dense_block(int64_t n, int64_t p, const int64_t* rowptr,
+                        const int32_t* colidx, const double* vals,
+                        const std::vector<int32_t>& dense_cols,
+                        std::vector<double>* D);
+
+#ifdef BBX_EMU_SHADOW_LOADS
+// Self-test builds only (make sanitize).  Walks the layout the way
+// tiled_spmv_kernel ISSUES its loads, including those that contribute nothing
+// to a sum: the ring's steps past a slice end and the loads of marker / END
+// batches (slot 0 of the workgroup's stretch of ids and vals), rowids[d_row +
+// lane] of all 64 lanes, the descriptor prefetch two blocks ahead, wg_quad0,
+// panel_fold[panel], [panel + 1], folds, and the slice fills of x (`wide`: the
+// 16-byte form, pairs while j + 1 < cols_here and one 8-byte load for an odd
+// tail; else one 8-byte load per column).  Every array is first copied into a
+// heap block of exactly the bytes build_one (spmv_tiled.hip) uploads -- 8 bytes
+// for an empty array -- and x into exactly C doubles: neither form of the fill
+// reads past x[C - 1]; the 16-byte form's only requirement is that x itself is
+// 16-byte aligned (W is a multiple of 64).  Under AddressSanitizer an
+// over-read of the kernel's index arithmetic then aborts the program.
+// This model is written from the kernel by hand: it is worth exactly as much
+// as that reading is careful, and it has to follow every change of BBX_ISSUE.
+// Returns the number of loads walked.
+int64_t emulate_tiled_loads(const TiledHost& m, const double* x, bool wide);
+#endif
 
 // Structure check of a host CSR whose index arrays are 64-bit (what SciPy holds
 // once a matrix has 2^31 or more stored entries, or was built from int64

@@ -328,6 +328,38 @@ int bbx_design_fused_operator_bytes(const bbx_design* h, int64_t* bytes);
 int bbx_design_hybrid_info(const bbx_design* h, int* is_hybrid,
                            int64_t* ones_nnz, int64_t* rest_nnz,
                            int64_t* dense_nnz, int* dense_cols);
+/* Which form the LAST X~ v and the last X~^T w of a mixed design took (written
+ * on the host where the kernels are launched; 0 before the first product, and
+ * for designs that are not mixed):
+ *   *dot_form   BBX_HYB_DOT_EPI             dense block in the value-free
+ *                                           kernel's epilogue (kd <= 8)
+ *               BBX_HYB_DOT_FUSED_WAVE      one pass over the row-major block,
+ *                                           a wave per row; *dot_width = column
+ *                                           pairs per lane (1, 2, 4, 8)
+ *               BBX_HYB_DOT_FUSED_WG        ... a workgroup per row block;
+ *                                           *dot_width = 1, 2, 4
+ *               BBX_HYB_DOT_SEPARATE        addend kernel, direct epilogue
+ *               BBX_HYB_DOT_SEPARATE_SLABS  addend kernel, slabs + finalize
+ *   *tdot_form  BBX_HYB_TDOT_DW_REUSED      D^T w from the partials the X~ v
+ *                                           kernel of the same operator
+ *                                           application left
+ *               BBX_HYB_TDOT_SEPARATE       its own pass over D (or no D)
+ * Any output pointer may be NULL. */
+enum {
+  BBX_HYB_DOT_NONE = 0,
+  BBX_HYB_DOT_EPI = 1,
+  BBX_HYB_DOT_FUSED_WAVE = 2,
+  BBX_HYB_DOT_FUSED_WG = 3,
+  BBX_HYB_DOT_SEPARATE = 4,
+  BBX_HYB_DOT_SEPARATE_SLABS = 5
+};
+enum {
+  BBX_HYB_TDOT_NONE = 0,
+  BBX_HYB_TDOT_DW_REUSED = 1,
+  BBX_HYB_TDOT_SEPARATE = 2
+};
+int bbx_design_hybrid_forms(const bbx_design* h, int* dot_form, int* dot_width,
+                            int* tdot_form);
 /* Geometry of the tiled format (BBX_FORMAT_TILED only): which = 0 for X, 1 for
  * X^T; W = column-block width, n_block = column blocks, PR = rows per panel,
  * G = column-block groups (partial-sum slabs), n_quad = 1024-byte steps (16
@@ -368,6 +400,12 @@ int bbx_design_tdot_dev(bbx_design* h, const double* d_w, double* d_out);
  * the single-pass kernel, so the entry lets a test compare it with the two
  * separate products.  Host pointers, synchronous; `_dev`: device pointers,
  * asynchronous on the handle's stream.
+ * Mixed designs: the one-pass forms of the dense block (bbx_design_hybrid_forms:
+ * EPI, FUSED_WAVE, FUSED_WG) need v + intercept 16-byte aligned.  The host
+ * entry stages v at the start of an aligned buffer, so a design WITH an
+ * intercept runs the separate kernels here (the CG loop, whose vectors start
+ * one element into their buffers, runs the one-pass forms); a design without
+ * one, or a `_dev` caller who passes d_v with d_v + 1 aligned, gets them.
  */
 int bbx_design_gram_matvec(bbx_design* h, const double* obs_prec,
                            const double* v, double* out);

@@ -142,3 +142,76 @@ class TiledLayoutCpu:
         meta = dict(zip(keys, (int(v) for v in info)))
         meta['gather_cycles'] = cyc.value
         return out, meta
+
+
+class MixedSplitCpu:
+    """ctypes front of the mixed-design entry points of libbbx_layout.so: the
+    split's decision (plan_hybrid) and the row split of one orientation
+    (split_rows), csrc/tiled_layout.cpp -- the code spmv_tiled.hip calls."""
+
+    def __init__(self):
+        from ctypes import c_int, c_int64, c_void_p
+        self.lib = TiledLayoutCpu().lib
+        self.lib.bbx_layout_hybrid_plan.argtypes = (
+            [c_int64] * 3 + [c_void_p] * 4 + [c_int64])
+        self.lib.bbx_layout_hybrid_plan.restype = c_int
+        self.lib.bbx_layout_split_rows.argtypes = (
+            [c_int64] * 2 + [c_void_p] * 3 + [c_int, c_void_p, c_int64]
+            + [c_void_p] * 5)
+        self.lib.bbx_layout_split_rows.restype = c_int
+
+    def plan(self, n, p, cols, vals):
+        """dict(split, ones_nnz, dense_nnz, rest_nnz, dense_cols, max_kd) for
+        the stored entries (column ids, values) of an n x p design."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        assert len(cols) == len(vals)
+        info = np.zeros(6, dtype=np.int64)
+        dense = np.full(max(p, 1), -1, dtype=np.int32)
+        st = self.lib.bbx_layout_hybrid_plan(
+            n, p, len(cols), cols.ctypes.data, vals.ctypes.data,
+            info.ctypes.data, dense.ctypes.data, len(dense))
+        assert st == 0
+        return dict(split=bool(info[0]), ones_nnz=int(info[1]),
+                    dense_nnz=int(info[2]), rest_nnz=int(info[3]),
+                    dense_cols=[int(j) for j in dense[:info[4]]],
+                    max_kd=int(info[5]))
+
+    def split(self, A, dense_cols, transpose, n_cols_x):
+        """(B, S) as CSR matrices of A's shape: A is the CSR of X
+        (transpose=False) or of X^T (True), dense_cols the dense columns of
+        X, n_cols_x the number of columns of X."""
+        R, C = A.shape
+        indptr = np.ascontiguousarray(A.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(A.indices, dtype=np.int32)
+        data = np.ascontiguousarray(A.data, dtype=np.float64)
+        dc = np.ascontiguousarray(dense_cols, dtype=np.int32)
+        nnz = max(len(indices), 1)
+        p1, p2 = np.zeros(R + 1, np.int64), np.zeros(R + 1, np.int64)
+        c1, c2 = np.zeros(nnz, np.int32), np.zeros(nnz, np.int32)
+        v2 = np.zeros(nnz)
+        st = self.lib.bbx_layout_split_rows(
+            R, n_cols_x, indptr.ctypes.data, indices.ctypes.data,
+            data.ctypes.data, int(transpose), dc.ctypes.data, len(dc),
+            p1.ctypes.data, c1.ctypes.data, p2.ctypes.data, c2.ctypes.data,
+            v2.ctypes.data)
+        assert st == 0
+        B = sparse.csr_matrix((np.ones(p1[-1]), c1[:p1[-1]], p1), shape=(R, C))
+        S = sparse.csr_matrix((v2[:p2[-1]], c2[:p2[-1]], p2), shape=(R, C))
+        return B, S
+
+
+def tiled_part_info(hip, which):
+    """Geometry of one tiled part of a design (bbx_design_tiled_info): which =
+    0 / 1 the layout of X / X^T (a mixed design: of its value-free part B),
+    6 / 7 the valued rest S of a mixed design.  dict(W, n_block, PR, G, n_quad,
+    n_slice)."""
+    from ctypes import byref, c_int, c_int64
+    from bayesbridge_amd import _lib
+    W, nb, PR, G, pk = c_int(), c_int(), c_int(), c_int(), c_int()
+    nq, ns = c_int64(), c_int64()
+    _lib.check(hip._lib.bbx_design_tiled_info(
+        hip._h, which, byref(W), byref(nb), byref(PR), byref(G), byref(nq),
+        byref(ns), byref(pk)))
+    return dict(W=W.value, n_block=nb.value, PR=PR.value, G=G.value,
+                n_quad=nq.value, n_slice=ns.value)
