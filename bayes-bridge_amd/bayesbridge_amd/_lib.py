@@ -18,6 +18,7 @@ F64, F32 = 0, 1
 MODEL_LINEAR, MODEL_LOGIT = 0, 1
 MODEL_PROBIT = 2
 MODEL_STUDENT_T = 3
+MODEL_CENSORED = 4
 PRED_LINEAR, PRED_LOGIT, PRED_POISSON = 0, 1, 2   # BBX_PRED_*
 GSCALE_SAMPLE, GSCALE_OPTIMIZE, GSCALE_FIXED = 0, 1, 2
 BATCH_ALLOW_SLOW = 1
@@ -156,6 +157,9 @@ def _declare(lib):
         "bbx_chain_create": (
             [hp, c_int, c_void_p, c_void_p, c_int, c_void_p, c_double,
              c_double, c_double, c_double, c_uint64, POINTER(hp)], c_int),
+        "bbx_chain_create_censored": (
+            [hp, c_int, c_void_p, c_void_p, c_int, c_void_p, c_double,
+             c_double, c_double, c_double, c_uint64, POINTER(hp)], c_int),
         "bbx_chain_destroy": ([hp], c_int),
         "bbx_chain_set_state": (
             [hp, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
@@ -210,6 +214,9 @@ def _declare(lib):
             [c_int, c_uint64, c_int64, c_double, c_void_p], c_int),
         "bbx_device_truncated_normal": (
             [c_int, c_uint64, c_int64, c_void_p, c_void_p, c_void_p], c_int),
+        "bbx_device_censored_normal": (
+            [c_int, c_uint64, c_int64, c_void_p, c_void_p, c_void_p, c_double,
+             c_void_p], c_int),
         "bbx_device_normal": (
             [c_int, c_uint64, c_uint64, c_int64, c_void_p], c_int),
         "bbx_cox_create": (
@@ -247,6 +254,11 @@ def _declare(lib):
             [hp, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
              c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
              c_void_p], c_int),
+        "bbx_design_predictive_summary_censored": (
+            [hp, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+            c_int),
         "bbx_logit_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_poisson_create": ([hp, c_void_p, c_void_p, POINTER(hp)], c_int),
         "bbx_cpoisson_create": (

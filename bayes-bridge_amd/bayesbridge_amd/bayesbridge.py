@@ -52,6 +52,10 @@ NUTS_INFO_KEYS = HMC_INFO_KEYS[:6] + ('tree_height', 'ave_accept_prob')
 # -- but for the probit model, whose observation precision is fixed at 1 and
 # whose coefficients the Gaussian samplers draw ('cg', 'cholesky', 'woodbury')
 NO_OBS_PREC = ('cox', 'poisson', 'negbin', 'ordinal', 'weibull', 'probit')
+# the censored-normal models (csrc/censored.hip): one device family
+CENSORED = ('tobit', 'lognormal')
+# models whose observation precision is one number, the chain's tau
+SCALAR_OBS_PREC = ('linear', 'student_t') + CENSORED
 # models whose only coefficient samplers are 'hmc' and 'nuts', and what the
 # refusals call them
 HAMILTONIAN_ONLY = {'poisson': 'Poisson', 'negbin': 'negative-binomial',
@@ -195,6 +199,9 @@ class SamplerOptions():
             _check_probit_options(coef_sampler_type, options.get('rng'))
         if model_name == 'student_t':
             _check_student_t_options(coef_sampler_type, options.get('rng'))
+        if model_name in CENSORED:
+            _check_censored_options(model_name, coef_sampler_type,
+                                    options.get('rng'))
         if model_name == 'logit' and coef_sampler_type in ('hmc', 'nuts'):
             # gibbs_util.py:52-75 lets 'hmc' through for the logit model.  Its
             # draw exists on the reference's host streams only, and a logit
@@ -211,9 +218,10 @@ class SamplerOptions():
                 coef_sampler_type in ('cholesky', 'woodbury')
                 and _is_hip_dense(design)):
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
-        if model_name not in ('linear', 'logit', 'probit', 'student_t'):
-            raise ValueError("Only linear, logit, probit and student_t models "
-                             "use the CG sampler.")
+        if model_name not in ('linear', 'logit', 'probit', 'student_t') \
+                + CENSORED:
+            raise ValueError("Only linear, logit, probit, student_t, tobit "
+                             "and lognormal models use the CG sampler.")
         n_obs, n_pred = design.shape
         if n_pred > n_obs:
             # (the reference's TODO here, gibbs_util.py:66-68, is the
@@ -258,6 +266,23 @@ def _check_student_t_options(coef_sampler_type, rng):
             "The student_t model runs with rng='device' only: "
             "rng='reference' is not supported (the reference has no "
             "student_t model whose streams could be followed).")
+
+
+def _check_censored_options(model_name, coef_sampler_type, rng):
+    """The censored-normal chains ('tobit', 'lognormal') exist on the device
+    only: their precision and latents are drawn by csrc/censored.hip and
+    their coefficients by the Gaussian samplers."""
+    if coef_sampler_type in ('hmc', 'nuts'):
+        raise ValueError(
+            "The %s model draws its coefficients with 'cg', 'cholesky' or "
+            "'woodbury': the '%s' sampler is not supported (there is no "
+            "Hamiltonian handle for %s)."
+            % (model_name, coef_sampler_type, model_name))
+    if rng == 'reference':
+        raise ValueError(
+            "The %s model runs with rng='device' only: rng='reference' is "
+            "not supported (the reference has no %s model whose streams "
+            "could be followed)." % (model_name, model_name))
 
 
 def _is_hip_dense(design):
@@ -361,6 +386,9 @@ class BayesBridge():
                     "init['obs_prec'] is not supported.")
         if self.model.name == 'student_t':
             _check_student_t_options(options.coef_sampler_type, options.rng)
+        if self.model.name in CENSORED:
+            _check_censored_options(self.model.name,
+                                    options.coef_sampler_type, options.rng)
         if options.coef_sampler_type in ('cholesky', 'woodbury'):
             if not _is_hip_dense(self.model.design):
                 raise ValueError(
@@ -477,7 +505,7 @@ class BayesBridge():
         other).  Batches keep 'coef', 'global_scale', 'logp' and use
         the device RNG."""
         design = self.model.design
-        if self.model.name in ('probit', 'student_t'):
+        if self.model.name in ('probit', 'student_t') + CENSORED:
             return 0
         if options is not None and not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
@@ -545,6 +573,10 @@ class BayesBridge():
         if self.model.name == 'student_t':
             raise ValueError("gibbs_batch is not supported for the student_t "
                              "model: its chains run one at a time (gibbs).")
+        if self.model.name in CENSORED:
+            raise ValueError("gibbs_batch is not supported for the %s "
+                             "model: its chains run one at a time (gibbs)."
+                             % self.model.name)
         if not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
                 None, options, self.model.name, self.model.design)
@@ -610,6 +642,10 @@ class BayesBridge():
             raise ValueError("gibbs_multichain is not supported for the "
                              "student_t model: its chains run one at a time "
                              "(gibbs).")
+        if self.model.name in CENSORED:
+            raise ValueError("gibbs_multichain is not supported for the %s "
+                             "model: its chains run one at a time (gibbs)."
+                             % self.model.name)
         if self.model.name in NO_OBS_PREC:
             raise ValueError("gibbs_multichain draws the coefficients with "
                              "'cg' only; the Cox model needs 'hmc'")
@@ -638,13 +674,15 @@ class BayesBridge():
             samples['global_scale'] = np.zeros(n_sample)
         if 'obs_prec' in params_to_save \
                 and self.model.name not in NO_OBS_PREC:
-            if self.model.name in ('linear', 'student_t'):
+            if self.model.name in SCALAR_OBS_PREC:
                 samples['obs_prec'] = np.zeros(n_sample)
             else:
                 samples['obs_prec'] = np.zeros((self.n_obs, n_sample))
         if 'mixing_weight' in params_to_save \
                 and self.model.name == 'student_t':
             samples['mixing_weight'] = np.zeros((self.n_obs, n_sample))
+        if 'latent' in params_to_save and self.model.name in CENSORED:
+            samples['latent'] = np.zeros((self.n_obs, n_sample))
         if 'logp' in params_to_save:
             samples['logp'] = np.zeros(n_sample)
         aux = AUX_PARAM.get(self.model.name)
@@ -667,7 +705,7 @@ class BayesBridge():
             if obs_prec.size != expected:
                 raise ValueError('An invalid initial state.')
             return obs_prec if self.model.name == 'logit' else float(obs_prec)
-        if self.model.name in ('linear', 'student_t'):
+        if self.model.name in SCALAR_OBS_PREC:
             return np.mean(
                 (self.model.y - self.model.design.dot(coef)) ** 2) ** -1
         return LogisticModel.compute_polya_gamma_mean(
@@ -963,11 +1001,12 @@ class BayesBridge():
         model, prior = self.model, self.prior
         hyper = prior.param['gscale_neg_power']
         return HipGibbsChain(
-            model.design, model.name,
-            model.y if model.name in ('linear', 'student_t')
-            else model.n_success,
+            model.design,
+            'censored' if model.name in CENSORED else model.name,
+            model.y if model.name in SCALAR_OBS_PREC else model.n_success,
             n_trial=model.n_trial if model.name == 'logit' else None,
             df=model.df if model.name == 'student_t' else None,
+            status=model.status if model.name in CENSORED else None,
             sd_unshrunk=self.prior_sd_for_unshrunk,
             bridge_exponent=prior.bridge_exp, slab_size=prior.slab_size,
             gscale_shape=hyper['shape'], gscale_rate=hyper['rate'], seed=seed)
@@ -1052,11 +1091,12 @@ class BayesBridge():
                                  'obs_prec': 'obs_prec'}[k]: t.data_ptr()
                    for k, t in device_out.items()})
             kept = {'global_scale': gs, 'logp': lp, 'n_cg_iter': ncg}
-        elif 'mixing_weight' in samples:
+        elif 'mixing_weight' in samples or 'latent' in samples:
             kept, n_unconv = self._run_keeping_weights(
                 chain, n_iter, n_burnin, thin,
                 [k for k in ('coef', 'local_scale', 'obs_prec')
-                 if k in samples])
+                 if k in samples],
+                'latent' if 'latent' in samples else 'mixing_weight')
         else:
             kept, n_unconv = chain.run(
                 n_iter, n_burnin, thin, maxiter=500, atol=0.,
@@ -1067,11 +1107,12 @@ class BayesBridge():
                                     optim_info)
 
     @staticmethod
-    def _run_keeping_weights(chain, n_iter, n_burnin, thin, save):
+    def _run_keeping_weights(chain, n_iter, n_burnin, thin, save,
+                             key='mixing_weight'):
         """chain.run with the Student-t model's n mixing weights of every
-        kept iteration: the library keeps no n-vector per sample for this
-        model, so the run is cut at the kept iterations and the weights are
-        read there.  The chain does not notice the cuts: its draws are
+        kept iteration (key 'latent': the censored models' n latents): the
+        library keeps no n-vector per sample for these models, so the run is
+        cut at the kept iterations and the weights are read there.  The chain does not notice the cuts: its draws are
         addressed by (seed, iteration)."""
         n_sample = (n_iter - n_burnin) // thin
         _, n_unconv = chain.run(n_burnin, n_burnin, 1, maxiter=500, atol=0.,
@@ -1090,7 +1131,7 @@ class BayesBridge():
         keys = ['global_scale', 'logp', 'n_cg_iter'] + list(save)
         kept = {k: np.concatenate([part[k] for part in parts])
                 if parts else np.zeros((0,)) for k in keys}
-        kept['mixing_weight'] = np.array(weights).reshape(n_sample, chain.n)
+        kept[key] = np.array(weights).reshape(n_sample, chain.n)
         return kept, n_unconv
 
     def _device_setup(self, chain, seed, init, options, resume_from=None):
@@ -1117,7 +1158,7 @@ class BayesBridge():
             if model.name in NO_OBS_PREC:      # probit: Omega = I, no state
                 return None
             eta = model.design.dot(coef)
-            if model.name in ('linear', 'student_t'):
+            if model.name in SCALAR_OBS_PREC:
                 scale = np.sum((model.y - eta) ** 2) / 2
                 return 1 / (scale / host_rng.gamma(self.n_obs / 2, 1))
             out = np.empty(self.n_obs)
@@ -1180,10 +1221,12 @@ class BayesBridge():
                 samples[key][:] = kept[key].T
         if 'obs_prec' in samples:
             samples['obs_prec'][:] = kept['obs_prec'][:, 0] \
-                if model.name in ('linear', 'student_t') \
+                if model.name in SCALAR_OBS_PREC \
                 else kept['obs_prec'].T
         if 'mixing_weight' in samples:
             samples['mixing_weight'][:] = kept['mixing_weight'].T
+        if 'latent' in samples:
+            samples['latent'][:] = kept['latent'].T
         for key in ('global_scale', 'logp'):
             if key in samples:
                 samples[key][:] = kept[key]

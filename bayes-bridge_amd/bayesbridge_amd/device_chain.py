@@ -17,7 +17,8 @@ _GSCALE_MODES = {'sample': _lib.GSCALE_SAMPLE, 'optimize': _lib.GSCALE_OPTIMIZE,
 
 _MODEL_CODES = {'linear': _lib.MODEL_LINEAR, 'logit': _lib.MODEL_LOGIT,
                 'probit': _lib.MODEL_PROBIT,
-                'student_t': _lib.MODEL_STUDENT_T}
+                'student_t': _lib.MODEL_STUDENT_T,
+                'censored': _lib.MODEL_CENSORED}
 
 
 def _ptr(a):
@@ -33,17 +34,22 @@ class HipGibbsChain():
     def __init__(self, design, family, outcome, n_trial=None,
                  sd_unshrunk=(float('inf'),), bridge_exponent=.5,
                  slab_size=float('inf'), gscale_shape=0., gscale_rate=0.,
-                 seed=0, df=None):
+                 seed=0, df=None, status=None):
         """family: 'linear' (outcome = y), 'logit' (outcome = n_success),
         'probit' (outcome = y in {0, 1}; n_trial None or all ones) or
         'student_t' (outcome = y, finite; n_trial None; df: the degrees of
-        freedom, None = the library's default 4);
+        freedom, None = the library's default 4) or 'censored' (outcome = the
+        rows' values, finite; status: 0 observed, 1 right-censored, 2
+        left-censored; n_trial None);
         sd_unshrunk: prior sd of the unshrunk coefficients, intercept first
         (bayesbridge.py:26-32); gscale_shape/rate: Gamma prior on
         tau^-bridge_exponent (prior.py:77-81), raw parametrisation."""
         if family not in _MODEL_CODES:
-            raise ValueError("family must be 'linear', 'logit', 'probit' or "
-                             "'student_t'")
+            raise ValueError("family must be 'linear', 'logit', 'probit', "
+                             "'student_t' or 'censored'")
+        if (status is not None) != (family == 'censored'):
+            raise ValueError("status is the 'censored' family's and required "
+                             "there: family = %r" % family)
         if df is not None and family != 'student_t':
             raise ValueError("df is the 'student_t' family's: family = %r"
                              % family)
@@ -59,7 +65,18 @@ class HipGibbsChain():
             raise ValueError("outcome must have one entry per design row")
         if n_trial is not None:
             n_trial = _f64(n_trial)
-        _lib.check(self._lib.bbx_chain_create(
+        create = self._lib.bbx_chain_create
+        if family == 'censored':
+            if n_trial is not None:
+                raise ValueError("censored: n_trial must be None")
+            status = np.asarray(status)
+            if status.shape != (self.n,):
+                raise ValueError("status must have one entry per design row")
+            if ((status != 0) & (status != 1) & (status != 2)).any():
+                raise ValueError("status must be 0, 1 or 2")
+            n_trial = np.ascontiguousarray(status, dtype=np.uint8)
+            create = self._lib.bbx_chain_create_censored
+        _lib.check(create(
             design.handle,
             _MODEL_CODES[family],
             _ptr(outcome), _ptr(n_trial), self.n_unshrunk, _ptr(sd),
@@ -114,21 +131,21 @@ class HipGibbsChain():
 
     def get_state(self):
         """(coef, obs_prec, local_scale, global_scale); obs_prec is a float
-        for the linear and Student-t models (tau) and None for the probit
-        model."""
+        for the linear, Student-t and censored models (tau) and None for the
+        probit model."""
         coef = np.empty(self.P)
         ls = np.empty(self.n_shrunk)
         obs = None if self.family == 'probit' else np.empty(self._obs_len)
         g = c_double()
         _lib.check(self._lib.bbx_chain_get_state(
             self._c, _ptr(coef), _ptr(obs), _ptr(ls), byref(g)))
-        if self.family in ('linear', 'student_t'):
+        if self.family in ('linear', 'student_t', 'censored'):
             obs = float(obs[0])
         return coef, obs, ls, float(g.value)
 
     def get_latent(self):
-        """The n latents z of a probit chain's current state, or the n mixing
-        weights omega of a Student-t chain's."""
+        """The n latents z of a probit or censored chain's current state, or
+        the n mixing weights omega of a Student-t chain's."""
         out = np.empty(self.n)
         _lib.check(self._lib.bbx_chain_get_latent(self._c, _ptr(out)))
         return out
@@ -147,9 +164,9 @@ class HipGibbsChain():
         return float(df.value)
 
     def get_zbase(self):
-        """X~^T kappa (logit), X~^T y (linear), X~^T z (probit) or X~^T (tau
-        omega y) (Student-t): what the next draw's right-hand side is scaled
-        from."""
+        """X~^T kappa (logit), X~^T y (linear), X~^T z (probit, censored) or
+        X~^T (tau omega y) (Student-t): what the next draw's right-hand side
+        is scaled from."""
         out = np.empty(self.P)
         _lib.check(self._lib.bbx_chain_get_zbase(self._c, _ptr(out)))
         return out

@@ -205,11 +205,13 @@ class _Predictive():
     def _predictive_summary(self, draws, X_new, n_row, y=None, obs_prec=None,
                             offset=None, n_trial=None, ll_const=None,
                             return_draws=False, draws_per_pass=0,
-                            n_plane=None):
+                            n_plane=None, tail=()):
         """Every check is done: the device from here on.  obs_prec is the
         family's per-draw input (the negative binomial's dispersion, the
         ordinal model's cutpoints (S, K - 1)).  n_plane=K: 'mean' and 'sd'
-        are (n, K), and the entry point has no argument for the draws."""
+        are (n, K), and the entry point has no argument for the draws.  tail:
+        what the entry point takes after the draws (the censored model's
+        survival summary)."""
         n_draw = len(draws)
         if y is not None and n_draw < 2:
             raise ValueError(
@@ -235,7 +237,7 @@ class _Predictive():
             design.handle, *integers, *[_ptr(a) for a in arrays],
             int(draws_per_pass), _ptr(mean), _ptr(sd),
             *[_ptr(a) for a in score], *([_ptr(out)] if n_plane is None
-                                         else [])))
+                                         else []), *tail))
         res = {'mean': mean, 'sd': sd} if n_plane is None \
             else {'mean': mean.T, 'sd': sd.T}
         if y is not None:
@@ -780,6 +782,274 @@ class StudentTModel(_Predictive, _Model):
         rng = np.random.default_rng(seed)
         return np.asarray(X.dot(beta)).ravel() \
             + noise_scale * rng.standard_t(_checked_df(df), X.shape[0])
+
+
+def _censored_outcome(y, status, n_row):
+    """The outcome checks of the censored-normal model on n_row rows: y
+    finite, status in {0, 1, 2}; (y as float64, status as uint8)."""
+    y = np.asarray(y, dtype=np.float64)
+    st = np.asarray(status)
+    if y.shape != (n_row,) or st.shape != (n_row,):
+        raise ValueError(
+            "Incompatible sizes of the outcome and design matrix: %s values, "
+            "%s status codes, %d rows." % (y.shape, st.shape, n_row))
+    bad = np.flatnonzero(~np.isfinite(y))
+    if bad.size:
+        raise ValueError(
+            "The censored model takes finite values: y[%d] = %r."
+            % (bad[0], float(y[bad[0]])))
+    bad = np.flatnonzero(~((st == 0) | (st == 1) | (st == 2)))
+    if bad.size:
+        raise ValueError(
+            "status must be 0 (observed), 1 (right-censored) or 2 "
+            "(left-censored): status[%d] = %r." % (bad[0], st[bad[0]]))
+    return y, st.astype(np.uint8)
+
+
+def _obs_prec_draws(obs_prec, n_draw):
+    """One strictly positive, finite observation precision per draw."""
+    if obs_prec is None:
+        raise ValueError(
+            "obs_prec (one observation precision per draw, "
+            "samples['obs_prec']) is required.")
+    obs_prec = np.asarray(obs_prec, dtype=np.float64).reshape(-1)
+    if obs_prec.shape != (n_draw,):
+        raise ValueError(
+            "obs_prec must hold one value per draw: %d values, %d draws."
+            % (len(obs_prec), n_draw))
+    if not np.all(np.isfinite(obs_prec)) or (obs_prec <= 0).any():
+        raise ValueError(
+            "Every obs_prec must be strictly positive and finite.")
+    return obs_prec
+
+
+class CensoredNormalModel(_Predictive, _Model):
+    """Linear regression of an outcome that is censored in some rows (the
+    Tobit model; no counterpart in the reference): z_i = eta_i + e_i, e_i ~
+    N(0, 1 / tau), and row i shows y_i with status_i: 0 -- observed, z_i =
+    y_i; 1 -- right-censored, z_i > y_i; 2 -- left-censored, z_i <= y_i.  The
+    chain augments the censored rows with truncated-normal latents (Chib
+    1992; csrc/censored.hip), after which the coefficients' conditional is the
+    linear model's with z for y: 'cg', 'cholesky' and 'woodbury' draw them on
+    the device.  The augmentation mixes slowly when most rows are censored:
+    the latents and the coefficients then move together in small steps.
+    Interval censoring is not supported.  Agreement with R's AER::tobit is
+    not tested."""
+
+    _exp_mean = 0
+
+    def __init__(self, y, status, design):
+        self.y, self.status = _censored_outcome(y, status, design.shape[0])
+        self.design = design
+        self.name = 'tobit'
+
+    def compute_loglik_and_gradient(self, beta, obs_prec=1.,
+                                    loglik_only=False):
+        """The chain's log-likelihood -- sum over observed rows of 1/2 log
+        tau - 1/2 tau (y - eta)^2 (the linear model's convention: -1/2 log
+        2 pi dropped), over right-censored rows of log Phi(-a) and over
+        left-censored rows of log Phi(a), a = (y - eta) sqrt(tau) -- and its
+        gradient X~^T g, g = tau (y - eta), sqrt(tau) phi(a) / Phi(-a) and
+        -sqrt(tau) phi(a) / Phi(a)."""
+        from scipy.special import log_ndtr
+        tau = float(obs_prec)
+        rt = math.sqrt(tau)
+        a = (self.y - self.design.dot(beta)) * rt
+        obs, right = self.status == 0, self.status == 1
+        sign = np.where(right, -1., 1.)
+        tail = log_ndtr(sign * a)
+        loglik = float(np.sum(np.where(
+            obs, .5 * math.log(tau) - .5 * a * a, tail)))
+        grad = None
+        if not loglik_only:
+            ratio = np.exp(-.5 * a * a - .5 * math.log(2. * math.pi) - tail)
+            grad = self.design.Tdot(np.where(obs, rt * a, -sign * rt * ratio))
+        return loglik, grad
+
+    def calc_intercept_mle(self):
+        """The mean of the values, censored ones at their bounds: a starting
+        point, not the maximiser."""
+        return float(np.mean(self.y))
+
+    def _pred_call(self, n_draw, draws, obs_prec, offset, y, n_trial,
+                   ll_const):
+        # (n_trial's place holds the status)
+        status = None if n_trial is None else n_trial.astype(np.uint8)
+        return 'bbx_design_predictive_summary_censored', \
+            (n_draw, self._exp_mean), \
+            (draws, obs_prec, offset, y, status, ll_const)
+
+    def _predict_censored(self, coef, obs_prec, X_new, y, status,
+                          ll_const=None, return_draws=False,
+                          draws_per_pass=0, points=None):
+        """predict and predict_survival behind their checks of the outcome:
+        y and status on the latent scale or None; points: where the survival
+        summary is asked for (the result then has 'surv_mean' and 'surv_sd',
+        (n, T))."""
+        draws, X_new, n_row = self._predict_rows(coef, X_new)
+        obs_prec = _obs_prec_draws(obs_prec, len(draws))
+        if points is None:
+            tail = (0, None, None, None)
+        else:
+            points = np.ascontiguousarray(points, dtype=np.float64)
+            surv = np.empty((2, len(points), n_row))
+            tail = (len(points), _ptr(points), _ptr(surv[0]), _ptr(surv[1]))
+        res = self._predictive_summary(
+            draws, X_new, n_row, y=y, obs_prec=obs_prec, n_trial=status,
+            ll_const=ll_const, return_draws=return_draws,
+            draws_per_pass=draws_per_pass, tail=tail)
+        if points is not None:
+            res['surv_mean'], res['surv_sd'] = surv[0].T, surv[1].T
+        return res
+
+    def predict(self, coef, obs_prec=None, X_new=None, y_new=None,
+                status_new=None, return_draws=False, _draws_per_pass=0):
+        """Posterior prediction over the draws coef (P,) or (P, S) -- what
+        samples['coef'] is -- with obs_prec (S,) -- samples['obs_prec'], the
+        draws' tau.  X_new=None: the training rows with the model's own
+        outcome; otherwise n_new rows of the model's raw columns (NumPy or
+        SciPy), centred with the TRAINING design's column means, with y_new
+        and status_new (both) or without.  A dict: 'mean' and 'sd' (n,), the
+        posterior mean of eta (the mean of the uncensored outcome) and its
+        population standard deviation over the draws; with an outcome 'lpd',
+        'loglik_mean' and 'loglik_var' (n,) and the floats 'lppd' = sum lpd,
+        'p_waic' = sum loglik_var and 'waic' = -2 (lppd - p_waic), the log
+        density being the full one: the normal density with -1/2 log 2 pi on
+        an observed row, the log tail probability on a censored one; with
+        return_draws 'draws' (n, S).  One device call for all the draws."""
+        _training_rows_only(X_new, y_new=y_new, status_new=status_new)
+        y = status = None
+        if X_new is None:
+            y, status = self.y, self.status
+        elif y_new is not None or status_new is not None:
+            if y_new is None or status_new is None:
+                raise ValueError(
+                    "y_new and status_new are given together or not at all.")
+            y, status = _censored_outcome(y_new, status_new,
+                                          np.shape(X_new)[0])
+        return self._predict_censored(
+            coef, obs_prec, X_new, y, status, return_draws=return_draws,
+            draws_per_pass=_draws_per_pass)
+
+    @staticmethod
+    def simulate_outcome(X, beta, noise_sd=1., lower=None, upper=None,
+                         seed=None):
+        """(y, status): z = X beta + noise_sd N(0, 1); a z <= lower is shown
+        as lower with status 2, a z > upper as upper with status 1."""
+        rng = np.random.default_rng(seed)
+        z = np.asarray(X.dot(beta)).ravel() \
+            + noise_sd * rng.standard_normal(X.shape[0])
+        y, status = z.copy(), np.zeros(len(z), dtype=np.uint8)
+        if lower is not None:
+            left = z <= lower
+            y[left], status[left] = lower, 2
+        if upper is not None:
+            right = z > upper
+            y[right], status[right] = upper, 1
+        return y, status
+
+
+class LogNormalAFTModel(CensoredNormalModel):
+    """Accelerated-failure-time regression of right-censored times with
+    log-normal errors: log T_i = eta_i + e_i, e_i ~ N(0, 1 / tau), on the
+    Weibull model's outcome (event_time, censoring_time).  It is the
+    censored-normal model on log t with status 1 for the censored rows, so
+    the Gaussian samplers 'cg', 'cholesky' and 'woodbury' draw its
+    coefficients.  The coefficients are log TIME ratios: a positive one
+    lengthens survival, the opposite sign to the log hazard ratios of the Cox
+    and Weibull models.  The augmentation mixes slowly under heavy
+    censoring.  Agreement with R's survreg(dist='lognormal') is not
+    tested."""
+
+    _exp_mean = 1
+
+    def __init__(self, event_time, censoring_time, design):
+        event, time = _survival_outcome(event_time, censoring_time,
+                                        design.shape[0])
+        super().__init__(np.log(time), (event == 0.).astype(np.uint8), design)
+        self.event = event
+        self.time = time
+        self.log_time = self.y
+        self.event_time = np.asarray(event_time, dtype=np.float64)
+        self.censoring_time = np.asarray(censoring_time, dtype=np.float64)
+        self.name = 'lognormal'
+
+    def predict(self, coef, obs_prec=None, X_new=None, event_time_new=None,
+                censoring_time_new=None, return_draws=False,
+                _draws_per_pass=0):
+        """CensoredNormalModel.predict for times: 'mean' and 'sd' are the
+        posterior mean of the median survival time exp(eta) and its population
+        standard deviation over the draws; with an outcome (the training
+        rows' own, or event_time_new and censoring_time_new together) the
+        scores are under the density of t -- the normal density of log t
+        with the Jacobian -log t on an event row, log(1 - Phi((log t - eta)
+        sqrt(tau))) on a censored one -- which makes 'lppd' and 'waic'
+        comparable with WeibullModel.predict's."""
+        _training_rows_only(X_new, event_time_new=event_time_new,
+                            censoring_time_new=censoring_time_new)
+        y = status = None
+        if X_new is None:
+            y, status = self.y, self.status
+        elif event_time_new is not None or censoring_time_new is not None:
+            if event_time_new is None or censoring_time_new is None:
+                raise ValueError(
+                    "event_time_new and censoring_time_new are given "
+                    "together or not at all.")
+            event, time = _survival_outcome(
+                event_time_new, censoring_time_new, np.shape(X_new)[0])
+            y, status = np.log(time), (event == 0.).astype(np.uint8)
+        jacobian = None if y is None else np.where(status == 0, -y, 0.)
+        return self._predict_censored(
+            coef, obs_prec, X_new, y, status, ll_const=jacobian,
+            return_draws=return_draws, draws_per_pass=_draws_per_pass)
+
+    def predict_survival(self, coef, obs_prec, X_new=None, times=None):
+        """Posterior survival S(t | x) = 1 - Phi((log t - x~ . beta)
+        sqrt(tau)) over the draws coef (P,) or (P, S) with obs_prec (S,): a
+        dict with 'time' (T,), 'mean' and 'sd' (n, T), the mean and the
+        population standard deviation over the draws.  X_new=None: the
+        training rows; otherwise rows of the model's raw columns, centred
+        with the training design's column means.  times: strictly positive
+        and increasing (None: the distinct event times of the training
+        rows); any t may be asked for, before the first and past the last
+        observed time too."""
+        if times is None:
+            times = np.unique(self.time[self.event == 1.])
+        times = np.ascontiguousarray(np.atleast_1d(times), dtype=np.float64)
+        if times.ndim != 1 or times.size == 0 \
+                or not np.all(np.isfinite(times)) or (times <= 0).any() \
+                or np.any(np.diff(times) <= 0):
+            raise ValueError("times must be finite, strictly positive and "
+                             "strictly increasing.")
+        res = self._predict_censored(coef, obs_prec, X_new, None, None,
+                                     points=np.log(times))
+        return {'time': times, 'mean': res['surv_mean'],
+                'sd': res['surv_sd']}
+
+    @staticmethod
+    def simulate_outcome(X, beta, noise_sd=1., censoring_frac=.5, seed=None):
+        """(event_time, censoring_time) with log T = X beta + noise_sd N(0, 1)
+        and independent log-normal censoring times of the same spread whose
+        common location is chosen so that the expected censored fraction is
+        censoring_frac; exactly one of a row's two times is finite."""
+        from scipy.special import ndtr
+        if not 0. <= censoring_frac < 1.:
+            raise ValueError("censoring_frac must lie in [0, 1).")
+        rng = np.random.default_rng(seed)
+        eta = np.asarray(X.dot(beta), dtype=np.float64).ravel()
+        log_t = eta + noise_sd * rng.standard_normal(len(eta))
+        log_c = np.full(len(eta), np.inf)
+        if censoring_frac > 0.:
+            # P(C < T) = mean Phi((eta - q) / (sd sqrt 2)), decreasing in q
+            lo, hi = eta.min() - 40. * noise_sd, eta.max() + 40. * noise_sd
+            for _ in range(200):
+                q = .5 * (lo + hi)
+                frac = np.mean(ndtr((eta - q) / (noise_sd * math.sqrt(2.))))
+                lo, hi = (q, hi) if frac > censoring_frac else (lo, q)
+            log_c = .5 * (lo + hi) + noise_sd * rng.standard_normal(len(eta))
+        censored = log_c < log_t
+        return np.where(censored, np.inf, np.exp(log_t)), \
+            np.where(censored, np.exp(log_c), np.inf)
 
 
 class PoissonModel(_DeviceHamiltonian, _Predictive, _Model):
@@ -2620,7 +2890,12 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     family='probit', outcome = y in {0, 1}; a tuple with n_trial is refused
     (the binomial outcome is the logit model's).  For family='student_t',
     outcome = y, finite, and `df` > 0 (None: 4) is the fixed degrees of
-    freedom of the errors.  (The
+    freedom of the errors.  For family='tobit', outcome = (y, status) with
+    status 0 (observed), 1 (right-censored: the truth lies above y) or 2
+    (left-censored: at or below y); for family='lognormal', outcome =
+    (event_time, censoring_time) as for the Weibull model, fitted as the
+    log-normal accelerated-failure-time model (coefficients are log time
+    ratios).  (The
     seven keywords stand before `competing_time`, which stays the last one:
     pass them by name.)"""
     if entry_time is not None and family != 'cox':
@@ -2671,6 +2946,18 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     if family == 'student_t':
         outcome = _finite_outcome(outcome, X.shape[0])
         df = _checked_df(4. if df is None else df)
+    if family in ('tobit', 'lognormal'):
+        if not (isinstance(outcome, tuple) and len(outcome) == 2):
+            raise ValueError(
+                "The %s model takes outcome = %s." % (
+                    family, "(y, status)" if family == 'tobit'
+                    else "(event_time, censoring_time): strata are not "
+                    "supported"))
+        # (before the design goes to the GPU)
+        if family == 'tobit':
+            outcome = _censored_outcome(outcome[0], outcome[1], X.shape[0])
+        else:
+            _survival_outcome(outcome[0], outcome[1], X.shape[0])
     stratified_poisson = (family == 'poisson' and isinstance(outcome, tuple)
                           and len(outcome) == 3)
     if add_intercept is None:
@@ -2822,6 +3109,10 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         return ProbitModel(outcome, design)
     if family == 'student_t':
         return StudentTModel(outcome, design, df)
+    if family == 'tobit':
+        return CensoredNormalModel(outcome[0], outcome[1], design)
+    if family == 'lognormal':
+        return LogNormalAFTModel(outcome[0], outcome[1], design)
     if family == 'cox':
         if competing_time is not None:
             return CoxModel._finegray(event_time, censoring_time,

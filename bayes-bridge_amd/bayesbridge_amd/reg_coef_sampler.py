@@ -242,7 +242,8 @@ class HipRegressionCoefficientSampler():
         design = model.design
 
         def loglik_and_grad(beta, loglik_only):
-            if model.name in ('linear', 'student_t'):
+            if model.name in ('linear', 'student_t') \
+                    or model.name in ('tobit', 'lognormal'):
                 return model.compute_loglik_and_gradient(
                     beta, obs_prec, loglik_only=loglik_only)
             return model.compute_loglik_and_gradient(

@@ -148,6 +148,34 @@ def truncated_normal(seed, stream, psi, positive, variant=0, trace=False):
     return (out, trials) if trace else out
 
 
+def censored_normal(seed, stream, psi, bound, status, tau, variant=0,
+                    trace=False):
+    """The censored model's latents as chain_censored_kernel draws them
+    (csrc/censored.hip): bound_i where status_i == 0, else bound_i + u /
+    sqrt(tau) with u = truncated_normal at psi' = (psi_i - bound_i) sqrt(tau),
+    positive where status_i == 1; with trace, (draws, trials) -- 0 trials on an
+    observed row and where psi' is not finite (the draw is then a NaN on a
+    censored row).  `variant` is truncated_normal's; the kernel forms psi' and
+    u / sqrt(tau) with the same product and the same true division as this
+    function, so no further form belongs to variant 1.  `stream` as for
+    truncated_normal; the bare STREAM_LATENT for bbx_device_censored_normal."""
+    psi = np.ascontiguousarray(psi, dtype=np.float64)
+    bound = np.ascontiguousarray(bound, dtype=np.float64)
+    status = np.asarray(status)
+    assert psi.ndim == 1 and bound.shape == psi.shape \
+        and status.shape == psi.shape
+    rt = np.sqrt(np.float64(tau))
+    with np.errstate(invalid='ignore', over='ignore'):
+        scaled = (psi - bound) * rt
+    u, trials = truncated_normal(seed, stream, scaled, status == 1, variant,
+                                 trace=True)
+    censored = status != 0
+    with np.errstate(invalid='ignore'):
+        out = np.where(censored, bound + u / rt, bound)
+    trials = np.where(censored, trials, 0).astype(np.int32)
+    return (out, trials) if trace else out
+
+
 def log_norm_cdf(x):
     """log Phi(x) in the host form of csrc/samplers.hpp."""
     x = np.ascontiguousarray(x, dtype=np.float64)

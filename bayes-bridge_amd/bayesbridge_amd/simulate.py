@@ -101,7 +101,10 @@ def simulate_outcome(X, beta, model, intercept=0., n_trial=None, seed=None,
     (WeibullModel.simulate_outcome); for 'probit', y in {0, 1} with
     P(y = 1) = Phi(intercept + X beta); for 'student_t', y = intercept +
     X beta + a standard Student-t variate on 4 degrees of freedom
-    (StudentTModel.simulate_outcome takes df and the noise scale)."""
+    (StudentTModel.simulate_outcome takes df and the noise scale); for
+    'lognormal', (event_time, censoring_time) with log T = intercept + X beta
+    + N(0, 1) and the censoring fraction asked for; for 'tobit', (y, status)
+    with z = intercept + X beta + N(0, 1) left-censored at 0."""
     if model == 'cox':
         from .model import CoxModel
         return CoxModel.simulate_outcome(X, beta, censoring_frac, seed)
@@ -132,6 +135,20 @@ def simulate_outcome(X, beta, model, intercept=0., n_trial=None, seed=None,
     if model == 'student_t':
         eta = np.asarray(intercept + X.dot(beta)).ravel()
         return eta + np.random.standard_t(4., size=X.shape[0])
+    if model in ('lognormal', 'tobit'):
+        from .model import CensoredNormalModel, LogNormalAFTModel
+
+        class _Shifted():   # X beta + intercept behind the models' X.dot
+            shape = X.shape
+
+            @staticmethod
+            def dot(b):
+                return np.asarray(intercept + X.dot(b)).ravel()
+        if model == 'lognormal':
+            return LogNormalAFTModel.simulate_outcome(
+                _Shifted, beta, 1., censoring_frac, seed)
+        return CensoredNormalModel.simulate_outcome(
+            _Shifted, beta, 1., lower=0., seed=seed)
     raise NotImplementedError(model)
 
 

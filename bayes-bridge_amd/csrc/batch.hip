@@ -704,6 +704,10 @@ int bbx_batch_create_opts(bbx_design* design, int n_chain,
       return fail(BBX_ERR_INVALID,
                   "batched chains are linear or logit: a student_t chain runs "
                   "on its own");
+    if (chains[c]->model == BBX_MODEL_CENSORED)
+      return fail(BBX_ERR_INVALID,
+                  "batched chains are linear or logit: a censored chain runs "
+                  "on its own");
     if (chains[c]->n_unshrunk != chains[0]->n_unshrunk)
       return fail(BBX_ERR_INVALID,
                   "the chains of a batch must agree on n_unshrunk");

@@ -47,7 +47,9 @@ __global__ __launch_bounds__(256) void chain_prior_kernel(
     double* __restrict__ z, int store_idx, double* __restrict__ samp_gs,
     double* __restrict__ samp_lp) {
   const double g = sc->gscale;
-  const double zs = (model == BBX_MODEL_LINEAR) ? sc->obs_prec : 1.;
+  const double zs =
+      (model == BBX_MODEL_LINEAR || model == BBX_MODEL_CENSORED) ? sc->obs_prec
+                                                                 : 1.;
   // global scale and log posterior of the PREVIOUS iteration, if it was kept
   // (chain_save_sample defers them to here: the scalars are untouched between
   // the end of an iteration and this kernel, and a launch of its own for two
@@ -194,7 +196,7 @@ __device__ inline double sum_row_parts(const double* part, int count) {
 }
 
 // Finishes the observation-level reductions (single block).
-//   logit, probit: loglik = sum of partials
+//   logit, probit, censored: loglik = sum of partials
 //   linear: obs_prec ~ Gamma(n/2, 1) / (rss/2); loglik = n log(w)/2 - w rss/2
 //           (bayesbridge.py:400-404; linear_model.py:13-17); `init` => 1/mean
 __global__ __launch_bounds__(256) void chain_obs_finish_kernel(
@@ -202,7 +204,8 @@ __global__ __launch_bounds__(256) void chain_obs_finish_kernel(
     const double* __restrict__ part, int count, ChainScalars* __restrict__ sc) {
   const double tot = sum_row_parts(part, count);
   if (threadIdx.x != 0) return;
-  if (model == BBX_MODEL_LOGIT || model == BBX_MODEL_PROBIT) {
+  if (model == BBX_MODEL_LOGIT || model == BBX_MODEL_PROBIT ||
+      model == BBX_MODEL_CENSORED) {
     sc->loglik = tot;
   } else {
     double w;
@@ -228,7 +231,8 @@ __global__ __launch_bounds__(256) void chain_fill_obs_prec_kernel(
 
 // The `count` (<= ROW_GRID) block sums of an n-vector folded onto the NPART
 // slots launch_tdot re-adds: slot t takes blocks t, t + NPART, ... in that
-// order (the probit model's sum z, the Student-t model's sum kappa).
+// order (the probit and censored models' sum z, the Student-t model's sum
+// kappa).
 __global__ __launch_bounds__(NPART) void chain_sumw_fold_kernel(
     const double* __restrict__ z_part, int count, double* __restrict__ part) {
   double acc = 0.;
@@ -634,6 +638,50 @@ static int chain_student_t_refresh(bbx_chain* c) {
   return BBX_OK;
 }
 
+// z | beta, tau of a censored-outcome chain from the psi in place, with the
+// latent stream of iteration `it` (-1: a chain that has not run); `draw_tau`:
+// first tau | beta, z by the linear model's two kernels with the latents in
+// place for y (an iteration; a refresh keeps its tau; the log-likelihood that
+// pass writes is replaced below).  Then zbase = X~^T z: the one product a
+// censored iteration adds.  The log-likelihood partials are left in
+// row_part[0 .. *row_blocks) for chain_obs_finish_kernel.
+static int chain_censored_update(bbx_chain* c, int64_t it, bool draw_tau,
+                                 int* row_blocks) {
+  bbx_design* h = c->h;
+  if (draw_tau) {
+    const int rg = grid_for(h->n, ROW_GRID);
+    double* rp = c->row_part.as<double>();
+    BBX_LAUNCH(chain_rss_kernel, dim3(rg), dim3(256), 0, h->stream, h->n,
+               c->latent.as<double>(), c->psi.as<double>(), rp);
+    BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, h->stream,
+               BBX_MODEL_LINEAR, 0, h->n, c->seed,
+               iter_stream(STREAM_OBSVAR, it), rp, rg,
+               c->scalars.as<ChainScalars>());
+    BBX_HIP(hipGetLastError());
+  }
+  BBX_TRY(launch_chain_censored(c, iter_stream(STREAM_LATENT, it), row_blocks));
+  TdotEpilogue ep;
+  return launch_tdot(h, c->latent.as<double>(), part_slot(h, PS_SUMW), ep,
+                     c->zbase.as<double>());
+}
+
+// psi, z, zbase and the log-likelihood of a censored-outcome chain recomputed
+// from (coef, tau): z is a function of (seed, iteration, row, psi, tau), so the
+// state a finished iteration left is reproduced bit for bit.  tau is not
+// redrawn.
+static int chain_censored_refresh(bbx_chain* c) {
+  bbx_design* h = c->h;
+  BBX_TRY(chain_linear_predictor(c));
+  int rg = 0;
+  BBX_TRY(chain_censored_update(c, c->iter - 1, false, &rg));
+  BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, h->stream,
+             c->model, 0, h->n, c->seed, 0, c->row_part.as<double>(), rg,
+             c->scalars.as<ChainScalars>());
+  BBX_HIP(hipGetLastError());
+  BBX_HIP(hipStreamSynchronize(h->stream));
+  return BBX_OK;
+}
+
 // The pass for X~ beta enqueued by the CG loop itself, right behind a look at
 // the stop flag (bbx_design::tail_hook): when the host wakes up from that look
 // the pass is already running, and the kernels of both branches are launched
@@ -678,7 +726,7 @@ int chain_pre_draw(bbx_chain* c) {
                      c->sd.as<double>(), c->z.as<double>(), c->pending_store,
                      c->samp_gscale.as<double>(), c->samp_logp.as<double>());
   c->pending_store = -1;
-  if (c->model == BBX_MODEL_LINEAR)
+  if (c->model == BBX_MODEL_LINEAR || c->model == BBX_MODEL_CENSORED)
     BBX_LAUNCH(chain_fill_obs_prec_kernel, dim3(grid_for(n, ROW_GRID)),
                        dim3(256), 0, s, n, sc, c->obs_prec.as<double>());
   BBX_HIP(hipGetLastError());
@@ -833,6 +881,8 @@ int chain_post_draw(bbx_chain* c, bool have_psi, int phases,
     BBX_TRY(chain_probit_update(c, c->iter, &rg));
   } else if (c->model == BBX_MODEL_STUDENT_T) {
     BBX_TRY(chain_student_t_update(c, c->iter, true, &rg));
+  } else if (c->model == BBX_MODEL_CENSORED) {
+    BBX_TRY(chain_censored_update(c, c->iter, true, &rg));
   } else {
     BBX_LAUNCH(chain_rss_kernel, dim3(rg), dim3(256), 0, s, n,
                        c->outcome.as<double>(), c->psi.as<double>(), rp);
@@ -878,8 +928,10 @@ static int chain_step(bbx_chain* c, int maxiter, double atol, int* n_cg_iter) {
     }
     // (probit: the linear model's branch at the fixed precision 1 -- the
     // cached Gram, no weighted one; Student-t: the logit model's branch with
-    // Omega = tau omega, a weighted Gram every iteration)
-    const bool linear = c->model == BBX_MODEL_LINEAR;
+    // Omega = tau omega, a weighted Gram every iteration; censored: the linear
+    // model's branch as it is, the cached Gram scaled by tau)
+    const bool linear = c->model == BBX_MODEL_LINEAR ||
+                        c->model == BBX_MODEL_CENSORED;
     const bool probit = c->model == BBX_MODEL_PROBIT;
     const int st = chol_sample_device(
         h, linear || probit ? nullptr : c->obs_prec.as<double>(), 1.,
@@ -908,16 +960,18 @@ static int chain_step(bbx_chain* c, int maxiter, double atol, int* n_cg_iter) {
       BBX_TRY(launch_fill_normal(h, h->P, cg_draw_seed(c, it), STREAM_ETA2,
                                  c->eta2_next.as<double>()));
     }
-    const bool linear = c->model == BBX_MODEL_LINEAR;
+    const bool censored = c->model == BBX_MODEL_CENSORED;
+    const bool linear = c->model == BBX_MODEL_LINEAR || censored;
     const bool probit = c->model == BBX_MODEL_PROBIT;
     // logit: kappa = Omega y (the pseudo-outcome is kappa / Omega); probit: the
-    // linear branch with the latents as outcome at the fixed precision 1
+    // linear branch with the latents as outcome at the fixed precision 1;
+    // censored: the linear branch with the latents as outcome at tau
     const int st = woodbury_sample_device(
         h, linear || probit ? nullptr : c->obs_prec.as<double>(), 1.,
         linear ? &c->scalars.as<ChainScalars>()->obs_prec : nullptr,
         c->phi.as<double>(),
-        linear   ? c->outcome.as<double>()
-        : probit ? c->latent.as<double>()
+        censored || probit ? c->latent.as<double>()
+        : linear           ? c->outcome.as<double>()
                  : c->kappa.as<double>(),
         linear || probit ? 0 : 1, c->eta1_next.as<double>(), c->eta2_next.as<double>(),
         c->coef.as<double>());
@@ -1025,17 +1079,36 @@ using namespace bbx;
 
 extern "C" {
 
-int bbx_chain_create(bbx_design* design, int model, const double* outcome,
-                     const double* n_trial, int n_unshrunk,
-                     const double* sd_unshrunk, double bridge_exp,
-                     double slab_size, double gscale_shape0,
-                     double gscale_rate0, uint64_t seed, bbx_chain** out) {
+// bbx_chain_create and bbx_chain_create_censored: `status` is the censored
+// model's row status (then n_trial is NULL), NULL for every other model.
+static int chain_create_impl(bbx_design* design, int model,
+                             const double* outcome, const double* n_trial,
+                             const unsigned char* status, int n_unshrunk,
+                             const double* sd_unshrunk, double bridge_exp,
+                             double slab_size, double gscale_shape0,
+                             double gscale_rate0, uint64_t seed,
+                             bbx_chain** out) {
   if (!out) return fail(BBX_ERR_INVALID, "out is NULL");
   *out = nullptr;
   if (!design || !outcome) return fail(BBX_ERR_INVALID, "NULL argument");
   if (model != BBX_MODEL_LINEAR && model != BBX_MODEL_LOGIT &&
-      model != BBX_MODEL_PROBIT && model != BBX_MODEL_STUDENT_T)
+      model != BBX_MODEL_PROBIT && model != BBX_MODEL_STUDENT_T &&
+      model != BBX_MODEL_CENSORED)
     return fail(BBX_ERR_INVALID, "unknown model");
+  if (model == BBX_MODEL_CENSORED) {
+    if (!status)
+      return fail(BBX_ERR_INVALID,
+                  "censored: the row status is NULL (bbx_chain_create_censored "
+                  "creates this model)");
+    for (int64_t i = 0; i < design->n; ++i) {
+      if (!std::isfinite(outcome[i]))
+        return fail(BBX_ERR_INVALID, "censored: bound[" + std::to_string(i) +
+                                         "] is not finite");
+      if (status[i] > 2)
+        return fail(BBX_ERR_INVALID, "censored: status[" + std::to_string(i) +
+                                         "] is not 0, 1 or 2");
+    }
+  }
   if (model == BBX_MODEL_STUDENT_T) {
     if (n_trial)
       return fail(BBX_ERR_INVALID,
@@ -1082,8 +1155,16 @@ int bbx_chain_create(bbx_design* design, int model, const double* outcome,
     BBX_TRY(c->kappa.alloc(nb));
     BBX_TRY(c->obs_prec.alloc(nb));
     BBX_TRY(c->psi.alloc(nb));
-    if (model == BBX_MODEL_PROBIT || model == BBX_MODEL_STUDENT_T)
+    if (model == BBX_MODEL_PROBIT || model == BBX_MODEL_STUDENT_T ||
+        model == BBX_MODEL_CENSORED)
       BBX_TRY(c->latent.alloc(nb));
+    if (model == BBX_MODEL_CENSORED) {
+      // z = b: the latents start at the bounds, zbase below at X~^T b
+      BBX_TRY(c->status.alloc((size_t)n));
+      BBX_HIP(hipMemcpy(c->status.ptr, status, (size_t)n,
+                        hipMemcpyHostToDevice));
+      BBX_HIP(hipMemcpy(c->latent.ptr, outcome, nb, hipMemcpyHostToDevice));
+    }
     for (DevMem* m : {&c->zbase, &c->coef, &c->phi, &c->x0, &c->sd, &c->z,
                       &c->mean, &c->square})
       BBX_TRY(m->alloc(Pb));
@@ -1178,6 +1259,33 @@ int bbx_chain_create(bbx_design* design, int model, const double* outcome,
   return BBX_OK;
 }
 
+int bbx_chain_create(bbx_design* design, int model, const double* outcome,
+                     const double* n_trial, int n_unshrunk,
+                     const double* sd_unshrunk, double bridge_exp,
+                     double slab_size, double gscale_shape0,
+                     double gscale_rate0, uint64_t seed, bbx_chain** out) {
+  return chain_create_impl(design, model, outcome, n_trial, nullptr,
+                           n_unshrunk, sd_unshrunk, bridge_exp, slab_size,
+                           gscale_shape0, gscale_rate0, seed, out);
+}
+
+int bbx_chain_create_censored(bbx_design* design, int model,
+                              const double* bound, const unsigned char* status,
+                              int n_unshrunk, const double* sd_unshrunk,
+                              double bridge_exp, double slab_size,
+                              double gscale_shape0, double gscale_rate0,
+                              uint64_t seed, bbx_chain** out) {
+  if (out) *out = nullptr;
+  if (model != BBX_MODEL_CENSORED)
+    return fail(BBX_ERR_INVALID,
+                "bbx_chain_create_censored: model must be BBX_MODEL_CENSORED");
+  if (!status)
+    return fail(BBX_ERR_INVALID, "bbx_chain_create_censored: NULL argument");
+  return chain_create_impl(design, model, bound, nullptr, status, n_unshrunk,
+                           sd_unshrunk, bridge_exp, slab_size, gscale_shape0,
+                           gscale_rate0, seed, out);
+}
+
 int bbx_chain_destroy(bbx_chain* c) {
   if (!c) return BBX_OK;
   // (the design may have been destroyed first -- a garbage collector finalises
@@ -1224,6 +1332,7 @@ static int bbx_chain_set_state_impl(bbx_chain* c, const double* coef,
   BBX_HIP(hipMemcpy(c->scalars.ptr, &sc, sizeof(sc), hipMemcpyHostToDevice));
   if (c->model == BBX_MODEL_PROBIT) BBX_TRY(chain_probit_refresh(c));
   if (c->model == BBX_MODEL_STUDENT_T) BBX_TRY(chain_student_t_refresh(c));
+  if (c->model == BBX_MODEL_CENSORED) BBX_TRY(chain_censored_refresh(c));
   return BBX_OK;
 }
 
@@ -1386,9 +1495,11 @@ int bbx_chain_get_logp(bbx_chain* c, double* loglik, double* logp) {
 int bbx_chain_get_latent(bbx_chain* c, double* out) {
   return no_throw([&]() -> int {
     BBX_TRY(chain_check(c));
-    if (c->model != BBX_MODEL_PROBIT && c->model != BBX_MODEL_STUDENT_T)
+    if (c->model != BBX_MODEL_PROBIT && c->model != BBX_MODEL_STUDENT_T &&
+        c->model != BBX_MODEL_CENSORED)
       return fail(BBX_ERR_INVALID,
-                  "bbx_chain_get_latent: not a probit or student_t chain");
+                  "bbx_chain_get_latent: not a probit, student_t or censored "
+                  "chain");
     if (!out) return fail(BBX_ERR_INVALID, "bbx_chain_get_latent: out is NULL");
     BBX_HIP(hipSetDevice(c->h->device));
     BBX_HIP(hipStreamSynchronize(c->h->stream));
@@ -1453,6 +1564,18 @@ int bbx_chain_init_obs_prec(bbx_chain* c) {
                c->scalars.as<ChainScalars>());
     BBX_HIP(hipGetLastError());
     return chain_student_t_refresh(c);
+  }
+  if (c->model == BBX_MODEL_CENSORED) {
+    // tau = 1 / mean((b - psi)^2), the linear model's rule on the bounds, then
+    // the latents under it
+    double* rp = c->row_part.as<double>();
+    BBX_LAUNCH(chain_rss_kernel, dim3(rg), dim3(256), 0, h->stream, h->n,
+               c->outcome.as<double>(), c->psi.as<double>(), rp);
+    BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, h->stream,
+               BBX_MODEL_LINEAR, 1, h->n, c->seed, 0, rp, rg,
+               c->scalars.as<ChainScalars>());
+    BBX_HIP(hipGetLastError());
+    return chain_censored_refresh(c);
   }
   if (c->model == BBX_MODEL_LOGIT) {
     BBX_LAUNCH(chain_pg_mean_kernel, dim3(rg), dim3(256), 0, h->stream,
@@ -1735,10 +1858,10 @@ int bbx_chain_set_coef_sampler(bbx_chain* c, int sampler) {
                   "the woodbury sampler needs a dense design (this one is sparse)");
     if (sampler == BBX_SAMPLER_WOODBURY && c->model != BBX_MODEL_LINEAR &&
         c->model != BBX_MODEL_LOGIT && c->model != BBX_MODEL_PROBIT &&
-        c->model != BBX_MODEL_STUDENT_T)
+        c->model != BBX_MODEL_STUDENT_T && c->model != BBX_MODEL_CENSORED)
       return fail(BBX_ERR_INVALID,
-                  "the woodbury sampler draws linear, logit, probit and "
-                  "student_t models only");
+                  "the woodbury sampler draws linear, logit, probit, student_t "
+                  "and censored models only");
     if (sampler == BBX_SAMPLER_CHOLESKY && c->h->sparse)
       return fail(BBX_ERR_INVALID,
                   "the cholesky sampler needs a dense design (this one is sparse)");

@@ -21,7 +21,7 @@ struct alignas(128) ChainScalars {
   long long n_gscale_clamped;
   long long n_lscale_fixed;
   // ---- written by the Omega branch
-  alignas(128) double obs_prec;  // linear model; Student-t: tau
+  alignas(128) double obs_prec;  // linear model; Student-t, censored: tau
   double loglik;                 // of the current coef
   // log posterior (bayesbridge.py:480-511)
   __host__ __device__ double logp() const { return loglik + logprior; }
@@ -54,8 +54,10 @@ struct bbx_chain {
   bbx::DevMem coef, phi, x0, sd, z, mean, square, sd_unshrunk;  // P-length
   bbx::DevMem lscale;                   // P - n_unshrunk
   bbx::DevMem obs_prec, psi;            // n
-  bbx::DevMem latent;                   // n: the probit model's z, the Student-t
-                                        // model's omega (else empty)
+  bbx::DevMem latent;                   // n: the probit and censored models' z,
+                                        // the Student-t model's omega (else empty)
+  bbx::DevMem status;                   // n bytes: the censored model's row status
+                                        // (outcome holds the bounds; else empty)
   bbx::DevMem scalars;                 // ChainScalars
   bbx::DevMem row_part;                 // ROW_GRID partials x 2
   bbx::DevMem misc_part;                // NPART x 3: sums over the coefficients (tau branch)
@@ -133,5 +135,13 @@ int launch_student_t_tau(bbx_chain* c, uint64_t stream);
 int launch_student_t_mix(bbx_chain* c, uint64_t stream, int* row_blocks);
 int launch_student_t_finish(bbx_chain* c, int row_blocks);
 double student_t_row_const(double nu);
+
+// z | beta, tau of a censored-outcome chain (censored.hip), on the design's
+// stream, under the tau in scalars->obs_prec: latent_i = outcome_i on an
+// observed row, else outcome_i + u / sqrt(tau) with u the truncated normal at
+// (psi_i - outcome_i) sqrt(tau), row i from Philox(seed, stream, i, trial); the
+// log-likelihood partials into row_part[0 .. *row_blocks), the partials of
+// sum_i latent_i into PS_SUMW.
+int launch_chain_censored(bbx_chain* c, uint64_t stream, int* row_blocks);
 
 }  // namespace bbx

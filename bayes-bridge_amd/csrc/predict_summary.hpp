@@ -4,7 +4,8 @@
 // summary kernel of the one-mean families with its host side (predict.hip:
 // linear, logit, Poisson; negbin_predict.hip: negative binomial;
 // weibull_predict.hip: Weibull; probit_predict.hip: probit;
-// student_t_predict.hip: Student-t).  Kernels and
+// student_t_predict.hip: Student-t; censored_predict.hip: censored normal).
+// Kernels and
 // drivers are static: a translation unit holds the instantiations it launches
 // and no others.  predict.hip describes the method.
 //
@@ -61,6 +62,16 @@ constexpr int PRED_PROBIT = 5;
 // The Student-t regression model's, likewise (student_t_predict.hip): mu = eta,
 // ll = the full t-density at the draw's tau and the model's df.
 constexpr int PRED_STUDENT_T = 6;
+// The censored-outcome model's, likewise (censored_predict.hip): mu = eta, ll =
+// the full normal density on an observed row, log Phi of the censored side's
+// tail on a censored one.
+constexpr int PRED_CENSORED = 7;
+// The same with mu = exp(eta): the median time of the log-normal AFT model,
+// whose latent scale is log t.
+constexpr int PRED_LOGNORMAL = 8;
+constexpr bool pred_censored(int family) {
+  return family == PRED_CENSORED || family == PRED_LOGNORMAL;
+}
 
 struct PredArgs {
   int64_t n;
@@ -68,15 +79,17 @@ struct PredArgs {
   int kn;           // draws of this pass
   int64_t n_draw;   // all draws: the last pass writes the results
   const double* eta;      // [kn][n]
-  const double* tau;      // [n_draw] linear, Student-t: obs_prec; Weibull: the
-                          // shape k
+  const double* tau;      // [n_draw] linear, Student-t, censored: obs_prec;
+                          // Weibull: the shape k
   const double* hlt;      // [n_draw] linear: 0.5 log(obs_prec); Weibull: log k;
-                          // Student-t: the draw's normalising constant
+                          // Student-t: the draw's normalising constant;
+                          // censored: 0.5 log(obs_prec / (2 pi))
   const double* gtab;     // [n_draw][NEGBIN_GTAB] negbin: negbin_gtab(r);
                           // Student-t: [2] = (df + 1) / 2, df
   const double* offset;   // [n] or null
   const double* y;        // [n]   (SCORE)
-  const double* m;        // [n] or null (logit, SCORE); Weibull: log t (SCORE)
+  const double* m;        // [n] or null (logit, SCORE); Weibull: log t (SCORE);
+                          // censored: the row status 0, 1, 2 (SCORE)
   const double* c;        // [n] or null (SCORE)
   double* state;          // [PRED_STATE][n]
   double* out;            // [5][n]: mean, sd, lpd, ll_mean, ll_var
@@ -122,6 +135,13 @@ __device__ __forceinline__ void pred_terms(double eta, double y, double m,
     if (SCORE) {
       const double r = y - eta;
       *ll = hlt - gtab[0] * log1p(tau * (r * r) / gtab[1]);
+    }
+  } else if (pred_censored(FAMILY)) {
+    // y is the row's value, m its status; hlt = 1/2 log(tau / (2 pi))
+    *mu = FAMILY == PRED_LOGNORMAL ? exp(eta) : eta;
+    if (SCORE) {
+      const double a = (y - eta) * sqrt(tau);
+      *ll = m == 0. ? hlt - 0.5 * (a * a) : log_norm_cdf(m == 1. ? -a : a);
     }
   } else if (FAMILY == PRED_PROBIT) {
     // Phi(eta) = erfc(-eta / sqrt 2) / 2: absolute error ~1e-16, what a mean
@@ -225,7 +245,8 @@ static __global__ __launch_bounds__(PRED_BLOCK) void predict_summary_kernel(
   const bool has_off = a.offset != nullptr;
   const double off = has_off ? a.offset[i] : 0.;
   const double y = SCORE ? a.y[i] : 0.;
-  const bool has_m = FAMILY == BBX_PRED_LOGIT || FAMILY == PRED_WEIBULL;
+  const bool has_m = FAMILY == BBX_PRED_LOGIT || FAMILY == PRED_WEIBULL ||
+                     pred_censored(FAMILY);
   const double m = SCORE && has_m && a.m ? a.m[i] : 1.;
   const bool has_c = SCORE && a.c != nullptr;
   const double c = has_c ? a.c[i] : 0.;
@@ -237,7 +258,9 @@ static __global__ __launch_bounds__(PRED_BLOCK) void predict_summary_kernel(
     if (has_off) eta += off;
     const double k = (double)(a.k0 + d + 1);
     double tau = 0., hlt = 0.;
-    if (((FAMILY == BBX_PRED_LINEAR || FAMILY == PRED_STUDENT_T) && SCORE) ||
+    if (((FAMILY == BBX_PRED_LINEAR || FAMILY == PRED_STUDENT_T ||
+          pred_censored(FAMILY)) &&
+         SCORE) ||
         FAMILY == PRED_WEIBULL) {
       tau = a.tau[a.k0 + d];
       hlt = a.hlt[a.k0 + d];
@@ -383,6 +406,7 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
   const bool negbin = q.family == PRED_NEGBIN;
   const bool weibull = q.family == PRED_WEIBULL;
   const bool student_t = q.family == PRED_STUDENT_T;
+  const bool censored = pred_censored(q.family);
 
   PredPasses p;
   DevMem d_state, d_out;
@@ -423,6 +447,14 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
     tau_host[2 * S] = (q.df + 1.) / 2.;
     tau_host[2 * S + 1] = q.df;
   }
+  if (censored && q.obs_prec) {
+    // (without an outcome too: the survival summary needs the draws' tau)
+    tau_host.resize(2 * (size_t)S);
+    for (int64_t d = 0; d < S; ++d) {
+      tau_host[d] = q.obs_prec[d];
+      tau_host[S + d] = 0.5 * log(q.obs_prec[d] / (2. * M_PI));
+    }
+  }
   const double* tab = nullptr;
   if (!tau_host.empty())
     BBX_TRY(p.upload(tau_host.data(), d8 * tau_host.size(), &tab));
@@ -431,7 +463,7 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
   a.n = n;
   a.n_draw = S;
   a.eta = p.d_eta.as<const double>();
-  if (linear || weibull || student_t) {
+  if (linear || weibull || student_t || censored) {
     a.tau = tab;
     a.hlt = tab ? tab + S : nullptr;
     if (student_t) a.gtab = tab ? tab + 2 * S : nullptr;
@@ -440,9 +472,10 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
   }
   BBX_TRY(p.row(q.offset, &a.offset));
   BBX_TRY(p.row(score ? q.y : nullptr, &a.y));
-  BBX_TRY(p.row(score && (q.family == BBX_PRED_LOGIT || weibull) ? q.n_trial
-                                                                   : nullptr,
-                &a.m));
+  BBX_TRY(p.row(
+      score && (q.family == BBX_PRED_LOGIT || weibull || censored) ? q.n_trial
+                                                                    : nullptr,
+      &a.m));
   BBX_TRY(p.row(score ? q.ll_const : nullptr, &a.c));
   a.state = d_state.as<double>();
   a.out = d_out.as<double>();

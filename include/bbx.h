@@ -74,6 +74,10 @@ extern "C" {
  *      (BBX_MODEL_STUDENT_T, bbx_chain_set_df, bbx_chain_get_df,
  *      bbx_design_predictive_summary_student_t; bbx_chain_get_latent serves
  *      it too).  Again a new model code and new symbols: the number stays 113.
+ *      + the censored-outcome model on the device chain (BBX_MODEL_CENSORED,
+ *      bbx_chain_create_censored, bbx_device_censored_normal,
+ *      bbx_design_predictive_summary_censored; bbx_chain_get_latent serves it
+ *      too).  Again a new model code and new symbols: the number stays 113.
  * 112: + the Cox model in counting-process form (bbx_coxcp_*): delayed entry
  *      and (start, stop] rows, with the trajectory and the No-U-Turn sampler
  *      of the Cox handle.
@@ -127,6 +131,9 @@ extern "C" {
 #define BBX_MODEL_LOGIT 1
 #define BBX_MODEL_PROBIT 2 /* Albert-Chib latents: no counterpart in the
                               reference; see bbx_chain_create                   */
+#define BBX_MODEL_CENSORED 4 /* normal outcome with right- and left-censored
+                                rows (log-normal AFT, Tobit): no counterpart in
+                                the reference; see bbx_chain_create_censored   */
 #define BBX_MODEL_STUDENT_T 3 /* linear regression with Student-t errors as a
                                  scale mixture of normals: no counterpart in
                                  the reference; see bbx_chain_create            */
@@ -668,6 +675,43 @@ int bbx_chain_create(bbx_design* design, int model, const double* outcome,
                      const double* sd_unshrunk, double bridge_exp,
                      double slab_size, double gscale_shape0,
                      double gscale_rate0, uint64_t seed, bbx_chain** out);
+/*
+ * BBX_MODEL_CENSORED (no counterpart in the reference): bbx_chain_create's
+ * arguments with the row status where n_trial stands; bbx_chain_create itself
+ * refuses the model, and this entry refuses every other one.  Row i has a value
+ * bound[i] (finite) and status[i]: 0 observed (z_i = bound_i), 1 right-censored
+ * (z_i > bound_i), 2 left-censored (z_i <= bound_i; the open and closed sides
+ * are the probit model's); BBX_ERR_INVALID names the first row with a bound
+ * that is not finite or a status above 2.  z_i ~ N(psi_i, 1 / tau): the
+ * accelerated-failure-time model with log-normal errors when bound = log t,
+ * the Tobit model when the outcome is censored at a limit.  After the
+ * coefficient draw of iteration `it`:
+ *   tau = gamma_draw(Philox(seed, 6 | it << 8, 0), n/2) / (S/2), S = sum_i
+ *         (z_i - psi_i)^2 with the latents of the iteration before: the linear
+ *         model's rule and kernels with z for y;
+ *   z_i = bound_i + u / sqrt(tau) on a censored row, u ~ N(psi', 1) on u > 0
+ *         (status 1) or u <= 0 (status 2), psi' = (psi_i - bound_i) sqrt(tau),
+ *         trial t on Philox(seed, 7 | it << 8, i, t), with the new tau;
+ *   beta | tau, z is the linear model's conditional with z for y, drawn by any
+ *         of the three samplers (the direct ones from the cached Gram).
+ * obs_prec is the scalar tau (length 1, as for the linear model);
+ * bbx_chain_get_latent returns z.  The log-likelihood is sum over observed rows
+ * of 1/2 log tau - 1/2 tau (bound - psi)^2 (the linear model's convention:
+ * -1/2 log 2 pi dropped) plus sum over censored rows of log Phi(+-psi').  At
+ * creation z = bound.  bbx_chain_set_state and bbx_chain_init_obs_prec (which
+ * first sets tau = 1 / mean((bound - psi)^2)) recompute psi, z, X~^T z and the
+ * log-likelihood from (coef, tau) with the stream of iteration `iteration - 1`
+ * (-1: a chain that has not run), without redrawing tau, so a chain resumed
+ * from (coef, obs_prec, lscale, gscale, iteration, summaries, seed) continues
+ * bit for bit.  A psi_i that is not finite gives a NaN log-likelihood and, on a
+ * censored row, a NaN latent.  bbx_batch_create refuses censored chains.
+ */
+int bbx_chain_create_censored(bbx_design* design, int model,
+                              const double* bound, const unsigned char* status,
+                              int n_unshrunk, const double* sd_unshrunk,
+                              double bridge_exp, double slab_size,
+                              double gscale_shape0, double gscale_rate0,
+                              uint64_t seed, bbx_chain** out);
 int bbx_chain_destroy(bbx_chain* c);
 
 /* Markov-chain state, host pointers.  obs_prec has n entries for logit and 1
@@ -724,8 +768,9 @@ int bbx_chain_eta(bbx_chain* c, int64_t iteration, double* eta1, double* eta2);
 /* Log-likelihood and log-posterior of the state left by the last iteration
  * (bayesbridge.py:480-511), host pointers, either may be NULL. */
 int bbx_chain_get_logp(bbx_chain* c, double* loglik, double* logp);
-/* The n latents of a BBX_MODEL_PROBIT chain's current state, or the n mixing
- * weights omega of a BBX_MODEL_STUDENT_T chain's (host pointer);
+/* The n latents of a BBX_MODEL_PROBIT or BBX_MODEL_CENSORED chain's current
+ * state, or the n mixing weights omega of a BBX_MODEL_STUDENT_T chain's (host
+ * pointer);
  * BBX_ERR_INVALID for a chain of another model or a NULL out. */
 int bbx_chain_get_latent(bbx_chain* c, double* out);
 /* The degrees of freedom nu of a BBX_MODEL_STUDENT_T chain (4 at creation).
@@ -855,6 +900,17 @@ int bbx_device_gamma(int device, uint64_t seed, int64_t n_draw, double shape,
 int bbx_device_truncated_normal(int device, uint64_t seed, int64_t n_draw,
                                 const double* psi,
                                 const unsigned char* positive, double* out);
+/* The censored model's latent draw on Philox stream 7 (the chain's latent
+ * stream at iteration 0): out[i] = bound[i] where status[i] == 0, else bound[i]
+ * + u / sqrt(tau) with u ~ N(psi', 1), psi' = (psi[i] - bound[i]) sqrt(tau), on
+ * u > 0 (status 1) or u <= 0 (status 2); a psi' that is not finite gives a NaN
+ * on a censored row.  BBX_ERR_INVALID for n_draw < 0, a NULL psi, bound, status
+ * or out, a tau that is not finite and positive, a status above 2 or a bound
+ * that is not finite (the first offending row is named). */
+int bbx_device_censored_normal(int device, uint64_t seed, int64_t n_draw,
+                               const double* psi, const double* bound,
+                               const unsigned char* status, double tau,
+                               double* out);
 /* n_draw standard normals of Philox stream `stream` (element i = counter i):
  * the generator behind eta1 / eta2 (cg_sampler.py:61-62 uses
  * np.random.randn). */
@@ -1453,6 +1509,40 @@ int bbx_design_predictive_summary_student_t(
     const double* obs_prec, const double* offset, const double* y,
     const double* ll_const, int draws_per_pass, double* mean, double* sd,
     double* lpd, double* ll_mean, double* ll_var, double* mu_draws);
+
+/* The same summary for the censored-outcome model (BBX_MODEL_CENSORED;
+ * csrc/censored_predict.hip), from draws of the coefficients and of the
+ * precision tau, obs_prec[n_draw].  With eta = X~ coef_s + offset and a = (y -
+ * eta) sqrt(tau_s), per row and draw
+ *
+ *   mu = eta, or exp(eta) with exp_mean != 0 (the median time of the
+ *        log-normal AFT model, whose y is log t; its density of t then takes
+ *        c = -log t on the observed rows)
+ *   ll = 1/2 log(tau_s / (2 pi)) - 1/2 a^2 + c   status 0 (observed)
+ *        log Phi(-a) + c                          status 1 (right-censored)
+ *        log Phi(a) + c                           status 2 (left-censored)
+ *
+ * the FULL density.  y[n] finite with status[n] in {0, 1, 2}, or both NULL;
+ * without an outcome lpd, ll_mean and ll_var may be NULL.  With n_point > 0 the
+ * survival summary as well: S_j = 1 - Phi((points[j] - eta) sqrt(tau_s)), its
+ * mean and population sd over the draws into surv_mean[n_point][n] and
+ * surv_sd[n_point][n] (points of the latent scale: log t for the log-normal
+ * AFT model; -inf and +inf give 1 and 0); obs_prec is then required without an
+ * outcome too.  Passes, synchronisation and the other outputs are those of
+ * bbx_design_predictive_summary.  BBX_ERR_INVALID for a NULL or destroyed
+ * design, n_draw < 1 (< 2 with an outcome), a NULL coef, mean or sd, an
+ * outcome with a NULL status, obs_prec, lpd, ll_mean or ll_var, n_point < 0,
+ * n_point > 0 with a NULL points, obs_prec, surv_mean or surv_sd, an
+ * obs_prec[d] that is not finite and positive, a NaN point, a y[i] that is
+ * not finite, a status above 2, draws_per_pass < 0: checked before anything
+ * touches the device. */
+int bbx_design_predictive_summary_censored(
+    bbx_design* design, int64_t n_draw, int exp_mean, const double* coef,
+    const double* obs_prec, const double* offset, const double* y,
+    const unsigned char* status, const double* ll_const, int draws_per_pass,
+    double* mean, double* sd, double* lpd, double* ll_mean, double* ll_var,
+    double* mu_draws, int64_t n_point, const double* points, double* surv_mean,
+    double* surv_sd);
 
 /* The summary of the proportional-odds model (csrc/ordinal_predict.hip: a
  * kernel of its own), from draws of the coefficients, coef[n_draw][P], and of
