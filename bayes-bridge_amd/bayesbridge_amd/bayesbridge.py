@@ -56,6 +56,9 @@ NO_OBS_PREC = ('cox', 'poisson', 'negbin', 'ordinal', 'weibull', 'probit')
 CENSORED = ('tobit', 'lognormal')
 # models whose observation precision is one number, the chain's tau
 SCALAR_OBS_PREC = ('linear', 'student_t') + CENSORED
+# the latent-variable families of the Gaussian samplers (csrc/latent_rows.hpp):
+# device RNG only, one chain at a time
+LATENT = ('probit', 'student_t') + CENSORED
 # models whose only coefficient samplers are 'hmc' and 'nuts', and what the
 # refusals call them
 HAMILTONIAN_ONLY = {'poisson': 'Poisson', 'negbin': 'negative-binomial',
@@ -195,13 +198,9 @@ class SamplerOptions():
                     % (HAMILTONIAN_ONLY[model_name], coef_sampler_type))
             options['coef_sampler_type'] = coef_sampler_type or 'hmc'
             return SamplerOptions(**options)
-        if model_name == 'probit':
-            _check_probit_options(coef_sampler_type, options.get('rng'))
-        if model_name == 'student_t':
-            _check_student_t_options(coef_sampler_type, options.get('rng'))
-        if model_name in CENSORED:
-            _check_censored_options(model_name, coef_sampler_type,
-                                    options.get('rng'))
+        if model_name in LATENT:
+            _check_latent_options(model_name, coef_sampler_type,
+                                  options.get('rng'))
         if model_name == 'logit' and coef_sampler_type in ('hmc', 'nuts'):
             # gibbs_util.py:52-75 lets 'hmc' through for the logit model.  Its
             # draw exists on the reference's host streams only, and a logit
@@ -218,8 +217,7 @@ class SamplerOptions():
                 coef_sampler_type in ('cholesky', 'woodbury')
                 and _is_hip_dense(design)):
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
-        if model_name not in ('linear', 'logit', 'probit', 'student_t') \
-                + CENSORED:
+        if model_name not in ('linear', 'logit') + LATENT:
             raise ValueError("Only linear, logit, probit, student_t, tobit "
                              "and lognormal models use the CG sampler.")
         n_obs, n_pred = design.shape
@@ -236,42 +234,11 @@ class SamplerOptions():
         return SamplerOptions(**options)
 
 
-def _check_probit_options(coef_sampler_type, rng):
-    """The probit chain exists on the device only: its latents are drawn by
-    csrc/probit.hip and its coefficients by the Gaussian samplers."""
-    if coef_sampler_type in ('hmc', 'nuts'):
-        raise ValueError(
-            "The probit model draws its coefficients with 'cg', 'cholesky' "
-            "or 'woodbury': the '%s' sampler is not supported (there is no "
-            "Hamiltonian handle for probit)." % coef_sampler_type)
-    if rng == 'reference':
-        raise ValueError(
-            "The probit model runs with rng='device' only: rng='reference' "
-            "is not supported (the reference has no probit model whose "
-            "streams could be followed).")
-
-
-def _check_student_t_options(coef_sampler_type, rng):
-    """The Student-t chain exists on the device only: its precision and mixing
-    weights are drawn by csrc/student_t.hip and its coefficients by the
-    Gaussian samplers."""
-    if coef_sampler_type in ('hmc', 'nuts'):
-        raise ValueError(
-            "The student_t model draws its coefficients with 'cg', "
-            "'cholesky' or 'woodbury': the '%s' sampler is not supported "
-            "(there is no Hamiltonian handle for student_t)."
-            % coef_sampler_type)
-    if rng == 'reference':
-        raise ValueError(
-            "The student_t model runs with rng='device' only: "
-            "rng='reference' is not supported (the reference has no "
-            "student_t model whose streams could be followed).")
-
-
-def _check_censored_options(model_name, coef_sampler_type, rng):
-    """The censored-normal chains ('tobit', 'lognormal') exist on the device
-    only: their precision and latents are drawn by csrc/censored.hip and
-    their coefficients by the Gaussian samplers."""
+def _check_latent_options(model_name, coef_sampler_type, rng):
+    """The latent-variable Gaussian families (LATENT) exist on the device
+    only: their latents, mixing weights and precision are drawn by
+    csrc/probit.hip, student_t.hip and censored.hip on csrc/latent_rows.hpp,
+    and their coefficients by the Gaussian samplers."""
     if coef_sampler_type in ('hmc', 'nuts'):
         raise ValueError(
             "The %s model draws its coefficients with 'cg', 'cholesky' or "
@@ -378,17 +345,13 @@ class BayesBridge():
         if not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
                 coef_sampler_type, options, self.model.name, self.model.design)
-        if self.model.name == 'probit':
-            _check_probit_options(options.coef_sampler_type, options.rng)
-            if isinstance(init, dict) and 'obs_prec' in init:
-                raise ValueError(
-                    "The probit model has no observation precision: "
-                    "init['obs_prec'] is not supported.")
-        if self.model.name == 'student_t':
-            _check_student_t_options(options.coef_sampler_type, options.rng)
-        if self.model.name in CENSORED:
-            _check_censored_options(self.model.name,
-                                    options.coef_sampler_type, options.rng)
+        if self.model.name in LATENT:
+            _check_latent_options(self.model.name, options.coef_sampler_type,
+                                  options.rng)
+        if self.model.name == 'probit' and isinstance(init, dict) \
+                and 'obs_prec' in init:
+            raise ValueError("The probit model has no observation precision: "
+                             "init['obs_prec'] is not supported.")
         if options.coef_sampler_type in ('cholesky', 'woodbury'):
             if not _is_hip_dense(self.model.design):
                 raise ValueError(
@@ -505,7 +468,7 @@ class BayesBridge():
         other).  Batches keep 'coef', 'global_scale', 'logp' and use
         the device RNG."""
         design = self.model.design
-        if self.model.name in ('probit', 'student_t') + CENSORED:
+        if self.model.name in LATENT:
             return 0
         if options is not None and not isinstance(options, SamplerOptions):
             options = SamplerOptions.pick_default_and_create(
@@ -567,13 +530,7 @@ class BayesBridge():
         below single chains raises unless `allow_slow`."""
         import copy
         from .device_chain import HipChainBatch
-        if self.model.name == 'probit':
-            raise ValueError("gibbs_batch is not supported for the probit "
-                             "model: its chains run one at a time (gibbs).")
-        if self.model.name == 'student_t':
-            raise ValueError("gibbs_batch is not supported for the student_t "
-                             "model: its chains run one at a time (gibbs).")
-        if self.model.name in CENSORED:
+        if self.model.name in LATENT:
             raise ValueError("gibbs_batch is not supported for the %s "
                              "model: its chains run one at a time (gibbs)."
                              % self.model.name)
@@ -634,15 +591,7 @@ class BayesBridge():
         samples[name] shaped (n_chain, ..., n_sample) on rank 0.  `batch`:
         False (default; chain k's samples do not depend on the number of
         ranks), 'auto' or a width -- see chains.run_chains."""
-        if self.model.name == 'probit':
-            raise ValueError("gibbs_multichain is not supported for the "
-                             "probit model: its chains run one at a time "
-                             "(gibbs).")
-        if self.model.name == 'student_t':
-            raise ValueError("gibbs_multichain is not supported for the "
-                             "student_t model: its chains run one at a time "
-                             "(gibbs).")
-        if self.model.name in CENSORED:
+        if self.model.name in LATENT:
             raise ValueError("gibbs_multichain is not supported for the %s "
                              "model: its chains run one at a time (gibbs)."
                              % self.model.name)

@@ -132,7 +132,7 @@ def tilted_stable(seed, stream, char_exp, tilt, variant=0, trace=False):
 
 def truncated_normal(seed, stream, psi, positive, variant=0, trace=False):
     """N(psi_i, 1) on z > 0 where positive[i], else on z <= 0, as
-    chain_probit_kernel draws it (csrc/probit.hip); with trace, (draws,
+    the probit row policy draws it (csrc/probit.hip); with trace, (draws,
     trials): the trials each element took (0: psi was not finite, the draw is
     a NaN).  `stream`: `iter_stream(STREAM_LATENT, it)` for the chain's
     iteration `it` (`it = -1`: the state of a chain that has not run), the
@@ -150,7 +150,7 @@ def truncated_normal(seed, stream, psi, positive, variant=0, trace=False):
 
 def censored_normal(seed, stream, psi, bound, status, tau, variant=0,
                     trace=False):
-    """The censored model's latents as chain_censored_kernel draws them
+    """The censored model's latents as the censored row policy draws them
     (csrc/censored.hip): bound_i where status_i == 0, else bound_i + u /
     sqrt(tau) with u = truncated_normal at psi' = (psi_i - bound_i) sqrt(tau),
     positive where status_i == 1; with trace, (draws, trials) -- 0 trials on an

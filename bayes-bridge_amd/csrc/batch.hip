@@ -696,18 +696,10 @@ int bbx_batch_create_opts(bbx_design* design, int n_chain,
     if (chains[c]->coef_sampler != BBX_SAMPLER_CG)
       return fail(BBX_ERR_INVALID,
                   "batched chains draw the coefficients with BBX_SAMPLER_CG only");
-    if (chains[c]->model == BBX_MODEL_PROBIT)
+    if (const char* name = latent_family_name(chains[c]->model))
       return fail(BBX_ERR_INVALID,
-                  "batched chains are linear or logit: a probit chain runs on "
-                  "its own");
-    if (chains[c]->model == BBX_MODEL_STUDENT_T)
-      return fail(BBX_ERR_INVALID,
-                  "batched chains are linear or logit: a student_t chain runs "
-                  "on its own");
-    if (chains[c]->model == BBX_MODEL_CENSORED)
-      return fail(BBX_ERR_INVALID,
-                  "batched chains are linear or logit: a censored chain runs "
-                  "on its own");
+                  std::string("batched chains are linear or logit: a ") + name +
+                      " chain runs on its own");
     if (chains[c]->n_unshrunk != chains[0]->n_unshrunk)
       return fail(BBX_ERR_INVALID,
                   "the chains of a batch must agree on n_unshrunk");

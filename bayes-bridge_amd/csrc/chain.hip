@@ -14,20 +14,6 @@
 
 namespace bbx {
 
-__device__ inline double wsum(double x) { return wave_allsum(x); }
-
-__device__ inline double block_total_256(double x) {
-  __shared__ double s_w[256 / WAVE];
-  x = wsum(x);
-  if ((threadIdx.x & (WAVE - 1)) == 0) s_w[threadIdx.x / WAVE] = x;
-  __syncthreads();
-  double r = 0.;
-  if (threadIdx.x == 0)
-    for (int k = 0; k < 256 / WAVE; ++k) r += s_w[k];
-  __syncthreads();
-  return r;  // thread 0 only
-}
-
 __device__ inline double shrunk_scale(double gscale, double lscale,
                                       double slab) {
   // reg_coef_sampler.py:194-201
@@ -39,7 +25,7 @@ __device__ inline double shrunk_scale(double gscale, double lscale,
 // phi, CG warm start, preconditioner sd, z  (reg_coef_sampler.py:74-89;
 // reg_coef_posterior_summarizer.py:25-29,105-124).
 __global__ __launch_bounds__(256) void chain_prior_kernel(
-    int64_t P, int nu, int model, double slab, long long n_avg,
+    int64_t P, int nu, int scale_z, double slab, long long n_avg,
     const ChainScalars* __restrict__ sc, const double* __restrict__ lscale,
     const double* __restrict__ sd_unshrunk, const double* __restrict__ mean,
     const double* __restrict__ square, const double* __restrict__ zbase,
@@ -47,9 +33,9 @@ __global__ __launch_bounds__(256) void chain_prior_kernel(
     double* __restrict__ z, int store_idx, double* __restrict__ samp_gs,
     double* __restrict__ samp_lp) {
   const double g = sc->gscale;
-  const double zs =
-      (model == BBX_MODEL_LINEAR || model == BBX_MODEL_CENSORED) ? sc->obs_prec
-                                                                 : 1.;
+  // (scale_z: the linear model and the families drawn as one, whose zbase is
+  // scaled by the chain's tau)
+  const double zs = scale_z ? sc->obs_prec : 1.;
   // global scale and log posterior of the PREVIOUS iteration, if it was kept
   // (chain_save_sample defers them to here: the scalars are untouched between
   // the end of an iteration and this kernel, and a launch of its own for two
@@ -188,25 +174,22 @@ __global__ __launch_bounds__(256) void chain_rss_kernel(
   if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
-__device__ inline double sum_row_parts(const double* part, int count) {
-  // one block, fixed order
-  double acc = 0.;
-  for (int k = threadIdx.x; k < count; k += 256) acc += part[k];
-  return block_total_256(acc);
-}
-
-// Finishes the observation-level reductions (single block).
-//   logit, probit, censored: loglik = sum of partials
-//   linear: obs_prec ~ Gamma(n/2, 1) / (rss/2); loglik = n log(w)/2 - w rss/2
+// Finishes the observation-level reductions (single block), by `rule`:
+//   OBS_SUM (logit, probit, censored): loglik = sum of partials
+//   OBS_SUM_CONST (Student-t): ... + n row_const
+//   OBS_LINEAR: obs_prec ~ Gamma(n/2, 1) / (rss/2); loglik = n log(w)/2 - w rss/2
 //           (bayesbridge.py:400-404; linear_model.py:13-17); `init` => 1/mean
+enum { OBS_SUM = 0, OBS_SUM_CONST = 1, OBS_LINEAR = 2 };
 __global__ __launch_bounds__(256) void chain_obs_finish_kernel(
-    int model, int init, int64_t n, uint64_t seed, uint64_t stream,
-    const double* __restrict__ part, int count, ChainScalars* __restrict__ sc) {
+    int rule, int init, int64_t n, uint64_t seed, uint64_t stream,
+    double row_const, const double* __restrict__ part, int count,
+    ChainScalars* __restrict__ sc) {
   const double tot = sum_row_parts(part, count);
   if (threadIdx.x != 0) return;
-  if (model == BBX_MODEL_LOGIT || model == BBX_MODEL_PROBIT ||
-      model == BBX_MODEL_CENSORED) {
+  if (rule == OBS_SUM) {
     sc->loglik = tot;
+  } else if (rule == OBS_SUM_CONST) {
+    sc->loglik = tot + (double)n * row_const;
   } else {
     double w;
     if (init) {
@@ -561,13 +544,6 @@ static inline uint64_t iter_stream(uint64_t stream, int64_t iter) {
   return stream | ((uint64_t)iter << 8);
 }
 
-static int grid_for(int64_t len, int cap) {
-  int64_t nb = (len + 255) / 256;
-  if (nb > cap) nb = cap;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
-
 // psi = X~ coef
 static int chain_linear_predictor(bbx_chain* c) {
   bbx_design* h = c->h;
@@ -579,104 +555,164 @@ static int chain_linear_predictor(bbx_chain* c) {
                     nullptr);
 }
 
-// z | beta of a probit chain from the psi in place, with the latent stream of
-// iteration `it` (-1: the reserved index of a chain that has not run), then
-// zbase = X~^T z: the one product a probit iteration adds.  The log-likelihood
-// partials are left in row_part[0 .. *row_blocks) for chain_obs_finish_kernel.
-static int chain_probit_update(bbx_chain* c, int64_t it, int* row_blocks) {
-  bbx_design* h = c->h;
-  BBX_TRY(launch_chain_probit(c, iter_stream(STREAM_LATENT, it), row_blocks));
-  TdotEpilogue ep;
-  return launch_tdot(h, c->latent.as<double>(), part_slot(h, PS_SUMW), ep,
-                     c->zbase.as<double>());
-}
+// ---- the latent families: probit (probit.hip), Student-t (student_t.hip) and
+// censored (censored.hip), each a Gaussian conditional for the coefficients
+// given one drawn value per row (latent_rows.hpp)
 
-// psi, z, zbase and the log-likelihood of a probit chain recomputed from its
-// coefficients: z is a function of (seed, iteration, element, psi), so the
-// state a finished iteration left is reproduced bit for bit.
-static int chain_probit_refresh(bbx_chain* c) {
-  bbx_design* h = c->h;
-  BBX_TRY(chain_linear_predictor(c));
-  int rg = 0;
-  BBX_TRY(chain_probit_update(c, c->iter - 1, &rg));
-  BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, h->stream,
-             c->model, 0, h->n, c->seed, 0, c->row_part.as<double>(), rg,
-             c->scalars.as<ChainScalars>());
-  BBX_HIP(hipGetLastError());
-  BBX_HIP(hipStreamSynchronize(h->stream));
+// tau before the rows: none, Student-t's rule on the weighted residuals, or the
+// linear model's with the latents for y
+enum { TAU_NONE, TAU_WEIGHTED, TAU_LINEAR };
+// how 'cholesky' and 'woodbury' take a model: the linear branch at the fixed
+// precision 1 (the cached Gram), that branch at the chain's tau (the cached
+// Gram scaled), or the logit branch with per-row weights (a weighted Gram)
+enum { DIRECT_UNIT, DIRECT_TAU, DIRECT_WEIGHTS };
+
+static int probit_rows_valid(const double* outcome, const double* n_trial,
+                             const unsigned char*, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) {
+    if (!(outcome[i] == 0. || outcome[i] == 1.))
+      return fail(BBX_ERR_INVALID, "probit: outcome[" + std::to_string(i) +
+                                       "] is not 0 or 1");
+    if (n_trial && n_trial[i] != 1.)
+      return fail(BBX_ERR_INVALID,
+                  "probit: n_trial[" + std::to_string(i) +
+                      "] is not 1 (a binomial outcome is the logit model's)");
+  }
   return BBX_OK;
 }
 
-// omega | beta, tau of a Student-t chain from the psi in place, with the
-// mixing stream of iteration `it` (-1: a chain that has not run); `draw_tau`:
-// first tau | beta, omega with the weights in place (an iteration; a refresh
-// keeps its tau).  Then zbase = X~^T kappa: the one product a Student-t
-// iteration adds.  The log-likelihood partials are left in row_part[0 ..
-// *row_blocks) for launch_student_t_finish.
-static int chain_student_t_update(bbx_chain* c, int64_t it, bool draw_tau,
-                                  int* row_blocks) {
-  bbx_design* h = c->h;
-  if (draw_tau)
-    BBX_TRY(launch_student_t_tau(c, iter_stream(STREAM_OBSVAR, it)));
-  BBX_TRY(launch_student_t_mix(c, iter_stream(STREAM_MIX, it), row_blocks));
-  TdotEpilogue ep;
-  return launch_tdot(h, c->kappa.as<double>(), part_slot(h, PS_SUMW), ep,
-                     c->zbase.as<double>());
-}
-
-// psi, omega, Omega, kappa, zbase and the log-likelihood of a Student-t chain
-// recomputed from (coef, tau): omega is a function of (seed, iteration, row,
-// nu, psi, tau), so the state a finished iteration left is reproduced bit for
-// bit.  tau is not redrawn.
-static int chain_student_t_refresh(bbx_chain* c) {
-  bbx_design* h = c->h;
-  BBX_TRY(chain_linear_predictor(c));
-  int rg = 0;
-  BBX_TRY(chain_student_t_update(c, c->iter - 1, false, &rg));
-  BBX_TRY(launch_student_t_finish(c, rg));
-  BBX_HIP(hipStreamSynchronize(h->stream));
+static int student_t_rows_valid(const double* outcome, const double* n_trial,
+                                const unsigned char*, int64_t n) {
+  if (n_trial)
+    return fail(BBX_ERR_INVALID,
+                "student_t: n_trial must be NULL (the outcome is continuous)");
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(outcome[i]))
+      return fail(BBX_ERR_INVALID, "student_t: outcome[" + std::to_string(i) +
+                                       "] is not finite");
   return BBX_OK;
 }
 
-// z | beta, tau of a censored-outcome chain from the psi in place, with the
-// latent stream of iteration `it` (-1: a chain that has not run); `draw_tau`:
-// first tau | beta, z by the linear model's two kernels with the latents in
-// place for y (an iteration; a refresh keeps its tau; the log-likelihood that
-// pass writes is replaced below).  Then zbase = X~^T z: the one product a
-// censored iteration adds.  The log-likelihood partials are left in
+static int censored_rows_valid(const double* outcome, const double*,
+                               const unsigned char* status, int64_t n) {
+  if (!status)
+    return fail(BBX_ERR_INVALID,
+                "censored: the row status is NULL (bbx_chain_create_censored "
+                "creates this model)");
+  for (int64_t i = 0; i < n; ++i) {
+    if (!std::isfinite(outcome[i]))
+      return fail(BBX_ERR_INVALID, "censored: bound[" + std::to_string(i) +
+                                       "] is not finite");
+    if (status[i] > 2)
+      return fail(BBX_ERR_INVALID, "censored: status[" + std::to_string(i) +
+                                       "] is not 0, 1 or 2");
+  }
+  return BBX_OK;
+}
+
+struct LatentFamily {
+  const char* name;      // in messages
+  uint64_t stream;       // Philox stream of the row draw
+  int tau_rule;          // how an iteration draws tau before the rows
+  bool kappa;            // zbase = X~^T kappa (else X~^T latent)
+  bool row_const;        // the log-likelihood adds n x bbx_chain::df_const
+  bool has_obs_prec;     // a tau in ChainScalars::obs_prec (always one number)
+  int direct;
+  bool draws_at_create;  // create draws the rows at coef = 0 (else: the latents
+                         // at the outcome, zbase = X~^T outcome)
+  int (*rows)(bbx_chain*, uint64_t, int*);
+  int (*valid)(const double* outcome, const double* n_trial,
+               const unsigned char* status, int64_t n);
+};
+
+// The description of a latent model; nullptr for every other model
+static const LatentFamily* latent_family(int model) {
+  static const LatentFamily probit{
+      "probit", STREAM_LATENT, TAU_NONE, false, false, false, DIRECT_UNIT,
+      true, launch_latent_rows<BBX_MODEL_PROBIT>, probit_rows_valid};
+  static const LatentFamily student_t{
+      "student_t", STREAM_MIX, TAU_WEIGHTED, true, true, true, DIRECT_WEIGHTS,
+      true, launch_latent_rows<BBX_MODEL_STUDENT_T>, student_t_rows_valid};
+  static const LatentFamily censored{
+      "censored", STREAM_LATENT, TAU_LINEAR, false, false, true, DIRECT_TAU,
+      false, launch_latent_rows<BBX_MODEL_CENSORED>, censored_rows_valid};
+  switch (model) {
+    case BBX_MODEL_PROBIT: return &probit;
+    case BBX_MODEL_STUDENT_T: return &student_t;
+    case BBX_MODEL_CENSORED: return &censored;
+    default: return nullptr;
+  }
+}
+
+const char* latent_family_name(int model) {
+  const LatentFamily* f = latent_family(model);
+  return f ? f->name : nullptr;
+}
+
+// ... of any chain the direct samplers draw
+static int direct_branch(const bbx_chain* c) {
+  const LatentFamily* f = latent_family(c->model);
+  return f ? f->direct
+           : c->model == BBX_MODEL_LINEAR ? DIRECT_TAU : DIRECT_WEIGHTS;
+}
+
+// The rule of chain_obs_finish_kernel for the chain's log-likelihood
+static int finish_rule(const bbx_chain* c) {
+  const LatentFamily* f = latent_family(c->model);
+  if (f) return f->row_const ? OBS_SUM_CONST : OBS_SUM;
+  return c->model == BBX_MODEL_LOGIT ? OBS_SUM : OBS_LINEAR;
+}
+
+// Set, get and run refuse the obs_prec of a model that has none
+static int check_obs_prec(const bbx_chain* c, const void* obs_prec) {
+  const LatentFamily* f = latent_family(c->model);
+  if (obs_prec && f && !f->has_obs_prec)
+    return fail(BBX_ERR_INVALID,
+                std::string("a ") + f->name + " chain has no obs_prec");
+  return BBX_OK;
+}
+
+// The rows | beta[, tau] of a latent chain from the psi in place, with the
+// family's stream of iteration `it` (-1: the reserved index of a chain that has
+// not run); `draw_tau`: first tau by the family's rule with the rows in place
+// (an iteration; a refresh keeps its tau; the log-likelihood the linear rule
+// writes is replaced below).  Then zbase = X~^T latent or X~^T kappa: the one
+// product a latent iteration adds.  The log-likelihood partials are left in
 // row_part[0 .. *row_blocks) for chain_obs_finish_kernel.
-static int chain_censored_update(bbx_chain* c, int64_t it, bool draw_tau,
-                                 int* row_blocks) {
+static int chain_latent_update(bbx_chain* c, int64_t it, bool draw_tau,
+                               int* row_blocks) {
+  const LatentFamily* f = latent_family(c->model);
   bbx_design* h = c->h;
-  if (draw_tau) {
-    const int rg = grid_for(h->n, ROW_GRID);
+  if (draw_tau && f->tau_rule == TAU_WEIGHTED)
+    BBX_TRY(launch_student_t_tau(c, iter_stream(STREAM_OBSVAR, it)));
+  if (draw_tau && f->tau_rule == TAU_LINEAR) {
+    const int rg = row_grid(h->n);
     double* rp = c->row_part.as<double>();
     BBX_LAUNCH(chain_rss_kernel, dim3(rg), dim3(256), 0, h->stream, h->n,
                c->latent.as<double>(), c->psi.as<double>(), rp);
     BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, h->stream,
-               BBX_MODEL_LINEAR, 0, h->n, c->seed,
-               iter_stream(STREAM_OBSVAR, it), rp, rg,
-               c->scalars.as<ChainScalars>());
+               OBS_LINEAR, 0, h->n, c->seed, iter_stream(STREAM_OBSVAR, it), 0.,
+               rp, rg, c->scalars.as<ChainScalars>());
     BBX_HIP(hipGetLastError());
   }
-  BBX_TRY(launch_chain_censored(c, iter_stream(STREAM_LATENT, it), row_blocks));
+  BBX_TRY(f->rows(c, iter_stream(f->stream, it), row_blocks));
   TdotEpilogue ep;
-  return launch_tdot(h, c->latent.as<double>(), part_slot(h, PS_SUMW), ep,
-                     c->zbase.as<double>());
+  return launch_tdot(h, (f->kappa ? c->kappa : c->latent).as<double>(),
+                     part_slot(h, PS_SUMW), ep, c->zbase.as<double>());
 }
 
-// psi, z, zbase and the log-likelihood of a censored-outcome chain recomputed
-// from (coef, tau): z is a function of (seed, iteration, row, psi, tau), so the
-// state a finished iteration left is reproduced bit for bit.  tau is not
-// redrawn.
-static int chain_censored_refresh(bbx_chain* c) {
+// psi, the rows, zbase and the log-likelihood of a latent chain recomputed from
+// (coef, tau): a row's draw is a function of (seed, iteration, row, psi, tau
+// [, nu]), so the state a finished iteration left is reproduced bit for bit.
+// tau is not redrawn.
+static int chain_latent_refresh(bbx_chain* c) {
   bbx_design* h = c->h;
   BBX_TRY(chain_linear_predictor(c));
   int rg = 0;
-  BBX_TRY(chain_censored_update(c, c->iter - 1, false, &rg));
+  BBX_TRY(chain_latent_update(c, c->iter - 1, false, &rg));
   BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, h->stream,
-             c->model, 0, h->n, c->seed, 0, c->row_part.as<double>(), rg,
-             c->scalars.as<ChainScalars>());
+             finish_rule(c), 0, h->n, c->seed, 0, c->df_const,
+             c->row_part.as<double>(), rg, c->scalars.as<ChainScalars>());
   BBX_HIP(hipGetLastError());
   BBX_HIP(hipStreamSynchronize(h->stream));
   return BBX_OK;
@@ -718,7 +754,7 @@ int chain_pre_draw(bbx_chain* c) {
   ChainScalars* sc = c->scalars.as<ChainScalars>();
   // --- beta | Omega, tau, lambda  (bayesbridge.py:372-395)
   BBX_LAUNCH(chain_prior_kernel, dim3(NPART), dim3(256), 0, s, P,
-                     c->n_unshrunk, c->model, c->slab,
+                     c->n_unshrunk, direct_branch(c) == DIRECT_TAU, c->slab,
                      (long long)c->n_averaged, sc, c->lscale.as<double>(),
                      c->sd_unshrunk.as<double>(), c->mean.as<double>(),
                      c->square.as<double>(), c->zbase.as<double>(),
@@ -726,7 +762,7 @@ int chain_pre_draw(bbx_chain* c) {
                      c->sd.as<double>(), c->z.as<double>(), c->pending_store,
                      c->samp_gscale.as<double>(), c->samp_logp.as<double>());
   c->pending_store = -1;
-  if (c->model == BBX_MODEL_LINEAR || c->model == BBX_MODEL_CENSORED)
+  if (direct_branch(c) == DIRECT_TAU)
     BBX_LAUNCH(chain_fill_obs_prec_kernel, dim3(grid_for(n, ROW_GRID)),
                        dim3(256), 0, s, n, sc, c->obs_prec.as<double>());
   BBX_HIP(hipGetLastError());
@@ -877,22 +913,16 @@ int chain_post_draw(bbx_chain* c, bool have_psi, int phases,
     else if (elems >= 4) BBX_PG_LAUNCH(chain_pg_kernel<4>, 1024);
     else BBX_PG_LAUNCH(chain_pg_kernel<1>, 256);
 #undef BBX_PG_LAUNCH
-  } else if (c->model == BBX_MODEL_PROBIT) {
-    BBX_TRY(chain_probit_update(c, c->iter, &rg));
-  } else if (c->model == BBX_MODEL_STUDENT_T) {
-    BBX_TRY(chain_student_t_update(c, c->iter, true, &rg));
-  } else if (c->model == BBX_MODEL_CENSORED) {
-    BBX_TRY(chain_censored_update(c, c->iter, true, &rg));
+  } else if (latent_family(c->model)) {
+    BBX_TRY(chain_latent_update(c, c->iter, true, &rg));
   } else {
     BBX_LAUNCH(chain_rss_kernel, dim3(rg), dim3(256), 0, s, n,
                        c->outcome.as<double>(), c->psi.as<double>(), rp);
   }
-  if (c->model == BBX_MODEL_STUDENT_T)
-    BBX_TRY(launch_student_t_finish(c, rg));
-  else
-    BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, s,
-                       c->model, 0, n, c->seed,
-                       iter_stream(STREAM_OBSVAR, c->iter), rp, rg, sc);
+  BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, s,
+                     finish_rule(c), 0, n, c->seed,
+                     iter_stream(STREAM_OBSVAR, c->iter), c->df_const, rp, rg,
+                     sc);
 
   }  // POST_MAIN
 
@@ -926,16 +956,12 @@ static int chain_step(bbx_chain* c, int maxiter, double atol, int* n_cg_iter) {
       BBX_TRY(launch_fill_normal(h, h->P, cg_draw_seed(c, it), STREAM_ETA2,
                                  c->eta2_next.as<double>()));
     }
-    // (probit: the linear model's branch at the fixed precision 1 -- the
-    // cached Gram, no weighted one; Student-t: the logit model's branch with
-    // Omega = tau omega, a weighted Gram every iteration; censored: the linear
-    // model's branch as it is, the cached Gram scaled by tau)
-    const bool linear = c->model == BBX_MODEL_LINEAR ||
-                        c->model == BBX_MODEL_CENSORED;
-    const bool probit = c->model == BBX_MODEL_PROBIT;
+    // (Student-t: Omega = tau omega)
+    const int direct = direct_branch(c);
     const int st = chol_sample_device(
-        h, linear || probit ? nullptr : c->obs_prec.as<double>(), 1.,
-        linear ? &c->scalars.as<ChainScalars>()->obs_prec : nullptr,
+        h, direct == DIRECT_WEIGHTS ? c->obs_prec.as<double>() : nullptr, 1.,
+        direct == DIRECT_TAU ? &c->scalars.as<ChainScalars>()->obs_prec
+                             : nullptr,
         c->phi.as<double>(), c->z.as<double>(), c->eta2_next.as<double>(),
         c->coef.as<double>());
     c->eta_iter = -1;
@@ -960,20 +986,20 @@ static int chain_step(bbx_chain* c, int maxiter, double atol, int* n_cg_iter) {
       BBX_TRY(launch_fill_normal(h, h->P, cg_draw_seed(c, it), STREAM_ETA2,
                                  c->eta2_next.as<double>()));
     }
-    const bool censored = c->model == BBX_MODEL_CENSORED;
-    const bool linear = c->model == BBX_MODEL_LINEAR || censored;
-    const bool probit = c->model == BBX_MODEL_PROBIT;
-    // logit: kappa = Omega y (the pseudo-outcome is kappa / Omega); probit: the
-    // linear branch with the latents as outcome at the fixed precision 1;
-    // censored: the linear branch with the latents as outcome at tau
+    const LatentFamily* f = latent_family(c->model);
+    const int direct = direct_branch(c);
+    // weights: kappa = Omega y (the pseudo-outcome is kappa / Omega); a latent
+    // family on a linear branch: the latents as outcome
     const int st = woodbury_sample_device(
-        h, linear || probit ? nullptr : c->obs_prec.as<double>(), 1.,
-        linear ? &c->scalars.as<ChainScalars>()->obs_prec : nullptr,
+        h, direct == DIRECT_WEIGHTS ? c->obs_prec.as<double>() : nullptr, 1.,
+        direct == DIRECT_TAU ? &c->scalars.as<ChainScalars>()->obs_prec
+                             : nullptr,
         c->phi.as<double>(),
-        censored || probit ? c->latent.as<double>()
-        : linear           ? c->outcome.as<double>()
-                 : c->kappa.as<double>(),
-        linear || probit ? 0 : 1, c->eta1_next.as<double>(), c->eta2_next.as<double>(),
+        direct == DIRECT_WEIGHTS ? c->kappa.as<double>()
+        : f                      ? c->latent.as<double>()
+                                 : c->outcome.as<double>(),
+        direct == DIRECT_WEIGHTS ? 1 : 0, c->eta1_next.as<double>(),
+        c->eta2_next.as<double>(),
         c->coef.as<double>());
     c->eta_iter = -1;
     if (st < 0) return st;
@@ -1035,7 +1061,8 @@ int chain_save_sample(bbx_chain* c, int idx, double* d_coef, double* d_lscale,
     BBX_HIP(hipMemcpyAsync(d_lscale + (size_t)idx * n_shrunk, c->lscale.ptr,
                            sizeof(double) * (size_t)n_shrunk,
                            hipMemcpyDeviceToDevice, h->stream));
-  if (d_obs_prec && c->model != BBX_MODEL_PROBIT) {
+  const LatentFamily* f = latent_family(c->model);
+  if (d_obs_prec && (!f || f->has_obs_prec)) {
     if (c->model == BBX_MODEL_LOGIT)
       BBX_HIP(hipMemcpyAsync(d_obs_prec + (size_t)idx * n, c->obs_prec.ptr,
                              sizeof(double) * (size_t)n,
@@ -1091,44 +1118,10 @@ static int chain_create_impl(bbx_design* design, int model,
   if (!out) return fail(BBX_ERR_INVALID, "out is NULL");
   *out = nullptr;
   if (!design || !outcome) return fail(BBX_ERR_INVALID, "NULL argument");
-  if (model != BBX_MODEL_LINEAR && model != BBX_MODEL_LOGIT &&
-      model != BBX_MODEL_PROBIT && model != BBX_MODEL_STUDENT_T &&
-      model != BBX_MODEL_CENSORED)
+  const LatentFamily* f = latent_family(model);
+  if (model != BBX_MODEL_LINEAR && model != BBX_MODEL_LOGIT && !f)
     return fail(BBX_ERR_INVALID, "unknown model");
-  if (model == BBX_MODEL_CENSORED) {
-    if (!status)
-      return fail(BBX_ERR_INVALID,
-                  "censored: the row status is NULL (bbx_chain_create_censored "
-                  "creates this model)");
-    for (int64_t i = 0; i < design->n; ++i) {
-      if (!std::isfinite(outcome[i]))
-        return fail(BBX_ERR_INVALID, "censored: bound[" + std::to_string(i) +
-                                         "] is not finite");
-      if (status[i] > 2)
-        return fail(BBX_ERR_INVALID, "censored: status[" + std::to_string(i) +
-                                         "] is not 0, 1 or 2");
-    }
-  }
-  if (model == BBX_MODEL_STUDENT_T) {
-    if (n_trial)
-      return fail(BBX_ERR_INVALID,
-                  "student_t: n_trial must be NULL (the outcome is continuous)");
-    for (int64_t i = 0; i < design->n; ++i)
-      if (!std::isfinite(outcome[i]))
-        return fail(BBX_ERR_INVALID, "student_t: outcome[" +
-                                         std::to_string(i) + "] is not finite");
-  }
-  if (model == BBX_MODEL_PROBIT) {
-    for (int64_t i = 0; i < design->n; ++i) {
-      if (!(outcome[i] == 0. || outcome[i] == 1.))
-        return fail(BBX_ERR_INVALID, "probit: outcome[" + std::to_string(i) +
-                                         "] is not 0 or 1");
-      if (n_trial && n_trial[i] != 1.)
-        return fail(BBX_ERR_INVALID,
-                    "probit: n_trial[" + std::to_string(i) +
-                        "] is not 1 (a binomial outcome is the logit model's)");
-    }
-  }
+  if (f) BBX_TRY(f->valid(outcome, n_trial, status, design->n));
   if (n_unshrunk < 0 || n_unshrunk > design->P)
     return fail(BBX_ERR_INVALID, "n_unshrunk out of range");
   if (n_unshrunk > 0 && !sd_unshrunk)
@@ -1155,11 +1148,9 @@ static int chain_create_impl(bbx_design* design, int model,
     BBX_TRY(c->kappa.alloc(nb));
     BBX_TRY(c->obs_prec.alloc(nb));
     BBX_TRY(c->psi.alloc(nb));
-    if (model == BBX_MODEL_PROBIT || model == BBX_MODEL_STUDENT_T ||
-        model == BBX_MODEL_CENSORED)
-      BBX_TRY(c->latent.alloc(nb));
-    if (model == BBX_MODEL_CENSORED) {
-      // z = b: the latents start at the bounds, zbase below at X~^T b
+    if (f) BBX_TRY(c->latent.alloc(nb));
+    if (status) {
+      // (censored) z = b: the latents start at the bounds, zbase below at X~^T b
       BBX_TRY(c->status.alloc((size_t)n));
       BBX_HIP(hipMemcpy(c->status.ptr, status, (size_t)n,
                         hipMemcpyHostToDevice));
@@ -1197,9 +1188,8 @@ static int chain_create_impl(bbx_design* design, int model,
                          c->n_trial.as<double>(), c->kappa.as<double>());
       src = c->kappa.as<double>();
     }
-    // (probit: zbase = X~^T z, from the latents drawn below; Student-t:
-    // X~^T kappa, from the weights drawn below)
-    if (model != BBX_MODEL_PROBIT && model != BBX_MODEL_STUDENT_T) {
+    // (a family that draws at create: zbase from the rows drawn below)
+    if (!f || !f->draws_at_create) {
       BBX_TRY(launch_sum_n(h, src, n, part_slot(h, PS_SUMW)));
       TdotEpilogue ep;
       BBX_TRY(launch_tdot(h, src, part_slot(h, PS_SUMW), ep,
@@ -1233,19 +1223,15 @@ static int chain_create_impl(bbx_design* design, int model,
                          c->psi.as<double>(), c->obs_prec.as<double>());
     else
       BBX_HIP(hipMemsetAsync(c->obs_prec.ptr, 0, nb, h->stream));
-    if (model == BBX_MODEL_PROBIT) {
-      // Omega = I, filled once (the scalar obs_prec stays 1), and the latents
-      // of coef = 0 on the reserved stream index
+    // (probit) Omega = I, filled once: the scalar obs_prec stays 1
+    if (f && f->direct == DIRECT_UNIT)
       BBX_LAUNCH(chain_fill_obs_prec_kernel, dim3(grid_for(n, ROW_GRID)),
                  dim3(256), 0, h->stream, n, c->scalars.as<ChainScalars>(),
                  c->obs_prec.as<double>());
-      BBX_TRY(chain_probit_refresh(c));
-    }
-    if (model == BBX_MODEL_STUDENT_T) {
-      // nu = 4, tau = 1, and the weights of coef = 0 on the reserved stream index
-      c->df_const = student_t_row_const(c->df);
-      BBX_TRY(chain_student_t_refresh(c));
-    }
+    // (Student-t) nu = 4, tau = 1
+    if (f && f->row_const) c->df_const = student_t_row_const(c->df);
+    // the rows of coef = 0 on the reserved stream index
+    if (f && f->draws_at_create) BBX_TRY(chain_latent_refresh(c));
     BBX_HIP(hipGetLastError());
     BBX_HIP(hipStreamSynchronize(h->stream));
     return BBX_OK;
@@ -1313,8 +1299,7 @@ static int bbx_chain_set_state_impl(bbx_chain* c, const double* coef,
   if (coef)
     BBX_HIP(hipMemcpy(c->coef.ptr, coef, sizeof(double) * (size_t)h->P,
                       hipMemcpyHostToDevice));
-  if (obs_prec && c->model == BBX_MODEL_PROBIT)
-    return fail(BBX_ERR_INVALID, "a probit chain has no obs_prec");
+  BBX_TRY(check_obs_prec(c, obs_prec));
   ChainScalars sc;
   BBX_HIP(hipMemcpy(&sc, c->scalars.ptr, sizeof(sc), hipMemcpyDeviceToHost));
   if (obs_prec) {
@@ -1330,9 +1315,7 @@ static int bbx_chain_set_state_impl(bbx_chain* c, const double* coef,
                       hipMemcpyHostToDevice));
   if (gscale) sc.gscale = *gscale;
   BBX_HIP(hipMemcpy(c->scalars.ptr, &sc, sizeof(sc), hipMemcpyHostToDevice));
-  if (c->model == BBX_MODEL_PROBIT) BBX_TRY(chain_probit_refresh(c));
-  if (c->model == BBX_MODEL_STUDENT_T) BBX_TRY(chain_student_t_refresh(c));
-  if (c->model == BBX_MODEL_CENSORED) BBX_TRY(chain_censored_refresh(c));
+  if (latent_family(c->model)) BBX_TRY(chain_latent_refresh(c));
   return BBX_OK;
 }
 
@@ -1349,8 +1332,7 @@ static int bbx_chain_get_state_impl(bbx_chain* c, double* coef, double* obs_prec
                         double* lscale, double* gscale) {
   BBX_TRY(chain_check(c));
   bbx_design* h = c->h;
-  if (obs_prec && c->model == BBX_MODEL_PROBIT)
-    return fail(BBX_ERR_INVALID, "a probit chain has no obs_prec");
+  BBX_TRY(check_obs_prec(c, obs_prec));
   BBX_HIP(hipSetDevice(h->device));
   BBX_HIP(hipStreamSynchronize(h->stream));
   if (coef)
@@ -1495,8 +1477,7 @@ int bbx_chain_get_logp(bbx_chain* c, double* loglik, double* logp) {
 int bbx_chain_get_latent(bbx_chain* c, double* out) {
   return no_throw([&]() -> int {
     BBX_TRY(chain_check(c));
-    if (c->model != BBX_MODEL_PROBIT && c->model != BBX_MODEL_STUDENT_T &&
-        c->model != BBX_MODEL_CENSORED)
+    if (!latent_family(c->model))
       return fail(BBX_ERR_INVALID,
                   "bbx_chain_get_latent: not a probit, student_t or censored "
                   "chain");
@@ -1520,7 +1501,7 @@ int bbx_chain_set_df(bbx_chain* c, double df) {
     BBX_HIP(hipSetDevice(c->h->device));
     c->df = df;
     c->df_const = student_t_row_const(df);
-    return chain_student_t_refresh(c);
+    return chain_latent_refresh(c);
   });
 }
 
@@ -1551,45 +1532,27 @@ int bbx_chain_init_obs_prec(bbx_chain* c) {
   BBX_TRY(chain_check(c));
   bbx_design* h = c->h;
   BBX_HIP(hipSetDevice(h->device));
-  if (c->model == BBX_MODEL_PROBIT) return chain_probit_refresh(c);
+  const LatentFamily* f = latent_family(c->model);
+  if (f && !f->has_obs_prec) return chain_latent_refresh(c);
   BBX_TRY(chain_linear_predictor(c));
   const int rg = grid_for(h->n, ROW_GRID);
-  if (c->model == BBX_MODEL_STUDENT_T) {
-    // tau = 1 / mean(r^2), the linear model's rule, then the weights under it
-    double* rp = c->row_part.as<double>();
-    BBX_LAUNCH(chain_rss_kernel, dim3(rg), dim3(256), 0, h->stream, h->n,
-               c->outcome.as<double>(), c->psi.as<double>(), rp);
-    BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, h->stream,
-               BBX_MODEL_LINEAR, 1, h->n, c->seed, 0, rp, rg,
-               c->scalars.as<ChainScalars>());
-    BBX_HIP(hipGetLastError());
-    return chain_student_t_refresh(c);
-  }
-  if (c->model == BBX_MODEL_CENSORED) {
-    // tau = 1 / mean((b - psi)^2), the linear model's rule on the bounds, then
-    // the latents under it
-    double* rp = c->row_part.as<double>();
-    BBX_LAUNCH(chain_rss_kernel, dim3(rg), dim3(256), 0, h->stream, h->n,
-               c->outcome.as<double>(), c->psi.as<double>(), rp);
-    BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0, h->stream,
-               BBX_MODEL_LINEAR, 1, h->n, c->seed, 0, rp, rg,
-               c->scalars.as<ChainScalars>());
-    BBX_HIP(hipGetLastError());
-    return chain_censored_refresh(c);
-  }
   if (c->model == BBX_MODEL_LOGIT) {
     BBX_LAUNCH(chain_pg_mean_kernel, dim3(rg), dim3(256), 0, h->stream,
                        h->n, c->n_trial.as<double>(), c->psi.as<double>(),
                        c->obs_prec.as<double>());
   } else {
+    // tau = 1 / mean(r^2), r = outcome - psi: the linear model's rule (censored:
+    // on the bounds)
     double* rp = c->row_part.as<double>();
     BBX_LAUNCH(chain_rss_kernel, dim3(rg), dim3(256), 0, h->stream,
                        h->n, c->outcome.as<double>(), c->psi.as<double>(), rp);
     BBX_LAUNCH(chain_obs_finish_kernel, dim3(1), dim3(256), 0,
-                       h->stream, c->model, 1, h->n, c->seed, 0, rp, rg,
+                       h->stream, OBS_LINEAR, 1, h->n, c->seed, 0, 0., rp, rg,
                        c->scalars.as<ChainScalars>());
   }
   BBX_HIP(hipGetLastError());
+  // ... then a latent family's rows under it
+  if (f) return chain_latent_refresh(c);
   BBX_HIP(hipStreamSynchronize(h->stream));
   return BBX_OK;
 }
@@ -1601,8 +1564,7 @@ static int bbx_chain_run_impl(bbx_chain* c, int n_iter, int n_burnin, int thin,
   BBX_TRY(chain_check(c));
   if (n_iter < 0 || n_burnin < 0 || thin < 1 || n_burnin > n_iter)
     return fail(BBX_ERR_INVALID, "bad n_iter / n_burnin / thin");
-  if (d_obs_prec && c->model == BBX_MODEL_PROBIT)
-    return fail(BBX_ERR_INVALID, "a probit chain has no obs_prec");
+  BBX_TRY(check_obs_prec(c, d_obs_prec));
   bbx_design* h = c->h;
   BBX_HIP(hipSetDevice(h->device));
   const int64_t P = h->P;
@@ -1662,8 +1624,7 @@ static int bbx_chain_run_host_impl(bbx_chain* c, int n_iter, int n_burnin, int t
   BBX_TRY(chain_check(c));
   if (n_iter < 0 || n_burnin < 0 || thin < 1 || n_burnin > n_iter)
     return fail(BBX_ERR_INVALID, "bad n_iter / n_burnin / thin");
-  if (obs_prec && c->model == BBX_MODEL_PROBIT)
-    return fail(BBX_ERR_INVALID, "a probit chain has no obs_prec");
+  BBX_TRY(check_obs_prec(c, obs_prec));
   bbx_design* h = c->h;
   BBX_HIP(hipSetDevice(h->device));
   const int64_t P = h->P, n = h->n;
@@ -1857,8 +1818,7 @@ int bbx_chain_set_coef_sampler(bbx_chain* c, int sampler) {
       return fail(BBX_ERR_INVALID,
                   "the woodbury sampler needs a dense design (this one is sparse)");
     if (sampler == BBX_SAMPLER_WOODBURY && c->model != BBX_MODEL_LINEAR &&
-        c->model != BBX_MODEL_LOGIT && c->model != BBX_MODEL_PROBIT &&
-        c->model != BBX_MODEL_STUDENT_T && c->model != BBX_MODEL_CENSORED)
+        c->model != BBX_MODEL_LOGIT && !latent_family(c->model))
       return fail(BBX_ERR_INVALID,
                   "the woodbury sampler draws linear, logit, probit, student_t "
                   "and censored models only");

@@ -111,37 +111,79 @@ int chain_save_sample(bbx_chain* c, int idx, double* d_coef, double* d_lscale,
                       double* d_obs_prec);
 int chain_end_run(bbx_chain* c, int n_sample, double* gscale, double* logp);
 
-// z | beta of a probit chain (probit.hip), on the design's stream: latent_i ~
-// N(psi_i, 1) on the half-line outcome_i selects, element i from Philox(seed,
-// stream, i, trial); the partials of sum_i log Phi(+-psi_i) into row_part[0 ..
-// *row_blocks) and the NPART partials of sum_i latent_i into the design's
-// PS_SUMW slot, what launch_tdot(latent) reads.
-int launch_chain_probit(bbx_chain* c, uint64_t stream, int* row_blocks);
 // The `count` (<= ROW_GRID) block sums of an n-vector w folded onto the NPART
 // slots of the design's PS_SUMW that launch_tdot(w) re-adds: slot t takes
 // blocks t, t + NPART, ... in that order (chain.hip).
 int launch_sumw_fold(bbx_design* h, const double* block_sums, int count);
 
-// The Student-t model's updates (student_t.hip), on the design's stream, from
-// the psi in place.  launch_student_t_tau: S = sum_i latent_i (y_i - psi_i)^2
-// with the weights in place, then scalars->obs_prec = gamma_draw(Philox(seed,
-// stream, 0), n/2) / (S/2).  launch_student_t_mix: with that obs_prec (tau),
-// latent_i = gamma_draw(Philox(seed, stream, i), (df+1)/2) / ((df + tau
-// r_i^2)/2), obs_prec_i = tau latent_i, kappa_i = obs_prec_i y_i; the
-// log-likelihood partials into row_part[0 .. *row_blocks), the partials of
-// sum_i kappa_i into PS_SUMW.  launch_student_t_finish sums the former into
-// scalars->loglik.  student_t_row_const: the log-likelihood's per-row constant.
+// The row update of a latent family (probit.hip, student_t.hip, censored.hip:
+// each defines its model's specialisation on latent_rows.hpp, which states
+// what the call leaves where), and what the Student-t model needs besides:
+// launch_student_t_tau draws scalars->obs_prec = gamma_draw(Philox(seed,
+// stream, 0), n/2) / (S/2), S = sum_i latent_i (y_i - psi_i)^2 with the
+// weights in place; student_t_row_const is the log-likelihood's row constant.
+// latent_family_name: a latent model's name in messages, else nullptr.
+template <int MODEL>
+int launch_latent_rows(bbx_chain* c, uint64_t stream, int* row_blocks);
+template <> int launch_latent_rows<BBX_MODEL_PROBIT>(bbx_chain*, uint64_t, int*);
+template <> int launch_latent_rows<BBX_MODEL_STUDENT_T>(bbx_chain*, uint64_t, int*);
+template <> int launch_latent_rows<BBX_MODEL_CENSORED>(bbx_chain*, uint64_t, int*);
 int launch_student_t_tau(bbx_chain* c, uint64_t stream);
-int launch_student_t_mix(bbx_chain* c, uint64_t stream, int* row_blocks);
-int launch_student_t_finish(bbx_chain* c, int row_blocks);
 double student_t_row_const(double nu);
+const char* latent_family_name(int model);
 
-// z | beta, tau of a censored-outcome chain (censored.hip), on the design's
-// stream, under the tau in scalars->obs_prec: latent_i = outcome_i on an
-// observed row, else outcome_i + u / sqrt(tau) with u the truncated normal at
-// (psi_i - outcome_i) sqrt(tau), row i from Philox(seed, stream, i, trial); the
-// log-likelihood partials into row_part[0 .. *row_blocks), the partials of
-// sum_i latent_i into PS_SUMW.
-int launch_chain_censored(bbx_chain* c, uint64_t stream, int* row_blocks);
+// ---- what the n-length kernels of chain.hip and of the latent families share
+
+inline int grid_for(int64_t len, int cap) {
+  int64_t nb = (len + 255) / 256;
+  if (nb > cap) nb = cap;
+  if (nb < 1) nb = 1;
+  return (int)nb;
+}
+
+// The grid of a row kernel: from ROW_GRID x 256 rows on a lane takes a second
+// row.
+inline int row_grid(int64_t n) { return grid_for(n, ROW_GRID); }
+
+// Block totals of blocks of 256 in a fixed order: the waves' sums, added by
+// thread 0 in index order.  Thread 0 holds the result.
+__device__ inline double block_total_256(double x) {
+  __shared__ double s_w[256 / WAVE];
+  x = wave_allsum(x);
+  if ((threadIdx.x & (WAVE - 1)) == 0) s_w[threadIdx.x / WAVE] = x;
+  __syncthreads();
+  double r = 0.;
+  if (threadIdx.x == 0)
+    for (int k = 0; k < 256 / WAVE; ++k) r += s_w[k];
+  __syncthreads();
+  return r;  // thread 0 only
+}
+
+// ... of two lane values at once, in place
+__device__ inline void block_totals_256(double& a, double& b) {
+  __shared__ double s_a[256 / WAVE], s_b[256 / WAVE];
+  a = wave_allsum(a);
+  b = wave_allsum(b);
+  if ((threadIdx.x & (WAVE - 1)) == 0) {
+    s_a[threadIdx.x / WAVE] = a;
+    s_b[threadIdx.x / WAVE] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a = 0.;
+    b = 0.;
+    for (int k = 0; k < 256 / WAVE; ++k) {
+      a += s_a[k];
+      b += s_b[k];
+    }
+  }
+}
+
+// One block: `count` partials, lane t taking t, t + 256, ... in that order
+__device__ inline double sum_row_parts(const double* part, int count) {
+  double acc = 0.;
+  for (int k = threadIdx.x; k < count; k += 256) acc += part[k];
+  return block_total_256(acc);
+}
 
 }  // namespace bbx

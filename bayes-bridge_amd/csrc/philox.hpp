@@ -86,8 +86,8 @@ enum PhiloxStream : uint64_t {
   STREAM_GSCALE = 4, // bayesbridge.py:438
   STREAM_LSCALE = 5, // bayesbridge.py:463
   STREAM_OBSVAR = 6, // bayesbridge.py:403
-  STREAM_LATENT = 7, // the probit model's truncated-normal latents (probit.hip)
-  STREAM_MIX = 8     // the Student-t model's mixing weights (student_t.hip)
+  STREAM_LATENT = 7, // the probit and censored models' latents (latent_rows.hpp)
+  STREAM_MIX = 8     // the Student-t model's mixing weights (latent_rows.hpp)
 };
 
 }  // namespace bbx

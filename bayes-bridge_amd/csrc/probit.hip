@@ -5,6 +5,9 @@
 // on the way.  The stand-alone sampler bbx_device_truncated_normal lives here
 // too.
 //
+// The row kernel, its launch and the sampler's host front are
+// latent_rows.hpp's; this file states the per-row expressions.
+//
 // One lane per row.  A trial is one Philox block, one log and either a sqrt
 // and a cospi or an exp; every trial is accepted with probability >= 1/2, so
 // a wave of 64 rows waits ~7 trials for its slowest lane.  Trial t of element i
@@ -12,9 +15,7 @@
 // i, psi_i, y_i) alone, whatever the grid.
 #include <cmath>
 
-#include "chain.hpp"
-#include "philox.hpp"
-#include "samplers.hpp"
+#include "latent_rows.hpp"
 
 namespace bbx {
 
@@ -28,76 +29,41 @@ __device__ inline double probit_draw(uint64_t seed, uint64_t stream, int64_t i,
       positive, nullptr);
 }
 
-// block totals of two lane values (thread 0 holds them), fixed order
-__device__ inline void block_totals_256(double& a, double& b) {
-  __shared__ double s_a[256 / WAVE], s_b[256 / WAVE];
-  a = wave_allsum(a);
-  b = wave_allsum(b);
-  if ((threadIdx.x & (WAVE - 1)) == 0) {
-    s_a[threadIdx.x / WAVE] = a;
-    s_b[threadIdx.x / WAVE] = b;
+// Y: double (a chain's outcome) or unsigned char (the stand-alone sampler's
+// `positive`); the sums are those of log Phi(s_i psi_i) and of z_i.
+template <class Y>
+struct ProbitRows {
+  const Y* __restrict__ y;
+  const double* __restrict__ psi;
+  double* __restrict__ latent;
+  static constexpr bool reads_tau = false;
+  struct Once {};
+  __device__ Once once(double) const { return {}; }
+  __device__ double draw(const Once&, uint64_t seed, uint64_t stream,
+                         int64_t i) const {
+    return probit_draw(seed, stream, i, psi[i], y[i] != 0);
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a = 0.;
-    b = 0.;
-    for (int k = 0; k < 256 / WAVE; ++k) {
-      a += s_a[k];
-      b += s_b[k];
-    }
-  }
-}
-
-// ll_part[b], z_part[b]: block b's sums of log Phi(s_i psi_i) and of z_i.
-__global__ __launch_bounds__(256) void chain_probit_kernel(
-    int64_t n, uint64_t seed, uint64_t stream, const double* __restrict__ y,
-    const double* __restrict__ psi, double* __restrict__ latent,
-    double* __restrict__ ll_part, double* __restrict__ z_part) {
-  double ll = 0., zs = 0.;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * 256) {
+  __device__ void row(const Once&, uint64_t seed, uint64_t stream, int64_t i,
+                      double& ll, double& w) const {
     const double eta = psi[i];
     const bool positive = y[i] != 0.;
     const double z = probit_draw(seed, stream, i, eta, positive);
     latent[i] = z;
-    zs += z;
-    ll += log_norm_cdf(positive ? eta : -eta);
+    w = z;
+    ll = log_norm_cdf(positive ? eta : -eta);
   }
-  block_totals_256(ll, zs);
-  if (threadIdx.x == 0) {
-    ll_part[blockIdx.x] = ll;
-    z_part[blockIdx.x] = zs;
-  }
-}
-
-__global__ __launch_bounds__(256) void dev_truncated_normal_kernel(
-    int64_t n, uint64_t seed, const double* __restrict__ psi,
-    const unsigned char* __restrict__ positive, double* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * 256)
-    out[i] = probit_draw(seed, STREAM_LATENT, i, psi[i], positive[i] != 0);
-}
-
-int row_grid(int64_t n) {
-  int64_t nb = (n + 255) / 256;
-  if (nb > ROW_GRID) nb = ROW_GRID;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
+};
 
 }  // namespace
 
-int launch_chain_probit(bbx_chain* c, uint64_t stream, int* row_blocks) {
-  bbx_design* h = c->h;
-  const int rg = row_grid(h->n);
-  double* rp = c->row_part.as<double>();
-  BBX_LAUNCH(chain_probit_kernel, dim3(rg), dim3(256), 0, h->stream, h->n,
-             c->seed, stream, c->outcome.as<double>(), c->psi.as<double>(),
-             c->latent.as<double>(), rp, rp + ROW_GRID);
-  BBX_HIP(hipGetLastError());
-  BBX_TRY(launch_sumw_fold(h, rp + ROW_GRID, rg));
-  if (row_blocks) *row_blocks = rg;
-  return BBX_OK;
+template <>
+int launch_latent_rows<BBX_MODEL_PROBIT>(bbx_chain* c, uint64_t stream,
+                                         int* row_blocks) {
+  return launch_rows(c, stream,
+                     ProbitRows<double>{c->outcome.as<double>(),
+                                        c->psi.as<double>(),
+                                        c->latent.as<double>()},
+                     row_blocks);
 }
 
 }  // namespace bbx
@@ -108,32 +74,18 @@ static int device_truncated_normal_impl(int device, uint64_t seed,
                                         int64_t n_draw, const double* psi,
                                         const unsigned char* positive,
                                         double* out) {
-  const char* who = "bbx_device_truncated_normal: ";
-  if (n_draw < 0) return fail(BBX_ERR_INVALID, std::string(who) + "n_draw < 0");
+  const std::string who = "bbx_device_truncated_normal: ";
+  if (n_draw < 0) return fail(BBX_ERR_INVALID, who + "n_draw < 0");
   if (!psi || !positive || !out)
-    return fail(BBX_ERR_INVALID, std::string(who) + "NULL argument");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return fail(BBX_ERR_NODEVICE, "no HIP device visible");
-  if (device < 0 || device >= count)
-    return fail(BBX_ERR_INVALID, std::string(who) + "device index out of range");
-  if (n_draw == 0) return BBX_OK;
-  BBX_HIP(hipSetDevice(device));
-  DevMem dp, ds, dout;
-  BBX_TRY(dp.alloc(sizeof(double) * (size_t)n_draw));
-  BBX_TRY(ds.alloc((size_t)n_draw));
-  BBX_TRY(dout.alloc(sizeof(double) * (size_t)n_draw));
-  BBX_HIP(hipMemcpy(dp.ptr, psi, sizeof(double) * (size_t)n_draw,
-                    hipMemcpyHostToDevice));
-  BBX_HIP(hipMemcpy(ds.ptr, positive, (size_t)n_draw, hipMemcpyHostToDevice));
-  // (the chain's grid: from ROW_GRID x 256 rows on a lane takes a second row)
-  BBX_LAUNCH(dev_truncated_normal_kernel, dim3(row_grid(n_draw)), dim3(256), 0,
-             0, n_draw, seed, dp.as<double>(), ds.as<unsigned char>(),
-             dout.as<double>());
-  BBX_HIP(hipGetLastError());
-  BBX_HIP(hipMemcpy(out, dout.ptr, sizeof(double) * (size_t)n_draw,
-                    hipMemcpyDeviceToHost));
-  return BBX_OK;
+    return fail(BBX_ERR_INVALID, who + "NULL argument");
+  return device_latent_draw(
+      who, device, seed, n_draw, 0.,
+      {{psi, sizeof(double) * (size_t)n_draw}, {positive, (size_t)n_draw}},
+      [](const DevMem* d) {
+        return ProbitRows<unsigned char>{d[1].as<unsigned char>(),
+                                         d[0].as<double>(), nullptr};
+      },
+      out);
 }
 
 extern "C" int bbx_device_truncated_normal(int device, uint64_t seed,

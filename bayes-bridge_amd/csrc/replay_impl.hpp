@@ -222,7 +222,7 @@ inline void tilted_stable(uint64_t seed, uint64_t stream, int64_t n, double a,
   }
 }
 
-// chain_probit_kernel / dev_truncated_normal_kernel (probit.hip): trials 0, 1,
+// latent_row_kernel / latent_draw_kernel<ProbitRows> (probit.hip): trials 0, 1,
 // 2, ... of element i in order, trial t on sub-stream t; the first accepted
 // proposal is the draw.  trials[i]: trials made (0: psi was not finite).
 inline void truncated_normal(uint64_t seed, uint64_t stream, int64_t n,

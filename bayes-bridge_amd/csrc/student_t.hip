@@ -7,46 +7,27 @@
 //   pass B   omega_i = gamma_draw((nu+1)/2) / ((nu + tau r_i^2)/2) on
 //            STREAM_MIX with the NEW tau; Omega_i = tau omega_i, kappa_i =
 //            Omega_i y_i, the block sums of kappa and of the log-likelihood
-//   finish   the log-likelihood partials summed in fixed order
+//   finish   the log-likelihood partials summed in fixed order, plus n times
+//            the row constant lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(nu/2)
+//            (chain.hip's finish kernel)
 //
 // tau is drawn before omega so that what an iteration leaves -- (beta, tau,
 // omega) with omega drawn under that beta and that tau -- is a function of
 // (beta, tau, seed, iteration): a refresh reproduces it without a redraw of
 // tau.
 //
-// Pass B is one lane per row.  gamma_draw accepts ~95 % of its proposals and
+// Pass B is latent_rows.hpp's row kernel with this file's per-row expression.
+// It is one lane per row.  gamma_draw accepts ~95 % of its proposals and
 // branches on (seed, stream, row, nu) alone, never on the data: a wave of 64
 // rows waits for its slowest lane (P(all 64 accept at once) ~ 4 %, two rounds
 // nearly always), and the data-dependent rate divides the draw afterwards.
 #include <cmath>
 
-#include "chain.hpp"
-#include "philox.hpp"
-#include "samplers.hpp"
+#include "latent_rows.hpp"
 
 namespace bbx {
 
 namespace {
-
-// block total of a lane value (thread 0 holds it), fixed order
-__device__ inline double block_total(double x) {
-  __shared__ double s_w[256 / WAVE];
-  x = wave_allsum(x);
-  if ((threadIdx.x & (WAVE - 1)) == 0) s_w[threadIdx.x / WAVE] = x;
-  __syncthreads();
-  double r = 0.;
-  if (threadIdx.x == 0)
-    for (int k = 0; k < 256 / WAVE; ++k) r += s_w[k];
-  __syncthreads();
-  return r;
-}
-
-// one block: the `count` partials in the order of chain.hip's sum_row_parts
-__device__ inline double sum_parts(const double* part, int count) {
-  double acc = 0.;
-  for (int k = threadIdx.x; k < count; k += 256) acc += part[k];
-  return block_total(acc);
-}
 
 // pass A: part[b] = block b's sum of omega_i (y_i - psi_i)^2
 __global__ __launch_bounds__(256) void student_t_wrss_kernel(
@@ -58,7 +39,7 @@ __global__ __launch_bounds__(256) void student_t_wrss_kernel(
     const double r = y[i] - psi[i];
     acc += omega[i] * (r * r);
   }
-  const double tot = block_total(acc);
+  const double tot = block_total_256(acc);
   if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
@@ -67,69 +48,51 @@ __global__ __launch_bounds__(256) void student_t_wrss_kernel(
 __global__ __launch_bounds__(256) void student_t_tau_kernel(
     int64_t n, uint64_t seed, uint64_t stream, const double* __restrict__ part,
     int count, ChainScalars* __restrict__ sc) {
-  const double S = sum_parts(part, count);
+  const double S = sum_row_parts(part, count);
   if (threadIdx.x != 0) return;
   Philox g(seed, stream, 0);
   sc->obs_prec = gamma_draw(g, (double)n / 2.) / (S / 2.);
 }
 
-// pass B.  ll_part[b], k_part[b]: block b's sums of the log-likelihood terms
-// 1/2 log tau - (nu+1)/2 log1p(tau r^2 / nu) and of kappa_i.  A residual that
-// is not finite gives a NaN weight and a NaN term (the draw itself never looks
-// at the data, so no row can loop on one).
-__global__ __launch_bounds__(256) void student_t_mix_kernel(
-    int64_t n, uint64_t seed, uint64_t stream, double nu,
-    const ChainScalars* __restrict__ sc, const double* __restrict__ y,
-    const double* __restrict__ psi, double* __restrict__ latent,
-    double* __restrict__ obs_prec, double* __restrict__ kappa,
-    double* __restrict__ ll_part, double* __restrict__ k_part) {
-  const double tau = sc->obs_prec;
-  const double shape = (nu + 1.) / 2.;
-  const double hlt = 0.5 * log(tau);
-  double ll = 0., ks = 0.;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * 256) {
+// pass B.  The sums are those of the log-likelihood terms 1/2 log tau -
+// (nu+1)/2 log1p(tau r^2 / nu) and of kappa_i.  A residual that is not finite
+// gives a NaN weight and a NaN term (the draw itself never looks at the data,
+// so no row can loop on one).
+struct StudentTRows {
+  double nu;
+  const double* __restrict__ y;
+  const double* __restrict__ psi;
+  double* __restrict__ latent;
+  double* __restrict__ obs_prec;
+  double* __restrict__ kappa;
+  static constexpr bool reads_tau = true;
+  struct Once {
+    double tau, shape, hlt;
+  };
+  __device__ Once once(double tau) const {
+    return {tau, (nu + 1.) / 2., 0.5 * log(tau)};
+  }
+  __device__ void row(const Once& c, uint64_t seed, uint64_t stream, int64_t i,
+                      double& ll, double& ks) const {
     const double yi = y[i];
     const double r = yi - psi[i];
-    const double q = tau * (r * r);
+    const double q = c.tau * (r * r);
     Philox g(seed, stream, (uint64_t)i);
-    double om = gamma_draw(g, shape) / ((nu + q) / 2.);
-    double term = hlt - shape * log1p(q / nu);
+    double om = gamma_draw(g, c.shape) / ((nu + q) / 2.);
+    double term = c.hlt - c.shape * log1p(q / nu);
     if (!(fabs(r) <= 1.7e308)) {
       om = r - r;
       term = om;
     }
-    const double w = tau * om;
+    const double w = c.tau * om;
     const double k = w * yi;
     latent[i] = om;
     obs_prec[i] = w;
     kappa[i] = k;
-    ks += k;
-    ll += term;
+    ks = k;
+    ll = term;
   }
-  const double tl = block_total(ll);
-  const double tk = block_total(ks);
-  if (threadIdx.x == 0) {
-    ll_part[blockIdx.x] = tl;
-    k_part[blockIdx.x] = tk;
-  }
-}
-
-// loglik = sum of the partials + n [lgamma((nu+1)/2) - lgamma(nu/2) -
-// 1/2 log(nu/2)], the bracket from the host (single block)
-__global__ __launch_bounds__(256) void student_t_finish_kernel(
-    int64_t n, double row_const, const double* __restrict__ part, int count,
-    ChainScalars* __restrict__ sc) {
-  const double tot = sum_parts(part, count);
-  if (threadIdx.x == 0) sc->loglik = tot + (double)n * row_const;
-}
-
-int row_grid(int64_t n) {
-  int64_t nb = (n + 255) / 256;
-  if (nb > ROW_GRID) nb = ROW_GRID;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
+};
 
 }  // namespace
 
@@ -151,28 +114,15 @@ int launch_student_t_tau(bbx_chain* c, uint64_t stream) {
   return BBX_OK;
 }
 
-int launch_student_t_mix(bbx_chain* c, uint64_t stream, int* row_blocks) {
-  bbx_design* h = c->h;
-  const int rg = row_grid(h->n);
-  double* rp = c->row_part.as<double>();
-  BBX_LAUNCH(student_t_mix_kernel, dim3(rg), dim3(256), 0, h->stream, h->n,
-             c->seed, stream, c->df, c->scalars.as<ChainScalars>(),
-             c->outcome.as<double>(), c->psi.as<double>(),
-             c->latent.as<double>(), c->obs_prec.as<double>(),
-             c->kappa.as<double>(), rp, rp + ROW_GRID);
-  BBX_HIP(hipGetLastError());
-  BBX_TRY(launch_sumw_fold(h, rp + ROW_GRID, rg));
-  if (row_blocks) *row_blocks = rg;
-  return BBX_OK;
-}
-
-int launch_student_t_finish(bbx_chain* c, int row_blocks) {
-  bbx_design* h = c->h;
-  BBX_LAUNCH(student_t_finish_kernel, dim3(1), dim3(256), 0, h->stream, h->n,
-             c->df_const, c->row_part.as<double>(), row_blocks,
-             c->scalars.as<ChainScalars>());
-  BBX_HIP(hipGetLastError());
-  return BBX_OK;
+template <>
+int launch_latent_rows<BBX_MODEL_STUDENT_T>(bbx_chain* c, uint64_t stream,
+                                            int* row_blocks) {
+  return launch_rows(
+      c, stream,
+      StudentTRows{c->df, c->outcome.as<double>(), c->psi.as<double>(),
+                   c->latent.as<double>(), c->obs_prec.as<double>(),
+                   c->kappa.as<double>()},
+      row_blocks);
 }
 
 }  // namespace bbx

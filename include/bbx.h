@@ -2085,7 +2085,7 @@ int bbx_replay_polya_gamma(uint64_t seed, uint64_t stream, int64_t n,
 int bbx_replay_tilted_stable(uint64_t seed, uint64_t stream, int64_t n,
                              double char_exp, const double* tilt, int variant,
                              double* out, int32_t* winner);
-/* chain_probit_kernel (csrc/probit.hip) restated: the trials 0, 1, 2, ... of
+/* The probit row policy (ProbitRows, csrc/probit.hip) restated: the trials 0, 1, 2, ... of
  * element i in order, trial t on Philox(seed, stream, i, t), the first accepted
  * proposal is the draw (TruncatedNormal of csrc/samplers.hpp; variant 1: the
  * kernel's forms of the proposal rate and of the exponential variate).

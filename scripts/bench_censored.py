@@ -14,7 +14,7 @@ product:
   dense   f32 storage 100 000 x 2 000, 'cholesky' and 'cg': lognormal and
           linear; weibull under 'hmc'.
 
-The kernel times (chain_censored_kernel, the rss pass and the finish kernels,
+The kernel times (latent_row_kernel<CensoredRows>, the rss pass and the finish kernels,
 the fold, the extra X~^T w) come from a `rocprofv3 --kernel-trace --stats` run
 of a case on its own (--profile wraps it; its rates are not the timed ones).
 

@@ -14,8 +14,9 @@ update:
   latent  bbx_device_truncated_normal and bbx_device_polya_gamma on n rows at
           psi ~ N(0, 1.5^2): wall time per call, uploads included, so only the
           difference of two sizes says anything about the kernels -- their
-          times come from a `rocprofv3 --kernel-trace --stats` run of the
-          sparse case on its own (--profile wraps it).
+          times (the chain's is latent_row_kernel<ProbitRows<double>>) come
+          from a `rocprofv3 --kernel-trace --stats` run of the sparse case on
+          its own (--profile wraps it).
 
 Each chain starts from coef = 0 with global_scale .01 (no mode search), runs
 `warmup` untimed iterations, then `steps` timed ones (gibbs_resume).  One JSON

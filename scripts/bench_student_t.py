@@ -13,7 +13,7 @@ two row passes and its extra product:
           and logit (the weighted Gram of every iteration is the logit model's
           cost).
 
-The kernel times (pass A student_t_wrss_kernel, pass B student_t_mix_kernel,
+The kernel times (pass A student_t_wrss_kernel, pass B latent_row_kernel<StudentTRows>,
 the fold, the extra X~^T w) come from a `rocprofv3 --kernel-trace --stats` run
 of a case on its own (--profile wraps it; its rates are not the timed ones).
 
