@@ -1,16 +1,17 @@
 // The blocked two-pass scan of the Cox handles (cox_family.hpp): the segment
-// descriptor, the max of eta and pass B.  Every scan runs over a FIXED
-// partition: each segment is cut into SCAN_G chunks; a pass A (cox_family.hpp's:
-// it forms the values) writes one sum per chunk, pass B re-adds the sums
-// of the chunks before its own in a fixed order and scans its chunk in tiles
-// of SCAN_BLOCK x SCAN_E.  No float atomics: the same inputs give the same
-// bits on every run.  The kernels are static, as hamiltonian.hpp's are: each
+// descriptor, the max of eta and pass B.  Every scan runs over the fixed
+// partition of seg_scan.hpp, whose header holds the contract, under the plain
+// sum: each segment is cut into SCAN_G chunks; a pass A (cox_family.hpp's: it
+// forms the values) writes one sum per chunk, pass B re-adds the sums of the
+// chunks before its own in a fixed order and scans its chunk in tiles of
+// SCAN_BLOCK x SCAN_E.  The kernels are static, as hamiltonian.hpp's are: each
 // translation unit that includes this file gets its own copy.
 #pragma once
 #include <math.h>
 
 #include "common.hpp"
 #include "hamiltonian.hpp"
+#include "seg_scan.hpp"
 
 #pragma clang fp contract(off)  // a + b * c rounded as NumPy rounds it
 
@@ -95,20 +96,24 @@ static __global__ __launch_bounds__(SCAN_BLOCK) void cox_scan_out_kernel(
     const double* __restrict__ csum, const int* __restrict__ skip) {
   if (skip && *skip) return;
   const int s = blockIdx.x / SCAN_G, b = blockIdx.x % SCAN_G;
-  const bool mirror = sg.rev[s] == 2;
+  // segment s, read once: with sg[s] read again at every element the compiler
+  // carries its fields through the tile loop in 52 more vector registers
+  const int64_t sbase = sg.base[s], slen = sg.len[s];
+  const int rev = sg.rev[s];
+  const bool mirror = rev == 2;
   const int fb = mirror ? SCAN_G - 1 - b : b;   // the chunk of the partition
-  const int64_t len = sg.len[s];
-  const int64_t L = (len + SCAN_G - 1) / SCAN_G;
-  const int64_t t0 = (int64_t)fb * L, t1 = t0 + L < len ? t0 + L : len;
+  const ChunkRange ch = chunk_range<SCAN_G>(slen, fb);
+  const int64_t t0 = ch.t0, t1 = ch.t1;
   if (t0 >= t1) return;
-  // position t of the chunk's walk -> element
+  // position t of the chunk's walk -> element (rev 0, 1: seg_elem's)
   auto elem = [&](int64_t t) {
-    return mirror ? sg.base[s] + (t0 + t1 - 1 - t) : seg_elem(sg, s, t);
+    if (mirror) return sbase + (t0 + t1 - 1 - t);
+    return rev ? sbase + slen - 1 - t : sbase + t;
   };
   __shared__ double s_off;
   __shared__ double s_wave[SCAN_BLOCK / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
   if (threadIdx.x < WAVE) {
+    const int lane = threadIdx.x;
     double acc = 0.;
     for (int c = lane; c < b; c += WAVE)
       acc += csum[s * SCAN_G + (mirror ? SCAN_G - 1 - c : c)];
@@ -127,35 +132,15 @@ static __global__ __launch_bounds__(SCAN_BLOCK) void cox_scan_out_kernel(
       run += t < t1 ? val[elem(t)] : 0.;
       x[e] = run;
     }
-    // inclusive scan of the thread totals across the wave
-    double incl = run;
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) {
-      const double y = __shfl_up(incl, off);
-      if (lane >= off) incl += y;
-    }
-    // the exclusive prefix is the previous lane's inclusive one, never
-    // incl - run: when a thread's run exceeds the lanes before it by more
-    // than 2^53 (1/H grows that fast across a few late risk sets) the
-    // difference loses them entirely
-    double excl = __shfl_up(incl, 1);
-    if (lane == 0) excl = 0.;
-    if (lane == WAVE - 1) s_wave[wid] = incl;
-    __syncthreads();
-    double wpre = 0., tot = 0.;
-#pragma unroll
-    for (int k = 0; k < SCAN_BLOCK / WAVE; ++k) {
-      if (k < wid) wpre += s_wave[k];
-      tot += s_wave[k];
-    }
-    const double base = carry + (wpre + excl);
+    double pre, tot;
+    block_scan<Sum, SCAN_BLOCK>(run, s_wave, pre, tot);
+    const double base = carry + pre;
 #pragma unroll
     for (int e = 0; e < SCAN_E; ++e) {
       const int64_t t = tb + e;
       if (t < t1) out[elem(t)] = base + x[e];
     }
     carry += tot;
-    __syncthreads();
   }
 }
 

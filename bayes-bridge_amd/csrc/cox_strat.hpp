@@ -17,18 +17,16 @@
 // partial likelihood is perfectly finite (it is invariant to a shift of eta
 // within the stratum).
 //
-// Scans.  One segmented scan serves all of them: elements carry a head flag
-// and the operator on (flag, value) pairs is
-//   (f1, v1) o (f2, v2) = (f1 | f2, f2 ? v2 : v1 (+) v2),   (+) = sum or max,
-// associative, so the blocked two-pass scheme of cox.hip carries over.  The
-// partition is FIXED by the length alone: the row range [0, n) (forward, and
-// reversed for the suffix sums over events) and the event range [0, n_event)
-// are each cut into SCAN_G chunks; pass A leaves one (flag, value) aggregate
-// per chunk, pass B combines the aggregates of the chunks before its own in
-// order and scans its chunk in tiles of SCAN_BLOCK x SCAN_E.  Neither the
-// number nor the sizes of the strata enter the partition or the number of
-// launches.  No float atomics: the same inputs give the same bits.
+// Scans.  One segmented scan serves all of them (seg_scan.hpp, whose header
+// holds the contract): elements carry a head flag; SegSum restarts a sum and
+// SegMax a max at every head.  The row range [0, n) (forward, and reversed for
+// the suffix sums over events) and the event range [0, n_event) are each cut
+// into SCAN_G chunks; pass A leaves one (flag, value) aggregate per chunk, pass
+// B scans its chunk in tiles of SCAN_BLOCK x SCAN_E after those before it.
 #pragma once
+#include <type_traits>
+
+#include "seg_scan.hpp"
 
 namespace bbx {
 
@@ -41,96 +39,11 @@ enum RowFlag : uint8_t {
 };
 constexpr int EF_HEAD = 1;   // event flag: first event of a stratum
 
-enum SegOp { OP_SUM = 0, OP_MAX = 1 };
-
-struct FV {
-  int f;
-  double v;
+struct NanMaxOp {
+  __device__ static double ident() { return -INFINITY; }
+  __device__ static double op(double a, double b) { return nanmax(a, b); }
 };
-
-template <int OP>
-__device__ inline FV seg_ident() {
-  FV r;
-  r.f = 0;
-  r.v = OP == OP_MAX ? -INFINITY : 0.;
-  return r;
-}
-
-template <int OP>
-__device__ inline double seg_op(double a, double b) {
-  return OP == OP_MAX ? nanmax(a, b) : a + b;
-}
-
-// a comes before b in scan order
-template <int OP>
-__device__ inline FV seg_comb(FV a, FV b) {
-  FV r;
-  r.f = a.f | b.f;
-  r.v = b.f ? b.v : seg_op<OP>(a.v, b.v);
-  return r;
-}
-
-template <int OP>
-__device__ inline FV wave_seg_incl(FV x, int lane) {
-#pragma unroll
-  for (int off = 1; off < WAVE; off <<= 1) {
-    FV y;
-    y.f = __shfl_up(x.f, off);
-    y.v = __shfl_up(x.v, off);
-    if (lane >= off) x = seg_comb<OP>(y, x);
-  }
-  return x;
-}
-
-// Block-wide segmented scan of one (flag, value) per thread, in thread order.
-// `pre`: everything before this thread (the exclusive prefix is the previous
-// lane's inclusive value, never a difference); `tot`: the whole block.
-template <int OP>
-__device__ inline void block_seg_scan(FV run, FV* s_wave, FV& pre, FV& tot) {
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  const FV incl = wave_seg_incl<OP>(run, lane);
-  FV excl;
-  excl.f = __shfl_up(incl.f, 1);
-  excl.v = __shfl_up(incl.v, 1);
-  if (lane == 0) excl = seg_ident<OP>();
-  if (lane == WAVE - 1) s_wave[wid] = incl;
-  __syncthreads();
-  FV wpre = seg_ident<OP>();
-  tot = seg_ident<OP>();
-#pragma unroll
-  for (int k = 0; k < SCAN_BLOCK / WAVE; ++k) {
-    const FV w = s_wave[k];
-    if (k < wid) wpre = seg_comb<OP>(wpre, w);
-    tot = seg_comb<OP>(tot, w);
-  }
-  pre = seg_comb<OP>(wpre, excl);
-  __syncthreads();
-}
-
-// The aggregates of the chunks before chunk b of direction d, combined in
-// order (every wave computes the same value)
-template <int OP>
-__device__ inline FV chunk_prefix(const double* aggv, const int* aggf, int d,
-                                  int b) {
-  static_assert(SCAN_G % WAVE == 0, "SCAN_G / WAVE chunks per lane");
-  const int lane = threadIdx.x & (WAVE - 1);
-  FV acc = seg_ident<OP>();
-#pragma unroll
-  for (int k = 0; k < SCAN_G / WAVE; ++k) {
-    const int c = lane * (SCAN_G / WAVE) + k;
-    if (c < b) {
-      FV x;
-      x.f = aggf[d * SCAN_G + c];
-      x.v = aggv[d * SCAN_G + c];
-      acc = seg_comb<OP>(acc, x);
-    }
-  }
-  acc = wave_seg_incl<OP>(acc, lane);
-  FV r;
-  r.f = __shfl(acc.f, WAVE - 1);
-  r.v = __shfl(acc.v, WAVE - 1);
-  return r;
-}
+using SegMax = Seg<NanMaxOp>;   // the NaN-keeping max, restarted at a head
 
 enum StratMode {
   SS_MAX = 0,   // eta_i, max                               (rows, forward)
@@ -174,19 +87,19 @@ template <int MODE>
 __global__ __launch_bounds__(SCAN_BLOCK) void coxs_agg_kernel(
     StratArgs a, const int* __restrict__ skip) {
   if (skip && *skip) return;
-  constexpr int OP = MODE == SS_MAX ? OP_MAX : OP_SUM;
+  using M = std::conditional_t<MODE == SS_MAX, SegMax, SegSum>;
+  using FV = typename M::T;
   __shared__ FV s_wave[SCAN_BLOCK / WAVE];
   const int d = blockIdx.x / SCAN_G, b = blockIdx.x % SCAN_G;
   const int mask = strat_mask<MODE>(d);
   const int64_t len = a.len;
-  const int64_t L = (len + SCAN_G - 1) / SCAN_G;
-  const int64_t t0 = (int64_t)b * L, t1 = t0 + L < len ? t0 + L : len;
-  FV carry = seg_ident<OP>();
+  const auto [t0, t1] = chunk_range<SCAN_G>(len, b);
+  FV carry = M::ident();
   double ll = 0.;
   bool zero = false;
   for (int64_t tile = t0; tile < t1; tile += SCAN_TILE) {
     const int64_t tb = tile + (int64_t)threadIdx.x * SCAN_E;
-    FV run = seg_ident<OP>();
+    FV run = M::ident();
 #pragma unroll
     for (int e = 0; e < SCAN_E; ++e) {
       const int64_t t = tb + e;
@@ -216,11 +129,11 @@ __global__ __launch_bounds__(SCAN_BLOCK) void coxs_agg_kernel(
       }
       // both directions compute the same value; the forward one stores it
       if (MODE != SS_MAX && d == 0) a.val[i] = x.v;
-      run = seg_comb<OP>(run, x);
+      run = M::comb(run, x);
     }
     FV pre, tot;
-    block_seg_scan<OP>(run, s_wave, pre, tot);
-    carry = seg_comb<OP>(carry, tot);
+    block_scan<M, SCAN_BLOCK>(run, s_wave, pre, tot);
+    carry = M::comb(carry, tot);
   }
   if (MODE == SS_INVH) {
     ll = block_sum<SCAN_BLOCK>(ll);
@@ -230,8 +143,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void coxs_agg_kernel(
     }
   }
   if (threadIdx.x == 0) {
-    a.aggv[blockIdx.x] = carry.v;
-    a.aggf[blockIdx.x] = carry.f;
+    M::put({a.aggv, a.aggf}, blockIdx.x, carry);
     if (MODE == SS_INVH) a.llpart[b] = ll;
   }
 }
@@ -251,20 +163,20 @@ __global__ __launch_bounds__(SCAN_BLOCK) void coxs_out_kernel(
     double* __restrict__ out, const double* __restrict__ aggv,
     const int* __restrict__ aggf, const int* __restrict__ skip) {
   if (skip && *skip) return;
-  constexpr int OP = OUT == SO_MAX ? OP_MAX : OP_SUM;
+  using M = std::conditional_t<OUT == SO_MAX, SegMax, SegSum>;
+  using FV = typename M::T;
   __shared__ FV s_wave[SCAN_BLOCK / WAVE];
   const int d = blockIdx.x / SCAN_G, b = blockIdx.x % SCAN_G;
   const int mask = OUT == SO_MAX ? RF_SHEAD
                    : OUT == SO_RISK ? (d ? RF_BWD : RF_FWD) : EF_HEAD;
-  const int64_t L = (len + SCAN_G - 1) / SCAN_G;
-  const int64_t t0 = (int64_t)b * L, t1 = t0 + L < len ? t0 + L : len;
+  const auto [t0, t1] = chunk_range<SCAN_G>(len, b);
   if (t0 >= t1) return;
-  FV carry = chunk_prefix<OP>(aggv, aggf, d, b);
+  FV carry = chunk_prefix<M, SCAN_G>({aggv, aggf}, d * SCAN_G, b);
   for (int64_t tile = t0; tile < t1; tile += SCAN_TILE) {
     const int64_t tb = tile + (int64_t)threadIdx.x * SCAN_E;
     double x[SCAN_E];
     unsigned seen = 0, fl[SCAN_E];
-    FV run = seg_ident<OP>();
+    FV run = M::ident();
 #pragma unroll
     for (int e = 0; e < SCAN_E; ++e) {
       const int64_t t = tb + e;
@@ -275,20 +187,20 @@ __global__ __launch_bounds__(SCAN_BLOCK) void coxs_out_kernel(
         FV y;
         y.f = (fl[e] & mask) != 0;
         y.v = val[i];
-        run = seg_comb<OP>(run, y);
+        run = M::comb(run, y);
       }
       x[e] = run.v;
       if (run.f) seen |= 1u << e;
     }
     FV pre, tot;
-    block_seg_scan<OP>(run, s_wave, pre, tot);
-    const FV base = seg_comb<OP>(carry, pre);
+    block_scan<M, SCAN_BLOCK>(run, s_wave, pre, tot);
+    const FV base = M::comb(carry, pre);
 #pragma unroll
     for (int e = 0; e < SCAN_E; ++e) {
       const int64_t t = tb + e;
       if (t >= t1) continue;
       const int64_t i = d ? len - 1 - t : t;
-      const double r = (seen >> e) & 1u ? x[e] : seg_op<OP>(base.v, x[e]);
+      const double r = (seen >> e) & 1u ? x[e] : M::op(base.v, x[e]);
       if (OUT == SO_MAX) {
         if (fl[e] & RF_SLAST) out[sid[i]] = r;
       } else if (OUT == SO_RISK) {
@@ -297,7 +209,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void coxs_out_kernel(
         out[i] = r;
       }
     }
-    carry = seg_comb<OP>(carry, tot);
+    carry = M::comb(carry, tot);
   }
 }
 

@@ -16,33 +16,29 @@
 //
 // The shift is per stratum (one global max would leave a stratum 800 below
 // another with every exp == 0), and the max and the sum are found together, in
-// one segmented pass over (head flag, m, s) triples under the associative
-// "online softmax" operator
-//   (m1, s1) o (m2, s2) = (m, s1 exp(m1 - m) + s2 exp(m2 - m)),  m = max(m1, m2)
-// which a stratum's first row restarts (cox_strat.hpp's seg_comb).  One of the
-// two exponents is always 0, so a combination costs one exp.  Since the sum of
-// a stratum is >= 1 after its shift, the likelihood is finite for every finite
-// eta: this family has no overflow or empty-sum case and never raises
-// CoxTraj::zero.  A NaN in eta comes out of the sums as a NaN.
+// one segmented pass over (head flag, m, s) triples under seg_scan.hpp's SegLse,
+// which a stratum's first row restarts.  Since the sum of a stratum is >= 1
+// after its shift, the likelihood is finite for every finite eta: this family
+// has no overflow or empty-sum case and never raises CoxTraj::zero.  A NaN in
+// eta comes out of the sums as a NaN.
 //
-// Contract (cox_strat.hpp, glm_rows.hpp): the partition is FIXED by n alone --
-// the row range [0, n) is cut into CP_G chunks of ceil(n / CP_G) rows, scanned
-// in tiles of CP_BLOCK x CP_E -- and neither the number nor the sizes of the
-// strata enter it or the number of launches.  Pass A (cp_agg_kernel) leaves one
-// triple per chunk; pass B (cp_out_kernel) combines the triples of the chunks
-// before its own in order, scans its chunk again and writes L_s at the last
-// row of every stratum; the row kernel (cp_row_kernel) computes pi, w and the
-// NPART partials of sum ll and sum w over the (i / VEC_BLOCK) % NPART partition
-// of glm_rows.hpp, which launch_tdot and the post kernels consume unchanged.
-// The Hessian's ubar_s is the same two passes under the plain sum.  No float
-// atomics, every combination in a fixed order: the same inputs give the same
-// bits on every run.  Nothing synchronises with the host.
+// Scans (seg_scan.hpp, whose header holds the contract: the partition fixed by
+// n alone, the order of combination, no float atomics): the row range [0, n)
+// is cut into CP_G chunks, scanned in tiles of CP_BLOCK x CP_E.  Pass A
+// (cp_agg_kernel) leaves one aggregate per chunk; pass B (cp_out_kernel)
+// scans its chunk again after the aggregates before it and writes L_s at the
+// last row of every stratum; the row kernel (cp_row_kernel) computes pi, w and
+// the NPART partials of sum ll and sum w over the (i / VEC_BLOCK) % NPART
+// partition of glm_rows.hpp, which launch_tdot and the post kernels consume
+// unchanged.  The Hessian's ubar_s is the same two passes under SegSum, which
+// leaves aggm alone.  Nothing synchronises with the host.
 #include <math.h>
 
 #include <vector>
 
 #include "common.hpp"
 #include "hamiltonian.hpp"
+#include "seg_scan.hpp"
 
 #pragma clang fp contract(off)  // a + b * c rounded as NumPy rounds it
 
@@ -58,7 +54,6 @@ constexpr int CP_TILE = 2048;   // rows per tile
 constexpr int CP_U = 2;         // rows in flight per thread of the row kernel
 
 static_assert(CP_TILE == CP_BLOCK * CP_E, "a tile is one row set per thread");
-static_assert(CP_G % WAVE == 0, "CP_G / WAVE chunks per lane");
 
 enum CpFlag : uint8_t {
   CF_HEAD = 1,   // first row of a stratum
@@ -73,142 +68,42 @@ struct __attribute__((aligned(32))) CpRow {
 };
 
 enum CpOp {
-  CO_LSE = 0,   // (m, s): log-sum-exp of a_i = eta_i + o_i
-  CO_SUM = 1    // s: sum of pi_i u_i
+  CO_LSE = 0,   // log-sum-exp of a_i = eta_i + o_i
+  CO_SUM = 1    // sum of pi_i u_i
 };
 
-struct Tri {
-  int f;        // a head flag was seen
-  double m, s;  // CO_LSE: the sum is s exp(m); CO_SUM: m unused
+// What the passes need of OP: the monoid, the value of a row (CO_LSE: x = eta,
+// z = o; CO_SUM: x = u, z = pi), a stratum's result from its scan, and the
+// handle's chunk aggregates as the monoid keeps them
+template <int OP>
+struct CpScan;
+
+template <>
+struct CpScan<CO_LSE> {
+  using M = SegLse;
+  __device__ static double value(double x, double z) { return x + z; }
+  __device__ static double result(M::T r) { return r.m + log(r.s); }
+  __device__ static M::In agg(const double* m, const double* s,
+                              const int* f) {
+    return {m, s, f};
+  }
+  __device__ static M::Out agg(double* m, double* s, int* f) {
+    return {m, s, f};
+  }
 };
 
-template <int OP>
-__device__ inline Tri tri_ident() {
-  Tri r;
-  r.f = 0;
-  r.m = OP == CO_LSE ? -INFINITY : 0.;
-  r.s = 0.;
-  return r;
-}
-
-// a comes before b in row order.  An s of 0 marks "no row yet" (a row
-// contributes 1 to its own s): the difference of two -inf is never formed.
-template <int OP>
-__device__ inline Tri tri_comb(Tri a, Tri b) {
-  Tri r;
-  r.f = a.f | b.f;
-  if (OP == CO_SUM) {
-    r.m = 0.;
-    r.s = b.f ? b.s : a.s + b.s;
-    return r;
+template <>
+struct CpScan<CO_SUM> {
+  using M = SegSum;
+  __device__ static double value(double x, double z) { return z * x; }
+  __device__ static double result(M::T r) { return r.v; }
+  __device__ static M::In agg(const double*, const double* s, const int* f) {
+    return {s, f};
   }
-  const double d = a.m - b.m;
-  const double e = exp(-fabs(d));
-  const bool a_top = d >= 0.;
-  r.m = a_top ? a.m : b.m;
-  r.s = a_top ? a.s + b.s * e : a.s * e + b.s;
-  if (b.f || a.s == 0.) {
-    r.m = b.m;
-    r.s = b.s;
-  } else if (b.s == 0.) {
-    r.m = a.m;
-    r.s = a.s;
-  }
-  return r;
-}
+  __device__ static M::Out agg(double*, double* s, int* f) { return {s, f}; }
+};
 
-// One more row behind the run of a thread
-template <int OP>
-__device__ inline void tri_push(Tri& run, bool head, double x) {
-  if (OP == CO_SUM) {
-    run.s = head ? x : run.s + x;
-  } else if (head || run.s == 0.) {
-    run.m = x;
-    run.s = 1.;
-  } else {
-    const double d = x - run.m;
-    const double e = exp(-fabs(d));
-    if (d > 0.) {
-      run.s = run.s * e + 1.;
-      run.m = x;
-    } else {
-      run.s = run.s + e;
-    }
-  }
-  run.f |= head;
-}
-
-template <int OP>
-__device__ inline Tri wave_tri_incl(Tri x, int lane) {
-#pragma unroll
-  for (int off = 1; off < WAVE; off <<= 1) {
-    Tri y;
-    y.f = __shfl_up(x.f, off);
-    y.m = __shfl_up(x.m, off);
-    y.s = __shfl_up(x.s, off);
-    if (lane >= off) x = tri_comb<OP>(y, x);
-  }
-  return x;
-}
-
-// Block-wide segmented scan of one triple per thread, in thread order.  `pre`:
-// everything before this thread; `tot`: the whole block.
-template <int OP>
-__device__ inline void block_tri_scan(Tri run, Tri* s_wave, Tri& pre, Tri& tot) {
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  const Tri incl = wave_tri_incl<OP>(run, lane);
-  Tri excl;
-  excl.f = __shfl_up(incl.f, 1);
-  excl.m = __shfl_up(incl.m, 1);
-  excl.s = __shfl_up(incl.s, 1);
-  if (lane == 0) excl = tri_ident<OP>();
-  if (lane == WAVE - 1) s_wave[wid] = incl;
-  __syncthreads();
-  Tri wpre = tri_ident<OP>();
-  tot = tri_ident<OP>();
-#pragma unroll
-  for (int k = 0; k < CP_BLOCK / WAVE; ++k) {
-    const Tri w = s_wave[k];
-    if (k < wid) wpre = tri_comb<OP>(wpre, w);
-    tot = tri_comb<OP>(tot, w);
-  }
-  pre = tri_comb<OP>(wpre, excl);
-  __syncthreads();
-}
-
-// The triples of the chunks before chunk b, combined in order (every wave
-// computes the same value)
-template <int OP>
-__device__ inline Tri chunk_tri_prefix(const double* aggm, const double* aggs,
-                                       const int* aggf, int b) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  Tri acc = tri_ident<OP>();
-#pragma unroll
-  for (int k = 0; k < CP_G / WAVE; ++k) {
-    const int c = lane * (CP_G / WAVE) + k;
-    if (c < b) {
-      Tri x;
-      x.f = aggf[c];
-      x.m = aggm[c];
-      x.s = aggs[c];
-      acc = tri_comb<OP>(acc, x);
-    }
-  }
-  acc = wave_tri_incl<OP>(acc, lane);
-  Tri r;
-  r.f = __shfl(acc.f, WAVE - 1);
-  r.m = __shfl(acc.m, WAVE - 1);
-  r.s = __shfl(acc.s, WAVE - 1);
-  return r;
-}
-
-// The value of row i under OP.  CO_LSE: x = eta, z = o; CO_SUM: x = u, z = pi
-template <int OP>
-__device__ inline double cp_value(double x, double z) {
-  return OP == CO_LSE ? x + z : z * x;
-}
-
-// Pass A: one triple per chunk.  Block b: chunk b.
+// Pass A: one aggregate per chunk.  Block b: chunk b.
 template <int OP>
 static __global__ __launch_bounds__(CP_BLOCK) void cp_agg_kernel(
     int64_t n, const uint8_t* __restrict__ flag, const double* __restrict__ x,
@@ -216,11 +111,13 @@ static __global__ __launch_bounds__(CP_BLOCK) void cp_agg_kernel(
     double* __restrict__ aggs, int* __restrict__ aggf,
     const int* __restrict__ skip) {
   if (skip && *skip) return;
-  __shared__ Tri s_wave[CP_BLOCK / WAVE];
+  using S = CpScan<OP>;
+  using M = typename S::M;
+  using T = typename M::T;
+  __shared__ T s_wave[CP_BLOCK / WAVE];
   const int b = blockIdx.x;
-  const int64_t L = (n + CP_G - 1) / CP_G;
-  const int64_t t0 = (int64_t)b * L, t1 = t0 + L < n ? t0 + L : n;
-  Tri carry = tri_ident<OP>();
+  const auto [t0, t1] = chunk_range<CP_G>(n, b);
+  T carry = M::ident();
   for (int64_t tile = t0; tile < t1; tile += CP_TILE) {
     const int64_t tb = tile + (int64_t)threadIdx.x * CP_E;
     double v[CP_E];
@@ -230,28 +127,24 @@ static __global__ __launch_bounds__(CP_BLOCK) void cp_agg_kernel(
       const int64_t i = tb + e;
       v[e] = 0.;
       if (i < t1) {
-        v[e] = cp_value<OP>(x[i], z[i]);
+        v[e] = S::value(x[i], z[i]);
         if (flag[i] & CF_HEAD) head |= 1u << e;
       }
     }
-    Tri run = tri_ident<OP>();
+    T run = M::ident();
 #pragma unroll
     for (int e = 0; e < CP_E; ++e)
-      if (tb + e < t1) tri_push<OP>(run, (head >> e) & 1u, v[e]);
-    Tri pre, tot;
-    block_tri_scan<OP>(run, s_wave, pre, tot);
-    carry = tri_comb<OP>(carry, tot);
+      if (tb + e < t1) M::push(run, (head >> e) & 1u, v[e]);
+    T pre, tot;
+    block_scan<M, CP_BLOCK>(run, s_wave, pre, tot);
+    carry = M::comb(carry, tot);
   }
-  if (threadIdx.x == 0) {
-    aggm[b] = carry.m;
-    aggs[b] = carry.s;
-    aggf[b] = carry.f;
-  }
+  if (threadIdx.x == 0) M::put(S::agg(aggm, aggs, aggf), b, carry);
 }
 
-// Pass B: the inclusive segmented scan of each chunk, after the triples of the
-// chunks before it; the last row of stratum s writes out[s]: L_s (CO_LSE) or
-// ubar_s (CO_SUM).
+// Pass B: the inclusive segmented scan of each chunk, after the aggregates of
+// the chunks before it; the last row of stratum s writes out[s]: L_s (CO_LSE)
+// or ubar_s (CO_SUM).
 template <int OP>
 static __global__ __launch_bounds__(CP_BLOCK) void cp_out_kernel(
     int64_t n, const uint8_t* __restrict__ flag,
@@ -260,50 +153,50 @@ static __global__ __launch_bounds__(CP_BLOCK) void cp_out_kernel(
     const double* __restrict__ aggm, const double* __restrict__ aggs,
     const int* __restrict__ aggf, const int* __restrict__ skip) {
   if (skip && *skip) return;
-  __shared__ Tri s_wave[CP_BLOCK / WAVE];
+  using S = CpScan<OP>;
+  using M = typename S::M;
+  using T = typename M::T;
+  __shared__ T s_wave[CP_BLOCK / WAVE];
   const int b = blockIdx.x;
-  const int64_t L = (n + CP_G - 1) / CP_G;
-  const int64_t t0 = (int64_t)b * L, t1 = t0 + L < n ? t0 + L : n;
+  const auto [t0, t1] = chunk_range<CP_G>(n, b);
   if (t0 >= t1) return;
-  Tri carry = chunk_tri_prefix<OP>(aggm, aggs, aggf, b);
+  T carry = chunk_prefix<M, CP_G>(S::agg(aggm, aggs, aggf), 0, b);
   for (int64_t tile = t0; tile < t1; tile += CP_TILE) {
     const int64_t tb = tile + (int64_t)threadIdx.x * CP_E;
-    double v[CP_E], rm[CP_E], rs[CP_E];
+    double v[CP_E];
+    T at[CP_E];   // the thread's run up to each of its rows
     unsigned seen = 0, last = 0, head = 0;
 #pragma unroll
     for (int e = 0; e < CP_E; ++e) {
       const int64_t i = tb + e;
       v[e] = 0.;
       if (i < t1) {
-        v[e] = cp_value<OP>(x[i], z[i]);
+        v[e] = S::value(x[i], z[i]);
         const unsigned fl = flag[i];
         if (fl & CF_HEAD) head |= 1u << e;
         if (fl & CF_LAST) last |= 1u << e;
       }
     }
-    Tri run = tri_ident<OP>();
+    T run = M::ident();
 #pragma unroll
     for (int e = 0; e < CP_E; ++e) {
-      if (tb + e < t1) tri_push<OP>(run, (head >> e) & 1u, v[e]);
-      rm[e] = run.m;
-      rs[e] = run.s;
+      if (tb + e < t1) M::push(run, (head >> e) & 1u, v[e]);
+      at[e] = run;
       if (run.f) seen |= 1u << e;
     }
-    Tri pre, tot;
-    block_tri_scan<OP>(run, s_wave, pre, tot);
-    const Tri base = tri_comb<OP>(carry, pre);
+    T pre, tot;
+    block_scan<M, CP_BLOCK>(run, s_wave, pre, tot);
+    const T base = M::comb(carry, pre);
 #pragma unroll
     for (int e = 0; e < CP_E; ++e) {
       const int64_t i = tb + e;
       if (i >= t1 || !((last >> e) & 1u)) continue;
-      Tri r;
+      T r = at[e];
       r.f = 0;
-      r.m = rm[e];
-      r.s = rs[e];
-      if (!((seen >> e) & 1u)) r = tri_comb<OP>(base, r);
-      out[sid[i]] = OP == CO_LSE ? r.m + log(r.s) : r.s;
+      if (!((seen >> e) & 1u)) r = M::comb(base, r);
+      out[sid[i]] = S::result(r);
     }
-    carry = tri_comb<OP>(carry, tot);
+    carry = M::comb(carry, tot);
   }
 }
 
@@ -389,7 +282,7 @@ struct bbx_cpoisson : HamCore {
   DevMem flag, sid;       // n: CpFlag, stratum of a row
   DevMem ls, ubar;        // ns: L_s, ubar_s
   DevMem pi_loc;          // n: the Hessian's location
-  DevMem aggm, aggs, aggf;   // CP_G chunk triples
+  DevMem aggm, aggs, aggf;   // CP_G chunk aggregates (aggm: CO_LSE only)
 };
 
 namespace {
