@@ -204,6 +204,8 @@ def _declare(lib):
              c_void_p, c_void_p], c_int),
         "bbx_batch_dot": ([hp, c_void_p, c_void_p], c_int),
         "bbx_batch_tdot": ([hp, c_void_p, c_void_p], c_int),
+        "bbx_batch_dot_scaled": (
+            [hp, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
         "bbx_batch_bytes": (
             [hp, POINTER(c_int64), POINTER(c_int64)], c_int),
         "bbx_device_polya_gamma": (

@@ -380,12 +380,38 @@ class HipChainBatch():
         _lib.check(self._lib.bbx_batch_bytes(self._b, byref(d), byref(t)))
         return int(d.value), int(t.value)
 
-    def dot(self, v):
-        """[n_chain, P] -> [n_chain, n]: X~ v_c through the batched kernel."""
+    N_PART = 256     # partials per chain of a batched reduction (NPART)
+
+    def dot(self, v, rowscale=None, return_twt=False):
+        """[n_chain, P] -> [n_chain, n]: X~ v_c through the batched kernel.
+
+        With `rowscale` ([n_chain, n]) or `return_twt` the kernel is launched
+        as the CG loop launches it (`bbx_batch_dot_scaled`): the result is
+        rowscale_c .* (X~ v_c), written interleaved at the batch's stride, and
+        `return_twt` adds (partials [n_chain, 256] of <t_c, rowscale_c t_c>,
+        t_c = X~ v_c, as the kernel wrote them; their sums in index order,
+        [n_chain]) to the returned tuple."""
+        K, n = self.n_chain, self.chains[0].n
         v = _f64(v)
-        out = np.empty((self.n_chain, self.chains[0].n))
-        _lib.check(self._lib.bbx_batch_dot(self._b, _ptr(v), _ptr(out)))
-        return out
+        out = np.empty((K, n))
+        if rowscale is None and not return_twt:
+            _lib.check(self._lib.bbx_batch_dot(self._b, _ptr(v), _ptr(out)))
+            return out
+        if v.shape != (K, self.P):
+            raise ValueError("v must be [n_chain, P]")
+        if rowscale is not None:
+            rowscale = _f64(rowscale)
+            if rowscale.shape != (K, n):
+                raise ValueError("rowscale must be [n_chain, n]")
+        part = np.empty((K, self.N_PART))
+        _lib.check(self._lib.bbx_batch_dot_scaled(
+            self._b, _ptr(v), _ptr(rowscale), _ptr(out), _ptr(part)))
+        if not return_twt:
+            return out
+        twt = np.zeros(K)
+        for k in range(self.N_PART):       # index order
+            twt = twt + part[:, k]
+        return out, part, twt
 
     def Tdot(self, w):
         """[n_chain, n] -> [n_chain, P]: X~^T w_c through the batched kernel."""

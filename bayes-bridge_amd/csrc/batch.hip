@@ -872,6 +872,66 @@ int bbx_batch_dot(bbx_batch* b, const double* v, double* out) {
   });
 }
 
+// The product in the form the CG loop launches it (cg_sample_batch,
+// operator_and_update): per-chain rowscale pointers, the output interleaved at
+// the batch's stride into a buffer with the batch's row padding, the partials
+// of <t_c, Omega_c t_c> on.  The interleaved output goes to a buffer of the
+// call's own: the batch's vectors keep their contents and their zero padding.
+int bbx_batch_dot_scaled(bbx_batch* b, const double* v, const double* rowscale,
+                         double* out, double* twt_part) {
+  return no_throw([&]() -> int {
+    if (!b || !b->h || !v || !out || !twt_part)
+      return fail(BBX_ERR_INVALID, "NULL argument");
+    bbx_design* h = b->h;
+    const int K = b->K, KS = b->KS;
+    const int64_t P = h->P, n = h->n;
+    if (K < 2 || K > BATCH_MAX || KS < K || P < 1 || n < 1)
+      return fail(BBX_ERR_STATE, "not a live batch handle");
+    const BatchShape g = batch_shape(h);
+    BBX_HIP(hipSetDevice(h->device));
+    const size_t rows_n = b->t.bytes / (sizeof(double) * (size_t)KS);
+    if (rows_n < (size_t)n) return fail(BBX_ERR_STATE, "not a live batch handle");
+    DevMem dv, drs, dt;
+    BBX_TRY(dv.alloc(sizeof(double) * (size_t)(K * P)));
+    BBX_TRY(dt.alloc(sizeof(double) * rows_n * (size_t)KS));
+    BBX_HIP(hipMemcpyAsync(dv.ptr, v, sizeof(double) * (size_t)(K * P),
+                           hipMemcpyHostToDevice, h->stream));
+    BBX_HIP(hipMemsetAsync(dt.ptr, 0, sizeof(double) * rows_n * (size_t)KS,
+                           h->stream));
+    if (rowscale) {
+      BBX_TRY(drs.alloc(sizeof(double) * (size_t)(K * n)));
+      BBX_HIP(hipMemcpyAsync(drs.ptr, rowscale, sizeof(double) * (size_t)(K * n),
+                             hipMemcpyHostToDevice, h->stream));
+    }
+    ChainPtrs src{};
+    TiledBatchArgs ba;
+    double* t = dt.as<double>();
+    for (int c = 0; c < K; ++c) {
+      src.p[c] = dv.as<double>() + (size_t)c * P;
+      ba.rowscale.p[c] = rowscale ? drs.as<double>() + (size_t)c * n : nullptr;
+      ba.out.p[c] = t + c;
+    }
+    ba.out_stride = KS;
+    ba.part_stride = NPART;
+    double* sp = b->sp.as<double>();
+    BBX_KC_LAUNCH(K, b_prep_kernel, h->stream, P, KS, g.icpt, nullptr, src,
+                  nullptr, g.offset, sp, bpart(b, PS_C));
+    BBX_HIP(hipGetLastError());
+    BBX_TRY(batch_dot(b, sp, ba, true));
+    std::vector<double> il((size_t)n * (size_t)KS);
+    BBX_HIP(hipMemcpyAsync(il.data(), t, sizeof(double) * il.size(),
+                           hipMemcpyDeviceToHost, h->stream));
+    BBX_HIP(hipMemcpyAsync(twt_part, bpart(b, PS_TWT),
+                           sizeof(double) * (size_t)K * NPART,
+                           hipMemcpyDeviceToHost, h->stream));
+    BBX_HIP(hipStreamSynchronize(h->stream));
+    for (int c = 0; c < K; ++c)
+      for (int64_t i = 0; i < n; ++i)
+        out[(size_t)c * n + i] = il[(size_t)(i * KS + c)];
+    return BBX_OK;
+  });
+}
+
 int bbx_batch_tdot(bbx_batch* b, const double* w, double* out) {
   return no_throw([&]() -> int {
     if (!b || !b->h || !w || !out) return fail(BBX_ERR_INVALID, "NULL argument");

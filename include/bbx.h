@@ -878,6 +878,16 @@ int bbx_batch_run_host(bbx_batch* b, int n_iter, int n_burnin, int thin,
  * dot / Tdot, K at a time).  For the parity tests. */
 int bbx_batch_dot(bbx_batch* b, const double* v, double* out);
 int bbx_batch_tdot(bbx_batch* b, const double* w, double* out);
+/* bbx_batch_dot in the form the batch's CG loop launches it: out [n_chain][n] =
+ * rowscale_c .* (X~ v_c) for rowscale [n_chain][n] (NULL: no scaling), the
+ * kernel writing interleaved at the batch's stride into a buffer with the
+ * batch's row padding (de-interleaved here), and twt_part [n_chain][256]: the
+ * kernel's partials of <t_c, rowscale_c t_c>, t_c = X~ v_c, chain-major, as it
+ * wrote them (the CG loop re-adds them in index order).  BBX_ERR_INVALID for a
+ * NULL b, v, out or twt_part.  The batch's own vectors are left as they were.
+ * For the edge tests. */
+int bbx_batch_dot_scaled(bbx_batch* b, const double* v, const double* rowscale,
+                         double* out, double* twt_part);
 /* Bytes ONE batched launch of each product kernel moves (all chains together):
  * the figure the kernel timers of the design are divided into for a batch. */
 int bbx_batch_bytes(const bbx_batch* b, int64_t* dot_bytes,
