@@ -10,13 +10,13 @@ from .design_matrix import (HipDenseDesignMatrix, HipDesignMatrix,
                             HipSparseDesignMatrix)
 from .model import (CoxModel, LinearModel, LogisticModel, NegBinModel,
                     OrdinalModel, PoissonModel, ProbitModel, RegressionModel,
-                    StudentTModel, WeibullModel, cpoisson_preprocess,
+                    QuantileModel, StudentTModel, WeibullModel, cpoisson_preprocess,
                     CensoredNormalModel, LogNormalAFTModel)
 from .prior import RegressionCoefPrior
 
 __all__ = [
     "BayesBridge", "RegressionModel", "RegressionCoefPrior", "SamplerOptions",
     "HipDesignMatrix", "HipSparseDesignMatrix", "HipDenseDesignMatrix",
-    "HipCGSampler", "HipGibbsChain", "HipChainBatch", "LinearModel", "LogisticModel", "CoxModel", "PoissonModel", "NegBinModel", "OrdinalModel", "WeibullModel", "ProbitModel", "StudentTModel", "CensoredNormalModel", "LogNormalAFTModel", "cpoisson_preprocess", "BbxError",
+    "HipCGSampler", "HipGibbsChain", "HipChainBatch", "LinearModel", "LogisticModel", "CoxModel", "PoissonModel", "NegBinModel", "OrdinalModel", "WeibullModel", "ProbitModel", "StudentTModel", "QuantileModel", "CensoredNormalModel", "LogNormalAFTModel", "cpoisson_preprocess", "BbxError",
     "device_count",
 ]

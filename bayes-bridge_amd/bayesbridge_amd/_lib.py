@@ -19,6 +19,7 @@ MODEL_LINEAR, MODEL_LOGIT = 0, 1
 MODEL_PROBIT = 2
 MODEL_STUDENT_T = 3
 MODEL_CENSORED = 4
+MODEL_QUANTILE = 5
 PRED_LINEAR, PRED_LOGIT, PRED_POISSON = 0, 1, 2   # BBX_PRED_*
 GSCALE_SAMPLE, GSCALE_OPTIMIZE, GSCALE_FIXED = 0, 1, 2
 BATCH_ALLOW_SLOW = 1
@@ -183,6 +184,8 @@ def _declare(lib):
         "bbx_chain_get_zbase": ([hp, c_void_p], c_int),
         "bbx_chain_set_df": ([hp, c_double], c_int),
         "bbx_chain_get_df": ([hp, POINTER(c_double)], c_int),
+        "bbx_chain_set_quantile": ([hp, c_double], c_int),
+        "bbx_chain_get_quantile": ([hp, POINTER(c_double)], c_int),
         "bbx_chain_run": (
             [hp, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p,
              c_void_p, c_void_p, c_void_p, c_void_p], c_int),
@@ -219,6 +222,8 @@ def _declare(lib):
         "bbx_device_censored_normal": (
             [c_int, c_uint64, c_int64, c_void_p, c_void_p, c_void_p, c_double,
              c_void_p], c_int),
+        "bbx_device_inverse_gaussian": (
+            [c_int, c_uint64, c_int64, c_void_p, c_double, c_void_p], c_int),
         "bbx_device_normal": (
             [c_int, c_uint64, c_uint64, c_int64, c_void_p], c_int),
         "bbx_cox_create": (
@@ -253,6 +258,10 @@ def _declare(lib):
              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
             c_int),
         "bbx_design_predictive_summary_student_t": (
+            [hp, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+             c_void_p], c_int),
+        "bbx_design_predictive_summary_quantile": (
             [hp, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
              c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
              c_void_p], c_int),

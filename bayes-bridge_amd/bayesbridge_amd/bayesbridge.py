@@ -55,10 +55,10 @@ NO_OBS_PREC = ('cox', 'poisson', 'negbin', 'ordinal', 'weibull', 'probit')
 # the censored-normal models (csrc/censored.hip): one device family
 CENSORED = ('tobit', 'lognormal')
 # models whose observation precision is one number, the chain's tau
-SCALAR_OBS_PREC = ('linear', 'student_t') + CENSORED
+SCALAR_OBS_PREC = ('linear', 'student_t', 'quantile') + CENSORED
 # the latent-variable families of the Gaussian samplers (csrc/latent_rows.hpp):
 # device RNG only, one chain at a time
-LATENT = ('probit', 'student_t') + CENSORED
+LATENT = ('probit', 'student_t', 'quantile') + CENSORED
 # models whose only coefficient samplers are 'hmc' and 'nuts', and what the
 # refusals call them
 HAMILTONIAN_ONLY = {'poisson': 'Poisson', 'negbin': 'negative-binomial',
@@ -218,8 +218,9 @@ class SamplerOptions():
                 and _is_hip_dense(design)):
             raise ValueError("Only 'cg' sampler supported with HIP matrices.")
         if model_name not in ('linear', 'logit') + LATENT:
-            raise ValueError("Only linear, logit, probit, student_t, tobit "
-                             "and lognormal models use the CG sampler.")
+            raise ValueError("Only linear, logit, probit, student_t, tobit, "
+                             "lognormal and quantile models use the CG "
+                             "sampler.")
         n_obs, n_pred = design.shape
         if n_pred > n_obs:
             # (the reference's TODO here, gibbs_util.py:66-68, is the
@@ -237,7 +238,8 @@ class SamplerOptions():
 def _check_latent_options(model_name, coef_sampler_type, rng):
     """The latent-variable Gaussian families (LATENT) exist on the device
     only: their latents, mixing weights and precision are drawn by
-    csrc/probit.hip, student_t.hip and censored.hip on csrc/latent_rows.hpp,
+    csrc/probit.hip, student_t.hip, censored.hip and quantile.hip on
+    csrc/latent_rows.hpp,
     and their coefficients by the Gaussian samplers."""
     if coef_sampler_type in ('hmc', 'nuts'):
         raise ValueError(
@@ -628,7 +630,7 @@ class BayesBridge():
             else:
                 samples['obs_prec'] = np.zeros((self.n_obs, n_sample))
         if 'mixing_weight' in params_to_save \
-                and self.model.name == 'student_t':
+                and self.model.name in ('student_t', 'quantile'):
             samples['mixing_weight'] = np.zeros((self.n_obs, n_sample))
         if 'latent' in params_to_save and self.model.name in CENSORED:
             samples['latent'] = np.zeros((self.n_obs, n_sample))
@@ -654,11 +656,20 @@ class BayesBridge():
             if obs_prec.size != expected:
                 raise ValueError('An invalid initial state.')
             return obs_prec if self.model.name == 'logit' else float(obs_prec)
+        if self.model.name == 'quantile':
+            # the asymmetric-Laplace likelihood's maximiser in tau
+            return 1. / np.mean(self._check_loss(coef))
         if self.model.name in SCALAR_OBS_PREC:
             return np.mean(
                 (self.model.y - self.model.design.dot(coef)) ** 2) ** -1
         return LogisticModel.compute_polya_gamma_mean(
             self.model.n_trial, self.model.design.dot(coef))
+
+    def _check_loss(self, coef):
+        """rho_q(y - X~ coef) of the quantile model, row by row."""
+        r = self.model.y - self.model.design.dot(coef)
+        q = self.model.quantile
+        return r * np.where(r < 0., q - 1., q)
 
     def _initial_aux(self, aux, init):
         """The chain's first value of the model's auxiliary parameter: the
@@ -955,6 +966,7 @@ class BayesBridge():
             model.y if model.name in SCALAR_OBS_PREC else model.n_success,
             n_trial=model.n_trial if model.name == 'logit' else None,
             df=model.df if model.name == 'student_t' else None,
+            quantile=model.quantile if model.name == 'quantile' else None,
             status=model.status if model.name in CENSORED else None,
             sd_unshrunk=self.prior_sd_for_unshrunk,
             bridge_exponent=prior.bridge_exp, slab_size=prior.slab_size,
@@ -1058,8 +1070,9 @@ class BayesBridge():
     @staticmethod
     def _run_keeping_weights(chain, n_iter, n_burnin, thin, save,
                              key='mixing_weight'):
-        """chain.run with the Student-t model's n mixing weights of every
-        kept iteration (key 'latent': the censored models' n latents): the
+        """chain.run with the Student-t or quantile model's n mixing weights
+        of every kept iteration (key 'latent': the censored models' n
+        latents): the
         library keeps no n-vector per sample for these models, so the run is
         cut at the kept iterations and the weights are read there.  The chain does not notice the cuts: its draws are
         addressed by (seed, iteration)."""
@@ -1106,6 +1119,11 @@ class BayesBridge():
             # bayesbridge.py:397-410 with the device samplers
             if model.name in NO_OBS_PREC:      # probit: Omega = I, no state
                 return None
+            if model.name == 'quantile':
+                # tau | beta under the marginal likelihood and the prior
+                # 1 / tau: Gamma(n, rate sum rho_q(r))
+                return host_rng.gamma(self.n_obs, 1) \
+                    / np.sum(self._check_loss(coef))
             eta = model.design.dot(coef)
             if model.name in SCALAR_OBS_PREC:
                 scale = np.sum((model.y - eta) ** 2) / 2

@@ -18,11 +18,26 @@ _GSCALE_MODES = {'sample': _lib.GSCALE_SAMPLE, 'optimize': _lib.GSCALE_OPTIMIZE,
 _MODEL_CODES = {'linear': _lib.MODEL_LINEAR, 'logit': _lib.MODEL_LOGIT,
                 'probit': _lib.MODEL_PROBIT,
                 'student_t': _lib.MODEL_STUDENT_T,
-                'censored': _lib.MODEL_CENSORED}
+                'censored': _lib.MODEL_CENSORED,
+                'quantile': _lib.MODEL_QUANTILE}
 
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(c_void_p)
+
+
+def checked_quantile(quantile):
+    """The level of a quantile model as a float strictly between 0 and 1
+    (QuantileModel, RegressionModel and HipGibbsChain share this check)."""
+    try:
+        value = float(quantile)
+    except (TypeError, ValueError):
+        value = float('nan')
+    if not 0. < value < 1.:
+        raise ValueError(
+            "The quantile level must lie strictly between 0 and 1: %r."
+            % (quantile,))
+    return value
 
 
 def _f64(a):
@@ -34,25 +49,32 @@ class HipGibbsChain():
     def __init__(self, design, family, outcome, n_trial=None,
                  sd_unshrunk=(float('inf'),), bridge_exponent=.5,
                  slab_size=float('inf'), gscale_shape=0., gscale_rate=0.,
-                 seed=0, df=None, status=None):
+                 seed=0, df=None, status=None, quantile=None):
         """family: 'linear' (outcome = y), 'logit' (outcome = n_success),
         'probit' (outcome = y in {0, 1}; n_trial None or all ones) or
         'student_t' (outcome = y, finite; n_trial None; df: the degrees of
         freedom, None = the library's default 4) or 'censored' (outcome = the
         rows' values, finite; status: 0 observed, 1 right-censored, 2
-        left-censored; n_trial None);
+        left-censored; n_trial None) or 'quantile' (outcome = y, finite;
+        n_trial None; quantile: the level q in (0, 1), None = the library's
+        default 1/2);
         sd_unshrunk: prior sd of the unshrunk coefficients, intercept first
         (bayesbridge.py:26-32); gscale_shape/rate: Gamma prior on
         tau^-bridge_exponent (prior.py:77-81), raw parametrisation."""
         if family not in _MODEL_CODES:
             raise ValueError("family must be 'linear', 'logit', 'probit', "
-                             "'student_t' or 'censored'")
+                             "'student_t', 'censored' or 'quantile'")
         if (status is not None) != (family == 'censored'):
             raise ValueError("status is the 'censored' family's and required "
                              "there: family = %r" % family)
         if df is not None and family != 'student_t':
             raise ValueError("df is the 'student_t' family's: family = %r"
                              % family)
+        if quantile is not None and family != 'quantile':
+            raise ValueError("quantile is the 'quantile' family's: family = %r"
+                             % family)
+        if quantile is not None:
+            quantile = checked_quantile(quantile)
         self._lib = _lib.load()
         self._c = c_void_p()
         self.design = design            # keeps the operator alive
@@ -85,6 +107,8 @@ class HipGibbsChain():
             byref(self._c)))
         if df is not None:
             self.set_df(df)
+        if quantile is not None:
+            self.set_quantile(quantile)
 
     def close(self):
         c = getattr(self, '_c', None)
@@ -131,21 +155,22 @@ class HipGibbsChain():
 
     def get_state(self):
         """(coef, obs_prec, local_scale, global_scale); obs_prec is a float
-        for the linear, Student-t and censored models (tau) and None for the
-        probit model."""
+        for the linear, Student-t, censored and quantile models (tau) and
+        None for the probit model."""
         coef = np.empty(self.P)
         ls = np.empty(self.n_shrunk)
         obs = None if self.family == 'probit' else np.empty(self._obs_len)
         g = c_double()
         _lib.check(self._lib.bbx_chain_get_state(
             self._c, _ptr(coef), _ptr(obs), _ptr(ls), byref(g)))
-        if self.family in ('linear', 'student_t', 'censored'):
+        if self.family in ('linear', 'student_t', 'censored', 'quantile'):
             obs = float(obs[0])
         return coef, obs, ls, float(g.value)
 
     def get_latent(self):
         """The n latents z of a probit or censored chain's current state, or
-        the n mixing weights omega of a Student-t chain's."""
+        the n mixing weights omega of a Student-t chain's, or the n mixing
+        weights w of a quantile chain's."""
         out = np.empty(self.n)
         _lib.check(self._lib.bbx_chain_get_latent(self._c, _ptr(out)))
         return out
@@ -163,9 +188,20 @@ class HipGibbsChain():
         _lib.check(self._lib.bbx_chain_get_df(self._c, byref(df)))
         return float(df.value)
 
+    def set_quantile(self, quantile):
+        """The level q in (0, 1) of a quantile chain; the weights, zbase and
+        the log-likelihood are recomputed under it."""
+        _lib.check(self._lib.bbx_chain_set_quantile(
+            self._c, checked_quantile(quantile)))
+
+    def get_quantile(self):
+        q = c_double()
+        _lib.check(self._lib.bbx_chain_get_quantile(self._c, byref(q)))
+        return float(q.value)
+
     def get_zbase(self):
         """X~^T kappa (logit), X~^T y (linear), X~^T z (probit, censored) or
-        X~^T (tau omega y) (Student-t): what the next draw's right-hand side
+        X~^T (tau omega y) (Student-t) or X~^T kappa (quantile): what the next draw's right-hand side
         is scaled from."""
         out = np.empty(self.P)
         _lib.check(self._lib.bbx_chain_get_zbase(self._c, _ptr(out)))

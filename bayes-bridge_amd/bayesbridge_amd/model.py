@@ -34,6 +34,7 @@ import numpy as np
 import scipy.sparse as sparse
 
 from . import _lib
+from .device_chain import checked_quantile as _checked_quantile
 from .design_matrix import (HipDenseDesignMatrix, HipDesignMatrix,
                             HipSparseDesignMatrix)
 
@@ -667,11 +668,12 @@ class ProbitModel(_Predictive, _Model):
             .astype(np.float64)
 
 
-def _finite_outcome(y, n_row):
-    """The outcome check of the Student-t model on n_row rows: y finite."""
+def _finite_outcome(y, n_row, who='Student-t'):
+    """The outcome check of the Student-t and quantile models (`who`) on n_row
+    rows: y finite."""
     if isinstance(y, tuple):
         raise ValueError(
-            "The Student-t model takes a continuous outcome y, not a tuple.")
+            "The %s model takes a continuous outcome y, not a tuple." % who)
     y = np.asarray(y, dtype=np.float64)
     if y.shape != (n_row,):
         raise ValueError(
@@ -680,8 +682,8 @@ def _finite_outcome(y, n_row):
     bad = np.flatnonzero(~np.isfinite(y))
     if bad.size:
         raise ValueError(
-            "The Student-t model takes a finite outcome: y[%d] = %r."
-            % (bad[0], float(y[bad[0]])))
+            "The %s model takes a finite outcome: y[%d] = %r."
+            % (who, bad[0], float(y[bad[0]])))
     return y
 
 
@@ -782,6 +784,97 @@ class StudentTModel(_Predictive, _Model):
         rng = np.random.default_rng(seed)
         return np.asarray(X.dot(beta)).ravel() \
             + noise_scale * rng.standard_t(_checked_df(df), X.shape[0])
+
+
+class QuantileModel(_Predictive, _Model):
+    """Regression of the q-th conditional quantile, q = `quantile` fixed in
+    (0, 1), no counterpart in the reference: the asymmetric-Laplace
+    likelihood p(y_i) = q (1 - q) tau exp(-tau rho_q(y_i - eta_i)) with the
+    check function rho_q(u) = u (q - 1[u < 0]), whose mode in eta_i is the
+    quantile.  As a scale mixture of normals (Kozumi & Kobayashi 2011), v_i ~
+    Exp(rate tau) and y_i | v_i ~ N(eta_i + theta v_i, kappa2 v_i / tau) with
+    theta = (1 - 2q) / (q (1 - q)) and kappa2 = 2 / (q (1 - q)), the
+    coefficients' conditional is Gaussian with the per-row precision tau /
+    (kappa2 v_i): the chain draws them with 'cg', 'cholesky' or 'woodbury' on
+    the device (csrc/quantile.hip draws tau and w = 1 / v).  Several levels
+    are several fits."""
+
+    def __init__(self, y, design, quantile=.5):
+        self.y = _finite_outcome(y, design.shape[0], 'quantile')
+        self.quantile = _checked_quantile(quantile)
+        self.design = design
+        self.name = 'quantile'
+
+    def compute_loglik_and_gradient(self, beta, obs_prec=1.,
+                                    loglik_only=False):
+        """The chain's log-likelihood, sum_i [log tau - tau rho_q(r_i)] + n
+        log(q (1 - q)), and its gradient tau X~^T (q - 1[r < 0]) (a
+        subgradient where a residual is zero)."""
+        q, tau = self.quantile, float(obs_prec)
+        r = self.y - self.design.dot(beta)
+        side = np.where(r < 0., q - 1., q)
+        loglik = float(np.sum(math.log(tau) - tau * (r * side))
+                       + len(r) * math.log(q * (1. - q)))
+        grad = None
+        if not loglik_only:
+            grad = self.design.Tdot(tau * side)
+        return loglik, grad
+
+    def calc_intercept_mle(self):
+        """The sample q-quantile of y."""
+        return float(np.quantile(self.y, self.quantile))
+
+    def _pred_call(self, n_draw, draws, obs_prec, offset, y, n_trial,
+                   ll_const):
+        return 'bbx_design_predictive_summary_quantile', \
+            (n_draw, self.quantile), (draws, obs_prec, offset, y, ll_const)
+
+    def predict(self, coef, obs_prec=None, X_new=None, y_new=None,
+                return_draws=False, _draws_per_pass=0):
+        """Posterior prediction over the draws coef (P,) or (P, S) -- what
+        samples['coef'] is -- with obs_prec (S,) -- samples['obs_prec'], the
+        draws' tau.  X_new=None: the training rows with the model's own
+        outcome; otherwise n_new rows of the model's raw columns (NumPy or
+        SciPy), centred with the TRAINING design's column means, with y_new or
+        without.  A dict: 'mean' and 'sd' (n,), the posterior mean of eta
+        (the conditional q-quantile) and its population standard deviation
+        over the draws; with an outcome 'lpd', 'loglik_mean' and 'loglik_var'
+        (n,) and the floats 'lppd' = sum lpd, 'p_waic' = sum loglik_var and
+        'waic' = -2 (lppd - p_waic), the log density being the full
+        asymmetric-Laplace density at level q with precision obs_prec; with
+        return_draws 'draws' (n, S).  One device call for all the draws."""
+        draws, X_new, n_row = self._predict_rows(coef, X_new)
+        _training_rows_only(X_new, y_new=y_new)
+        y = self.y if X_new is None else y_new
+        if y is not None:
+            y = _finite_outcome(y, n_row, 'quantile')
+        if obs_prec is None:
+            raise ValueError(
+                "obs_prec (one observation precision per draw, "
+                "samples['obs_prec']) is required.")
+        obs_prec = np.asarray(obs_prec, dtype=np.float64).reshape(-1)
+        if obs_prec.shape != (len(draws),):
+            raise ValueError(
+                "obs_prec must hold one value per draw: %d values, %d draws."
+                % (len(obs_prec), len(draws)))
+        if not np.all(np.isfinite(obs_prec)) or (obs_prec <= 0).any():
+            raise ValueError(
+                "Every obs_prec must be strictly positive and finite.")
+        return self._predictive_summary(
+            draws, X_new, n_row, y=y, obs_prec=obs_prec,
+            return_draws=return_draws, draws_per_pass=_draws_per_pass)
+
+    @staticmethod
+    def simulate_outcome(X, beta, quantile=.5, noise_scale=1., seed=None):
+        """y_i = eta_i + noise_scale times an asymmetric-Laplace variate at
+        level q (precision 1), whose q-quantile is 0: e = E1 / q - E2 / (1 -
+        q) with two standard exponentials."""
+        q = _checked_quantile(quantile)
+        rng = np.random.default_rng(seed)
+        n = X.shape[0]
+        noise = rng.standard_exponential(n) / q \
+            - rng.standard_exponential(n) / (1. - q)
+        return np.asarray(X.dot(beta)).ravel() + noise_scale * noise
 
 
 def _censored_outcome(y, status, n_row):
@@ -2846,8 +2939,9 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
                     dense_storage_dtype='float64', entry_time=None,
                     ties='breslow', weights=None, dispersion=None,
                     dispersion_prior=None, cutpoints=None,
-                    cutpoint_prior=None, df=None, weibull_shape=None,
-                    weibull_shape_prior=None, competing_time=None):
+                    cutpoint_prior=None, df=None, quantile=None,
+                    weibull_shape=None, weibull_shape_prior=None,
+                    competing_time=None):
     """model/factory.py:10-68 with the design placed on an MI355X.  `X` may be
     a SciPy sparse matrix, a NumPy array, or an already built HipDesignMatrix.
     For family='cox', outcome = (event_time, censoring_time) or, for the
@@ -2890,13 +2984,15 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
     family='probit', outcome = y in {0, 1}; a tuple with n_trial is refused
     (the binomial outcome is the logit model's).  For family='student_t',
     outcome = y, finite, and `df` > 0 (None: 4) is the fixed degrees of
-    freedom of the errors.  For family='tobit', outcome = (y, status) with
+    freedom of the errors.  For family='quantile', outcome = y, finite, and
+    `quantile` in (0, 1) (None: 1/2, the median) is the fixed level whose
+    conditional quantile is modelled.  For family='tobit', outcome = (y, status) with
     status 0 (observed), 1 (right-censored: the truth lies above y) or 2
     (left-censored: at or below y); for family='lognormal', outcome =
     (event_time, censoring_time) as for the Weibull model, fitted as the
     log-normal accelerated-failure-time model (coefficients are log time
     ratios).  (The
-    seven keywords stand before `competing_time`, which stays the last one:
+    eight keywords stand before `competing_time`, which stays the last one:
     pass them by name.)"""
     if entry_time is not None and family != 'cox':
         raise ValueError("entry_time is an argument of family='cox' only.")
@@ -2940,6 +3036,12 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
             "negative-binomial form here.")
     if df is not None and family != 'student_t':
         raise ValueError("df is an argument of family='student_t' only.")
+    if quantile is not None and family != 'quantile':
+        raise ValueError(
+            "quantile is an argument of family='quantile' only.")
+    if family == 'quantile':
+        outcome = _finite_outcome(outcome, X.shape[0], 'quantile')
+        quantile = _checked_quantile(.5 if quantile is None else quantile)
     if family == 'probit':
         # (before the design goes to the GPU)
         outcome = _binary_outcome(outcome, X.shape[0])
@@ -3109,6 +3211,8 @@ def RegressionModel(outcome, X, family='linear', add_intercept=None,
         return ProbitModel(outcome, design)
     if family == 'student_t':
         return StudentTModel(outcome, design, df)
+    if family == 'quantile':
+        return QuantileModel(outcome, design, quantile)
     if family == 'tobit':
         return CensoredNormalModel(outcome[0], outcome[1], design)
     if family == 'lognormal':

@@ -243,7 +243,8 @@ class HipRegressionCoefficientSampler():
 
         def loglik_and_grad(beta, loglik_only):
             if model.name in ('linear', 'student_t') \
-                    or model.name in ('tobit', 'lognormal'):
+                    or model.name in ('tobit', 'lognormal') \
+                    or model.name == 'quantile':
                 return model.compute_loglik_and_gradient(
                     beta, obs_prec, loglik_only=loglik_only)
             return model.compute_loglik_and_gradient(

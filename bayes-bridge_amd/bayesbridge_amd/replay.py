@@ -18,6 +18,7 @@ STREAM_ETA1, STREAM_ETA2, STREAM_PG, STREAM_GSCALE, STREAM_LSCALE, \
     STREAM_OBSVAR = 1, 2, 3, 4, 5, 6
 STREAM_LATENT = 7
 STREAM_MIX = 8
+STREAM_QMIX = 9
 
 _SIGS = {
     "bbx_replay_philox_block": [c_void_p, c_void_p, c_void_p],
@@ -32,6 +33,9 @@ _SIGS = {
                                  c_void_p, c_int, c_void_p, c_void_p],
     "bbx_replay_truncated_normal": [c_uint64, c_uint64, c_int64, c_void_p,
                                     c_void_p, c_int, c_void_p, c_void_p],
+    "bbx_replay_inverse_gaussian": [c_uint64, c_uint64, c_int64, c_void_p,
+                                    c_double, c_int, c_void_p, c_void_p,
+                                    c_void_p],
     "bbx_host_log_norm_cdf": [c_int64, c_void_p, c_void_p],
     "bbx_replay_gamma": [c_uint64, c_uint64, c_uint64, c_int64, c_double,
                          c_void_p],
@@ -174,6 +178,30 @@ def censored_normal(seed, stream, psi, bound, status, tau, variant=0,
         out = np.where(censored, bound + u / rt, bound)
     trials = np.where(censored, trials, 0).astype(np.int32)
     return (out, trials) if trace else out
+
+
+def inverse_gaussian(seed, stream, m, lam, variant=0, trace=False,
+                     margin=False):
+    """InverseGaussian(mean 1 / m_i, shape lam) as the quantile row policy
+    draws it (csrc/quantile.hip, InverseGaussian of csrc/samplers.hpp): one
+    normal and one uniform of Philox(seed, stream, i); m_i = 0 is Levy's law.
+    With trace, (draws, branch): 0 where the smaller root was taken, 1 for the
+    other; with margin as well, (draws, branch, u (1 + m x)): the number the
+    draw compares with 1.  The draw has no device form of its own, so
+    `variant` 1 is variant 0.  `stream`: `iter_stream(STREAM_QMIX, it)` for
+    the chain's iteration `it` (`it = -1`: a chain that has not run), the
+    bare STREAM_LATENT for bbx_device_inverse_gaussian."""
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    assert m.ndim == 1
+    out = np.empty(m.size)
+    branch = np.zeros(m.size, dtype=np.int32)
+    mar = np.zeros(m.size)
+    _check(_lib().bbx_replay_inverse_gaussian(
+        seed, stream, m.size, _p(m), float(lam), int(variant), _p(out),
+        _p(branch), _p(mar)), 'inverse-Gaussian')
+    if trace and margin:
+        return out, branch, mar
+    return (out, branch) if trace else out
 
 
 def log_norm_cdf(x):

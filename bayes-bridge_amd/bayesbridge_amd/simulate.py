@@ -91,7 +91,7 @@ def demo_beta(n_pred):
 
 def simulate_outcome(X, beta, model, intercept=0., n_trial=None, seed=None,
                      censoring_frac=.9, dispersion=1., exposure=None,
-                     weibull_shape=1.):
+                     weibull_shape=1., quantile=.5):
     """simulate_data.py:8-27 for the linear and logit families; for 'cox',
     (event_time, censoring_time) of cox_model.py:275-298; for 'negbin',
     counts with mean exposure exp(intercept + X beta) and size `dispersion`
@@ -104,7 +104,10 @@ def simulate_outcome(X, beta, model, intercept=0., n_trial=None, seed=None,
     (StudentTModel.simulate_outcome takes df and the noise scale); for
     'lognormal', (event_time, censoring_time) with log T = intercept + X beta
     + N(0, 1) and the censoring fraction asked for; for 'tobit', (y, status)
-    with z = intercept + X beta + N(0, 1) left-censored at 0."""
+    with z = intercept + X beta + N(0, 1) left-censored at 0; for 'quantile',
+    y = intercept + X beta + an asymmetric-Laplace variate at level
+    `quantile`, whose quantile of that level is 0
+    (QuantileModel.simulate_outcome takes the noise scale)."""
     if model == 'cox':
         from .model import CoxModel
         return CoxModel.simulate_outcome(X, beta, censoring_frac, seed)
@@ -118,6 +121,10 @@ def simulate_outcome(X, beta, model, intercept=0., n_trial=None, seed=None,
         eta = intercept + np.asarray(X.dot(beta), dtype=np.float64).ravel()
         return WeibullModel._simulate_from_eta(eta, weibull_shape,
                                                censoring_frac, seed)
+    if model == 'quantile':
+        from .model import QuantileModel
+        return intercept + QuantileModel.simulate_outcome(
+            X, beta, quantile, 1., seed)
     if seed is not None:
         np.random.seed(seed)
     if model == 'linear':

@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void chain_rss_kernel(
 
 // Finishes the observation-level reductions (single block), by `rule`:
 //   OBS_SUM (logit, probit, censored): loglik = sum of partials
-//   OBS_SUM_CONST (Student-t): ... + n row_const
+//   OBS_SUM_CONST (Student-t, quantile): ... + n row_const
 //   OBS_LINEAR: obs_prec ~ Gamma(n/2, 1) / (rss/2); loglik = n log(w)/2 - w rss/2
 //           (bayesbridge.py:400-404; linear_model.py:13-17); `init` => 1/mean
 enum { OBS_SUM = 0, OBS_SUM_CONST = 1, OBS_LINEAR = 2 };
@@ -555,13 +555,14 @@ static int chain_linear_predictor(bbx_chain* c) {
                     nullptr);
 }
 
-// ---- the latent families: probit (probit.hip), Student-t (student_t.hip) and
-// censored (censored.hip), each a Gaussian conditional for the coefficients
-// given one drawn value per row (latent_rows.hpp)
+// ---- the latent families: probit (probit.hip), Student-t (student_t.hip),
+// censored (censored.hip) and quantile (quantile.hip), each a Gaussian
+// conditional for the coefficients given one drawn value per row
+// (latent_rows.hpp)
 
-// tau before the rows: none, Student-t's rule on the weighted residuals, or the
-// linear model's with the latents for y
-enum { TAU_NONE, TAU_WEIGHTED, TAU_LINEAR };
+// tau before the rows: none, Student-t's rule on the weighted residuals, the
+// linear model's with the latents for y, or the quantile model's Gamma(3n/2)
+enum { TAU_NONE, TAU_WEIGHTED, TAU_LINEAR, TAU_QUANTILE };
 // how 'cholesky' and 'woodbury' take a model: the linear branch at the fixed
 // precision 1 (the cached Gram), that branch at the chain's tau (the cached
 // Gram scaled), or the logit branch with per-row weights (a weighted Gram)
@@ -589,6 +590,18 @@ static int student_t_rows_valid(const double* outcome, const double* n_trial,
   for (int64_t i = 0; i < n; ++i)
     if (!std::isfinite(outcome[i]))
       return fail(BBX_ERR_INVALID, "student_t: outcome[" + std::to_string(i) +
+                                       "] is not finite");
+  return BBX_OK;
+}
+
+static int quantile_rows_valid(const double* outcome, const double* n_trial,
+                               const unsigned char*, int64_t n) {
+  if (n_trial)
+    return fail(BBX_ERR_INVALID,
+                "quantile: n_trial must be NULL (the outcome is continuous)");
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(outcome[i]))
+      return fail(BBX_ERR_INVALID, "quantile: outcome[" + std::to_string(i) +
                                        "] is not finite");
   return BBX_OK;
 }
@@ -636,10 +649,14 @@ static const LatentFamily* latent_family(int model) {
   static const LatentFamily censored{
       "censored", STREAM_LATENT, TAU_LINEAR, false, false, true, DIRECT_TAU,
       false, launch_latent_rows<BBX_MODEL_CENSORED>, censored_rows_valid};
+  static const LatentFamily quantile{
+      "quantile", STREAM_QMIX, TAU_QUANTILE, true, true, true, DIRECT_WEIGHTS,
+      true, launch_latent_rows<BBX_MODEL_QUANTILE>, quantile_rows_valid};
   switch (model) {
     case BBX_MODEL_PROBIT: return &probit;
     case BBX_MODEL_STUDENT_T: return &student_t;
     case BBX_MODEL_CENSORED: return &censored;
+    case BBX_MODEL_QUANTILE: return &quantile;
     default: return nullptr;
   }
 }
@@ -654,6 +671,12 @@ static int direct_branch(const bbx_chain* c) {
   const LatentFamily* f = latent_family(c->model);
   return f ? f->direct
            : c->model == BBX_MODEL_LINEAR ? DIRECT_TAU : DIRECT_WEIGHTS;
+}
+
+// The log-likelihood's row constant of a family that has one
+static double latent_row_const(const bbx_chain* c) {
+  return c->model == BBX_MODEL_QUANTILE ? quantile_row_const(c->quantile)
+                                        : student_t_row_const(c->df);
 }
 
 // The rule of chain_obs_finish_kernel for the chain's log-likelihood
@@ -685,6 +708,8 @@ static int chain_latent_update(bbx_chain* c, int64_t it, bool draw_tau,
   bbx_design* h = c->h;
   if (draw_tau && f->tau_rule == TAU_WEIGHTED)
     BBX_TRY(launch_student_t_tau(c, iter_stream(STREAM_OBSVAR, it)));
+  if (draw_tau && f->tau_rule == TAU_QUANTILE)
+    BBX_TRY(launch_quantile_tau(c, iter_stream(STREAM_OBSVAR, it), false));
   if (draw_tau && f->tau_rule == TAU_LINEAR) {
     const int rg = row_grid(h->n);
     double* rp = c->row_part.as<double>();
@@ -1228,8 +1253,8 @@ static int chain_create_impl(bbx_design* design, int model,
       BBX_LAUNCH(chain_fill_obs_prec_kernel, dim3(grid_for(n, ROW_GRID)),
                  dim3(256), 0, h->stream, n, c->scalars.as<ChainScalars>(),
                  c->obs_prec.as<double>());
-    // (Student-t) nu = 4, tau = 1
-    if (f && f->row_const) c->df_const = student_t_row_const(c->df);
+    // (Student-t) nu = 4, tau = 1; (quantile) q = 1/2, tau = 1
+    if (f && f->row_const) c->df_const = latent_row_const(c);
     // the rows of coef = 0 on the reserved stream index
     if (f && f->draws_at_create) BBX_TRY(chain_latent_refresh(c));
     BBX_HIP(hipGetLastError());
@@ -1479,8 +1504,8 @@ int bbx_chain_get_latent(bbx_chain* c, double* out) {
     BBX_TRY(chain_check(c));
     if (!latent_family(c->model))
       return fail(BBX_ERR_INVALID,
-                  "bbx_chain_get_latent: not a probit, student_t or censored "
-                  "chain");
+                  "bbx_chain_get_latent: not a probit, student_t, censored or "
+                  "quantile chain");
     if (!out) return fail(BBX_ERR_INVALID, "bbx_chain_get_latent: out is NULL");
     BBX_HIP(hipSetDevice(c->h->device));
     BBX_HIP(hipStreamSynchronize(c->h->stream));
@@ -1516,6 +1541,36 @@ int bbx_chain_get_df(bbx_chain* c, double* df) {
   });
 }
 
+int bbx_chain_set_quantile(bbx_chain* c, double quantile) {
+  return no_throw([&]() -> int {
+    BBX_TRY(chain_check(c));
+    if (c->model != BBX_MODEL_QUANTILE)
+      return fail(BBX_ERR_INVALID,
+                  "bbx_chain_set_quantile: not a quantile chain");
+    if (!(quantile > 0.) || !(quantile < 1.))
+      return fail(BBX_ERR_INVALID,
+                  "bbx_chain_set_quantile: quantile must lie in (0, 1)");
+    BBX_HIP(hipSetDevice(c->h->device));
+    c->quantile = quantile;
+    c->df_const = quantile_row_const(quantile);
+    return chain_latent_refresh(c);
+  });
+}
+
+int bbx_chain_get_quantile(bbx_chain* c, double* quantile) {
+  return no_throw([&]() -> int {
+    BBX_TRY(chain_check(c));
+    if (c->model != BBX_MODEL_QUANTILE)
+      return fail(BBX_ERR_INVALID,
+                  "bbx_chain_get_quantile: not a quantile chain");
+    if (!quantile)
+      return fail(BBX_ERR_INVALID,
+                  "bbx_chain_get_quantile: quantile is NULL");
+    *quantile = c->quantile;
+    return BBX_OK;
+  });
+}
+
 int bbx_chain_get_zbase(bbx_chain* c, double* out) {
   return no_throw([&]() -> int {
     BBX_TRY(chain_check(c));
@@ -1540,6 +1595,9 @@ int bbx_chain_init_obs_prec(bbx_chain* c) {
     BBX_LAUNCH(chain_pg_mean_kernel, dim3(rg), dim3(256), 0, h->stream,
                        h->n, c->n_trial.as<double>(), c->psi.as<double>(),
                        c->obs_prec.as<double>());
+  } else if (f && f->tau_rule == TAU_QUANTILE) {
+    // tau = 1 / mean rho_q(r): the asymmetric-Laplace law's ML scale
+    BBX_TRY(launch_quantile_tau(c, 0, true));
   } else {
     // tau = 1 / mean(r^2), r = outcome - psi: the linear model's rule (censored:
     // on the bounds)
@@ -1820,8 +1878,8 @@ int bbx_chain_set_coef_sampler(bbx_chain* c, int sampler) {
     if (sampler == BBX_SAMPLER_WOODBURY && c->model != BBX_MODEL_LINEAR &&
         c->model != BBX_MODEL_LOGIT && !latent_family(c->model))
       return fail(BBX_ERR_INVALID,
-                  "the woodbury sampler draws linear, logit, probit, student_t "
-                  "and censored models only");
+                  "the woodbury sampler draws linear, logit, probit, student_t, "
+                  "censored and quantile models only");
     if (sampler == BBX_SAMPLER_CHOLESKY && c->h->sparse)
       return fail(BBX_ERR_INVALID,
                   "the cholesky sampler needs a dense design (this one is sparse)");

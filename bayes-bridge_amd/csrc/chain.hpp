@@ -21,7 +21,8 @@ struct alignas(128) ChainScalars {
   long long n_gscale_clamped;
   long long n_lscale_fixed;
   // ---- written by the Omega branch
-  alignas(128) double obs_prec;  // linear model; Student-t, censored: tau
+  alignas(128) double obs_prec;  // linear model; Student-t, censored,
+                                 // quantile: tau
   double loglik;                 // of the current coef
   // log posterior (bayesbridge.py:480-511)
   __host__ __device__ double logp() const { return loglik + logprior; }
@@ -44,6 +45,9 @@ struct bbx_chain {
   // log-likelihood's per-row constant lgamma((nu+1)/2) - lgamma(nu/2) -
   // 1/2 log(nu/2), computed on the host when nu is set
   double df = 4., df_const = 0.;
+  // BBX_MODEL_QUANTILE: the level q (bbx_chain_set_quantile); df_const then
+  // holds its row constant log(q (1 - q))
+  double quantile = .5;
   // bbx_chain_set_progress: called from the host loop of a run every
   // `progress_every` iterations (gibbs_util.py:214-238 prints from there)
   void (*progress)(int, void*) = nullptr;
@@ -55,7 +59,8 @@ struct bbx_chain {
   bbx::DevMem lscale;                   // P - n_unshrunk
   bbx::DevMem obs_prec, psi;            // n
   bbx::DevMem latent;                   // n: the probit and censored models' z,
-                                        // the Student-t model's omega (else empty)
+                                        // the Student-t model's omega, the
+                                        // quantile model's w (else empty)
   bbx::DevMem status;                   // n bytes: the censored model's row status
                                         // (outcome holds the bounds; else empty)
   bbx::DevMem scalars;                 // ChainScalars
@@ -116,7 +121,8 @@ int chain_end_run(bbx_chain* c, int n_sample, double* gscale, double* logp);
 // blocks t, t + NPART, ... in that order (chain.hip).
 int launch_sumw_fold(bbx_design* h, const double* block_sums, int count);
 
-// The row update of a latent family (probit.hip, student_t.hip, censored.hip:
+// The row update of a latent family (probit.hip, student_t.hip, censored.hip,
+// quantile.hip:
 // each defines its model's specialisation on latent_rows.hpp, which states
 // what the call leaves where), and what the Student-t model needs besides:
 // launch_student_t_tau draws scalars->obs_prec = gamma_draw(Philox(seed,
@@ -128,8 +134,15 @@ int launch_latent_rows(bbx_chain* c, uint64_t stream, int* row_blocks);
 template <> int launch_latent_rows<BBX_MODEL_PROBIT>(bbx_chain*, uint64_t, int*);
 template <> int launch_latent_rows<BBX_MODEL_STUDENT_T>(bbx_chain*, uint64_t, int*);
 template <> int launch_latent_rows<BBX_MODEL_CENSORED>(bbx_chain*, uint64_t, int*);
+template <> int launch_latent_rows<BBX_MODEL_QUANTILE>(bbx_chain*, uint64_t, int*);
 int launch_student_t_tau(bbx_chain* c, uint64_t stream);
 double student_t_row_const(double nu);
+// The quantile model's (quantile.hip): scalars->obs_prec = gamma_draw(Philox(
+// seed, stream, 0), 3n/2) / S, S = sum_i [1 / w_i + w_i (r_i - theta / w_i)^2 /
+// (2 kappa2)] with the weights in place; `init`: n / sum_i rho_q(r_i), no draw.
+// quantile_row_const is log(q (1 - q)).
+int launch_quantile_tau(bbx_chain* c, uint64_t stream, bool init);
+double quantile_row_const(double q);
 const char* latent_family_name(int model);
 
 // ---- what the n-length kernels of chain.hip and of the latent families share

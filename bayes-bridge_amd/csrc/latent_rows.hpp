@@ -1,11 +1,12 @@
 // What the latent families of the Gaussian samplers share (probit.hip,
-// student_t.hip, censored.hip): the one row kernel of the update that follows
+// student_t.hip, censored.hip, quantile.hip): the one row kernel of the update that follows
 // the coefficient draw, its launch, and the stand-alone draw kernel with its
 // C-ABI front.  Given psi = X~ beta, a family draws one value per row -- the
 // probit and censored models' latent z_i, the Student-t model's mixing weight
 // omega_i -- and collects two sums over the rows on the way: the
 // log-likelihood, and the sum of the vector w whose product X~^T w is the next
-// draw's zbase (w = z; Student-t: w = kappa), which centres that product.
+// draw's zbase (w = z; Student-t, quantile: w = kappa), which centres that
+// product.
 //
 // A family states a policy V, passed to the kernels by value (the row arrays
 // it reads and writes, and the few numbers its expressions need):

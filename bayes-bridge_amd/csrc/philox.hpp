@@ -87,7 +87,8 @@ enum PhiloxStream : uint64_t {
   STREAM_LSCALE = 5, // bayesbridge.py:463
   STREAM_OBSVAR = 6, // bayesbridge.py:403
   STREAM_LATENT = 7, // the probit and censored models' latents (latent_rows.hpp)
-  STREAM_MIX = 8     // the Student-t model's mixing weights (latent_rows.hpp)
+  STREAM_MIX = 8,    // the Student-t model's mixing weights (latent_rows.hpp)
+  STREAM_QMIX = 9    // the quantile model's mixing weights (quantile.hip)
 };
 
 }  // namespace bbx

@@ -4,7 +4,8 @@
 // summary kernel of the one-mean families with its host side (predict.hip:
 // linear, logit, Poisson; negbin_predict.hip: negative binomial;
 // weibull_predict.hip: Weibull; probit_predict.hip: probit;
-// student_t_predict.hip: Student-t; censored_predict.hip: censored normal).
+// student_t_predict.hip: Student-t; censored_predict.hip: censored normal;
+// quantile_predict.hip: quantile).
 // Kernels and
 // drivers are static: a translation unit holds the instantiations it launches
 // and no others.  predict.hip describes the method.
@@ -69,6 +70,10 @@ constexpr int PRED_CENSORED = 7;
 // The same with mu = exp(eta): the median time of the log-normal AFT model,
 // whose latent scale is log t.
 constexpr int PRED_LOGNORMAL = 8;
+// The quantile model's, likewise (quantile_predict.hip): mu = eta, the
+// conditional q-quantile; ll = the asymmetric-Laplace density at the draw's tau
+// and the model's level q.
+constexpr int PRED_QUANTILE = 9;
 constexpr bool pred_censored(int family) {
   return family == PRED_CENSORED || family == PRED_LOGNORMAL;
 }
@@ -79,13 +84,16 @@ struct PredArgs {
   int kn;           // draws of this pass
   int64_t n_draw;   // all draws: the last pass writes the results
   const double* eta;      // [kn][n]
-  const double* tau;      // [n_draw] linear, Student-t, censored: obs_prec;
+  const double* tau;      // [n_draw] linear, Student-t, censored, quantile:
+                          // obs_prec;
                           // Weibull: the shape k
   const double* hlt;      // [n_draw] linear: 0.5 log(obs_prec); Weibull: log k;
                           // Student-t: the draw's normalising constant;
-                          // censored: 0.5 log(obs_prec / (2 pi))
+                          // censored: 0.5 log(obs_prec / (2 pi)); quantile:
+                          // log(obs_prec) + log(q (1 - q))
   const double* gtab;     // [n_draw][NEGBIN_GTAB] negbin: negbin_gtab(r);
-                          // Student-t: [2] = (df + 1) / 2, df
+                          // Student-t: [2] = (df + 1) / 2, df; quantile:
+                          // [1] = q
   const double* offset;   // [n] or null
   const double* y;        // [n]   (SCORE)
   const double* m;        // [n] or null (logit, SCORE); Weibull: log t (SCORE);
@@ -135,6 +143,14 @@ __device__ __forceinline__ void pred_terms(double eta, double y, double m,
     if (SCORE) {
       const double r = y - eta;
       *ll = hlt - gtab[0] * log1p(tau * (r * r) / gtab[1]);
+    }
+  } else if (FAMILY == PRED_QUANTILE) {
+    // hlt = log tau + log(q (1 - q)); rho_q(r) = r (q - 1[r < 0])
+    *mu = eta;
+    if (SCORE) {
+      const double r = y - eta;
+      const double q = gtab[0];
+      *ll = hlt - tau * (r * (r < 0. ? q - 1. : q));
     }
   } else if (pred_censored(FAMILY)) {
     // y is the row's value, m its status; hlt = 1/2 log(tau / (2 pi))
@@ -259,7 +275,7 @@ static __global__ __launch_bounds__(PRED_BLOCK) void predict_summary_kernel(
     const double k = (double)(a.k0 + d + 1);
     double tau = 0., hlt = 0.;
     if (((FAMILY == BBX_PRED_LINEAR || FAMILY == PRED_STUDENT_T ||
-          pred_censored(FAMILY)) &&
+          FAMILY == PRED_QUANTILE || pred_censored(FAMILY)) &&
          SCORE) ||
         FAMILY == PRED_WEIBULL) {
       tau = a.tau[a.k0 + d];
@@ -269,8 +285,9 @@ static __global__ __launch_bounds__(PRED_BLOCK) void predict_summary_kernel(
     const double* gtab =
         FAMILY == PRED_NEGBIN && SCORE
             ? a.gtab + (a.k0 + d) * (int64_t)NEGBIN_GTAB
-        : FAMILY == PRED_STUDENT_T && SCORE ? a.gtab
-                                            : nullptr;
+        : (FAMILY == PRED_STUDENT_T || FAMILY == PRED_QUANTILE) && SCORE
+            ? a.gtab
+            : nullptr;
     pred_terms<FAMILY, SCORE>(eta, y, m, c, has_c, tau, hlt, gtab, &mu, &ll);
     if (a.mu_draws) a.mu_draws[(int64_t)d * n + i] = mu;
     mom.push(mu, k);
@@ -392,7 +409,7 @@ struct PredCall {
   const double *coef, *obs_prec, *offset, *y, *n_trial, *ll_const;
   int draws_per_pass;
   double *mean, *sd, *lpd, *ll_mean, *ll_var, *mu_draws;
-  double df = 0.;   // Student-t: the degrees of freedom
+  double df = 0.;   // Student-t: the degrees of freedom; quantile: the level q
 };
 
 // `launch(stream, score, args)` starts the summary kernel of q.family: the
@@ -407,6 +424,7 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
   const bool weibull = q.family == PRED_WEIBULL;
   const bool student_t = q.family == PRED_STUDENT_T;
   const bool censored = pred_censored(q.family);
+  const bool quantile = q.family == PRED_QUANTILE;
 
   PredPasses p;
   DevMem d_state, d_out;
@@ -447,6 +465,16 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
     tau_host[2 * S] = (q.df + 1.) / 2.;
     tau_host[2 * S + 1] = q.df;
   }
+  if (quantile && score) {
+    // per draw tau and log tau + log(q (1 - q)), then q
+    tau_host.resize(2 * (size_t)S + 1);
+    const double lqq = log(q.df * (1. - q.df));
+    for (int64_t d = 0; d < S; ++d) {
+      tau_host[d] = q.obs_prec[d];
+      tau_host[S + d] = log(q.obs_prec[d]) + lqq;
+    }
+    tau_host[2 * S] = q.df;
+  }
   if (censored && q.obs_prec) {
     // (without an outcome too: the survival summary needs the draws' tau)
     tau_host.resize(2 * (size_t)S);
@@ -463,10 +491,10 @@ static int predictive_summary_impl(const PredCall& q, Launch&& launch) {
   a.n = n;
   a.n_draw = S;
   a.eta = p.d_eta.as<const double>();
-  if (linear || weibull || student_t || censored) {
+  if (linear || weibull || student_t || censored || quantile) {
     a.tau = tab;
     a.hlt = tab ? tab + S : nullptr;
-    if (student_t) a.gtab = tab ? tab + 2 * S : nullptr;
+    if (student_t || quantile) a.gtab = tab ? tab + 2 * S : nullptr;
   } else {
     a.gtab = tab;
   }

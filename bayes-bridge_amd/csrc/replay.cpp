@@ -1,5 +1,6 @@
 // libbbx_hostrng.so, second part: a sequential host replay of the device
-// chain's Philox draws (normals, Polya-Gamma, tilted stable, Gamma), element by
+// chain's Philox draws (normals, Polya-Gamma, tilted stable, truncated normal,
+// inverse Gaussian, Gamma), element by
 // element, for the tests that pin the kernels draw by draw
 // (tests/test_hip_sampler_replay.py).  The loops are in replay_impl.hpp.
 // Plain C++ (g++), no HIP.
@@ -96,6 +97,17 @@ int bbx_replay_truncated_normal(uint64_t seed, uint64_t stream, int64_t n,
                                               out, trials);
   else
     ref::truncated_normal(seed, stream, n, psi, positive, out, trials);
+  return BBX_OK;
+}
+
+int bbx_replay_inverse_gaussian(uint64_t seed, uint64_t stream, int64_t n,
+                                const double* m, double lambda, int variant,
+                                double* out, int32_t* branch, double* margin) {
+  if (!m || !out || n < 0 || (variant != 0 && variant != 1))
+    return BBX_ERR_INVALID;
+  if (!(lambda > 0.)) return BBX_ERR_INVALID;
+  // (no device form of its own: both variants are the one expression)
+  ref::inverse_gaussian(seed, stream, n, m, lambda, out, branch, margin);
   return BBX_OK;
 }
 

@@ -253,6 +253,23 @@ inline void truncated_normal(uint64_t seed, uint64_t stream, int64_t n,
   }
 }
 
+// latent_row_kernel<QuantileRows> / latent_draw_kernel<InverseGaussianDraws>
+// (quantile.hip): element i draws one normal and one uniform of Philox(seed,
+// stream, i).  branch[i]: 0 the smaller root, 1 the other; margin[i]: the
+// number compared with 1.
+inline void inverse_gaussian(uint64_t seed, uint64_t stream, int64_t n,
+                             const double* m, double lambda, double* out,
+                             int32_t* branch, double* margin) {
+  for (int64_t i = 0; i < n; ++i) {
+    HostPhilox g(seed, stream, (uint64_t)i);
+    int b = 0;
+    double t = 0.;
+    out[i] = bbx::InverseGaussian::draw(g, m[i], lambda, &b, &t);
+    if (branch) branch[i] = b;
+    if (margin) margin[i] = t;
+  }
+}
+
 inline double gamma(uint64_t seed, uint64_t stream, uint64_t index,
                     double shape) {
   HostPhilox g(seed, stream, index);

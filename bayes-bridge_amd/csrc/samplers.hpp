@@ -651,6 +651,39 @@ struct TruncatedNormal {
   }
 };
 
+// ------------------------------------------------------- inverse Gaussian
+
+// w ~ InverseGaussian(mean 1 / m, shape lambda), m >= 0: the mixing weight of
+// the quantile model under Kozumi & Kobayashi's (2011) augmentation.  Michael,
+// Schucany & Haas (1976) in reciprocal form: with s = z^2 / (2 lambda), the
+// smaller root of their quadratic is
+//   x = 1 / (m + s + sqrt(s^2 + 2 s m)),
+// taken with probability 1 / (1 + m x), else the other root 1 / (m^2 x).
+// Nothing cancels, m^2 is never formed (m (m x) <= m) and m = 0 needs no
+// branch: x = lambda / z^2, Levy's law, always taken.  One normal and one
+// uniform whatever the arguments: straight-line code, six Philox words per
+// draw.  Finite and positive for m up to 1e150 at least; from about 1e300 on
+// s m can overflow (then x = 0).  `branch` (may be null): 0 the smaller root, 1 the other; `margin`
+// (may be null): u (1 + m x), the number compared with 1.  Arguments that are
+// not finite are the caller's business.
+struct InverseGaussian {
+  template <class G>
+  BBX_HD static inline double draw(G& g, double m, double lambda,
+                                   int* branch = nullptr,
+                                   double* margin = nullptr) {
+    const double z = g.normal();
+    const double u = g.uniform();
+    const double s = (z * z) / (2. * lambda);
+    const double x = 1. / (m + s + sqrt(s * s + 2. * s * m));
+    const double mx = m * x;
+    const double t = u * (1. + mx);
+    const bool small = t <= 1.;
+    if (branch) *branch = small ? 0 : 1;
+    if (margin) *margin = t;
+    return small ? x : 1. / (m * mx);
+  }
+};
+
 // ------------------------------------------------------------------ Gamma
 
 // Gamma(shape, 1), Marsaglia & Tsang (2000).  Device-only use (the reference

@@ -78,6 +78,12 @@ extern "C" {
  *      bbx_chain_create_censored, bbx_device_censored_normal,
  *      bbx_design_predictive_summary_censored; bbx_chain_get_latent serves it
  *      too).  Again a new model code and new symbols: the number stays 113.
+ *      + the quantile regression model on the device chain
+ *      (BBX_MODEL_QUANTILE, bbx_chain_set_quantile, bbx_chain_get_quantile,
+ *      bbx_device_inverse_gaussian, bbx_design_predictive_summary_quantile;
+ *      bbx_chain_get_latent serves it too; in libbbx_hostrng
+ *      bbx_replay_inverse_gaussian).  Again a new model code and new symbols:
+ *      the number stays 113.
  * 112: + the Cox model in counting-process form (bbx_coxcp_*): delayed entry
  *      and (start, stop] rows, with the trajectory and the No-U-Turn sampler
  *      of the Cox handle.
@@ -137,6 +143,10 @@ extern "C" {
 #define BBX_MODEL_STUDENT_T 3 /* linear regression with Student-t errors as a
                                  scale mixture of normals: no counterpart in
                                  the reference; see bbx_chain_create            */
+#define BBX_MODEL_QUANTILE 5 /* quantile regression at a fixed level q: the
+                                asymmetric-Laplace likelihood as a scale
+                                mixture of normals; no counterpart in the
+                                reference; see bbx_chain_create                 */
 
 /* global-scale update of a chain: SamplerOptions.gscale_update
  * (gibbs_util.py:9-31; bayesbridge.py:412-448) */
@@ -669,6 +679,39 @@ int bbx_hbm_probe(int device, int64_t bytes, int reps, double* read_gbps,
  * gscale, iteration, summaries, seed, nu) continues bit for bit.  A psi_i that
  * is not finite gives a NaN omega_i and log-likelihood.  bbx_batch_create
  * refuses student_t chains.
+ *
+ * BBX_MODEL_QUANTILE (no counterpart in the reference): regression of the q-th
+ * conditional quantile, q fixed in (0, 1) (1/2 at creation:
+ * bbx_chain_set_quantile), under the asymmetric-Laplace likelihood p(y_i) = q (1
+ * - q) tau exp(-tau rho_q(y_i - psi_i)), rho_q(u) = u (q - 1[u < 0]), written
+ * (Kozumi & Kobayashi 2011) with theta = (1 - 2q) / (q (1 - q)) and kappa2 = 2 /
+ * (q (1 - q)) as v_i ~ Exp(rate tau), y_i | v_i ~ N(psi_i + theta v_i, kappa2
+ * v_i / tau); the stored latent is w_i = 1 / v_i.  outcome[n] must be finite
+ * (BBX_ERR_INVALID names the first offending row) and n_trial NULL.  After the
+ * coefficient draw of iteration `it`, with r = y - psi:
+ *   tau  = gamma_draw(Philox(seed, 6 | it << 8, 0), 3n/2) / S, S = sum_i [1 /
+ *          w_i + w_i (r_i - theta / w_i)^2 / (2 kappa2)] with the w of the
+ *          iteration before (the prior is 1 / tau, the linear model's);
+ *   w_i  ~ InverseGaussian(mean 1 / (q (1 - q) |r_i|), shape tau / (2 q (1 -
+ *          q))) with the new tau, from one normal z and one uniform u of
+ *          Philox(seed, 9 | it << 8, i) in this order: with m = q (1 - q) |r_i|,
+ *          lambda the shape and s = z^2 / (2 lambda), x = 1 / (m + s + sqrt(s^2 +
+ *          2 s m)), w = x where u (1 + m x) <= 1, else 1 / (m (m x)); at r_i = 0
+ *          that is Levy's law lambda / z^2;
+ *   beta | tau, w is the Gaussian conditional at the per-row precision Omega_i =
+ *          tau w_i / kappa2 with kappa_i = Omega_i y_i - tau theta / kappa2,
+ *          drawn by any of the three samplers.
+ * obs_prec is the scalar tau (length 1, as for the linear model) in set_state,
+ * get_state and the runs; bbx_chain_get_latent returns w.  The log-likelihood is
+ * sum_i [log tau - tau rho_q(r_i)] + n log(q (1 - q)).  bbx_chain_set_state,
+ * bbx_chain_set_quantile and bbx_chain_init_obs_prec (which first sets tau = 1 /
+ * mean rho_q(r), the likelihood's maximiser in tau) recompute psi, w, X~^T kappa
+ * and the log-likelihood from (coef, tau) with the stream of iteration
+ * `iteration - 1`, without redrawing tau, so a chain resumed from (coef,
+ * obs_prec, lscale, gscale, iteration, summaries, seed, q) continues bit for
+ * bit.  A psi_i that is not finite gives a NaN w_i and log-likelihood; |r_i| up
+ * to 1e150 gives a finite positive w_i (beyond about 1e300 the draw's s m can
+ * overflow and the weight be 0).  bbx_batch_create refuses quantile chains.
  */
 int bbx_chain_create(bbx_design* design, int model, const double* outcome,
                      const double* n_trial, int n_unshrunk,
@@ -769,8 +812,8 @@ int bbx_chain_eta(bbx_chain* c, int64_t iteration, double* eta1, double* eta2);
  * (bayesbridge.py:480-511), host pointers, either may be NULL. */
 int bbx_chain_get_logp(bbx_chain* c, double* loglik, double* logp);
 /* The n latents of a BBX_MODEL_PROBIT or BBX_MODEL_CENSORED chain's current
- * state, or the n mixing weights omega of a BBX_MODEL_STUDENT_T chain's (host
- * pointer);
+ * state, or the n mixing weights omega of a BBX_MODEL_STUDENT_T chain's, or the
+ * n mixing weights w of a BBX_MODEL_QUANTILE chain's (host pointer);
  * BBX_ERR_INVALID for a chain of another model or a NULL out. */
 int bbx_chain_get_latent(bbx_chain* c, double* out);
 /* The degrees of freedom nu of a BBX_MODEL_STUDENT_T chain (4 at creation).
@@ -780,6 +823,12 @@ int bbx_chain_get_latent(bbx_chain* c, double* out);
  * positive, a NULL df pointer. */
 int bbx_chain_set_df(bbx_chain* c, double df);
 int bbx_chain_get_df(bbx_chain* c, double* df);
+/* The level q of a BBX_MODEL_QUANTILE chain (1/2 at creation).  Setting it
+ * recomputes the weights, X~^T kappa and the log-likelihood of the current
+ * (coef, tau) under the new q, as bbx_chain_set_state does.  BBX_ERR_INVALID for
+ * a chain of another model, a q outside (0, 1), a NULL quantile pointer. */
+int bbx_chain_set_quantile(bbx_chain* c, double quantile);
+int bbx_chain_get_quantile(bbx_chain* c, double* quantile);
 /* The P-vector the next draw's right-hand side is scaled from: X~^T kappa
  * (logit), X~^T y (linear), X~^T z of the current latents (probit), X~^T (tau
  * omega y) of the current weights (student_t); host pointer.  For the tests that pin it to the latents. */
@@ -921,6 +970,13 @@ int bbx_device_censored_normal(int device, uint64_t seed, int64_t n_draw,
                                const double* psi, const double* bound,
                                const unsigned char* status, double tau,
                                double* out);
+/* InverseGaussian(mean 1 / m[i], shape lambda) on Philox stream 7, the quantile
+ * chain's draw (bbx_chain_create) with m given; m[i] = 0 is Levy's law.
+ * BBX_ERR_INVALID for n_draw < 0, a NULL m or out, a lambda that is not finite
+ * and positive, an m[i] that is not finite and non-negative (the first
+ * offending element is named). */
+int bbx_device_inverse_gaussian(int device, uint64_t seed, int64_t n_draw,
+                                const double* m, double lambda, double* out);
 /* n_draw standard normals of Philox stream `stream` (element i = counter i):
  * the generator behind eta1 / eta2 (cg_sampler.py:61-62 uses
  * np.random.randn). */
@@ -1520,6 +1576,28 @@ int bbx_design_predictive_summary_student_t(
     const double* ll_const, int draws_per_pass, double* mean, double* sd,
     double* lpd, double* ll_mean, double* ll_var, double* mu_draws);
 
+/* The same summary for the quantile regression model
+ * (csrc/quantile_predict.hip), from draws of the coefficients and of the
+ * precision tau, obs_prec[n_draw], at the fixed level `quantile` = q.  With eta
+ * = X~ coef_s + offset and r = y - eta, per row and draw
+ *
+ *   mu = eta   (the conditional q-quantile)
+ *   ll = log tau_s + log(q (1 - q)) - tau_s r (q - 1[r < 0]) + c
+ *
+ * the FULL asymmetric-Laplace density.  y[n] finite or NULL; without it lpd,
+ * ll_mean, ll_var and obs_prec may be NULL.  Passes, synchronisation and
+ * outputs are those of bbx_design_predictive_summary.  BBX_ERR_INVALID for a
+ * NULL or destroyed design, n_draw < 1 (< 2 with an outcome), a NULL coef, mean
+ * or sd, a quantile outside (0, 1), an outcome with a NULL obs_prec, lpd,
+ * ll_mean or ll_var, an obs_prec[d] that is not finite and positive, a y[i]
+ * that is not finite, draws_per_pass < 0: checked before anything touches the
+ * device. */
+int bbx_design_predictive_summary_quantile(
+    bbx_design* design, int64_t n_draw, double quantile, const double* coef,
+    const double* obs_prec, const double* offset, const double* y,
+    const double* ll_const, int draws_per_pass, double* mean, double* sd,
+    double* lpd, double* ll_mean, double* ll_var, double* mu_draws);
+
 /* The same summary for the censored-outcome model (BBX_MODEL_CENSORED;
  * csrc/censored_predict.hip), from draws of the coefficients and of the
  * precision tau, obs_prec[n_draw].  With eta = X~ coef_s + offset and a = (y -
@@ -2106,6 +2184,16 @@ int bbx_replay_truncated_normal(uint64_t seed, uint64_t stream, int64_t n,
                                 const double* psi,
                                 const unsigned char* positive, int variant,
                                 double* out, int32_t* trials);
+/* The quantile row policy's draw (QuantileRows, csrc/quantile.hip) restated:
+ * out[i] = InverseGaussian::draw (csrc/samplers.hpp) at (m[i], lambda) on
+ * Philox(seed, stream, i): one normal, then one uniform.  The draw is sums,
+ * products, quotients and a square root, the same on host and device, so
+ * variant 1 is variant 0.  branch[i] (optional) = 0 where the smaller root was
+ * taken, 1 for the other; margin[i] (optional) = u (1 + m x), the number
+ * compared with 1.  BBX_ERR_INVALID for a lambda that is not positive. */
+int bbx_replay_inverse_gaussian(uint64_t seed, uint64_t stream, int64_t n,
+                                const double* m, double lambda, int variant,
+                                double* out, int32_t* branch, double* margin);
 /* out[k] = gamma_draw on Philox(seed, stream, index + k). */
 int bbx_replay_gamma(uint64_t seed, uint64_t stream, uint64_t index, int64_t n,
                      double shape, double* out);
